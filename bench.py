@@ -1,6 +1,6 @@
 """Benchmark of the segmented htdemucs inference path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dtype f32|bf16|f16]
+    python bench.py [--gpus N --steps K --warmup W] [--dtype f32|bf16|f16] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" = one `apply_model(shifts=0, split=True, overlap=0.25)` pass over a synthetic 44.1 kHz stereo track.
@@ -46,6 +46,22 @@ SR = 44100
 TRACK_SECONDS = 180               # configs[1]
 FIXED_SECONDS = 3600              # configs[3]
 FLOP_PER_SEGMENT = 334.9e9
+DUMP_TIME_SAMPLES = 1 << 20       # --dump-outputs: time positions kept per stem and channel (4 x 2 x 2^20 float32 = 32 MiB)
+DUMP_SEED = 0
+
+
+def output_sample(out):
+    """--dump-outputs: the stems (B, S, C, L) the timed step returned, reduced to a fixed size -- every stem and channel at
+    one seeded, sorted set of time positions (the same for every run with the same arguments), their float64 positions, and
+    float64 sums and sums of squares over the whole length of every stem and channel."""
+    import numpy as np
+    length = out.shape[-1]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(length, size=min(length, DUMP_TIME_SAMPLES), replace=False))
+    sample = out.index_select(-1, torch.from_numpy(idx).to(out.device))
+    return {"stems_sample": sample.float().cpu().numpy(),
+            "stems_time_index": idx.astype(np.float64),
+            "stems_sum": out.sum(-1, dtype=torch.float64).cpu().numpy(),
+            "stems_sumsq": out.double().square().sum(-1).cpu().numpy()}
 
 
 def cpu_baseline(sd, sources, seconds=24, seconds_one_thread=7):
@@ -122,7 +138,7 @@ def cpu_model_name():
     return "unknown"
 
 
-def self_launch(n):
+def self_launch(n, dump_dir=None):
     """`python bench.py --gpus N` without a torchrun environment: start the N ranks as a CHILD `torch.distributed.run` (this
     process has made no GPU call yet and makes none), relay the child's output -- rank 0's JSON line is the last line on
     stdout -- and exit with its code.  Never an exec: a process replaced after GPU initialisation takes the box down."""
@@ -130,6 +146,8 @@ def self_launch(n):
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     argv = [a for a in sys.argv[1:] if a != "--spawn"]
+    if dump_dir:
+        argv += ["--dump-outputs", os.path.abspath(dump_dir)]          # the ranks run in ROOT: a relative DIR is the caller's
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + argv
     p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), stdout=subprocess.PIPE, text=True)
@@ -156,9 +174,14 @@ def main():
                     "collectives, max-over-ranks all_reduce) whatever WORLD_SIZE is: rehearses the multi-GPU code on one GPU")
     ap.add_argument("--spawn", action="store_true", help="start the ranks as a child torch.distributed.run even for --gpus 1 (what "
                     "--gpus N > 1 does by itself when no torchrun environment is present)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the run, write what the last timed step returned "
+                    "to DIR/<name>.npy (float32 / float64, 40 MiB at most): the stems at a fixed seeded sample of time positions, and "
+                    "per-stem-and-channel sums and sums of squares over the whole track")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
-        self_launch(args.gpus)
+        self_launch(args.gpus, args.dump_outputs)
 
     import torch.distributed as dist
     from demucs_amd import apply as P
@@ -241,6 +264,7 @@ def main():
     rows_timed = model.profile_end()
     log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms per step")
     assert out.shape == (1, 4, 2, length) and out.device == dev and bool(torch.isfinite(out[0, 0, 0, ::997]).all())
+    dumped = output_sample(out) if args.dump_outputs and rank == 0 else None      # outside the clock: every rank holds the full result
     del out
     # Per-kernel roofline pass.  In the timed region the waveform branch runs on a side stream beside the spectral branch, so a
     # kernel's event-bracketed duration there includes the time it shares the GPU with the other branch's kernels (those
@@ -553,6 +577,13 @@ def main():
         if not multi and not args.no_cpu_baseline:
             log(f"cpu baseline on {usable_cores()} threads, then 1")
             result["cpu_baseline"] = cpu_baseline(sd, cfg.sources)
+        if dumped is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+            result["dump_outputs"] = {name: list(arr.shape) for name, arr in dumped.items()}
+            log(f"outputs of the last timed step written to {args.dump_outputs}")
         log("done")
         print(json.dumps(result), flush=True)
     if multi:

@@ -51,11 +51,13 @@ def test_resample_needs_the_gpu_engine():
     assert audio.resample_frac(x, 44100, 44100, device="cpu") is x       # equal rates: no engine involved
 
 
-def test_prevent_clip_and_two_stems_host_logic_without_a_gpu():
+def test_prevent_clip_and_two_stems_host_logic_without_a_gpu(monkeypatch):
     """demucs/audio.py:218-234 and the --two-stems branch of demucs/separate.py:189-218: the arithmetic runs in HIP kernels
     (tests/test_gpu_resample.py checks it against the reference's fixture); here only what needs no device -- pass-through
-    modes, argument errors, and the loud refusal of host tensors (no CPU implementation)."""
+    modes, argument errors, and the loud refusal of host tensors when no GPU is available (no CPU implementation).  The
+    missing GPU is made explicit: on a GPU machine host tensors are staged through the device instead."""
     from demucs_amd._lib import EngineError
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     w = torch.tensor([[0.5, -2.0, 1.5]])
     assert audio.prevent_clip(w, None) is w and audio.prevent_clip(w, "none") is w
     with pytest.raises(ValueError):

@@ -373,6 +373,20 @@ def signature_fixture(name: str):
     print(f"  {name}: HTDemucs {len(out['HTDemucs'])} keywords, HDemucs {len(out['HDemucs'])}")
 
 
+def embedding_fixture(name: str, d_model: int, height: int, width: int):
+    """The float32 2-D sinusoidal embedding table the reference adds at the cross-transformer's input
+    (create_2d_sin_embedding), exactly as the reference computed it on the machine that made the float64 fixtures.  Its
+    float32 exp / sin / cos come from the host's vector math library, whose last bits depend on the CPU (MKL takes another
+    code path on a non-Intel CPU); the transformer then amplifies them to ~1e-6 in the float64 taps.  The float64 oracle
+    tests feed this table to the oracle, so that they pin the algorithm and not the host."""
+    import_reference()
+    from demucs.transformer import create_2d_sin_embedding
+    with torch.no_grad():
+        table = create_2d_sin_embedding(d_model, height, width)[0]          # (d_model, height, width) float32
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **{"f32/table": table.numpy()})
+    print(f"  {name}: {tuple(table.shape)} {table.dtype}")
+
+
 def clip_fixture(name: str):
     """`demucs.audio.prevent_clip` in its three modes, and the `--two-stems` arithmetic of
     demucs/separate.py:189-218 obtained by RUNNING the reference's `separate.main` with its `Separator` and `save_audio`
@@ -423,7 +437,7 @@ def clip_fixture(name: str):
 
 
 def main():
-    global hautocast_fixture, package_fixture, signature_fixture, clip_fixture
+    global hautocast_fixture, package_fixture, signature_fixture, clip_fixture, embedding_fixture
     global segment_fixture, apply_fixture, separator_fixture, autocast_fixture, hsegment_fixture, happly_fixture
     only = set(sys.argv[1:])
     if only:                                   # regenerate just the named fixtures
@@ -442,6 +456,8 @@ def main():
         package_fixture = lambda n, *a, **k: pk_all(n, *a, **k) if n in only else None      # noqa: E731
         signature_fixture = lambda n, *a, **k: sg_all(n, *a, **k) if n in only else None    # noqa: E731
         clip_fixture = lambda n, *a, **k: cl_all(n, *a, **k) if n in only else None         # noqa: E731
+        em_all = embedding_fixture
+        embedding_fixture = lambda n, *a, **k: em_all(n, *a, **k) if n in only else None    # noqa: E731
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
     cfg4 = HTDemucsConfig()
@@ -491,6 +507,7 @@ def main():
     package_fixture("pkg_hdemucs", "hdemucs", 6, synth_mix(32, 88200, "noise"))
     signature_fixture("ref_signatures")
     clip_fixture("clip_two_stems")
+    embedding_fixture("emb2d_512x8x336", 512, 8, 336)          # htdemucs: bottom channels 512, 8 bins x 336 frames at the transformer
     print("separator fixtures")
     # a loud, DC-shifted input so that the mono mean / std normalisation of api.py:267-269 is far from the identity
     separator_fixture("separator_shift1", cfg4, 3, 3.0 * synth_mix(12, int(1.3 * SL), "tones") + 0.2, rseed=11,
