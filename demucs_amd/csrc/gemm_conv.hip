@@ -727,6 +727,9 @@ static int x6_verified_launch(const mi_conv_desc &d, int tile, bool plain, hipSt
     return MI_OK;
 }
 
+// process-wide switch of the split-bf16 main loops (mi_set_split_bf16): 0 ignores every split weight image
+int g_split_bf16 = 1;
+
 int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     mi_conv_desc d = din;
     if (!d.sink) d.sink = conv_sink();
@@ -743,7 +746,7 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
                "conv: MI_FLAG_IMG4 needs a half-mode GLU layer with M %% 32 == 0 and an aligned phase image of >= B * yh_pq positions per plane");
     MI_REQUIRE(!(d.flags & MI_FLAG_STATS) || (d.epi == MI_EPI_LINEAR && d.stats && d.O2 >= 32 && d.row_mode == 0),
                "conv: MI_FLAG_STATS needs a LINEAR layer, a statistics buffer and O2 >= 32");
-    if (d.flags & MI_FLAG_STATS) d.wx = nullptr;             // the split-bf16 main loop is not instantiated with the statistics epilogue
+    if (!g_split_bf16) d.wx = nullptr;                      // mi_set_split_bf16(0): native fp32 MFMA kernels only
     MI_REQUIRE(!(d.flags & MI_FLAG_LN) || (d.pro_stats && d.scale && d.epi == MI_EPI_LINEAR), "conv: MI_FLAG_LN needs pro_stats and scale");
     // plain fast path: a 1x1 / linear layer whose gather is the identity
     const int64_t P = (int64_t)d.O1 * d.O2;

@@ -71,13 +71,19 @@ int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx,
 #define MI_X6_ABL 0          /* victim-side bisect builds: 1 = one MFMA per K step instead of 24, 4 = no epilogue, 8 = zero operands,
                                 16 = 32 idle cycles after every MFMA, 32 = 64 idle cycles after every 4 MFMAs */
 #endif
-template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN>
+// HALF_IMG: a 64-row tile that reads its rows out of the 128-row weight image (the small-batch tile of the plain linear
+// layers, launch_conv_x6): the same fragments, products and k order as the 128-row tile, so both give bit-identical results.
+template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false>
 __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc d, const int N, const int MT, const int Gm) {
     constexpr int BM = WM * TM * 32;
     static_assert(WN * TN * 32 == BN, "block N tile is 128");
     static_assert(WM * WN == 4, "4 waves");
     constexpr int A_BYTES = BM * 96, B_BYTES = BN * 96, STAGE = A_BYTES + B_BYTES;
     constexpr int A_CHUNKS = A_BYTES / 1024;                 // 1 KiB per wave-wide DMA instruction
+    static_assert(!HALF_IMG || BM == 64, "HALF_IMG: 64-row tile of a 128-row image");
+    // one K step of the image: [part 3][k-half 2][image rows][16 bytes]; the 64-row half of a 128-row image is the first or the
+    // second KiB of each 2 KiB (part, k-half) block
+    constexpr int A_KSTEP = HALF_IMG ? 2 * A_BYTES : A_BYTES, A_CHUNK_STRIDE = HALF_IMG ? 2048 : 1024;
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
     // plain layers: the fp32 activation tile [16][128] lands here by LDS-DMA two K steps ahead and is split from LDS
     // (a VMEM wave-instruction costs ~12-16 cycles whatever its width: 2 x 1 KiB DMA per wave replace 8 dword loads)
@@ -99,13 +105,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
     const int nk = d.Kpad / BK;
 
     // ---- A: LDS-DMA of the pre-split image; wave w moves chunks w, w + 4, ... -------------------------
-    const unsigned char *aimg = reinterpret_cast<const unsigned char *>(d.wx) + (size_t)mt * nk * A_BYTES + lane * 16;
+    const unsigned char *aimg = reinterpret_cast<const unsigned char *>(d.wx) + (size_t)(HALF_IMG ? mt >> 1 : mt) * nk * A_KSTEP +
+                                (HALF_IMG ? (mt & 1) * 1024 : 0) + lane * 16;
 #define MI_A_DMA(kt, stage)                                                                                         \
     do {                                                                                                            \
         _Pragma("unroll") for (int c = 0; c < (A_CHUNKS + 3) / 4; ++c) {                                             \
             const int chunk = c * 4 + wave;                                                                         \
             if (chunk < A_CHUNKS)                                                                                   \
-                __builtin_amdgcn_global_load_lds((gvoid_t *)(aimg + (size_t)(kt) * A_BYTES + chunk * 1024),         \
+                __builtin_amdgcn_global_load_lds((gvoid_t *)(aimg + (size_t)(kt) * A_KSTEP + chunk * A_CHUNK_STRIDE), \
                                                  (lvoid_t *)(smem + (stage) * STAGE + chunk * 1024), 16, 0, 0);     \
         }                                                                                                           \
     } while (0)
@@ -294,22 +301,29 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
     conv_epilogue<TM, TN, EPI, LFLAGS>(d, acc, m0, n0, wm, wn, N, P, o2v);
 }
 
-template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN>
+template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false>
 static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
     const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
     MI_REQUIRE(N64 < (1ll << 31) - 256, "conv: too many output positions (%lld)", (long long)N64);
-    MI_REQUIRE(d.Mpad % BM == 0, "conv: Mpad %d not a multiple of the %d-row tile", d.Mpad, BM);
+    MI_REQUIRE(d.Mpad % (HALF_IMG ? 2 * BM : BM) == 0, "conv: Mpad %d not a multiple of the %d-row tile", d.Mpad, BM);
     const int N = (int)N64, MT = d.Mpad / BM, NT = ceil_div(N, BN);
     const int Gm = pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 6);
     const unsigned grid = grouped_grid(MT, NT, Gm);
-    hipLaunchKernelGGL((conv_gemm_x6_kernel<WM, WN, TM, TN, EPI, LFLAGS, PLAIN>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
+    hipLaunchKernelGGL((conv_gemm_x6_kernel<WM, WN, TM, TN, EPI, LFLAGS, PLAIN, HALF_IMG>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }
 
 template <int EPI, int LFLAGS, bool PLAIN>
 static int launch_tile_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
+    if constexpr (PLAIN && EPI == MI_EPI_LINEAR) {
+        // small batches, as in the fp32 kernels (gemm_conv.hip launch_tile): a plain linear layer whose 128-row tiles give fewer
+        // workgroups than the chip has CUs runs on 64-row tiles that read the 128-row image (MI_SMALL_TILE=0: off)
+        static const int small = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
+        if (small && tile == 128 && (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200)
+            return launch_cfg_x6<1, 4, 2, 1, EPI, LFLAGS, PLAIN, true>(d, st);
+    }
     switch (tile) {
         case 128: return launch_cfg_x6<2, 2, 2, 2, EPI, LFLAGS, PLAIN>(d, st);
         case 96: return launch_cfg_x6<1, 4, 3, 1, EPI, LFLAGS, PLAIN>(d, st);
@@ -329,11 +343,12 @@ int launch_conv_x6(const mi_conv_desc &d, int tile, bool plain, hipStream_t st) 
 #define MI_LINEAR(F)                                                \
     case F: return plain ? launch_tile_x6<MI_EPI_LINEAR, F, true>(d, tile, st) : launch_tile_x6<MI_EPI_LINEAR, F, false>(d, tile, st)
     if (d.epi == MI_EPI_LINEAR) {
-        switch (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN)) {
+        switch (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) {
             MI_LINEAR(0);
             MI_LINEAR(MI_FLAG_GELU);
             MI_LINEAR(MI_FLAG_RES);
             MI_LINEAR(MI_FLAG_SCALE | MI_FLAG_RES);
+            MI_LINEAR(MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS);
             MI_LINEAR(MI_FLAG_LN);
             MI_LINEAR(MI_FLAG_LN | MI_FLAG_GELU);
         }

@@ -92,6 +92,7 @@ int launch_dconv_time_layer(const DConvTimeLayer &l, int C, int dil, int B, int 
 // gemm_conv.hip
 int launch_conv(const mi_conv_desc &d, hipStream_t st);
 int conv_pick_tile(int M);
+extern int g_split_bf16;     // 0 (mi_set_split_bf16): native fp32 MFMA kernels even where a split weight image exists
 // gemm_x6.hip
 bool conv_x6_supported(int tile);
 int launch_conv_x6(const mi_conv_desc &d, int tile, bool plain, hipStream_t st);

@@ -105,7 +105,7 @@ static const char *kEpiNames[6] = {"linear", "glu", "bias_stats", "stats_only", 
 // class id of a conv launch: epilogue x tile x prologue
 static int conv_class(const mi_conv_desc &d, int tile) {
     const int ti = tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3;
-    const bool x6 = d.half || (d.wx && conv_x6_supported(tile));     // bf16 / fp16 operand or split-bf16 main loops: own classes
+    const bool x6 = d.half || (d.wx && g_split_bf16 && conv_x6_supported(tile));   // bf16 / fp16 operand or split-bf16 main loops: own classes
     return (x6 ? 48 : 0) + d.epi * 8 + ti * 2 + (d.plain ? 1 : 0);
 }
 
@@ -172,13 +172,17 @@ int Model::attn_heads(const void *q, const void *k, const void *v, float *o, int
 // weight lookup and packing
 // ------------------------------------------------------------------------------------------------
 // Second copy of the packed weights as exact 3-term bf16 tile images: selects the 6-product bf16 MFMA main loop
-// (gemm_x6.hip).  Opt-in (MI_X6=1) this round: the kernels pass every single-process parity test and are ~1.4x faster
-// on the transformer's linear layers, but when several PROCESSES share one GPU their results are intermittently
-// corrupted (tests/test_gpu_distributed.py, tools/micro/det3.py; cause not found yet), so the engine stays on the
-// native fp32 MFMA kernels by default.
+// (gemm_x6.hip).  Scope: by default the float32 engine's 44 transformer linears (split_linears), where the split loop is
+// ~1.4x faster than the native fp32 MFMA kernels; MI_X6=0 packs none (A/B runs), MI_X6=1 every layer whose tile has the
+// split loop (the k x k convs measured slower on it).  When several PROCESSES share one GPU, split-loop results were
+// intermittently corrupted (tests/test_gpu_distributed.py, tools/micro/det3.py; cause not found), so such a process
+// selects the native kernels at run time (mi_set_split_bf16(0): demucs_amd/distributed.py does it for ranks that share
+// a device); one process per GPU is the supported deployment.
 int Model::pack_split(PackedConv *pc) {
-    static const bool x6 = getenv("MI_X6") != nullptr && atoi(getenv("MI_X6")) != 0;
-    if (!x6 || !conv_x6_supported(pc->tile)) return MI_OK;
+    static const char *env = getenv("MI_X6");
+    static const int scope = env ? (atoi(env) != 0 ? 2 : 0) : 1;      // 0 none, 1 transformer linears (float32), 2 all
+    const bool want = scope == 2 || (scope == 1 && split_linears && cfg.dtype == MI_DTYPE_F32);
+    if (!want || !conv_x6_supported(pc->tile)) return MI_OK;
     MI_TRY(dev_alloc(&pc->wx, (size_t)6 * pc->Kpad * pc->Mpad));
     MI_TRY(launch_pack_split(pc->wt, pc->Kpad, pc->Mpad, pc->tile, pc->wx, nullptr));
     MI_HIP(hipStreamSynchronize(nullptr));
@@ -527,6 +531,7 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         const float *w, *b;
         MI_TRY(wt.get(ni + ".weight", 512, &w)); MI_TRY(wt.get(ni + ".bias", 512, &b));
         MI_TRY(pack_vec(w, 512, 512, false, &norm_in_w[br])); MI_TRY(pack_vec(b, 512, 512, false, &norm_in_b[br]));
+        split_linears = true;
         for (int k = 0; k < 5; ++k) {
             const std::string p = std::string("crosstransformer.") + (br ? "layers_t." : "layers.") + std::to_string(k);
             const bool cross = k & 1;
@@ -559,6 +564,7 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
             MI_TRY(wt.get(p + ".gamma_1.scale", 512, &w)); MI_TRY(pack_vec(w, 512, 512, false, &l.gamma1));
             MI_TRY(wt.get(p + ".gamma_2.scale", 512, &w)); MI_TRY(pack_vec(w, 512, 512, false, &l.gamma2));
         }
+        split_linears = false;
     }
     {   // positional tables, float32 arithmetic like the reference (transformer.py:19-70), stored [512][tokens]
         std::vector<float> pe2((size_t)512 * Tf), pe1((size_t)512 * Tt);

@@ -33,11 +33,13 @@ from __future__ import annotations
 import contextlib
 import os
 import random
+import socket
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from . import apply as _apply
 from .hdemucs import HDemucs
 from .htdemucs import HTDemucs
@@ -152,6 +154,24 @@ def rng_draws_per_forward(model) -> int:
     return int(getattr(model, "rng_draws_per_forward", 0))
 
 
+_gpu_share_checked = set()
+
+
+def _native_kernels_if_gpu_shared(device, group) -> None:
+    """Once per process group: if another rank of `group` runs on this process's GPU, switch the engine to its native float32
+    MFMA kernels (mi_set_split_bf16(0)) before the first forward.  The split-bf16 transformer linears gave intermittently
+    corrupted results when several processes shared one GPU; one process per GPU keeps them."""
+    if id(group) in _gpu_share_checked:
+        return
+    _gpu_share_checked.add(id(group))
+    p = torch.cuda.get_device_properties(device)
+    mine = (socket.gethostname(), p.pci_domain_id, p.pci_bus_id, p.pci_device_id, str(getattr(p, "uuid", "")))
+    ids = [None] * dist.get_world_size(group)
+    dist.all_gather_object(ids, mine, group=group)
+    if sum(i == mine for i in ids) > 1:
+        _lib.load().mi_set_split_bf16(0)
+
+
 def _agree_on(value: int, device, group) -> int:
     """Rank 0's value on every rank (shift offsets come from each process's own Python RNG)."""
     t = torch.tensor([value], dtype=torch.int64, device=device if dist.get_backend(group) == "nccl" else "cpu")
@@ -206,6 +226,8 @@ def apply_model_sharded(model, mix: torch.Tensor, shifts: int = 0, overlap: floa
     engine = device.type == "cuda" and all(k != "generic" for k in kinds)
     if not engine:
         kinds = ["generic"] * len(models)
+    elif world > 1:
+        _native_kernels_if_gpu_shared(device, group)
     weight = _apply._transition_weight(segment_length, transition_power, device).to(torch.float32).contiguous()
     # one pass of one plain model: slabs are gathered un-normalised and divided after the stitch (bit-identical to one GPU);
     # any shift (its virtual offsets differ from the un-shifted plan) or bag (per-source weights) takes the per-pass branch

@@ -128,6 +128,11 @@ int mi_set_two_streams(int32_t enabled);
  *   (frames to memory, then a gather): same summation order, bit-identical output -- kept for A/B runs and as the check of the
  *   fused kernel.  Process-wide; returns the previous setting.  Initial value: 1 unless MI_ISTFT_SPLIT is set. */
 int mi_set_istft_fused(int32_t enabled);
+/* mi_set_split_bf16: the float32 engine runs its transformer linears (and, with MI_X6=1, every layer with a split image) on the
+ *   split-bf16 main loop (gemm_x6.hip: fp32 operands as three exact bf16 terms, six bf16 MFMA products, fp32 accumulate).  0
+ *   selects the native fp32 MFMA kernels for every later launch, e.g. in a process that shares its GPU with another rank
+ *   (demucs_amd/distributed.py does this by itself).  Process-wide; returns the previous setting.  Initial value: 1. */
+int mi_set_split_bf16(int32_t enabled);
 /* mi_set_transpose_tiles: the kernels either side of the transforms (demucs/htdemucs.py:420-471, demucs/spec.py:11-47).  0, the
  *   default: the STFT walks a run of consecutive frames per workgroup (twiddles and window read once per run, the next frame's samples
  *   prefetched), and the layout changes between the frame-major scratch and the conv layout x[b][c][bin][frame] move 32 bins x all
