@@ -413,7 +413,15 @@ int mi_gn_gelu_gram(float *x_dev, int32_t B, int32_t h, int32_t C_alloc, int32_t
     MI_REQUIRE(x_dev && stats_dev && w_dev && b_dev && gram_dev && B > 0 && h > 0 && D1 > 0 && D2 > 0 && slots > 0, "mi_gn_gelu_gram: bad argument");
     MI_REQUIRE(C_alloc >= h && pitch >= D2, "mi_gn_gelu_gram: C_alloc < h or pitch < D2");
     return launch_gn_gelu_gram(x_dev, B, h, C_alloc, D1, D2, pitch, row_mode, (const float2 *)stats_dev, w_dev, b_dev, gram_dev, slots,
-                               (hipStream_t)stream);
+                               false, (hipStream_t)stream);
+}
+
+int mi_dconv_gn_gelu_gram(float *x_dev, int32_t B, int32_t h, int32_t C_alloc, int32_t D1, int32_t D2, int32_t pitch, int32_t row_mode,
+                          const float *stats_dev, const float *w_dev, const float *b_dev, double *gram_dev, int32_t slots, void *stream) {
+    MI_REQUIRE(x_dev && stats_dev && w_dev && b_dev && gram_dev && B > 0 && h > 0 && D1 > 0 && D2 > 0 && slots > 0, "mi_dconv_gn_gelu_gram: bad argument");
+    MI_REQUIRE(C_alloc >= h && C_alloc <= gram_hp(h) && pitch >= D2, "mi_dconv_gn_gelu_gram: C_alloc outside [h, mi_gram_order(h)] or pitch < D2");
+    return launch_gn_gelu_gram(x_dev, B, h, C_alloc, D1, D2, pitch, row_mode, (const float2 *)stats_dev, w_dev, b_dev, gram_dev, slots,
+                               true, (hipStream_t)stream);
 }
 
 int mi_gram_finalize(double *gram_dev, int32_t rows, int32_t h, int32_t slots, const double *wt_dev, const double *ct_dev, double sum_b,

@@ -233,7 +233,7 @@ int HModel::hinit(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
             MI_TRY(A(&x_eimg[0][i], 2 * hCh[i] * pqf)); MI_TRY(A(&x_eimg[1][i], 2 * hCh[i] * pqt));
         }
     }
-    MI_HIP(hipMemset(x_h, 0, (hid + 64) * B * sizeof(float)));        // hidden tensors carry zero padding channels
+    MI_HIP(hipMemset(x_h, 0, (hid + 64) * B * sizeof(float)));        // hidden tensors carry zero padding channels (re-zeroed per layer by gn_gelu_gram_kernel)
     MI_HIP(hipMemset(x_th, 0, (hid + 64) * B * sizeof(float)));
     const size_t zsz = std::max<size_t>(C6 * (T5 + 2), std::max<size_t>(C6 * T + 64, C3 * (4 * T + 8)));   // largest: decoder.1's 384 x 8 x T
     MI_TRY(A(&x_zA, zsz)); MI_TRY(A(&x_zB, zsz));

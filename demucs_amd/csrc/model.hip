@@ -667,7 +667,8 @@ int Model::fill_workspace(Workspace &w) {
         MI_TRY(w.alloc((void **)p, (big * B + 64) * sizeof(float)));
         *p += 32;
     }
-    // DConv hidden tensors carry round_up(C/8, 16) channels; the padding channels must read as zero
+    // DConv hidden tensors carry round_up(C/8, 16) channels; the padding channels must read as zero: every layer shares this buffer
+    // at its own item stride, so gn_gelu_gram_kernel re-zeroes them in each use (zero_pad) (a NaN another item left there would survive 0 * x)
     MI_HIP(hipMemset(w.w_h, 0, (big / 2) * B * sizeof(float)));
     MI_HIP(hipMemset(w.w_th, 0, (big / 2) * B * sizeof(float)));
     const size_t Tf = 8 * (size_t)T, Tt = Lt[4];
@@ -782,7 +783,7 @@ int Model::run_dconv(const DConvW &w, int C, const Geo &g, float *x, float *tmp,
         const int gslots = g.row_mode ? 1 : 8, HP = gram_hp(h);
         MI_REQUIRE((size_t)rows * gslots * HP * HP * sizeof(double) <= gram2_cap, "dconv: Gram accumulators need %zu bytes, workspace has %zu",
                    (size_t)rows * gslots * HP * HP * sizeof(double), gram2_cap);
-        MI_TRY(launch_gn_gelu_gram(hidden, g.B, h, hp, g.D1, g.D2, g.pitch(), g.row_mode, st1, l.gn1_w, l.gn1_b, gram2, gslots, st));
+        MI_TRY(launch_gn_gelu_gram(hidden, g.B, h, hp, g.D1, g.D2, g.pitch(), g.row_mode, st1, l.gn1_w, l.gn1_b, gram2, gslots, true, st));
         MI_TRY(launch_gram_finalize(gram2, rows, h, gslots, l.gram_wt, l.gram_ct, l.sum_b, l.sum_bsq, cnt_row, cnt_row * 2 * C, 1e-5f, st2, st));
         mi_conv_desc e = base_desc(l.conv1, l.ktab1, hidden, (int64_t)hp * P, g);
         e.plain = 1;

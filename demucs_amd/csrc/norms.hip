@@ -224,7 +224,8 @@ typedef float gram_f32x16 __attribute__((ext_vector_type(16)));
 template <int HP>
 __global__ __launch_bounds__(256) void gn_gelu_gram_kernel(float *__restrict__ x, int h, int Cs, int D1, int D2, int pitch, int row_mode,
                                                            const float2 *__restrict__ st, const float *__restrict__ w,
-                                                           const float *__restrict__ bvec, double *__restrict__ gram, int slots) {
+                                                           const float *__restrict__ bvec, double *__restrict__ gram, int slots,
+                                                           int zero_pad) {
     constexpr int CT = HP > 96 ? 64 : 128, CG = 256 / CT, LDG = CT + 1, NT = HP / 32;      // column tile: <= 48 KiB of LDS
     __shared__ float Gs[HP][LDG];
     const int tid = threadIdx.x, row = blockIdx.y, col = tid & (CT - 1), cg = tid / CT;
@@ -249,8 +250,11 @@ __global__ __launch_bounds__(256) void gn_gelu_gram_kernel(float *__restrict__ x
         if (c < h && ok) {
             g = gelu_exact((v[k] - s.x) * s.y * w[c] + bvec[c]);
             xp[(size_t)c * D1 * pitch] = g;
-        } else if (c == h && ok) {
-            g = 1.f;
+        } else if (ok) {
+            if (c == h) g = 1.f;
+            // zero_pad: channels h..Cs-1 are the K padding of the 1x1 conv that follows (zero weights); they must read as zero,
+            // and the engine's shared hidden buffer holds whatever another layer or batch item wrote there (0 * NaN = NaN)
+            if (zero_pad && c < Cs) xp[(size_t)c * D1 * pitch] = 0.f;
         }
         Gs[c][col] = g;
     }
@@ -315,15 +319,16 @@ __global__ __launch_bounds__(256) void gram_finalize_kernel(double *__restrict__
 int gram_hp(int h) { return (h + 1 + 31) / 32 * 32; }
 
 int launch_gn_gelu_gram(float *x, int B, int h, int Cs, int D1, int D2, int pitch, int row_mode, const float2 *stats, const float *w,
-                        const float *b, double *gram, int slots, hipStream_t st) {
+                        const float *b, double *gram, int slots, bool zero_pad, hipStream_t st) {
     const int HP = gram_hp(h), rows = row_mode ? B * D1 : B, cols = row_mode ? D2 : D1 * D2;
     MI_REQUIRE(HP <= 128, "gn_gelu_gram: %d hidden channels not instantiated", h);
+    MI_REQUIRE(!zero_pad || Cs <= HP, "gn_gelu_gram: %d allocated channels, the pass zeroes padding up to %d", Cs, HP);
     MI_REQUIRE(row_mode || D1 == 1 || pitch == D2, "gn_gelu_gram: a per-item row needs contiguous positions");
     const dim3 grid(ceil_div(cols, HP > 96 ? 64 : 128), rows);
-    if (HP == 32) hipLaunchKernelGGL(gn_gelu_gram_kernel<32>, grid, dim3(256), 0, st, x, h, Cs, D1, D2, pitch, row_mode, stats, w, b, gram, slots);
-    else if (HP == 64) hipLaunchKernelGGL(gn_gelu_gram_kernel<64>, grid, dim3(256), 0, st, x, h, Cs, D1, D2, pitch, row_mode, stats, w, b, gram, slots);
-    else if (HP == 96) hipLaunchKernelGGL(gn_gelu_gram_kernel<96>, grid, dim3(256), 0, st, x, h, Cs, D1, D2, pitch, row_mode, stats, w, b, gram, slots);
-    else hipLaunchKernelGGL(gn_gelu_gram_kernel<128>, grid, dim3(256), 0, st, x, h, Cs, D1, D2, pitch, row_mode, stats, w, b, gram, slots);
+    if (HP == 32) hipLaunchKernelGGL(gn_gelu_gram_kernel<32>, grid, dim3(256), 0, st, x, h, Cs, D1, D2, pitch, row_mode, stats, w, b, gram, slots, (int)zero_pad);
+    else if (HP == 64) hipLaunchKernelGGL(gn_gelu_gram_kernel<64>, grid, dim3(256), 0, st, x, h, Cs, D1, D2, pitch, row_mode, stats, w, b, gram, slots, (int)zero_pad);
+    else if (HP == 96) hipLaunchKernelGGL(gn_gelu_gram_kernel<96>, grid, dim3(256), 0, st, x, h, Cs, D1, D2, pitch, row_mode, stats, w, b, gram, slots, (int)zero_pad);
+    else hipLaunchKernelGGL(gn_gelu_gram_kernel<128>, grid, dim3(256), 0, st, x, h, Cs, D1, D2, pitch, row_mode, stats, w, b, gram, slots, (int)zero_pad);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }

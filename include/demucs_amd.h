@@ -72,7 +72,9 @@ void mi_model_destroy(void *handle);
 
 /* ---- `model(padded_mix)` under no_grad (demucs/apply.py:316-317 -> HTDemucs.forward,
  *      demucs/htdemucs.py:527-660).  mix_dev: (B, 2, segment_length); out_dev:
- *      (B, n_sources, 2, segment_length).  1 <= B <= max_batch. ---------------------------- */
+ *      (B, n_sources, 2, segment_length).  1 <= B <= max_batch.  Batch items are independent of each other and of
+ *      earlier forwards on the handle, non-finite input included: a NaN / Inf in item k makes item k's output NaN and leaves
+ *      every other item, and every later forward, bit for bit what it would have been (tests/test_gpu_isolation.py). ------ */
 int mi_model_forward(void *handle, const float *mix_dev, float *out_dev, int32_t B, void *stream);
 
 /* ---- `HTDemucs.forward_core(mag, mix)` (demucs/htdemucs.py:662-759; the fork's ONNX "core", docs/onnx.md):
@@ -92,6 +94,8 @@ int mi_model_forward_core(void *handle, const float *mix_dev, const float *mag_d
  *      max(32, ceil(T / 4) * 4) floats per row. ------------------------------------------- */
 int mi_hmodel_create(const mi_config *cfg, const mi_tensor_desc *weights, size_t n_weights, void **handle);
 void mi_hmodel_destroy(void *handle);
+/* mi_hmodel_forward: the same independence as mi_model_forward -- between the B items of a call, and between successive calls of
+ *   any B and length on one handle, non-finite input included. */
 int mi_hmodel_forward(void *handle, const float *mix_dev, float *out_dev, int32_t B, int32_t length, void *stream);
 int mi_hmodel_tap(void *handle, const char *name, float *dst_dev, int32_t B, int64_t *numel_per_item, void *stream);
 int64_t mi_hmodel_device_bytes(void *handle);
@@ -285,6 +289,12 @@ int mi_gn_gelu(float *x_dev, int32_t B, int32_t C, int32_t C_alloc, int32_t D1, 
 int32_t mi_gram_order(int32_t h);
 int mi_gn_gelu_gram(float *x_dev, int32_t B, int32_t h, int32_t C_alloc, int32_t D1, int32_t D2, int32_t pitch, int32_t row_mode,
                     const float *stats_dev, const float *w_dev, const float *b_dev, double *gram_dev, int32_t slots, void *stream);
+/* mi_dconv_gn_gelu_gram: the form the engine's DConv runs -- mi_gn_gelu_gram, and in the same pass channels h..C_alloc-1 of the valid
+ *   columns (the K padding of the 1x1 conv that follows) are set to zero, whatever they held: the engine shares one hidden buffer
+ *   between layers of different item strides, so another layer or batch item may have left NaN there.  h <= C_alloc <=
+ *   mi_gram_order(h). */
+int mi_dconv_gn_gelu_gram(float *x_dev, int32_t B, int32_t h, int32_t C_alloc, int32_t D1, int32_t D2, int32_t pitch, int32_t row_mode,
+                          const float *stats_dev, const float *w_dev, const float *b_dev, double *gram_dev, int32_t slots, void *stream);
 int mi_gram_finalize(double *gram_dev, int32_t rows, int32_t h, int32_t slots, const double *wt_dev, const double *ct_dev, double sum_b,
                      double sum_bsq, double cols, double count, float eps, float *stats_out_dev, void *stream);
 
@@ -292,7 +302,8 @@ int mi_gram_finalize(double *gram_dev, int32_t rows, int32_t h, int32_t slots, c
  *   i, f, g, o): gx_dev (N, 2 directions, 4H, W) = W_ih x_t + b_ih + b_hh for every step (a GEMM done before), whh_host = the HOST
  *   array (2, 4H, H) of weight_hh_l{k} / weight_hh_l{k}_reverse; out_dev (N, 2H, W): forward hidden states in channels [0, H), backward
  *   ones in [H, 2H).  H = 192 or 384 (hdemucs_mmi's layers 4 / 5).  mode 0: one launch per time step; mode 1: the persistent kernel
- *   the engine uses (hidden state exchanged between workgroups as tagged 8-byte granules, bounded waits).  Synchronous (test entry). */
+ *   the engine uses (hidden state exchanged between workgroups as self-validating 4-byte values whose least significant mantissa bit
+ *   carries a step tag, bounded waits).  Synchronous (test entry). */
 int mi_lstm_seq(const float *gx_dev, const float *whh_host, int32_t N, int32_t H, int32_t W, float *out_dev, int32_t mode, void *stream);
 
 /* LayerNorm over the channel axis of channel-first tokens x (B, C, T), optional additive table

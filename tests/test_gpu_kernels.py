@@ -757,6 +757,81 @@ def test_gn_gelu_gram_gives_second_groupnorm_statistics(lib, case):
     assert float(gram.abs().max()) == 0.0                                    # accumulators re-zeroed
 
 
+@pytest.mark.parametrize("case", ["freq_h24", "time_h12"])
+def test_dconv_hidden_k_padding_never_reaches_the_1x1(lib, case, x6):
+    """The DConv hidden tensor (csrc/model.hip run_dconv) has hp = round_up(h, 16) channels; channels h..hp-1 are the K padding of
+    the 1x1 GN-GLU conv (zero weights).  The engine shares that buffer between layers of different item strides, so the padding
+    holds what another layer -- of another batch item, or of an earlier forward -- wrote there.  With NaN there (and in the pitch
+    columns), the engine's in-place GroupNorm + GELU + Gram pass (mi_dconv_gn_gelu_gram: it zeroes the K padding) followed by the
+    1x1 must give, bit for bit, the output of zero padding, and match float64."""
+    B, C, h, D1, D2, pitch, row_mode, slots = {"freq_h24": (2, 192, 24, 3, 200, 208, 1, 1),
+                                               "time_h12": (2, 48, 12, 1, 997, 1000, 0, 8)}[case]
+    hp, C2, P = (h + 15) // 16 * 16, 2 * C, D1 * pitch
+    rows, cols = (B * D1, D2) if row_mode else (B, D1 * D2)
+    x = rnd(B, hp, D1, pitch, seed=80, scale=1.5).float()
+    res = rnd(B, C, D1, pitch, seed=81).float()
+    st1 = torch.stack([rnd(rows, seed=82, scale=0.2), rnd(rows, seed=83).abs() + 0.5], 1).float().contiguous()
+    w, bb = (rnd(h, seed=84) + 1.0).float(), rnd(h, seed=85, scale=0.3).float()
+    W, b1 = rnd(C2, h, seed=86, scale=0.4).float(), rnd(C2, seed=87, scale=0.3).float()
+    g2w, g2b, ls = (1 + 0.2 * rnd(C2, seed=88)).float(), (0.1 * rnd(C2, seed=89)).float(), (1 + 0.3 * rnd(C, seed=90)).float()
+    # float64 reference on the real channels and valid columns
+    srow = st1.double().view(B, D1, 2) if row_mode else st1.double().view(B, 1, 2).expand(B, D1, 2)
+    g = F.gelu((x[:, :h, :, :D2].double() - srow[:, None, :, 0:1]) * srow[:, None, :, 1:2] * w.double()[None, :, None, None]
+               + bb.double()[None, :, None, None])
+    z = torch.einsum("mh,bhdt->bmdt", W.double(), g) + b1.double()[None, :, None, None]
+    zr = z.permute(0, 2, 1, 3) if row_mode else z.reshape(B, 1, C2, D1 * D2)            # (B, rows per item, C2, cols)
+    zn = (zr - zr.mean((2, 3), keepdim=True)) / torch.sqrt(zr.var((2, 3), unbiased=False, keepdim=True) + 1e-5)
+    zn = (zn.permute(0, 2, 1, 3) if row_mode else zn.reshape(B, C2, D1, D2)) * g2w.double()[None, :, None, None] + g2b.double()[None, :, None, None]
+    want = res[..., :D2].double() + ls.double()[None, :, None, None] * F.glu(zn, dim=1)
+    # the accumulator weights and the zero-padded 1x1 weights as csrc/model.hip load_dconv builds them
+    HP = lib.mi_gram_order(h)
+    Wd = W.double()
+    A = Wd.t() @ Wd
+    wt = torch.zeros(HP, HP, dtype=torch.float64)
+    for i in range(h):
+        for k in range(h):
+            if k // 32 >= i // 32:
+                wt[i, k] = A[i, k] * (2.0 if k // 32 > i // 32 else 1.0)
+    wt[:h, h] = 2.0 * (Wd.t() @ b1.double())
+    ct = torch.zeros(HP, dtype=torch.float64)
+    ct[:h] = Wd.sum(0)
+    wtd, ctd, std, wd, bd = wt.cuda(), ct.cuda(), st1.cuda(), w.cuda(), bb.cuda()
+    W3p = torch.zeros(C2, hp)
+    W3p[:, :h] = W
+    wt3, bias3, M3, Mpad3, K3, Kpad3, tile3 = pack_w(W3p, b1, glu=True)
+    assert K3 == Kpad3 == hp
+    kt3 = ktab(hp, 1, 1, 1, 1, 0, 0, P, D2, Kpad3)
+    pitched = dict(o2_valid=D2, x_ld=pitch) if pitch != D2 else {}
+    outs = {}
+    for fill in (0.0, float("nan")):
+        xf = x.clone()
+        xf[:, h:] = fill
+        xf[..., D2:] = float("nan")                      # pitch columns: computed over but never stored
+        xd = xf.cuda()
+        gram = torch.zeros(rows * slots * HP * HP, dtype=torch.float64, device="cuda")
+        st2 = torch.empty(rows, 2, device="cuda")
+        _lib.check(lib.mi_dconv_gn_gelu_gram(xd.data_ptr(), B, h, hp, D1, D2, pitch, row_mode, std.data_ptr(), wd.data_ptr(),
+                                             bd.data_ptr(), gram.data_ptr(), slots, stream()), "mi_dconv_gn_gelu_gram")
+        torch.cuda.synchronize()
+        assert float(xd[:, h:, :, :D2].abs().max()) == 0.0, "K padding channels not zeroed"
+        assert torch.isnan(xd[..., D2:]).all(), "pitch columns written"
+        _lib.check(lib.mi_gram_finalize(gram.data_ptr(), rows, h, slots, wtd.data_ptr(), ctd.data_ptr(), float(b1.double().sum()),
+                                        float((b1.double() ** 2).sum()), float(cols), float(cols * C2), 1e-5, st2.data_ptr(), stream()),
+                   "mi_gram_finalize")
+        y = torch.zeros(B, C, D1, pitch, device="cuda")
+        conv_call(x6=x6, wt=wt3, M=M3, Mpad=Mpad3, K=K3, Kpad=Kpad3, ktab=kt3, x=xd, x_bstride=hp * P, B=B, D1=D1, D2=D2, O1=D1,
+                  O2=pitch, S1=1, S2=1, row_mode=row_mode, bias=bias3, tile_m=tile3, plain=1, epi=EPI_GN_GLU, gn_stats=st2,
+                  gn_w=pack_vec(g2w, Mpad3, glu=True), gn_b=pack_vec(g2b, Mpad3, glu=True), scale=ls.cuda(), res=res.cuda(), y=y,
+                  y_bstride=C * P, y_cstride=P, **pitched)
+        outs[fill == 0.0] = y[..., :D2].cpu()
+    bad = int(torch.isnan(outs[False]).sum())
+    assert bad == 0, f"{case}: {bad} NaN outputs from NaN in the hidden tensor's K padding / pitch columns"
+    assert torch.equal(outs[False], outs[True]), f"{case}: K padding contents change the 1x1 output"
+    err = maxerr(outs[True], want)
+    print(f"{case}: 1x1 GN-GLU after NaN K padding, max err vs float64 {err:.2e}")
+    assert err < chained_tol(3e-5)
+
+
 @pytest.mark.parametrize("mode", ["bf16", "f16"])
 def test_ffn_operand_image_round_trip(lib, mode):
     """Half modes, transformer FFN (transformer.py:339-343 linear1 -> GELU -> linear2): lin1's epilogue writes the hidden
