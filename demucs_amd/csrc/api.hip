@@ -343,6 +343,13 @@ int mi_attention(const float *q_dev, const float *k_dev, const float *v_dev, flo
                             (hipStream_t)stream);
 }
 
+int mi_attention_split(const float *q_dev, const float *k_dev, const float *v_dev, float *o_dev, int32_t B, int32_t heads, int32_t Tq,
+                       int32_t Tk, int64_t q_batch_stride, int64_t kv_batch_stride, int64_t o_batch_stride, void *stream) {
+    MI_REQUIRE(q_dev && k_dev && v_dev && o_dev && B > 0 && heads > 0 && Tq > 0 && Tk > 0, "mi_attention_split: bad argument");
+    return launch_attention_x6(q_dev, k_dev, v_dev, o_dev, B, heads, Tq, Tk, q_batch_stride, kv_batch_stride, o_batch_stride,
+                               (hipStream_t)stream);
+}
+
 int mi_attention_heads(const void *q_dev, const void *k_dev, const void *v_dev, float *o_dev, int32_t B, int32_t heads, int32_t Tq, int32_t Tk,
                        int32_t Tq_pitch, int32_t Tk_pitch, int32_t dtype, void *stream) {
     MI_REQUIRE(q_dev && k_dev && v_dev && o_dev && B > 0 && heads > 0 && Tq > 0 && Tk > 0, "mi_attention_heads: bad argument");

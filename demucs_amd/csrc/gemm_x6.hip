@@ -17,25 +17,12 @@
 //                round-to-nearest residuals) and writes three 16-byte words.
 // Epilogues are the shared ones of gemm_tile.h (the accumulator layout of all 32x32 MFMAs is the same).
 #include "gemm_tile.h"
+#include "split_bf16.h"
 
 namespace mi {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) const void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
-
-// (x0, x1) -> packed bf16 pairs of the three terms; x == hi + mid + lo exactly (each residual is representable)
-__device__ __forceinline__ void split3(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-    const bf16x2 hh = {(__bf16)x0, (__bf16)x1};
-    const float r0 = x0 - (float)hh[0], r1 = x1 - (float)hh[1];
-    const bf16x2 mm = {(__bf16)r0, (__bf16)r1};
-    const float q0 = r0 - (float)mm[0], q1 = r1 - (float)mm[1];
-    const bf16x2 ll = {(__bf16)q0, (__bf16)q1};
-    h = __builtin_bit_cast(unsigned, hh);
-    m = __builtin_bit_cast(unsigned, mm);
-    l = __builtin_bit_cast(unsigned, ll);
-}
 
 // Wt[Kpad][Mpad] fp32 -> Wx[mt][kt][part][k-half][BM rows][8] bf16
 __global__ void pack_split_kernel(const float *__restrict__ wt, int Kpad, int Mpad, int BM, __bf16 *__restrict__ wx) {

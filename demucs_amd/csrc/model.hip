@@ -134,20 +134,35 @@ int Model::conv(const mi_conv_desc &d, hipStream_t st) {
     return r;
 }
 
+// MI_X6: 0 no split-bf16 kernels (A/B runs), unset the default scope, non-zero every layer with a split main loop (pack_split)
+static int x6_scope() {
+    static const char *env = getenv("MI_X6");
+    static const int scope = env ? (atoi(env) != 0 ? 2 : 0) : 1;      // 0 none, 1 default, 2 all
+    return scope;
+}
+
+// The float32 engine's attention core runs on the split-bf16 kernel (attention_x6.hip) in the scope of the split linears:
+// unless MI_X6=0, and while the process-wide switch is on (read here, at every launch, as launch_conv does).
 int Model::attn(const float *q, const float *k, const float *v, float *o, int B, int Tq, int Tk, int64_t q_bs, int64_t kv_bs,
                 int64_t o_bs, hipStream_t st, bool image) {
     void *oh = image ? (void *)o : nullptr;               // the image takes the place (half the bytes) of the float32 tensor
     const int64_t oh_n = (int64_t)B * Tq;
-    if (!prof.on) return launch_attention(q, k, v, o, B, 8, Tq, Tk, q_bs, kv_bs, o_bs, cfg.dtype, st, oh, oh_n);
-    const int cls = 100;
-    // QK^T and PV: 2 * 2 * Tq * Tk * 64 flops per head; bytes = q, k, v read once + o written
+    const bool x6 = cfg.dtype == MI_DTYPE_F32 && !image && g_split_bf16 && x6_scope() != 0;
+    auto launch = [&]() {
+        return x6 ? launch_attention_x6(q, k, v, o, B, 8, Tq, Tk, q_bs, kv_bs, o_bs, st)
+                  : launch_attention(q, k, v, o, B, 8, Tq, Tk, q_bs, kv_bs, o_bs, cfg.dtype, st, oh, oh_n);
+    };
+    if (!prof.on) return launch();
+    const int cls = x6 ? 104 : 100;          // 101-103 are the DConv and LSTM rows
+    // QK^T and PV: 2 * 2 * Tq * Tk * 64 flops per head (fp32-equivalent on the split kernel); bytes = q, k, v read once + o written
     Profiler::Pending p{cls, prof.get(), prof.get(), 4.0 * B * 8 * (double)Tq * Tk * 64.0,
                         4.0 * B * 512.0 * (2.0 * Tq + 2.0 * Tk)};
     MI_HIP(hipEventRecord(p.a, st));
-    const int r = launch_attention(q, k, v, o, B, 8, Tq, Tk, q_bs, kv_bs, o_bs, cfg.dtype, st, oh, oh_n);
+    const int r = launch();
     MI_HIP(hipEventRecord(p.b, st));
     prof.pending.push_back(p);
-    snprintf(prof.rows[cls].name, sizeof(prof.rows[cls].name), "attention%s_kernel", cfg.dtype == MI_DTYPE_BF16 ? "_bf16" : cfg.dtype == MI_DTYPE_F16 ? "_f16" : "");
+    snprintf(prof.rows[cls].name, sizeof(prof.rows[cls].name), "attention%s_kernel",
+             x6 ? "_x6" : cfg.dtype == MI_DTYPE_BF16 ? "_bf16" : cfg.dtype == MI_DTYPE_F16 ? "_f16" : "");
     return r;
 }
 
@@ -179,8 +194,7 @@ int Model::attn_heads(const void *q, const void *k, const void *v, float *o, int
 // selects the native kernels at run time (mi_set_split_bf16(0): demucs_amd/distributed.py does it for ranks that share
 // a device); one process per GPU is the supported deployment.
 int Model::pack_split(PackedConv *pc) {
-    static const char *env = getenv("MI_X6");
-    static const int scope = env ? (atoi(env) != 0 ? 2 : 0) : 1;      // 0 none, 1 transformer linears (float32), 2 all
+    const int scope = x6_scope();                 // 0 none, 1 transformer linears (float32), 2 all
     const bool want = scope == 2 || (scope == 1 && split_linears && cfg.dtype == MI_DTYPE_F32);
     if (!want || !conv_x6_supported(pc->tile)) return MI_OK;
     MI_TRY(dev_alloc(&pc->wx, (size_t)6 * pc->Kpad * pc->Mpad));

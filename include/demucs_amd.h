@@ -133,8 +133,9 @@ int mi_set_two_streams(int32_t enabled);
  *   fused kernel.  Process-wide; returns the previous setting.  Initial value: 1 unless MI_ISTFT_SPLIT is set. */
 int mi_set_istft_fused(int32_t enabled);
 /* mi_set_split_bf16: the float32 engine runs its transformer linears (and, with MI_X6=1, every layer with a split image) on the
- *   split-bf16 main loop (gemm_x6.hip: fp32 operands as three exact bf16 terms, six bf16 MFMA products, fp32 accumulate).  0
- *   selects the native fp32 MFMA kernels for every later launch, e.g. in a process that shares its GPU with another rank
+ *   split-bf16 main loop (gemm_x6.hip: fp32 operands as three exact bf16 terms, six bf16 MFMA products, fp32 accumulate), and
+ *   its attention core on the split-bf16 attention kernel (mi_attention_split).  0 selects the native fp32 MFMA kernels, the
+ *   linears' and mi_attention's, for every later launch, e.g. in a process that shares its GPU with another rank
  *   (demucs_amd/distributed.py does this by itself).  Process-wide; returns the previous setting.  Initial value: 1. */
 int mi_set_split_bf16(int32_t enabled);
 /* mi_set_transpose_tiles: the kernels either side of the transforms (demucs/htdemucs.py:420-471, demucs/spec.py:11-47).  0, the
@@ -257,6 +258,15 @@ int mi_conv_pack_half(const float *wt_dev, int32_t Kpad, int32_t Mpad, int32_t d
 int mi_attention(const float *q_dev, const float *k_dev, const float *v_dev, float *o_dev, int32_t B, int32_t heads,
                  int32_t Tq, int32_t Tk, int64_t q_batch_stride, int64_t kv_batch_stride, int64_t o_batch_stride,
                  int32_t dtype, void *stream);
+
+/* mi_attention_split: the float32 attention core of mi_attention (same arguments and layout, no dtype; stands in for the
+ *   attention inside nn.MultiheadAttention, called at demucs/transformer.py:418-419,506) on the bf16 matrix pipe: Q / 8, K, V
+ *   and the softmax probabilities are each carried as three exact bf16 terms, both products as six bf16 MFMA products
+ *   accumulated in float32 (dropped terms <= 2^-24 |ab|); the softmax stays float32.  The float32 engine's default
+ *   attention kernel (see mi_set_split_bf16).  Tk % 4 == 0; k_dev / v_dev 16-byte aligned, kv_batch_stride % 4 == 0. */
+int mi_attention_split(const float *q_dev, const float *k_dev, const float *v_dev, float *o_dev, int32_t B, int32_t heads,
+                       int32_t Tq, int32_t Tk, int64_t q_batch_stride, int64_t kv_batch_stride, int64_t o_batch_stride,
+                       void *stream);
 
 /* mi_attention_heads: the attention core of the half modes on the operands the projections really write in those modes:
  *   q / k / v_dev are 16-bit (bf16 / fp16 by `dtype`) per-head token-major tensors [B][heads][T pitch][64] (what the
