@@ -17,13 +17,13 @@ from __future__ import annotations
 
 import ctypes as C
 from pathlib import Path
-from typing import Callable, Dict, Optional, Tuple, Union
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _lib
 from .audio import convert_audio
-from .apply import BagOfModels, _is_engine, _to_host, apply_model
+from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
 
 __all__ = ["Separator", "LoadModelError", "list_models"]
 
@@ -36,6 +36,19 @@ def _with(d: Optional[dict], **subs) -> dict:
     out = dict(d) if d is not None else {}
     out.update(subs)
     return out
+
+
+def _shared_device_storage(wavs) -> bool:
+    """True when two GPU tensors of `wavs` are backed by the same storage."""
+    seen = set()
+    for w in wavs:
+        if w.device.type != "cuda":
+            continue
+        key = (w.device, w.untyped_storage().data_ptr())
+        if key in seen:
+            return True
+        seen.add(key)
+    return False
 
 
 class Separator:
@@ -95,43 +108,83 @@ class Separator:
         wav += ref.mean()
         return wav, dict(zip(self._model.sources, out[0]))
 
-    def _separate_on_device(self, wav: torch.Tensor, sr: Optional[int]):
-        """The engine's `separate_tensor` (module docstring): everything between the one H2D and the one D2H runs on the GPU."""
+    def separate_tensors(self, wavs: Sequence[torch.Tensor], sr: Optional[int] = None
+                         ) -> List[Tuple[torch.Tensor, Dict[str, torch.Tensor]]]:
+        """`separate_tensor` for many tracks of possibly different lengths: the result equals
+        `[self.separate_tensor(w, sr) for w in wavs]`, bit for bit.  Each track gets its own mono statistics and
+        normalisation; on the engine the segments of all tracks share batched forwards (`apply_model_many`).  With a
+        `callback` or `progress` (whose events follow the reference's per-track order), `split=False`, multi-GPU sharding,
+        a model that is not an engine or a non-GPU device, the tracks run one after another.  So do device tracks that share
+        storage (`[w, w]`, views of one buffer): a device track is normalised in place, and the packed route normalises every
+        track before the first forward, where the loop restores each before the next is read."""
+        from . import distributed
+        wavs = list(wavs)
+        if (not wavs or self._callback is not None or self._progress or not self._split or distributed.sharding_active()
+                or not _is_engine(self._model) or torch.device(self._device).type != "cuda"
+                or any(w.device != wavs[0].device for w in wavs) or _shared_device_storage(wavs)):
+            return [self.separate_tensor(w, sr) for w in wavs]
+        device = self._device_index()
+        with torch.cuda.device(device):
+            states = [self._normalise_on_device(w, sr, device) for w in wavs]
+            outs = apply_model_many(self._model, [st[0] for st in states], segment=self._segment, shifts=self._shifts,
+                                    split=self._split, overlap=self._overlap, device=device)
+            return [self._restore_on_device(st, out[None], device) for st, out in zip(states, outs)]
+
+    def _device_index(self) -> torch.device:
         device = torch.device(self._device)
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        lib = _lib.load()
-        host_in = wav.device.type == "cpu"
+        return device
+
+    def _separate_on_device(self, wav: torch.Tensor, sr: Optional[int]):
+        """The engine's `separate_tensor` (module docstring): everything between the one H2D and the one D2H runs on the GPU."""
+        device = self._device_index()
         with torch.cuda.device(device):
-            stream = lambda: C.c_void_p(_lib.current_stream_ptr())          # noqa: E731
-            dev = wav.to(device=device, dtype=torch.float32, non_blocking=True) if host_in else wav
-            if sr is not None and sr != self._samplerate:
-                dev = convert_audio(dev, sr, self._samplerate, self._audio_channels, device=device)
-                if host_in:
-                    wav = None                    # the reference returns the converted tensor: handed back from the device below
-            if not dev.is_contiguous() or dev.dtype != torch.float32:
-                dev = dev.contiguous().float()
-            channels, length = dev.shape
-            scratch = torch.empty(lib.mi_mono_stats_scratch_bytes(), dtype=torch.uint8, device=device)
-            stats = torch.empty(2, dtype=torch.float32, device=device)
-            _lib.check(lib.mi_mono_stats(dev.data_ptr(), channels, length, scratch.data_ptr(), stats.data_ptr(), stream()),
-                       "mi_mono_stats")
-            restore = dev.clone() if (host_in and wav is None) else None       # resampled host input: returned un-normalised
-            _lib.check(lib.mi_track_affine(dev.data_ptr(), dev.numel(), stats.data_ptr(), 0, stream()), "mi_track_affine")
+            st = self._normalise_on_device(wav, sr, device)
+            dev, length = st[0], st[0].shape[1]
             out = apply_model(self._model, dev[None], segment=self._segment, shifts=self._shifts, split=self._split,
                               overlap=self._overlap, device=device, num_workers=self._jobs, callback=self._callback,
                               callback_arg=_with(self._callback_arg, audio_length=length), progress=self._progress)
             if out is None:
                 raise KeyboardInterrupt
-            out = out.contiguous()
-            _lib.check(lib.mi_track_affine(out.data_ptr(), out.numel(), stats.data_ptr(), 1, stream()), "mi_track_affine")
+            return self._restore_on_device(st, out, device)
+
+    def _normalise_on_device(self, wav: torch.Tensor, sr: Optional[int], device: torch.device):
+        """One H2D of a host `wav`, the resampler when `sr` differs, then `(x - mean) / (std + 1e-8)` on the device copy.
+        Returns (normalised track, stats, wav as handed back, restore copy or None, host_in)."""
+        lib = _lib.load()
+        host_in = wav.device.type == "cpu"
+        stream = lambda: C.c_void_p(_lib.current_stream_ptr())          # noqa: E731
+        dev = wav.to(device=device, dtype=torch.float32, non_blocking=True) if host_in else wav
+        if sr is not None and sr != self._samplerate:
+            dev = convert_audio(dev, sr, self._samplerate, self._audio_channels, device=device)
             if host_in:
-                stems = _to_host(out, device)
-                if wav is None:
-                    wav = _to_host(restore, device)
-            else:
-                _lib.check(lib.mi_track_affine(dev.data_ptr(), dev.numel(), stats.data_ptr(), 1, stream()), "mi_track_affine")
-                stems, wav = out, dev
+                wav = None                    # the reference returns the converted tensor: handed back from the device below
+        if not dev.is_contiguous() or dev.dtype != torch.float32:
+            dev = dev.contiguous().float()
+        channels, length = dev.shape
+        scratch = torch.empty(lib.mi_mono_stats_scratch_bytes(), dtype=torch.uint8, device=device)
+        stats = torch.empty(2, dtype=torch.float32, device=device)
+        _lib.check(lib.mi_mono_stats(dev.data_ptr(), channels, length, scratch.data_ptr(), stats.data_ptr(), stream()),
+                   "mi_mono_stats")
+        restore = dev.clone() if (host_in and wav is None) else None       # resampled host input: returned un-normalised
+        _lib.check(lib.mi_track_affine(dev.data_ptr(), dev.numel(), stats.data_ptr(), 0, stream()), "mi_track_affine")
+        return dev, stats, wav, restore, host_in
+
+    def _restore_on_device(self, st, out: torch.Tensor, device: torch.device):
+        """`x * std + mean` on the (1, S, channels, length) stems (and on a device `wav`), ONE D2H for a host input."""
+        lib = _lib.load()
+        dev, stats, wav, restore, host_in = st
+        stream = lambda: C.c_void_p(_lib.current_stream_ptr())          # noqa: E731
+        out = out.contiguous()
+        _lib.check(lib.mi_track_affine(out.data_ptr(), out.numel(), stats.data_ptr(), 1, stream()), "mi_track_affine")
+        if host_in:
+            stems = _to_host(out, device)
+            if wav is None:
+                wav = _to_host(restore, device)
+        else:
+            _lib.check(lib.mi_track_affine(dev.data_ptr(), dev.numel(), stats.data_ptr(), 1, stream()), "mi_track_affine")
+            stems, wav = out, dev
         return wav, dict(zip(self._model.sources, stems[0]))
 
     @property

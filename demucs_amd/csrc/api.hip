@@ -243,6 +243,34 @@ int mi_ola_finish(float *acc_dev, int64_t acc_len, int32_t rows, int64_t acc_off
                              (hipStream_t)stream);
 }
 
+int mi_segments_gather_packed(const float *tracks_dev, int64_t tracks_capacity, int32_t channels, const int64_t *items_dev, int32_t B,
+                              int32_t valid, float *seg_dev, int64_t seg_capacity, void *stream) {
+    MI_REQUIRE(tracks_dev && items_dev && seg_dev && B > 0 && B <= 65535 && valid > 0 && channels > 0 && channels <= 65535 &&
+               tracks_capacity > 0, "mi_segments_gather_packed: bad argument");
+    MI_REQUIRE((int64_t)B * channels * valid <= seg_capacity, "mi_segments_gather_packed: %d x %d x %d floats do not fit seg_dev (%lld)",
+               B, channels, valid, (long long)seg_capacity);
+    return launch_segments_gather_packed(tracks_dev, tracks_capacity, channels, items_dev, B, valid, seg_dev, (hipStream_t)stream);
+}
+
+int mi_ola_accumulate_packed(float *acc_dev, int64_t acc_capacity, int32_t rows, const float *model_out_dev, int32_t valid,
+                             int64_t out_capacity, const int64_t *items_dev, int32_t B, const int64_t *tiles_dev, int32_t n_tiles,
+                             const float *weights_dev, int64_t weights_capacity, void *stream) {
+    MI_REQUIRE(acc_dev && model_out_dev && items_dev && tiles_dev && weights_dev && B > 0 && rows > 0 && rows <= 65535 && valid > 0 &&
+               n_tiles > 0 && acc_capacity > 0 && weights_capacity > 0, "mi_ola_accumulate_packed: bad argument");
+    MI_REQUIRE((int64_t)B * rows * valid <= out_capacity, "mi_ola_accumulate_packed: %d x %d x %d floats exceed model_out_dev (%lld)", B,
+               rows, valid, (long long)out_capacity);
+    return launch_ola_accumulate_packed(acc_dev, acc_capacity, rows, model_out_dev, valid, items_dev, B, tiles_dev, n_tiles, weights_dev,
+                                        weights_capacity, (hipStream_t)stream);
+}
+
+int mi_ola_finish_packed(float *acc_dev, int64_t acc_capacity, int32_t rows, const int64_t *tiles_dev, int32_t n_tiles,
+                         const int64_t *segs_dev, int32_t n_segs, const float *weights_dev, int64_t weights_capacity, void *stream) {
+    MI_REQUIRE(acc_dev && tiles_dev && segs_dev && weights_dev && rows > 0 && rows <= 65535 && n_tiles > 0 && n_segs > 0 &&
+               acc_capacity > 0 && weights_capacity > 0, "mi_ola_finish_packed: bad argument");
+    return launch_ola_finish_packed(acc_dev, acc_capacity, rows, tiles_dev, n_tiles, segs_dev, n_segs, weights_dev, weights_capacity,
+                                    (hipStream_t)stream);
+}
+
 int32_t mi_mono_stats_scratch_bytes(void) { return post_stats_scratch_bytes(); }
 
 int mi_mono_stats(const float *wav_dev, int32_t channels, int64_t length, void *scratch_dev, float *stats_dev, void *stream) {

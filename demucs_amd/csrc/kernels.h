@@ -142,6 +142,14 @@ int launch_ola_accumulate(float *acc, int64_t acc_len, int rows, const float *mo
 int launch_ola_finish(float *acc, int64_t acc_len, int rows, int64_t acc_off0, const int64_t *offs_dev, const int32_t *lens_dev,
                       int n_segments, int max_len, const float *weight, hipStream_t st);
 
+int launch_segments_gather_packed(const float *tracks, int64_t tracks_cap, int channels, const int64_t *items_dev, int B, int valid,
+                                  float *seg, hipStream_t st);
+int launch_ola_accumulate_packed(float *acc, int64_t acc_cap, int rows, const float *model_out, int valid, const int64_t *items_dev,
+                                 int B, const int64_t *tiles_dev, int n_tiles, const float *weights, int64_t weights_cap,
+                                 hipStream_t st);
+int launch_ola_finish_packed(float *acc, int64_t acc_cap, int rows, const int64_t *tiles_dev, int n_tiles, const int64_t *segs_dev,
+                             int n_segs, const float *weights, int64_t weights_cap, hipStream_t st);
+
 // resample.hip
 int launch_resample_frac(const float *x, int rows, int64_t L, const float *table, int old_sr, int new_sr, int width, float *y,
                          int64_t Lout, hipStream_t st);

@@ -185,6 +185,52 @@ int mi_ola_accumulate(float *acc_dev, int64_t acc_len, int32_t rows, const float
 int mi_ola_finish(float *acc_dev, int64_t acc_len, int32_t rows, int64_t acc_off0, const int64_t *offs_idx_dev,
                   const int32_t *lens_idx_dev, int32_t n_segments, int32_t max_len, const float *weight_dev, void *stream);
 
+/* ---- packed scheduler pieces: many tracks / accumulators per launch (demucs_amd/packed.py) -------------------------------
+ * The one-track entries above are the single-track case of the same kernels.  All tables are int64 DEVICE arrays.
+ *
+ * Item table (B rows of MI_PACK_ITEM_COLS): item b is a segment of the track stored (channels, src_len) at float offset src_off
+ *   of the packed track buffer; its window starts at track sample `start` (zero fill outside [0, src_len)); its output is
+ *   overlap-added into the accumulator (rows, acc_len) at float offset acc_base of the accumulator buffer, at position `off`,
+ *   `len` samples from output sample `trim` on (mi_ola_accumulate's offs / lens / trim).
+ * Tile table (MI_PACK_TILE_COLS per tile): the accumulator (acc_base, acc_len), its positions [pos, pos + MI_PACK_TILE_SPAN),
+ *   the item range [lo, hi) -- or, for the finish, the segment range of `segs` -- that may touch them (at most 256 items per
+ *   accumulate tile), and the weight ramp of w_len floats at float offset w_off of the weight buffer.  Within a tile items are
+ *   summed in ascending index order; only items whose (acc_base, acc_len) equal the tile's count.
+ * Every device-side read or write is clamped to the declared capacities (floats) of the track buffer, the model output, the
+ *   accumulator buffer and the weight buffer: a wrong table changes results, never memory outside them. */
+#define MI_PACK_SRC_OFF 0
+#define MI_PACK_SRC_LEN 1
+#define MI_PACK_START 2
+#define MI_PACK_ACC_BASE 3
+#define MI_PACK_ACC_LEN 4
+#define MI_PACK_OFF 5
+#define MI_PACK_LEN 6
+#define MI_PACK_TRIM 7
+#define MI_PACK_ITEM_COLS 8
+#define MI_PACK_T_ACC_BASE 0
+#define MI_PACK_T_ACC_LEN 1
+#define MI_PACK_T_POS 2
+#define MI_PACK_T_LO 3
+#define MI_PACK_T_HI 4
+#define MI_PACK_T_W_OFF 5
+#define MI_PACK_T_W_LEN 6
+#define MI_PACK_TILE_COLS 7
+#define MI_PACK_TILE_SPAN 1024
+
+/* mi_segments_gather_packed: seg_dev (B, channels, valid) from the item table's (src_off, src_len, start) columns. */
+int mi_segments_gather_packed(const float *tracks_dev, int64_t tracks_capacity, int32_t channels, const int64_t *items_dev,
+                              int32_t B, int32_t valid, float *seg_dev, int64_t seg_capacity, void *stream);
+
+/* mi_ola_accumulate_packed: mi_ola_accumulate for the B items of model_out_dev (B, rows, valid), over n_tiles tiles. */
+int mi_ola_accumulate_packed(float *acc_dev, int64_t acc_capacity, int32_t rows, const float *model_out_dev, int32_t valid,
+                             int64_t out_capacity, const int64_t *items_dev, int32_t B, const int64_t *tiles_dev, int32_t n_tiles,
+                             const float *weights_dev, int64_t weights_capacity, void *stream);
+
+/* mi_ola_finish_packed: mi_ola_finish for every accumulator of a run in one launch.  segs_dev holds n_segs (offset, length)
+ *   pairs in accumulator positions, each accumulator's run sorted by offset; a tile's [lo, hi) is its accumulator's run. */
+int mi_ola_finish_packed(float *acc_dev, int64_t acc_capacity, int32_t rows, const int64_t *tiles_dev, int32_t n_tiles,
+                         const int64_t *segs_dev, int32_t n_segs, const float *weights_dev, int64_t weights_capacity, void *stream);
+
 /* mi_resample_frac: `julius.resample_frac` as called by `demucs.audio.convert_audio` (demucs/audio.py:169-172), the step
  *   `Separator.separate_tensor` runs first when the input sample rate differs from the model's (demucs/api.py:265-266).
  *   old_sr / new_sr already divided by their gcd; table_dev (new_sr, 2*width + old_sr) is julius' windowed-sinc kernel bank
