@@ -384,8 +384,10 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_dmatap_kernel(const mi_conv_
     conv_epilogue<TM, TN, EPI, 0>(d, acc, m0, n0, wm, wn, N, P, o2v);
 }
 
-// float32, stride-1 k x k conv with K2 = 3 whose geometry the descriptor states (ntaps, tap_k2, tap_pad*): the DMA loop above
-static bool dmatap_eligible(const mi_conv_desc &d, int tile) {
+// float32, stride-1 k x k conv with K2 = 3 whose geometry the descriptor states (ntaps, tap_k2, tap_pad*): the DMA loop above,
+// or, for a layer with a split weight image (`split`), the same shifted-run loader in front of the split-bf16 main loop (gemm_x6.hip
+// conv_tap_x6_kernel; GLU only)
+static bool dmatap_eligible(const mi_conv_desc &d, int tile, bool split = false) {
     static const bool off = getenv("MI_NO_DMA_TAP") != nullptr;
     const int ld = d.x_ld ? d.x_ld : d.D2;
     static const bool off_dconv = getenv("MI_NO_DMA_DCONV") != nullptr;      // A/B switch for the BIAS_STATS kind alone
@@ -394,7 +396,7 @@ static bool dmatap_eligible(const mi_conv_desc &d, int tile) {
     // GLU: the decoders' 3 x 3 / k = 3 rewrite convs (96- / 128-row tiles); BIAS_STATS: the DConv blocks' dilated k = 3 convs (32- / 64-row)
     const bool kind = (d.epi == MI_EPI_GLU && (tile == 96 || tile == 128) && (d.ntaps == 9 || d.ntaps == 3) && dil == 1) ||
                       (d.epi == MI_EPI_BIAS_STATS && (tile == 32 || tile == 64) && d.ntaps == 3 && (dil == 1 || dil == 2) && d.flags == 0);
-    return !off && !d.half && !d.wx && kind && d.tap_k2 == 3 && d.Mpad % tile == 0 &&
+    return !off && !d.half && (split ? d.wx && d.epi == MI_EPI_GLU : !d.wx) && kind && d.tap_k2 == 3 && d.Mpad % tile == 0 &&
            d.K % d.ntaps == 0 && d.S1 == 1 && d.S2 == 1 && d.O1 == d.D1 && d.O2 == ld && ld % 4 == 0 && d.tap_pad2 == dil &&
            d.tap_pad1 == (d.ntaps / 3 - 1) / 2 && !(d.flags & (MI_FLAG_IMG | MI_FLAG_IMG4)) && d.x_bstride == (int64_t)(d.K / d.ntaps) * d.D1 * ld;
 }
@@ -699,9 +701,10 @@ static void x6_verify_dump() {
 
 static int launch_conv_fp32_only(const mi_conv_desc &d, hipStream_t st);
 
-static int x6_verified_launch(const mi_conv_desc &d, int tile, bool plain, hipStream_t st) {
+static int x6_verified_launch(const mi_conv_desc &d, int tile, bool plain, hipStream_t st, bool tap = false) {
+    auto launch_x6 = [&]() { return tap ? launch_conv_tap_x6(d, tile, st) : launch_conv_x6(d, tile, plain, st); };
     const bool checkable = d.epi != MI_EPI_STATS_ONLY && d.epi != MI_EPI_BIAS_STATS && d.res != d.y && (int)g_vinfo.size() < kVerifyMax;
-    if (!checkable) return launch_conv_x6(d, tile, plain, st);
+    if (!checkable) return launch_x6();
     if (!g_vlog) {
         MI_HIP(hipMalloc((void **)&g_vlog, kVerifyMax * sizeof(X6VerifyRec)));
         std::vector<X6VerifyRec> init(kVerifyMax, X6VerifyRec{0, 0, 1 << 30, -1, 1 << 30, -1, 1 << 30, -1});
@@ -716,7 +719,7 @@ static int x6_verified_launch(const mi_conv_desc &d, int tile, bool plain, hipSt
         g_vscratch_elems = elems;
     }
     MI_HIP(hipMemcpyAsync(g_vscratch, d.y, elems * sizeof(float), hipMemcpyDeviceToDevice, st));     // unwritten positions compare equal
-    MI_TRY(launch_conv_x6(d, tile, plain, st));
+    MI_TRY(launch_x6());
     mi_conv_desc e = d;
     e.wx = nullptr; e.y = g_vscratch;
     MI_TRY(launch_conv_fp32_only(e, st));
@@ -775,6 +778,14 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
                "conv: MI_FLAG_HEADS needs a half-precision LINEAR layer on tokens (O1 = 1) with M %% 512 == 0 and an aligned output");
     MI_REQUIRE(!d.xh || d.half, "conv: an operand-image input needs a half-precision layer");
     if (d.half) { g_last_conv_route = 5; return launch_conv_half(d, tile, plain, st); }
+    static const int x6_mode = getenv("MI_X6_MODE") ? atoi(getenv("MI_X6_MODE")) : 0;   // bisecting: 1 plain only, 2 gather only
+    static const int x6_class = getenv("MI_X6_CLASS") ? atoi(getenv("MI_X6_CLASS")) : -1;   // bisecting: one kernel class only
+    const bool x6_class_ok = x6_class < 0 || x6_class == d.epi * 8 + (tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3) * 2 + (plain ? 1 : 0);
+    // the decoders' 3 x 3 / k = 3 rewrite convs with a split image: shifted-run DMA taps in front of the split-bf16 main loop (its
+    // own small-batch tile: launch_conv_tap_x6)
+    static const bool x6_verify = getenv("MI_X6_VERIFY") != nullptr;
+    if (!plain && x6_mode == 0 && x6_class_ok && dmatap_eligible(d, tile, true))
+        return x6_verify ? x6_verified_launch(d, tile, false, st, true) : launch_conv_tap_x6(d, tile, st);
     // small batches: a k x k GLU conv whose 128-row tiles under-fill the chip (B = 1: 6 x 21 workgroups) takes 96-row tiles
     static const int small_tile = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
     int ktile = tile;
@@ -791,11 +802,8 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
             case MI_EPI_GN_GLU: return launch_dmarow<MI_EPI_GN_GLU, 0>(d, tile, st);
         }
     }
-    static const int x6_mode = getenv("MI_X6_MODE") ? atoi(getenv("MI_X6_MODE")) : 0;   // bisecting: 1 plain only, 2 gather only
-    static const int x6_class = getenv("MI_X6_CLASS") ? atoi(getenv("MI_X6_CLASS")) : -1;   // bisecting: one kernel class only
-    if (x6_class >= 0 && x6_class != d.epi * 8 + (tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3) * 2 + (plain ? 1 : 0)) d.wx = nullptr;
+    if (!x6_class_ok) d.wx = nullptr;
     if (d.wx && conv_x6_supported(tile) && x6_mode == 3) return launch_conv_x6(d, tile, false, st);      // 3: table loader for all
-    static const bool x6_verify = getenv("MI_X6_VERIFY") != nullptr;
     if (d.wx && conv_x6_supported(tile) && (x6_mode == 0 || (x6_mode == 1) == plain))
         return x6_verify ? x6_verified_launch(d, tile, plain, st) : launch_conv_x6(d, tile, plain, st);
 #define MI_DISPATCH(E)                                              \

@@ -12,9 +12,10 @@
 // fragment (lane l: row l&31, k = 8*(l>>5) .. +7) is ONE conflict-free ds_read_b128 per part.
 //   A (weights): split once at load time into exactly this image per (M tile, K step) (pack_split_kernel),
 //                so the loader is pure LDS-DMA (global_load_lds_dwordx4, no registers, no ds_write).
-//   B (activations): thread (column n = tid & 127, k-half = tid >> 7) loads its 8 k values (coalesced dwords,
-//                through the same gather table as the fp32 kernel), splits them in registers (v_cvt_pk_bf16_f32,
-//                round-to-nearest residuals) and writes three 16-byte words.
+//   B (activations): thread (column n = tid & 127, k-half = tid >> 7) takes its 8 k values, splits them in registers
+//                (v_cvt_pk_bf16_f32, round-to-nearest residuals) and writes three 16-byte words.  The values come from
+//                the raw fp32 tile that LDS-DMA lands two K steps ahead (plain layers: channel runs; the decoders' 3 x 3 /
+//                k = 3 convs, conv_tap_x6_kernel: tap-shifted runs), or else through the gather table of the fp32 kernel.
 // Epilogues are the shared ones of gemm_tile.h (the accumulator layout of all 32x32 MFMAs is the same).
 #include "gemm_tile.h"
 #include "split_bf16.h"
@@ -59,10 +60,22 @@ int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx,
                                 16 = 32 idle cycles after every MFMA, 32 = 64 idle cycles after every 4 MFMAs */
 #endif
 // HALF_IMG: a 64-row tile that reads its rows out of the 128-row weight image (the small-batch tile of the plain linear
-// layers, launch_conv_x6): the same fragments, products and k order as the 128-row tile, so both give bit-identical results.
-template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false>
-__global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc d, const int N, const int MT, const int Gm) {
+// layers and of the tap convs, launch_cfg_x6): the same fragments, products and k order as the 128-row tile, so both give
+// bit-identical results.
+// NT (taps, 9 or 3; 0 = none): the B loader of the float32 decoders' stride-1 3 x 3 / k = 3 rewrite convs (conv_tap_x6_kernel).
+// Row k = ci * NT + tap of the raw [16][128] activation tile is, for 128 consecutive output positions, a run of input row ci
+// shifted by the tap's offset (t1 - pad1) * pitch + (t2 - pad2): it goes global -> LDS by DMA into the same braw ring as a plain
+// layer's tile (a 4-byte-aligned source is enough, tools/micro/dma_unaligned.hip), two K steps ahead, and is split from LDS
+// by the same code.  A tap whose input ROW lies outside [0, D1), the K padding and columns past the valid width read the zero
+// page.  What the shift drags in at the two ends of an input row (the neighbouring row's sample or a pitch-padding column) is
+// OVERWRITTEN with the conv's zero padding by the lane that issued the transfer, after its wait and before the barrier that
+// ends the K step (at most two ds_write_b32 per lane and K step, as in gemm_conv.hip conv_gemm_dmatap_kernel): a zero weight
+// would not do, NaN * 0 is NaN.  The k order is the packed weights' one, so the split image is pack_split's as for any layer.
+template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG, int NT>
+__device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N, const int MT, const int Gm) {
     constexpr int BM = WM * TM * 32;
+    constexpr bool RAW = PLAIN || NT > 0;                    // the activation tile goes through the braw ring
+    static_assert(NT == 0 || (!PLAIN && EPI == MI_EPI_GLU), "tap loader: GLU rewrite convs");
     static_assert(WN * TN * 32 == BN, "block N tile is 128");
     static_assert(WM * WN == 4, "4 waves");
     constexpr int A_BYTES = BM * 96, B_BYTES = BN * 96, STAGE = A_BYTES + B_BYTES;
@@ -74,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
     // plain layers: the fp32 activation tile [16][128] lands here by LDS-DMA two K steps ahead and is split from LDS
     // (a VMEM wave-instruction costs ~12-16 cycles whatever its width: 2 x 1 KiB DMA per wave replace 8 dword loads)
-    __shared__ __attribute__((aligned(16))) float braw[PLAIN ? 2 * BK * BN : 4];
+    __shared__ __attribute__((aligned(16))) float braw[RAW ? 2 * BK * BN : 4];
 
     {   // keeps the MFMA accumulators in AGPRs (see the note above the kernel); the Makefile builds this file with
         // -amdgpu-mfma-vgpr-form=0
@@ -115,15 +128,45 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
     float breg[8];
     // plain DMA loader: this lane's 16 bytes of rows 4*wave + 2*i + (lane >> 5), i = 0, 1
     const int rc4 = (lane & 31) * 4, rrow = 4 * wave + (lane >> 5);
-    const ColInfo rcol = decompose(n0 + rc4, N, P, d.O2, d.O2);
-    const float *rsrc = rcol.valid ? d.x + (size_t)rcol.b * d.x_bstride + rcol.p + (size_t)rrow * P : d.sink + 256;
+    const ColInfo rcol = decompose(n0 + rc4, N, P, d.O2, NT ? o2v : d.O2);
+    const float *rsrc = rcol.valid ? d.x + (size_t)rcol.b * d.x_bstride + rcol.p + (NT ? 0 : (size_t)rrow * P) : d.sink + 256;
     const size_t r_row2 = rcol.valid ? (size_t)2 * P : 0, r_step = rcol.valid ? (size_t)BK * P : 0;
+    // taps: this lane's column chunk rcol.o2 .. + 3 (one input row, the pitch is a multiple of 4); the element that a tap with
+    // d2 = -1 / +1 reads from outside the row [0, D2), or -1
+    constexpr int K2 = 3;
+    const int x_ld = d.x_ld ? d.x_ld : d.D2;
+    const int fix_l = (NT && rcol.valid && rcol.o2 == 0) ? 0 : -1;
+    const int fr = d.D2 - 1 - rcol.o2;
+    const int fix_r = (NT && rcol.valid && fr >= 0 && fr < 4) ? fr : -1;
 #define MI_BRAW_DMA(kt, rs)                                                                                         \
     do {                                                                                                            \
         float *dst = braw + (rs) * (BK * BN) + (4 * wave) * BN;                                                     \
-        const float *g = rsrc + (size_t)(kt) * r_step;                                                              \
-        __builtin_amdgcn_global_load_lds((gvoid_t *)g, (lvoid_t *)dst, 16, 0, 0);                                   \
-        __builtin_amdgcn_global_load_lds((gvoid_t *)(g + r_row2), (lvoid_t *)(dst + 2 * BN), 16, 0, 0);             \
+        if constexpr (NT > 0) {                                                                                     \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
+                const int k = (kt) * BK + rrow + 2 * i, ci = k / NT, tap = k - ci * NT, t1 = tap / K2, t2 = tap - t1 * K2; \
+                const int i1 = rcol.o1 + t1 - d.tap_pad1;                                                           \
+                const bool ok = rcol.valid && k < d.K && (unsigned)i1 < (unsigned)d.D1;                             \
+                const float *g = rsrc + (int64_t)ci * P + (int64_t)(t1 - d.tap_pad1) * x_ld + (t2 - d.tap_pad2);    \
+                __builtin_amdgcn_global_load_lds((gvoid_t *)(ok ? g : d.sink + 256), (lvoid_t *)(dst + 2 * i * BN), 16, 0, 0); \
+            }                                                                                                       \
+        } else {                                                                                                    \
+            const float *g = rsrc + (size_t)(kt) * r_step;                                                          \
+            __builtin_amdgcn_global_load_lds((gvoid_t *)g, (lvoid_t *)dst, 16, 0, 0);                               \
+            __builtin_amdgcn_global_load_lds((gvoid_t *)(g + r_row2), (lvoid_t *)(dst + 2 * BN), 16, 0, 0);         \
+        }                                                                                                           \
+    } while (0)
+// taps: the conv's zero padding over what this lane's transfers of tile kt dragged in from outside the input row (after this
+// wave's wait for them, before the barrier)
+#define MI_BRAW_FIX(kt, rs)                                                                                         \
+    do {                                                                                                            \
+        if constexpr (NT > 0) {                                                                                     \
+            float *row = braw + (rs) * (BK * BN) + rrow * BN + rc4;                                                 \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
+                const int k = (kt) * BK + rrow + 2 * i, dd2 = (k % NT) % K2 - d.tap_pad2;                           \
+                if (dd2 < 0 && fix_l >= 0) row[2 * i * BN + fix_l] = 0.f;                                           \
+                if (dd2 > 0 && fix_r >= 0) row[2 * i * BN + fix_r] = 0.f;                                           \
+            }                                                                                                       \
+        }                                                                                                           \
     } while (0)
 #define MI_BRAW_READ(rs)                                                                                            \
     do {                                                                                                            \
@@ -167,10 +210,12 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
     // the six products, smallest terms first
     constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
     MI_A_DMA(0, 0);
-    if constexpr (PLAIN) {
+    if constexpr (RAW) {
         MI_BRAW_DMA(0, 0);
         if (nk > 1) MI_BRAW_DMA(1, 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        MI_BRAW_FIX(0, 0);
+        if (nk > 1) MI_BRAW_FIX(1, 1);
         __syncthreads();
         MI_BRAW_READ(0);
     } else {
@@ -237,13 +282,13 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
         __builtin_amdgcn_sched_barrier(0);
         if (kt + 1 < nk) {
             MI_A_DMA(kt + 1, cur ^ 1);
-            if constexpr (PLAIN) {
+            if constexpr (RAW) {
                 if (kt + 2 < nk) MI_BRAW_DMA(kt + 2, kt & 1);   // raw stage kt & 1 was consumed during step kt - 1
             } else {
                 MI_B_LOAD(kt + 1);
             }
         }
-        if constexpr (PLAIN) {
+        if constexpr (RAW) {
             // landed and fenced by the barrier that ended step kt - 1.  Unconditional (the last step re-splits a stale
             // tile into the unused stage) so that split and MFMAs share one basic block and can be interleaved.
             MI_BRAW_READ((kt + 1) & 1);
@@ -260,8 +305,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
                         if (MI_X6_ABL & 16) asm volatile("s_nop 15\n\ts_nop 15");                     // gap after every MFMA
                         if ((MI_X6_ABL & 32) && a == TM - 1 && b == TN - 1) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15");   // gap after each group
                     }
-        if (PLAIN || kt + 1 < nk) MI_B_STORE(cur ^ 1);
-        if constexpr (PLAIN) {
+        if (RAW || kt + 1 < nk) MI_B_STORE(cur ^ 1);
+        if constexpr (RAW) {
             // the split of the next activation tile (~70 VALU) issues in the shadow of this step's MFMAs
 #pragma unroll
             for (int i = 0; i < 6 * TM * TN; ++i) {
@@ -270,12 +315,14 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's share of the next A image / raw tile has landed
+        if (kt + 2 < nk) MI_BRAW_FIX(kt + 2, kt & 1);
         __syncthreads();
         cur ^= 1;
     }
 #undef MI_A_DMA
 #undef MI_B_LOAD
 #undef MI_BRAW_DMA
+#undef MI_BRAW_FIX
 #undef MI_BRAW_READ
 #undef MI_B_STORE
 
@@ -289,6 +336,17 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc
 }
 
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false>
+__global__ __launch_bounds__(256, 2) void conv_gemm_x6_kernel(const mi_conv_desc d, const int N, const int MT, const int Gm) {
+    conv_x6_body<WM, WN, TM, TN, EPI, LFLAGS, PLAIN, HALF_IMG, 0>(d, N, MT, Gm);
+}
+
+// the float32 decoders' rewrite convs: a symbol of their own, so that profiles keep them apart from the linears
+template <int WM, int WN, int TM, int TN, bool HALF_IMG, int NT>
+__global__ __launch_bounds__(256, 2) void conv_tap_x6_kernel(const mi_conv_desc d, const int N, const int MT, const int Gm) {
+    conv_x6_body<WM, WN, TM, TN, MI_EPI_GLU, 0, false, HALF_IMG, NT>(d, N, MT, Gm);
+}
+
+template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false, int NTAPS = 0>
 static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
     const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
@@ -297,7 +355,8 @@ static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     const int N = (int)N64, MT = d.Mpad / BM, NT = ceil_div(N, BN);
     const int Gm = pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 6);
     const unsigned grid = grouped_grid(MT, NT, Gm);
-    hipLaunchKernelGGL((conv_gemm_x6_kernel<WM, WN, TM, TN, EPI, LFLAGS, PLAIN, HALF_IMG>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
+    if constexpr (NTAPS > 0) hipLaunchKernelGGL((conv_tap_x6_kernel<WM, WN, TM, TN, HALF_IMG, NTAPS>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
+    else hipLaunchKernelGGL((conv_gemm_x6_kernel<WM, WN, TM, TN, EPI, LFLAGS, PLAIN, HALF_IMG>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }
@@ -320,6 +379,27 @@ static int launch_tile_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
 }
 
 bool conv_x6_supported(int tile) { return tile == 128 || tile == 96 || tile == 64; }
+
+template <int NT>
+static int launch_tile_tap_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
+    // small batches, as in the fp32 route (gemm_conv.hip launch_conv): a 128-row layer with fewer than 200 workgroups runs on
+    // 64-row tiles that read the 128-row image -- bit-identical to the 128-row tile, no second image (MI_SMALL_TILE=0: off)
+    static const int small = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
+    if (small && tile == 128 && (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200)
+        return launch_cfg_x6<1, 4, 2, 1, MI_EPI_GLU, 0, false, true, NT>(d, st);
+    if (tile == 128) return launch_cfg_x6<2, 2, 2, 2, MI_EPI_GLU, 0, false, false, NT>(d, st);
+    return launch_cfg_x6<1, 4, 3, 1, MI_EPI_GLU, 0, false, false, NT>(d, st);
+}
+
+// d has been validated by launch_conv (gemm_conv.hip): a stride-1 GLU conv with K2 = 3, dilation 1, NT = 9 or 3 taps, its row
+// pitch a multiple of 4 and equal to O2, tile 96 or 128 (dmatap_eligible)
+int launch_conv_tap_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
+    g_last_conv_route = 7;
+    MI_REQUIRE(d.wx && ((uintptr_t)d.wx & 15) == 0, "conv tap x6: split weight image missing or misaligned");
+    MI_REQUIRE(d.epi == MI_EPI_GLU && (tile == 96 || tile == 128) && (d.ntaps == 9 || d.ntaps == 3),
+               "conv tap x6: GLU layer with 9 or 3 taps on a 96- or 128-row tile (epi %d, tile %d, ntaps %d)", d.epi, tile, d.ntaps);
+    return d.ntaps == 9 ? launch_tile_tap_x6<9>(d, tile, st) : launch_tile_tap_x6<3>(d, tile, st);
+}
 
 // d has been validated by launch_conv (gemm_conv.hip), which also decided `plain`
 int launch_conv_x6(const mi_conv_desc &d, int tile, bool plain, hipStream_t st) {

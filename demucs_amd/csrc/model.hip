@@ -126,9 +126,15 @@ int Model::conv(const mi_conv_desc &d, hipStream_t st) {
     MI_HIP(hipEventRecord(p.a, st));
     const int r = launch_conv(d, st);
     MI_HIP(hipEventRecord(p.b, st));
+    // the split-bf16 tap convs (route 7, gemm_x6.hip conv_tap_x6_kernel): rows of their own, named after the kernel -- the
+    // conv_gemm_x6 rows stay the linears' ones
+    const bool tap_x6 = r == MI_OK && g_last_conv_route == 7;
+    if (tap_x6) p.cls = 105 + (d.ntaps == 9 ? 2 : 0) + (tile == 128 ? 1 : 0);
     prof.pending.push_back(p);
-    ProfRow &row = prof.rows[cls];
-    if (!row.name[0])
+    ProfRow &row = prof.rows[p.cls];
+    if (!row.name[0] && tap_x6)
+        snprintf(row.name, sizeof(row.name), "conv_tap_x6<%s,tile%d,taps%d>", kEpiNames[d.epi], tile, d.ntaps);
+    else if (!row.name[0])
         snprintf(row.name, sizeof(row.name), "conv_gemm%s<%s,tile%d%s>", d.half == MI_DTYPE_BF16 ? "_bf16" : d.half == MI_DTYPE_F16 ? "_f16" : cls >= 48 ? "_x6" : "",
                  kEpiNames[d.epi], tile, d.plain ? ",1x1" : "");
     return r;
@@ -188,14 +194,16 @@ int Model::attn_heads(const void *q, const void *k, const void *v, float *o, int
 // ------------------------------------------------------------------------------------------------
 // Second copy of the packed weights as exact 3-term bf16 tile images: selects the 6-product bf16 MFMA main loop
 // (gemm_x6.hip).  Scope: by default the float32 engine's 44 transformer linears (split_linears), where the split loop is
-// ~1.4x faster than the native fp32 MFMA kernels; MI_X6=0 packs none (A/B runs), MI_X6=1 every layer whose tile has the
-// split loop (the k x k convs measured slower on it).  When several PROCESSES share one GPU, split-loop results were
+// ~1.4x faster than the native fp32 MFMA kernels, and its eight decoder rewrite convs (split_taps: dec[j] 3 x 3, tdec[j] k = 3,
+// + GLU), which the shifted-run DMA tap loader feeds (conv_tap_x6_kernel; the table-driven gather in front of the split loop had
+// measured slower than the native DMA tap loop); MI_X6=0 packs none (A/B runs), MI_X6=1 every layer whose tile has the split
+// loop.  When several PROCESSES share one GPU, split-loop results were
 // intermittently corrupted (tests/test_gpu_distributed.py, tools/micro/det3.py; cause not found), so such a process
 // selects the native kernels at run time (mi_set_split_bf16(0): demucs_amd/distributed.py does it for ranks that share
 // a device); one process per GPU is the supported deployment.
 int Model::pack_split(PackedConv *pc) {
-    const int scope = x6_scope();                 // 0 none, 1 transformer linears (float32), 2 all
-    const bool want = scope == 2 || (scope == 1 && split_linears && cfg.dtype == MI_DTYPE_F32);
+    const int scope = x6_scope();                 // 0 none, 1 transformer linears + decoder rewrites (float32), 2 all
+    const bool want = scope == 2 || (scope == 1 && (split_linears || split_taps) && cfg.dtype == MI_DTYPE_F32);
     if (!want || !conv_x6_supported(pc->tile)) return MI_OK;
     MI_TRY(dev_alloc(&pc->wx, (size_t)6 * pc->Kpad * pc->Mpad));
     MI_TRY(launch_pack_split(pc->wt, pc->Kpad, pc->Mpad, pc->tile, pc->wx, nullptr));
@@ -502,7 +510,9 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(wt.get(p + ".rewrite.weight", (int64_t)2 * C * C * 9, &rw));
         MI_TRY(wt.get(p + ".rewrite.bias", 2 * C, &rb));
         DecW &dd = dec[j];
+        split_taps = true;
         MI_TRY(pack_conv(rw, rb, 2 * C, C * 9, true, &dd.rewrite, 9));
+        split_taps = false;
         MI_TRY(make_ktab(Gather{C, 3, 3, 1, 1, 1, 1, (int64_t)Fr * T, T}, dd.rewrite.Kpad, &dd.ktab_rw));
         MI_TRY(load_dconv(wt, p, C, (int64_t)Fr * T, T, true, &dd.dconv));
         MI_TRY(pack_convtr(w, b, C, Cout, &dd.convtr));
@@ -515,7 +525,9 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(wt.get(pt + ".rewrite.weight", (int64_t)2 * C * C * 3, &rw));
         MI_TRY(wt.get(pt + ".rewrite.bias", 2 * C, &rb));
         DecW &td = tdec[j];
+        split_taps = true;
         MI_TRY(pack_conv(rw, rb, 2 * C, C * 3, true, &td.rewrite, 3));
+        split_taps = false;
         MI_TRY(make_ktab(Gather{C, 1, 3, 1, 1, 0, 1, (int64_t)L, L}, td.rewrite.Kpad, &td.ktab_rw));
         MI_TRY(load_dconv(wt, pt, C, (int64_t)L, L, false, &td.dconv));
         MI_TRY(pack_convtr(w, b, C, Coutt, &td.convtr));
