@@ -548,8 +548,11 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_dmarow_kernel(const mi_conv_
     conv_epilogue<TM, TN, EPI, LFLAGS>(d, acc, m0, n0, wm, wn, N, P, o2v);
 }
 
-// float32 layer with row taps only (the caller vouches for the table: `dma_rows`; a plain layer's table is the identity): see above
-static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain) {
+// float32 layer with row taps only (the caller vouches for the table: `dma_rows`; a plain layer's table is the identity): see above.
+// `split`: such a layer with a split weight image -- a strided encoder conv (LINEAR + GELU) or transposed conv on a 96- / 128-row
+// tile, a 1 x 1 + GLU layer on a 128-row tile -- takes the same row loader in front of the split-bf16 main loop (gemm_x6.hip
+// conv_rows_x6_kernel); MI_NO_DMA_ROWS=1 turns both off
+static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain, bool split = false) {
     static const bool off = getenv("MI_NO_DMA_ROWS") != nullptr;
     const int ld = d.x_ld ? d.x_ld : d.D2;
     const int lf = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS | MI_FLAG_IMG | MI_FLAG_IMG4 | MI_FLAG_HEADS);
@@ -557,7 +560,8 @@ static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain) {
     // bound by their output), where the register-staged kernel's four workgroups per CU measured 3 % faster (476 vs 490 us)
     const bool epi_ok = (d.epi == MI_EPI_LINEAR && lf == MI_FLAG_GELU && !plain) || d.epi == MI_EPI_CONVTR ||
                         ((d.epi == MI_EPI_GLU || d.epi == MI_EPI_GN_GLU) && plain && tile == 128 && !(d.flags & (MI_FLAG_IMG | MI_FLAG_IMG4)));
-    return !off && !d.half && !d.wx && d.ktab && epi_ok && (plain || d.dma_rows) && (tile == 64 || tile == 96 || tile == 128) &&
+    if (split && (d.epi == MI_EPI_GN_GLU || tile == 64)) return false;
+    return !off && !d.half && (split ? d.wx != nullptr : !d.wx) && d.ktab && epi_ok && (plain || d.dma_rows) && (tile == 64 || tile == 96 || tile == 128) &&
            d.Mpad % tile == 0 && d.S2 == 1 && d.O2 == ld && ld % 4 == 0 && ((uintptr_t)d.x & 3) == 0 && ((uintptr_t)d.ktab & 63) == 0 &&
            (d.epi == MI_EPI_CONVTR || tile != 64 || d.epi == MI_EPI_LINEAR);
 }
@@ -701,8 +705,11 @@ static void x6_verify_dump() {
 
 static int launch_conv_fp32_only(const mi_conv_desc &d, hipStream_t st);
 
-static int x6_verified_launch(const mi_conv_desc &d, int tile, bool plain, hipStream_t st, bool tap = false) {
-    auto launch_x6 = [&]() { return tap ? launch_conv_tap_x6(d, tile, st) : launch_conv_x6(d, tile, plain, st); };
+// loader: 0 plain / gather table (launch_conv_x6), 1 shifted-run taps (launch_conv_tap_x6), 2 row taps (launch_conv_rows_x6)
+static int x6_verified_launch(const mi_conv_desc &d, int tile, bool plain, hipStream_t st, int loader = 0) {
+    auto launch_x6 = [&]() {
+        return loader == 1 ? launch_conv_tap_x6(d, tile, st) : loader == 2 ? launch_conv_rows_x6(d, tile, st) : launch_conv_x6(d, tile, plain, st);
+    };
     const bool checkable = d.epi != MI_EPI_STATS_ONLY && d.epi != MI_EPI_BIAS_STATS && d.res != d.y && (int)g_vinfo.size() < kVerifyMax;
     if (!checkable) return launch_x6();
     if (!g_vlog) {
@@ -785,7 +792,11 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     // own small-batch tile: launch_conv_tap_x6)
     static const bool x6_verify = getenv("MI_X6_VERIFY") != nullptr;
     if (!plain && x6_mode == 0 && x6_class_ok && dmatap_eligible(d, tile, true))
-        return x6_verify ? x6_verified_launch(d, tile, false, st, true) : launch_conv_tap_x6(d, tile, st);
+        return x6_verify ? x6_verified_launch(d, tile, false, st, 1) : launch_conv_tap_x6(d, tile, st);
+    // the frequency branch's encoder / transposed convs and the 1 x 1 + GLU rewrites with a split image: the DMA row loader in front
+    // of the split-bf16 main loop
+    if (x6_mode == 0 && x6_class_ok && dmarow_eligible(d, tile, plain, true))
+        return x6_verify ? x6_verified_launch(d, tile, false, st, 2) : launch_conv_rows_x6(d, tile, st);
     // small batches: a k x k GLU conv whose 128-row tiles under-fill the chip (B = 1: 6 x 21 workgroups) takes 96-row tiles
     static const int small_tile = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
     int ktile = tile;

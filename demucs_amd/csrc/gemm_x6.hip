@@ -15,7 +15,8 @@
 //   B (activations): thread (column n = tid & 127, k-half = tid >> 7) takes its 8 k values, splits them in registers
 //                (v_cvt_pk_bf16_f32, round-to-nearest residuals) and writes three 16-byte words.  The values come from
 //                the raw fp32 tile that LDS-DMA lands two K steps ahead (plain layers: channel runs; the decoders' 3 x 3 /
-//                k = 3 convs, conv_tap_x6_kernel: tap-shifted runs), or else through the gather table of the fp32 kernel.
+//                k = 3 convs, conv_tap_x6_kernel: tap-shifted runs; the frequency branch's strided and transposed convs,
+//                conv_rows_x6_kernel: row taps at the output's own columns), or else through the gather table of the fp32 kernel.
 // Epilogues are the shared ones of gemm_tile.h (the accumulator layout of all 32x32 MFMAs is the same).
 #include "gemm_tile.h"
 #include "split_bf16.h"
@@ -71,11 +72,24 @@ int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx,
 // OVERWRITTEN with the conv's zero padding by the lane that issued the transfer, after its wait and before the barrier that
 // ends the K step (at most two ds_write_b32 per lane and K step, as in gemm_conv.hip conv_gemm_dmatap_kernel): a zero weight
 // would not do, NaN * 0 is NaN.  The k order is the packed weights' one, so the split image is pack_split's as for any layer.
+// NT = kRowTaps: the B loader of the float32 layers whose taps move along ROWS only (conv_rows_x6_kernel: the frequency branch's
+// encoder convs k = 8, s = 4 and transposed convs as two-tap GEMMs, rows q and q - 1; the encoders' 1 x 1 + GLU rewrites, whose
+// table is the identity), gemm_conv.hip conv_gemm_dmarow_kernel's loader in front of this main loop: row k of the raw tile is a
+// run of input row i1 = o1 * S1 + d1 at the output tile's own columns (aligned 16-byte chunks, never a shifted run, so no fix-up), its (off, d1) from the gather table; a row outside [0, D1),
+// a column past the end and the K padding (d1 = -2^29) read the zero page.  The table entries of K step kt + 3 (this wave's four
+// rows) are SCALAR loads in inline asm, issued in the same asm statement as the end-of-step vmcnt(0) wait and counted with
+// lgkmcnt(0) there: their latency passes under the wait for the ring, and hipcc never sees them (as VMEM loads inside the loop it
+// would wait vmcnt(0) for them; as compiler-visible scalar loads its lgkmcnt bookkeeping would not know of them).
+constexpr int kRowTaps = -1;
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG, int NT>
 __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N, const int MT, const int Gm) {
     constexpr int BM = WM * TM * 32;
-    constexpr bool RAW = PLAIN || NT > 0;                    // the activation tile goes through the braw ring
-    static_assert(NT == 0 || (!PLAIN && EPI == MI_EPI_GLU), "tap loader: GLU rewrite convs");
+    constexpr bool RAW = PLAIN || NT != 0;                   // the activation tile goes through the braw ring
+    constexpr bool ROWS = NT == kRowTaps;
+    static_assert(NT <= 0 || (!PLAIN && EPI == MI_EPI_GLU), "tap loader: GLU rewrite convs");
+    static_assert(!ROWS || (!PLAIN && (EPI == MI_EPI_LINEAR || EPI == MI_EPI_CONVTR || EPI == MI_EPI_GLU)),
+                  "row-tap loader: encoder / transposed convs, 1 x 1 + GLU rewrites");
+    static_assert(NT >= kRowTaps, "NT: taps, 0 or kRowTaps");
     static_assert(WN * TN * 32 == BN, "block N tile is 128");
     static_assert(WM * WN == 4, "4 waves");
     constexpr int A_BYTES = BM * 96, B_BYTES = BN * 96, STAGE = A_BYTES + B_BYTES;
@@ -127,21 +141,41 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
     const size_t b_row = lc.valid ? (size_t)P : 0, b_step = lc.valid ? (size_t)BK * P : 0;
     float breg[8];
     // plain DMA loader: this lane's 16 bytes of rows 4*wave + 2*i + (lane >> 5), i = 0, 1
-    const int rc4 = (lane & 31) * 4, rrow = 4 * wave + (lane >> 5);
+    const int li = lane & 31, lh = lane >> 5;
+    const int rc4 = li * 4, rrow = 4 * wave + lh;
     const ColInfo rcol = decompose(n0 + rc4, N, P, d.O2, NT ? o2v : d.O2);
-    const float *rsrc = rcol.valid ? d.x + (size_t)rcol.b * d.x_bstride + rcol.p + (NT ? 0 : (size_t)rrow * P) : d.sink + 256;
+    const int x_ld = d.x_ld ? d.x_ld : d.D2;
+    const int ri1 = rcol.o1 * d.S1;                            // row taps: the input row of tap d1 = 0
+    const float *rsrc = !rcol.valid ? d.sink + 256
+                        : d.x + (size_t)rcol.b * d.x_bstride +
+                              (ROWS ? (size_t)ri1 * x_ld + rcol.o2 : (size_t)rcol.p + (NT ? 0 : (size_t)rrow * P));
     const size_t r_row2 = rcol.valid ? (size_t)2 * P : 0, r_step = rcol.valid ? (size_t)BK * P : 0;
+    // row taps: (off, d1) of this wave's rows 4 wave .. 4 wave + 3 of a K step, in SGPRs
+    const int4 *ktab4 = reinterpret_cast<const int4 *>(d.ktab) + 4 * wave;
+    typedef int v2i __attribute__((ext_vector_type(2)));
+    v2i e0, e1, e2, e3;
+#define MI_ROW_LOADS "s_load_dwordx2 %0, %4, 0x0\n\ts_load_dwordx2 %1, %4, 0x10\n\ts_load_dwordx2 %2, %4, 0x20\n\t" \
+                     "s_load_dwordx2 %3, %4, 0x30\n\t"
+#define MI_ROW_ENTRIES(kt)                                                                                          \
+    asm volatile(MI_ROW_LOADS "s_waitcnt lgkmcnt(0)"                                                               \
+                 : "=&s"(e0), "=&s"(e1), "=&s"(e2), "=&s"(e3) : "s"(ktab4 + (kt) * BK) : "memory")
     // taps: this lane's column chunk rcol.o2 .. + 3 (one input row, the pitch is a multiple of 4); the element that a tap with
     // d2 = -1 / +1 reads from outside the row [0, D2), or -1
     constexpr int K2 = 3;
-    const int x_ld = d.x_ld ? d.x_ld : d.D2;
     const int fix_l = (NT && rcol.valid && rcol.o2 == 0) ? 0 : -1;
     const int fr = d.D2 - 1 - rcol.o2;
     const int fix_r = (NT && rcol.valid && fr >= 0 && fr < 4) ? fr : -1;
 #define MI_BRAW_DMA(kt, rs)                                                                                         \
     do {                                                                                                            \
         float *dst = braw + (rs) * (BK * BN) + (4 * wave) * BN;                                                     \
-        if constexpr (NT > 0) {                                                                                     \
+        if constexpr (ROWS) {                                                                                       \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
+                const int off = i ? (lh ? e3.x : e2.x) : (lh ? e1.x : e0.x);                                        \
+                const int dd1 = i ? (lh ? e3.y : e2.y) : (lh ? e1.y : e0.y);                                        \
+                const bool ok = rcol.valid && (unsigned)(ri1 + dd1) < (unsigned)d.D1;                               \
+                __builtin_amdgcn_global_load_lds((gvoid_t *)(ok ? rsrc + off : d.sink + 256), (lvoid_t *)(dst + 2 * i * BN), 16, 0, 0); \
+            }                                                                                                       \
+        } else if constexpr (NT > 0) {                                                                              \
             _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
                 const int k = (kt) * BK + rrow + 2 * i, ci = k / NT, tap = k - ci * NT, t1 = tap / K2, t2 = tap - t1 * K2; \
                 const int i1 = rcol.o1 + t1 - d.tap_pad1;                                                           \
@@ -206,13 +240,17 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-    const int li = lane & 31, lh = lane >> 5;
     // the six products, smallest terms first
     constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
     MI_A_DMA(0, 0);
     if constexpr (RAW) {
+        if constexpr (ROWS) MI_ROW_ENTRIES(0);
         MI_BRAW_DMA(0, 0);
-        if (nk > 1) MI_BRAW_DMA(1, 1);
+        if (nk > 1) {
+            if constexpr (ROWS) MI_ROW_ENTRIES(1);
+            MI_BRAW_DMA(1, 1);
+        }
+        if constexpr (ROWS) { if (nk > 2) MI_ROW_ENTRIES(2); }        // for the transfer of tile 2 in step 0
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         MI_BRAW_FIX(0, 0);
         if (nk > 1) MI_BRAW_FIX(1, 1);
@@ -314,7 +352,13 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
                 __builtin_amdgcn_sched_group_barrier(0x002, (72 + 6 * TM * TN - 1) / (6 * TM * TN), 0);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's share of the next A image / raw tile has landed
+        // this wave's share of the next A image / raw tile has landed (row taps: and the table entries of tile kt + 3, which
+        // step kt + 1 transfers, are in SGPRs)
+        if (ROWS && kt + 3 < nk)
+            asm volatile(MI_ROW_LOADS "s_waitcnt vmcnt(0) lgkmcnt(0)"
+                         : "=&s"(e0), "=&s"(e1), "=&s"(e2), "=&s"(e3) : "s"(ktab4 + (kt + 3) * BK) : "memory");
+        else
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (kt + 2 < nk) MI_BRAW_FIX(kt + 2, kt & 1);
         __syncthreads();
         cur ^= 1;
@@ -324,6 +368,8 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
 #undef MI_BRAW_DMA
 #undef MI_BRAW_FIX
 #undef MI_BRAW_READ
+#undef MI_ROW_ENTRIES
+#undef MI_ROW_LOADS
 #undef MI_B_STORE
 
     if (MI_X6_ABL & 4) {                     // no epilogue: one store per thread keeps the loop alive
@@ -346,6 +392,12 @@ __global__ __launch_bounds__(256, 2) void conv_tap_x6_kernel(const mi_conv_desc 
     conv_x6_body<WM, WN, TM, TN, MI_EPI_GLU, 0, false, HALF_IMG, NT>(d, N, MT, Gm);
 }
 
+// the float32 row-tap layers (frequency encoder / transposed convs, 1 x 1 + GLU rewrites): a symbol of their own, as the tap convs
+template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool HALF_IMG>
+__global__ __launch_bounds__(256, 2) void conv_rows_x6_kernel(const mi_conv_desc d, const int N, const int MT, const int Gm) {
+    conv_x6_body<WM, WN, TM, TN, EPI, LFLAGS, false, HALF_IMG, kRowTaps>(d, N, MT, Gm);
+}
+
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false, int NTAPS = 0>
 static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
@@ -356,6 +408,8 @@ static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     const int Gm = pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 6);
     const unsigned grid = grouped_grid(MT, NT, Gm);
     if constexpr (NTAPS > 0) hipLaunchKernelGGL((conv_tap_x6_kernel<WM, WN, TM, TN, HALF_IMG, NTAPS>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
+    else if constexpr (NTAPS == kRowTaps)
+        hipLaunchKernelGGL((conv_rows_x6_kernel<WM, WN, TM, TN, EPI, LFLAGS, HALF_IMG>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
     else hipLaunchKernelGGL((conv_gemm_x6_kernel<WM, WN, TM, TN, EPI, LFLAGS, PLAIN, HALF_IMG>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
     MI_CHECK_LAUNCH();
     return MI_OK;
@@ -399,6 +453,36 @@ int launch_conv_tap_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
     MI_REQUIRE(d.epi == MI_EPI_GLU && (tile == 96 || tile == 128) && (d.ntaps == 9 || d.ntaps == 3),
                "conv tap x6: GLU layer with 9 or 3 taps on a 96- or 128-row tile (epi %d, tile %d, ntaps %d)", d.epi, tile, d.ntaps);
     return d.ntaps == 9 ? launch_tile_tap_x6<9>(d, tile, st) : launch_tile_tap_x6<3>(d, tile, st);
+}
+
+template <int EPI, int LFLAGS>
+static int launch_tile_rows_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
+    // small batches, as for the tap convs: a 128-row layer with fewer than 200 workgroups runs on 64-row tiles that read the
+    // 128-row image -- bit-identical to the 128-row tile (MI_SMALL_TILE=0: off)
+    static const int small = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
+    if (small && tile == 128 && (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200)
+        return launch_cfg_x6<1, 4, 2, 1, EPI, LFLAGS, false, true, kRowTaps>(d, st);
+    if (tile == 128) return launch_cfg_x6<2, 2, 2, 2, EPI, LFLAGS, false, false, kRowTaps>(d, st);
+    return launch_cfg_x6<1, 4, 3, 1, EPI, LFLAGS, false, false, kRowTaps>(d, st);
+}
+
+// d has been validated by launch_conv (gemm_conv.hip): a float32 layer whose table moves its taps along rows only (dma_rows, or a
+// plain layer's identity table), row pitch a multiple of 4 and equal to O2, S2 = 1, a 64-byte-aligned table (dmarow_eligible):
+// LINEAR + GELU (the encoder convs) or CONVTR (the transposed convs; the epilogue reads its flag set at run time) on 96 or 128
+// rows, 1 x 1 + GLU (the encoders' rewrites) on 128 rows -- the epilogue instantiations of conv_gemm_dmarow_kernel
+int launch_conv_rows_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
+    g_last_conv_route = 8;
+    MI_REQUIRE(d.wx && ((uintptr_t)d.wx & 15) == 0, "conv rows x6: split weight image missing or misaligned");
+    MI_REQUIRE(d.ktab && ((uintptr_t)d.ktab & 63) == 0, "conv rows x6: gather table missing or misaligned");
+    MI_REQUIRE(tile == 96 || tile == 128, "conv rows x6: 96- or 128-row tile (tile %d)", tile);
+    if (d.epi == MI_EPI_CONVTR) return launch_tile_rows_x6<MI_EPI_CONVTR, 0>(d, tile, st);
+    if (d.epi == MI_EPI_GLU) {
+        MI_REQUIRE(tile == 128, "conv rows x6: GLU on a 128-row tile (tile %d)", tile);
+        return launch_tile_rows_x6<MI_EPI_GLU, 0>(d, tile, st);
+    }
+    MI_REQUIRE(d.epi == MI_EPI_LINEAR && (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) == MI_FLAG_GELU,
+               "conv rows x6: LINEAR + GELU, CONVTR or GLU (epi %d, flags %d)", d.epi, d.flags);
+    return launch_tile_rows_x6<MI_EPI_LINEAR, MI_FLAG_GELU>(d, tile, st);
 }
 
 // d has been validated by launch_conv (gemm_conv.hip), which also decided `plain`

@@ -97,6 +97,7 @@ extern int g_split_bf16;     // 0 (mi_set_split_bf16): native fp32 MFMA kernels 
 bool conv_x6_supported(int tile);
 int launch_conv_x6(const mi_conv_desc &d, int tile, bool plain, hipStream_t st);
 int launch_conv_tap_x6(const mi_conv_desc &d, int tile, hipStream_t st);      // stride-1 3 x 3 / k = 3 GLU convs (route 7)
+int launch_conv_rows_x6(const mi_conv_desc &d, int tile, hipStream_t st);     // row-tap encoder / transposed convs (route 8)
 int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx, hipStream_t st);
 
 // gemm_half.hip: bf16 / fp16 operand main loop (mi_config.dtype)

@@ -165,6 +165,7 @@ struct Model : WorkspacePtrs {
     int fill_workspace(Workspace &w);
     bool split_linears = false;  // set while the transformer linears are packed: pack_split's default scope
     bool split_taps = false;     // ... and while the decoders' 3 x 3 / k = 3 rewrite convs are packed
+    bool split_rows = false;     // ... and while the frequency branch's encoder convs (levels 1-3), transposed convs (j = 0-2) and 128-row 1 x 1 + GLU rewrites are packed
     bool dconv_tap_dma = false;  // run_dconv may state the k = 3 convs' geometry (DMA tap route): only when x / tmp carry 128 bytes of slack
     int run_dconv(const DConvW &w, int C, const Geo &g, float *x, float *tmp, float *hidden, double *stats, float2 *st1, float2 *st2,
                   hipStream_t st, double *gram2 = nullptr, size_t gram2_cap = 0);

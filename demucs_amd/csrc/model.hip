@@ -128,12 +128,17 @@ int Model::conv(const mi_conv_desc &d, hipStream_t st) {
     MI_HIP(hipEventRecord(p.b, st));
     // the split-bf16 tap convs (route 7, gemm_x6.hip conv_tap_x6_kernel): rows of their own, named after the kernel -- the
     // conv_gemm_x6 rows stay the linears' ones
-    const bool tap_x6 = r == MI_OK && g_last_conv_route == 7;
+    // ... and so do the split-bf16 row-tap convs (route 8, conv_rows_x6_kernel: the frequency branch's encoder / transposed convs,
+    // the encoders' 1 x 1 + GLU rewrites)
+    const bool tap_x6 = r == MI_OK && g_last_conv_route == 7, rows_x6 = r == MI_OK && g_last_conv_route == 8;
     if (tap_x6) p.cls = 105 + (d.ntaps == 9 ? 2 : 0) + (tile == 128 ? 1 : 0);
+    if (rows_x6) p.cls = 109 + (d.epi == MI_EPI_CONVTR ? 4 : d.epi == MI_EPI_GLU ? 2 : 0) + (tile == 128 ? 1 : 0);
     prof.pending.push_back(p);
     ProfRow &row = prof.rows[p.cls];
     if (!row.name[0] && tap_x6)
         snprintf(row.name, sizeof(row.name), "conv_tap_x6<%s,tile%d,taps%d>", kEpiNames[d.epi], tile, d.ntaps);
+    else if (!row.name[0] && rows_x6)
+        snprintf(row.name, sizeof(row.name), "conv_rows_x6<%s,tile%d>", kEpiNames[d.epi], tile);
     else if (!row.name[0])
         snprintf(row.name, sizeof(row.name), "conv_gemm%s<%s,tile%d%s>", d.half == MI_DTYPE_BF16 ? "_bf16" : d.half == MI_DTYPE_F16 ? "_f16" : cls >= 48 ? "_x6" : "",
                  kEpiNames[d.epi], tile, d.plain ? ",1x1" : "");
@@ -196,14 +201,17 @@ int Model::attn_heads(const void *q, const void *k, const void *v, float *o, int
 // (gemm_x6.hip).  Scope: by default the float32 engine's 44 transformer linears (split_linears), where the split loop is
 // ~1.4x faster than the native fp32 MFMA kernels, and its eight decoder rewrite convs (split_taps: dec[j] 3 x 3, tdec[j] k = 3,
 // + GLU), which the shifted-run DMA tap loader feeds (conv_tap_x6_kernel; the table-driven gather in front of the split loop had
-// measured slower than the native DMA tap loop); MI_X6=0 packs none (A/B runs), MI_X6=1 every layer whose tile has the split
+// measured slower than the native DMA tap loop), and the row-tap layers of the DMA row route (split_rows: enc[1..3].conv, k = 8,
+// s = 4, + GELU; dec[0..2].convtr; the 128-row 1 x 1 + GLU rewrites of enc / tenc[2..3]), which the DMA row loader feeds
+// (conv_rows_x6_kernel; not with MI_NO_DMA_ROWS=1, whose layers keep the native table routes); MI_X6=0 packs none (A/B runs), MI_X6=1 every layer whose tile has the split
 // loop.  When several PROCESSES share one GPU, split-loop results were
 // intermittently corrupted (tests/test_gpu_distributed.py, tools/micro/det3.py; cause not found), so such a process
 // selects the native kernels at run time (mi_set_split_bf16(0): demucs_amd/distributed.py does it for ranks that share
 // a device); one process per GPU is the supported deployment.
 int Model::pack_split(PackedConv *pc) {
-    const int scope = x6_scope();                 // 0 none, 1 transformer linears + decoder rewrites (float32), 2 all
-    const bool want = scope == 2 || (scope == 1 && (split_linears || split_taps) && cfg.dtype == MI_DTYPE_F32);
+    const int scope = x6_scope();                 // 0 none, 1 transformer linears + decoder rewrites + row-tap convs (float32), 2 all
+    static const bool no_rows = getenv("MI_NO_DMA_ROWS") != nullptr;
+    const bool want = scope == 2 || (scope == 1 && (split_linears || split_taps || (split_rows && !no_rows)) && cfg.dtype == MI_DTYPE_F32);
     if (!want || !conv_x6_supported(pc->tile)) return MI_OK;
     MI_TRY(dev_alloc(&pc->wx, (size_t)6 * pc->Kpad * pc->Mpad));
     MI_TRY(launch_pack_split(pc->wt, pc->Kpad, pc->Mpad, pc->tile, pc->wx, nullptr));
@@ -470,10 +478,14 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(wt.get(p + ".rewrite.weight", (int64_t)2 * C * C, &rw));
         MI_TRY(wt.get(p + ".rewrite.bias", 2 * C, &rb));
         EncW &e = enc[i];
+        split_rows = i > 0;              // level 0 (K = 32) is bound by its output: native
         MI_TRY(pack_conv(w, b, C, Cin * 8, false, &e.conv));
+        split_rows = false;
         if (i) MI_TRY(pack_enc_tap(w, Cin, &e.conv));
         MI_TRY(make_ktab(Gather{Cin, 8, 1, 1, 1, 2, 0, (int64_t)kFr[i] * T, T}, e.conv.Kpad, &e.ktab_conv));
+        split_rows = i >= 2;             // 128-row rewrites; levels 0 / 1 (96 rows, K = 48 / 96) are bound by their output
         MI_TRY(pack_conv(rw, rb, 2 * C, C, true, &e.rewrite));
+        split_rows = false;
         MI_TRY(make_ktab(Gather{C, 1, 1, 1, 1, 0, 0, (int64_t)kFr[i + 1] * T, T}, e.rewrite.Kpad, &e.ktab_rw));
         MI_TRY(load_dconv(wt, p, C, (int64_t)kFr[i + 1] * T, T, true, &e.dconv));
 
@@ -487,7 +499,9 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(pack_conv(w, b, C, Cint * 8, false, &te.conv));
         if (i) MI_TRY(pack_enc_tap(w, Cint, &te.conv));
         MI_TRY(make_ktab(Gather{Cint, 1, 8, 1, 1, 0, 2, (int64_t)Lp[i], Lp[i]}, te.conv.Kpad, &te.ktab_conv));
+        split_rows = i >= 2;
         MI_TRY(pack_conv(rw, rb, 2 * C, C, true, &te.rewrite));
+        split_rows = false;
         MI_TRY(make_ktab(Gather{C, 1, 1, 1, 1, 0, 0, (int64_t)Lp[i + 1], Lp[i + 1]}, te.rewrite.Kpad, &te.ktab_rw));
         MI_TRY(load_dconv(wt, pt, C, (int64_t)Lp[i + 1], Lp[i + 1], false, &te.dconv));
     }
@@ -515,7 +529,9 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         split_taps = false;
         MI_TRY(make_ktab(Gather{C, 3, 3, 1, 1, 1, 1, (int64_t)Fr * T, T}, dd.rewrite.Kpad, &dd.ktab_rw));
         MI_TRY(load_dconv(wt, p, C, (int64_t)Fr * T, T, true, &dd.dconv));
+        split_rows = j < 3;              // the outermost one (K = 96, 64-row tile) is bound by its output: native
         MI_TRY(pack_convtr(w, b, C, Cout, &dd.convtr));
+        split_rows = false;
         MI_TRY(make_ktab(Gather{C, 2, 1, -1, 1, 0, 0, (int64_t)Fr * T, T}, dd.convtr.Kpad, &dd.ktab_tr));
 
         const int L = Lp[4 - j];          // row pitch of this level's time-branch tensors

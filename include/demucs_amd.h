@@ -132,10 +132,11 @@ int mi_set_two_streams(int32_t enabled);
  *   (frames to memory, then a gather): same summation order, bit-identical output -- kept for A/B runs and as the check of the
  *   fused kernel.  Process-wide; returns the previous setting.  Initial value: 1 unless MI_ISTFT_SPLIT is set. */
 int mi_set_istft_fused(int32_t enabled);
-/* mi_set_split_bf16: the float32 engine runs its transformer linears and its decoders' 3 x 3 / k = 3 rewrite convs (and, with
+/* mi_set_split_bf16: the float32 engine runs its transformer linears, its decoders' 3 x 3 / k = 3 rewrite convs and its frequency
+ *   branch's encoder convs (levels 1-3) and transposed convs (decoders 0-2) (and, with
  *   MI_X6=1, every layer with a split image) on the split-bf16 main loop (gemm_x6.hip: fp32 operands as three exact bf16 terms, six bf16 MFMA products, fp32 accumulate), and
  *   its attention core on the split-bf16 attention kernel (mi_attention_split).  0 selects the native fp32 MFMA kernels, the
- *   linears', the rewrite convs' and mi_attention's, for every later launch, e.g. in a process that shares its GPU with another rank
+ *   linears', the conv routes' and mi_attention's, for every later launch, e.g. in a process that shares its GPU with another rank
  *   (demucs_amd/distributed.py does this by itself).  Process-wide; returns the previous setting.  Initial value: 1. */
 int mi_set_split_bf16(int32_t enabled);
 /* mi_set_transpose_tiles: the kernels either side of the transforms (demucs/htdemucs.py:420-471, demucs/spec.py:11-47).  0, the
@@ -376,7 +377,9 @@ void mi_debug_set_post_launch_hook(void (*hook)(void *stream));
  * register-staged loader (conv_gemm_kernel), 1 LDS-DMA plain linear tile (conv_gemm_dma_kernel), 2 LDS-DMA shifted-run taps
  * (conv_gemm_dmatap_kernel), 3 LDS-DMA row taps (conv_gemm_dmarow_kernel), 4 split-bf16 (gemm_x6.hip), 5 half-mode loops
  * (gemm_half.hip), 6 half-mode tap images (gemm_tap.hip), 7 split-bf16 with LDS-DMA shifted-run taps (gemm_x6.hip
- * conv_tap_x6_kernel: stride-1 3 x 3 / k = 3 GLU convs with a split image and the geometry of route 2); -1 before any call.  A route is chosen from the descriptor alone, so a
+ * conv_tap_x6_kernel: stride-1 3 x 3 / k = 3 GLU convs with a split image and the geometry of route 2), 8 split-bf16 with LDS-DMA
+ * row taps (gemm_x6.hip conv_rows_x6_kernel: the row-tap layers of route 3 -- LINEAR + GELU or CONVTR, 96- / 128-row tiles -- with
+ * a split image); -1 before any call.  A route is chosen from the descriptor alone, so a
  * test that compares two routes bit for bit also has to see that they WERE two routes.  Process-wide, not thread-safe. */
 int mi_debug_last_conv_route(void);
 
