@@ -24,8 +24,9 @@ import torch
 from . import _lib
 from .audio import convert_audio
 from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
+from .stream import ModelStream
 
-__all__ = ["Separator", "LoadModelError", "list_models"]
+__all__ = ["Separator", "SeparatorStream", "LoadModelError", "list_models"]
 
 
 class LoadModelError(Exception):
@@ -130,6 +131,26 @@ class Separator:
                                     split=self._split, overlap=self._overlap, device=device)
             return [self._restore_on_device(st, out[None], device) for st, out in zip(states, outs)]
 
+    def separate_stream(self, mean: Optional[float] = None, std: Optional[float] = None, sr: Optional[int] = None,
+                        length: Optional[int] = None) -> "SeparatorStream":
+        """`separate_tensor` for a track that arrives block by block (demucs_amd/stream.py): `push(block)` takes (channels, n)
+        float32 and returns `{source: (channels, m)}` of the newly final samples, `finish()` the rest.
+
+        `separate_tensor` normalises by the whole track's mono mean and std, which a stream cannot know in advance.  Pass
+        them (from an earlier analysis pass, or `mi_mono_stats` on a prefix): blocks become `(x - mean) / s` and stems
+        `x * s + mean`, s = float32(std) + 1e-8 in float32, and with the track's own statistics the concatenated stems equal
+        `separate_tensor`'s bit for bit.  Without them nothing is normalised, which differs from `separate_tensor`.  `length`
+        is `apply_model_stream`'s.  The input must already be at the model's sample rate and channel count."""
+        if sr is not None and sr != self._samplerate:
+            raise ValueError(f"separate_stream: input sample rate {sr} is not the model's {self._samplerate}; a stream does not "
+                             "resample")
+        if (mean is None) != (std is None):
+            raise ValueError("separate_stream: give both mean and std, or neither")
+        st = ModelStream(self._model, shifts=self._shifts, overlap=self._overlap, segment=self._segment, split=self._split,
+                         device=self._device, length=length, progress=self._progress, callback=self._callback,
+                         affine=None if mean is None else (mean, std))
+        return SeparatorStream(st, self._model.sources)
+
     def _device_index(self) -> torch.device:
         device = torch.device(self._device)
         if device.index is None:
@@ -198,6 +219,27 @@ class Separator:
     @property
     def model(self):
         return self._model
+
+
+class SeparatorStream:
+    """What `Separator.separate_stream` returns: the stream's stems as `{source: (channels, m)}`."""
+
+    def __init__(self, stream, sources):
+        self.stream, self.sources = stream, list(sources)
+
+    def push(self, block: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return dict(zip(self.sources, self.stream.push(block)))
+
+    def finish(self) -> Dict[str, torch.Tensor]:
+        return dict(zip(self.sources, self.stream.finish()))
+
+    @property
+    def emitted(self) -> int:
+        return self.stream.emitted
+
+    @property
+    def latency(self) -> int:
+        return self.stream.latency
 
 
 def list_models(repo: Optional[Union[str, Path]] = None) -> Dict[str, Dict[str, Union[str, Path]]]:

@@ -36,7 +36,7 @@ from . import _lib
 from .hdemucs import HDemucs, MIN_LENGTH as _HDEMUCS_MIN_LENGTH
 from .htdemucs import HTDemucs
 
-__all__ = ["apply_model", "apply_model_many", "BagOfModels", "TensorChunk", "tensor_chunk", "center_trim", "DummyPoolExecutor"]
+__all__ = ["apply_model", "apply_model_many", "apply_model_stream", "BagOfModels", "TensorChunk", "tensor_chunk", "center_trim", "DummyPoolExecutor"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -679,3 +679,6 @@ def _to_host(out: torch.Tensor, device) -> torch.Tensor:
         host.copy_(out, non_blocking=True)
         torch.cuda.current_stream(device).synchronize()
     return host
+
+
+from .stream import ModelStream, apply_model_stream  # noqa: E402,F401  (block-by-block separation, demucs_amd/stream.py)

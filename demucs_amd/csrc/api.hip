@@ -271,6 +271,19 @@ int mi_ola_finish_packed(float *acc_dev, int64_t acc_capacity, int32_t rows, con
                                     (hipStream_t)stream);
 }
 
+int mi_stream_emit(const float *acc_dev, int64_t acc_capacity, int32_t n_sources, int32_t channels, const int64_t *passes_dev,
+                   int32_t n_passes, const int64_t *segs_dev, int32_t n_segs, const float *weights_dev, int64_t weights_capacity,
+                   const float *scales_dev, int32_t n_members, int32_t shifts, int32_t bag, const float *stats_dev, int64_t n,
+                   float *out_dev, int64_t out_capacity, void *stream) {
+    MI_REQUIRE(acc_dev && passes_dev && segs_dev && weights_dev && scales_dev && out_dev && n_sources > 0 && channels > 0 &&
+               (int64_t)n_sources * channels <= 65535 && n_passes > 0 && n_segs >= 0 && n_members > 0 && shifts >= 0 && n >= 1 &&
+               acc_capacity >= 0 && weights_capacity > 0, "mi_stream_emit: bad argument");
+    MI_REQUIRE((int64_t)n_sources * channels * n <= out_capacity, "mi_stream_emit: %d x %d x %lld floats exceed out_dev (%lld)",
+               n_sources, channels, (long long)n, (long long)out_capacity);
+    return launch_stream_emit(acc_dev, acc_capacity, n_sources, channels, passes_dev, n_passes, segs_dev, n_segs, weights_dev,
+                              weights_capacity, scales_dev, n_members, shifts, bag, stats_dev, n, out_dev, (hipStream_t)stream);
+}
+
 int32_t mi_mono_stats_scratch_bytes(void) { return post_stats_scratch_bytes(); }
 
 int mi_mono_stats(const float *wav_dev, int32_t channels, int64_t length, void *scratch_dev, float *stats_dev, void *stream) {

@@ -164,6 +164,9 @@ int launch_attention_heads(const void *q, const void *k, const void *v, const vo
 // post.hip: Separator normalisation, clip prevention, two-stems sums
 int post_stats_scratch_bytes();
 int launch_mono_stats(const float *wav, int channels, int64_t length, double *scratch, float *stats, hipStream_t st);
+int launch_stream_emit(const float *acc, int64_t acc_cap, int n_sources, int channels, const int64_t *passes, int n_passes,
+                       const int64_t *segs, int n_segs, const float *weights, int64_t weights_cap, const float *scales, int n_members,
+                       int shifts, int bag, const float *stats, int64_t n, float *out, hipStream_t st);
 int launch_track_affine(float *x, int64_t n, const float *stats, int mode, hipStream_t st);
 int launch_prevent_clip(const float *x, int64_t n, int mode, unsigned *peak, float *y, hipStream_t st);
 int launch_two_stems(const float *const *stems, int S, int sel, const float *origin, int mode, int64_t n, float *y, hipStream_t st);

@@ -232,6 +232,36 @@ int mi_ola_accumulate_packed(float *acc_dev, int64_t acc_capacity, int32_t rows,
 int mi_ola_finish_packed(float *acc_dev, int64_t acc_capacity, int32_t rows, const int64_t *tiles_dev, int32_t n_tiles,
                          const int64_t *segs_dev, int32_t n_segs, const float *weights_dev, int64_t weights_capacity, void *stream);
 
+/* mi_stream_emit: the final stems of the track span [t0, t0 + n) of a stream (demucs_amd/stream.py) from every (member, pass)
+ *   accumulator, in ONE launch, as these reference lines compute them on the device path, each step a separately rounded float32
+ *   operation in this order:
+ *     1. `out /= sum_weight` (demucs/apply.py:297-299), sum_weight rebuilt from the pass's segment list as mi_ola_finish does;
+ *     2. the shift average `out = piece.clone(); out.add_(piece) ...; out /= shifts` (apply.py:237-256), when shifts > 0;
+ *     3. the bag average `out[:, k] *= w[m][k]; estimates.add_(out) ...; estimates[:, k] /= totals[k]` (apply.py:201-229),
+ *        when bag != 0;
+ *     4. `x *= std; x += mean` (api.py:285-288, mi_track_affine inverse = 1), when stats_dev is not null.
+ *   PyTorch's CUDA kernels apply a host scalar divisor s as a product with float32(1 / s), the reciprocal taken in double:
+ *   scales_dev holds those float32 factors, per member [1 / shifts, w[m][0 .. S-1]] and then [1 / totals[k]] (n_members * (S + 1) + S floats).
+ *   Pass table (n_passes rows of MI_EMIT_PASS_COLS int64): the accumulator (S * channels, acc_len) at float offset acc_base of
+ *   acc_dev, the accumulator position q0 of sample t0, the pass's segments [seg_lo, seg_hi) of segs_dev ((offset, length)
+ *   int64 pairs in accumulator positions, ascending), its ramp of w_len floats at float offset w_off of weights_dev, and its
+ *   bag member.  Rows are grouped by member (ascending) and listed in pass order within a member.
+ *   out_dev (S, channels, n).  Reads are clamped to acc_capacity / weights_capacity / n_segs / n_members: a wrong table
+ *   changes results, never memory outside the buffers. */
+#define MI_EMIT_ACC_BASE 0
+#define MI_EMIT_ACC_LEN 1
+#define MI_EMIT_Q0 2
+#define MI_EMIT_SEG_LO 3
+#define MI_EMIT_SEG_HI 4
+#define MI_EMIT_W_OFF 5
+#define MI_EMIT_W_LEN 6
+#define MI_EMIT_MEMBER 7
+#define MI_EMIT_PASS_COLS 8
+int mi_stream_emit(const float *acc_dev, int64_t acc_capacity, int32_t n_sources, int32_t channels, const int64_t *passes_dev,
+                   int32_t n_passes, const int64_t *segs_dev, int32_t n_segs, const float *weights_dev, int64_t weights_capacity,
+                   const float *scales_dev, int32_t n_members, int32_t shifts, int32_t bag, const float *stats_dev, int64_t n,
+                   float *out_dev, int64_t out_capacity, void *stream);
+
 /* mi_resample_frac: `julius.resample_frac` as called by `demucs.audio.convert_audio` (demucs/audio.py:169-172), the step
  *   `Separator.separate_tensor` runs first when the input sample rate differs from the model's (demucs/api.py:265-266).
  *   old_sr / new_sr already divided by their gcd; table_dev (new_sr, 2*width + old_sr) is julius' windowed-sinc kernel bank
