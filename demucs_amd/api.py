@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .audio import convert_audio
 from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
-from .stream import ModelStream
+from .stream import ModelStream, StreamGroup
 
 __all__ = ["Separator", "SeparatorStream", "LoadModelError", "list_models"]
 
@@ -151,6 +151,15 @@ class Separator:
                          affine=None if mean is None else (mean, std))
         return SeparatorStream(st, self._model.sources)
 
+    def separate_stream_group(self) -> "SeparatorStreamGroup":
+        """Many `separate_stream`s of this separator's model at once (demucs_amd/stream.py, `StreamGroup`): `open(mean, std,
+        length)` starts a stream with `separate_stream`'s normalisation rule and returns its key, `push({key: block})` and
+        `finish(keys)` return `{key: {source: (channels, m)}}`.  The input must already be at the model's sample rate and channel
+        count."""
+        g = StreamGroup(self._model, shifts=self._shifts, overlap=self._overlap, segment=self._segment, split=self._split,
+                        device=self._device, progress=self._progress, callback=self._callback)
+        return SeparatorStreamGroup(g, self._model.sources)
+
     def _device_index(self) -> torch.device:
         device = torch.device(self._device)
         if device.index is None:
@@ -240,6 +249,35 @@ class SeparatorStream:
     @property
     def latency(self) -> int:
         return self.stream.latency
+
+
+class SeparatorStreamGroup:
+    """What `Separator.separate_stream_group` returns: every stream's stems as `{key: {source: (channels, m)}}`."""
+
+    def __init__(self, group, sources):
+        self.group, self.sources = group, list(sources)
+
+    def open(self, mean: Optional[float] = None, std: Optional[float] = None, length: Optional[int] = None):
+        if (mean is None) != (std is None):
+            raise ValueError("separate_stream_group: give both mean and std, or neither")
+        return self.group.open(length=length, affine=None if mean is None else (mean, std))
+
+    def push(self, blocks) -> Dict[object, Dict[str, torch.Tensor]]:
+        return {k: dict(zip(self.sources, v)) for k, v in self.group.push(blocks).items()}
+
+    def finish(self, keys) -> Dict[object, Dict[str, torch.Tensor]]:
+        return {k: dict(zip(self.sources, v)) for k, v in self.group.finish(keys).items()}
+
+    def emitted(self, key) -> int:
+        return self.group.emitted(key)
+
+    @property
+    def latency(self) -> int:
+        return self.group.latency
+
+    @property
+    def open_keys(self) -> list:
+        return self.group.open_keys
 
 
 def list_models(repo: Optional[Union[str, Path]] = None) -> Dict[str, Dict[str, Union[str, Path]]]:

@@ -36,7 +36,7 @@ from . import _lib
 from .hdemucs import HDemucs, MIN_LENGTH as _HDEMUCS_MIN_LENGTH
 from .htdemucs import HTDemucs
 
-__all__ = ["apply_model", "apply_model_many", "apply_model_stream", "BagOfModels", "TensorChunk", "tensor_chunk", "center_trim", "DummyPoolExecutor"]
+__all__ = ["apply_model", "apply_model_many", "apply_model_stream", "apply_model_stream_group", "BagOfModels", "TensorChunk", "tensor_chunk", "center_trim", "DummyPoolExecutor"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -681,4 +681,4 @@ def _to_host(out: torch.Tensor, device) -> torch.Tensor:
     return host
 
 
-from .stream import ModelStream, apply_model_stream  # noqa: E402,F401  (block-by-block separation, demucs_amd/stream.py)
+from .stream import ModelStream, StreamGroup, apply_model_stream, apply_model_stream_group  # noqa: E402,F401  (demucs_amd/stream.py)

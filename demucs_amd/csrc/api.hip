@@ -284,6 +284,35 @@ int mi_stream_emit(const float *acc_dev, int64_t acc_capacity, int32_t n_sources
                               weights_capacity, scales_dev, n_members, shifts, bag, stats_dev, n, out_dev, (hipStream_t)stream);
 }
 
+int mi_streams_emit(const float *acc_dev, int64_t acc_capacity, int32_t n_sources, int32_t channels, const int64_t *streams_dev,
+                    int32_t n_streams, int64_t max_n, const int64_t *passes_dev, int32_t n_passes, const int64_t *segs_dev, int32_t n_segs,
+                    const float *weights_dev, int64_t weights_capacity, const float *scales_dev, int32_t n_members, int32_t shifts,
+                    int32_t bag, const float *stats_dev, int32_t n_stats, float *out_dev, int64_t out_capacity, void *stream) {
+    MI_REQUIRE(acc_dev && streams_dev && passes_dev && segs_dev && weights_dev && scales_dev && out_dev && n_sources > 0 && channels > 0 &&
+               (int64_t)n_sources * channels <= 65535 && n_streams > 0 && n_streams <= 65535 && max_n >= 1 &&
+               max_n <= (int64_t)INT32_MAX * 256 && n_passes > 0 && n_segs >= 0 && n_members > 0 && shifts >= 0 && n_stats >= 0 &&
+               (n_stats == 0 || stats_dev) && acc_capacity >= 0 && weights_capacity > 0 && out_capacity >= 0,
+               "mi_streams_emit: bad argument");
+    return launch_streams_emit(acc_dev, acc_capacity, n_sources, channels, streams_dev, n_streams, max_n, passes_dev, n_passes, segs_dev,
+                               n_segs, weights_dev, weights_capacity, scales_dev, n_members, shifts, bag, stats_dev, n_stats, out_dev,
+                               out_capacity, (hipStream_t)stream);
+}
+
+int mi_streams_append(float *win_dev, int64_t win_capacity, int32_t channels, const int64_t *table_dev, int32_t n_streams, int64_t max_n,
+                      const float *stats_dev, int32_t n_stats, void *stream) {
+    MI_REQUIRE(win_dev && table_dev && channels > 0 && n_streams > 0 && (int64_t)n_streams * channels <= 65535 && max_n >= 1 &&
+               max_n <= (int64_t)INT32_MAX * 1024 && win_capacity > 0 && n_stats >= 0 && (n_stats == 0 || stats_dev),
+               "mi_streams_append: bad argument");
+    return launch_streams_append(win_dev, win_capacity, channels, table_dev, n_streams, max_n, stats_dev, n_stats, (hipStream_t)stream);
+}
+
+int mi_streams_compact(float *dst_dev, int64_t dst_capacity, const float *src_dev, int64_t src_capacity, const int64_t *table_dev,
+                       int32_t n_rows, int64_t max_len, void *stream) {
+    MI_REQUIRE(dst_dev && src_dev && table_dev && dst_dev != src_dev && n_rows > 0 && n_rows <= 65535 && max_len >= 1 && dst_capacity > 0 &&
+               src_capacity >= 0, "mi_streams_compact: bad argument");
+    return launch_streams_compact(dst_dev, dst_capacity, src_dev, src_capacity, table_dev, n_rows, max_len, (hipStream_t)stream);
+}
+
 int32_t mi_mono_stats_scratch_bytes(void) { return post_stats_scratch_bytes(); }
 
 int mi_mono_stats(const float *wav_dev, int32_t channels, int64_t length, void *scratch_dev, float *stats_dev, void *stream) {

@@ -167,6 +167,14 @@ int launch_mono_stats(const float *wav, int channels, int64_t length, double *sc
 int launch_stream_emit(const float *acc, int64_t acc_cap, int n_sources, int channels, const int64_t *passes, int n_passes,
                        const int64_t *segs, int n_segs, const float *weights, int64_t weights_cap, const float *scales, int n_members,
                        int shifts, int bag, const float *stats, int64_t n, float *out, hipStream_t st);
+int launch_streams_emit(const float *acc, int64_t acc_cap, int n_sources, int channels, const int64_t *streams, int n_streams, int64_t max_n,
+                        const int64_t *passes, int n_passes, const int64_t *segs, int n_segs, const float *weights, int64_t weights_cap,
+                        const float *scales, int n_members, int shifts, int bag, const float *stats, int n_stats, float *out,
+                        int64_t out_cap, hipStream_t st);
+int launch_streams_append(float *win, int64_t win_cap, int channels, const int64_t *table, int n_streams, int64_t max_n,
+                          const float *stats, int n_stats, hipStream_t st);
+int launch_streams_compact(float *dst, int64_t dst_cap, const float *src, int64_t src_cap, const int64_t *table, int n_rows, int64_t max_len,
+                           hipStream_t st);
 int launch_track_affine(float *x, int64_t n, const float *stats, int mode, hipStream_t st);
 int launch_prevent_clip(const float *x, int64_t n, int mode, unsigned *peak, float *y, hipStream_t st);
 int launch_two_stems(const float *const *stems, int S, int sel, const float *origin, int mode, int64_t n, float *y, hipStream_t st);

@@ -34,6 +34,7 @@ from __future__ import annotations
 
 import ctypes as C
 import random
+import weakref
 from typing import List, Optional
 
 import numpy as np
@@ -44,7 +45,7 @@ from . import _lib
 from .hdemucs import HDemucs, MIN_LENGTH as _HDEMUCS_MIN_LENGTH
 from .htdemucs import HTDemucs
 
-__all__ = ["apply_model_stream", "ModelStream", "EMIT_PASS_COLS"]
+__all__ = ["apply_model_stream", "apply_model_stream_group", "ModelStream", "StreamGroup", "EMIT_PASS_COLS"]
 
 # column layout of mi_stream_emit's pass table (include/demucs_amd.h, MI_EMIT_*)
 EMIT_PASS_COLS = 8
@@ -629,3 +630,535 @@ class _EngineExec:
                 if home is not None and st.bag_weights is not None:
                     m.model.to(home)
             return self._host(out)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# stream groups: many streams, one unit of work per push
+# ------------------------------------------------------------------------------------------------------------------------
+STREAMS_EMIT_COLS, APPEND_COLS, COMPACT_COLS = 7, 6, 4     # include/demucs_amd.h: MI_STREAMS_EMIT_*, MI_APPEND_*, MI_COMPACT_*
+ITEM_COLS = 8                                               # MI_PACK_ITEM_COLS
+
+
+def apply_model_stream_group(model, shifts: int = 1, overlap: float = 0.25, transition_power: float = 1.0, segment=None,
+                             device=None, split: bool = True, progress: bool = False, callback=None) -> "StreamGroup":
+    """Many streams of one model (see `StreamGroup`).  `device` defaults to the first pushed block's."""
+    return StreamGroup(model, shifts=shifts, overlap=overlap, transition_power=transition_power, segment=segment, device=device,
+                       split=split, progress=progress, callback=callback)
+
+
+class StreamGroup:
+    """Streams of one model that are pushed and finished together.  Each stream is a `ModelStream` whose own scheduler
+    (`_ready`, `_emit_limit`, `_keep_from`, `_segments_covering`, its RNG rules) decides what runs and what is final; the group
+    only pools the ready segments of all streams of a call into shared forwards.  A forward's item does not depend on its batch
+    position or on B, and every accumulator still receives its segments in ascending offset order, so `push({k: block, ...})`
+    returns for every key exactly what that stream's own `push(block)` would, in the mapping's order, with the same use of
+    `random`.
+
+    On the engines a call is a fixed amount of device work whatever the number of streams: one H2D of the call's int64 table
+    together with its host blocks, one `mi_streams_append`, the pooled forwards (each a gather, the forward and an overlap-add
+    driven by that table), one `mi_streams_emit` and one D2H of the host-bound stems, plus one `mi_streams_compact` when a
+    stream outgrows its room in the state buffer (every stream's window and accumulators).
+    Other models run the same scheduler one segment at a time on the plain-torch route."""
+
+    def __init__(self, model, shifts=1, overlap=0.25, transition_power=1.0, segment=None, device=None, split=True,
+                 progress=False, callback=None):
+        # shifts=0 draws nothing: the refusals and the members' geometry without any RNG call
+        probe = ModelStream(model, shifts=0, overlap=overlap, transition_power=transition_power, segment=segment, split=split,
+                            progress=progress, callback=callback)
+        self.model = model
+        self._kw = dict(shifts=shifts, overlap=overlap, transition_power=transition_power, segment=segment)
+        self.members, self.bag_weights = probe.members, probe.bag_weights
+        self.sources, self.audio_channels, self.samplerate = probe.sources, probe.audio_channels, probe.samplerate
+        self.latency = probe.latency
+        self.device = None if device is None else torch.device(device)
+        self._streams = {}
+        self._next = 0
+        self._exec = None
+
+    # ---- public --------------------------------------------------------------------------------------------------------
+    def open(self, length: Optional[int] = None, affine=None):
+        """A new stream; makes the RNG calls `ModelStream(..., length=length)` makes.  Returns its key."""
+        st = ModelStream(self.model, device=self.device, length=length, affine=affine, **self._kw)
+        key = self._next
+        self._next += 1
+        self._streams[key] = st
+        return key
+
+    @property
+    def open_keys(self) -> list:
+        return list(self._streams)
+
+    def emitted(self, key) -> int:
+        return self._stream(key).emitted
+
+    def pushed(self, key) -> int:
+        return self._stream(key).pushed
+
+    def device_bytes(self) -> int:
+        """Bytes of device memory the group itself holds (state buffer, stats, forward buffers)."""
+        return 0 if self._exec is None else self._exec.device_bytes()
+
+    def push(self, blocks) -> dict:
+        """`{key: (channels, n) block}` -> `{key: (S, channels, m) newly final stems}`, the streams taken in the mapping's order."""
+        items = list(blocks.items())
+        for key, block in items:
+            st = self._stream(key)
+            if not isinstance(block, torch.Tensor) or block.dim() != 2 or block.shape[0] != self.audio_channels:
+                shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
+                raise ValueError(f"expected a ({self.audio_channels}, n) block, got {shape}: a stream converts no channel layout")
+            if st.length is not None and st.pushed + block.shape[1] > st.length:
+                raise ValueError(f"pushed {st.pushed + block.shape[1]} samples, more than the declared length {st.length}")
+        if not items:
+            return {}
+        self._start(items[0][1].device)
+        return self._exec.push([(k, self._streams[k], b) for k, b in items])
+
+    def finish(self, keys) -> dict:
+        """Ends the streams `keys` (in that order) and returns `{key: remaining stems}`."""
+        keys = list(keys)
+        if len(set(keys)) != len(keys):
+            raise ValueError("finish: a stream key is listed twice")
+        for key in keys:
+            st = self._stream(key)
+            if st.length is not None and st.pushed != st.length:
+                raise ValueError(f"the stream ended after {st.pushed} samples, but length={st.length} was declared")
+            if st.pushed == 0:
+                raise ValueError("the stream ended before any sample was pushed")
+        if not keys:
+            return {}
+        out = self._exec.finish([(k, self._streams[k]) for k in keys])
+        for key in keys:
+            del self._streams[key]
+        return out
+
+    # ---- internals -----------------------------------------------------------------------------------------------------
+    def _stream(self, key) -> ModelStream:
+        try:
+            return self._streams[key]
+        except (KeyError, TypeError):
+            raise ValueError(f"unknown or finished stream key {key!r}") from None
+
+    def _start(self, block_device) -> None:
+        if self._exec is not None:
+            return
+        device = self.device if self.device is not None else torch.device(block_device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if all(m.kind != "generic" for m in self.members):
+            if device.type != "cuda":
+                raise ValueError("apply_model_stream: HTDemucs / HDemucs engines run on a GPU device")
+            self.device = device
+            self._exec = _GroupEngineExec(self)
+        else:
+            self.device = device
+            self._exec = _GroupTorchExec(self)
+
+
+class _GroupTorchExec:
+    """Models that are not the engine's: every stream's segments, one at a time, through its own `_TorchExec`."""
+
+    def __init__(self, g: StreamGroup):
+        self.g = weakref.proxy(g)          # no cycle: a dropped group frees its device memory at once
+        self.execs = {}
+
+    def device_bytes(self) -> int:
+        return sum(ex.device_bytes() for ex in self.execs.values())
+
+    def _exec(self, key, st: ModelStream) -> _TorchExec:
+        if key not in self.execs:
+            st.device = self.g.device
+            self.execs[key] = _TorchExec(st)
+        return self.execs[key]
+
+    def push(self, items) -> dict:
+        for key, st, block in items:
+            self._exec(key, st)._append(block)
+            st._out_device = block.device
+        for key, st, _ in items:
+            self.execs[key]._run(st._ready(final=False))
+        return {key: self.execs[key]._emit(st._emit_limit()) for key, st, _ in items}
+
+    def finish(self, items) -> dict:
+        return {key: self.execs.pop(key).finish() for key, _ in items}
+
+
+class _Slot:
+    """A stream's room in the group's state buffer: its window (channels, w_cap) at w_base, column 0 = track position w0, and
+    per pass an accumulator (rows, cap) at base, column 0 = the pass's `a0`.  Columns past what was written hold zeros."""
+
+    def __init__(self, st: ModelStream):
+        self.st = st
+        self.w_base = self.w_cap = self.w0 = 0
+        self.a_base = [0] * len(st.passes)
+        self.a_cap = [0] * len(st.passes)
+        self.stats = -1
+        self.placed = False
+
+
+class _GroupEngineExec:
+    def __init__(self, g: StreamGroup):
+        from .apply import _transition_weight
+        self.g = weakref.proxy(g)          # no cycle: a dropped group frees its device memory at once
+        dev = g.device
+        self.lib = _lib.load()
+        for m in g.members:
+            m.model.to(dev)
+            m.model.eval()
+        with torch.cuda.device(dev):
+            ramps = [_transition_weight(m.SL, m.transition_power, dev).to(torch.float32) for m in g.members]
+            self.w_offs = [sum(r.numel() for r in ramps[:e]) for e in range(len(ramps))]
+            self.weights = torch.cat(ramps).contiguous()
+            self.scales = _upload(emit_scales(g._kw["shifts"], len(g.members), g.bag_weights, len(g.sources)), torch.float32, dev)
+            self.state = torch.zeros(0, device=dev)
+            self.stats = torch.zeros(2, device=dev)
+        self.n_stats, self.stats_vals = 0, []
+        self.slots = {}
+        self.dead = False
+        self.bufs = {}
+        self.pad = max(m.V for m in g.members)
+
+    def device_bytes(self) -> int:
+        n = self.state.numel() + self.stats.numel() + sum(t.numel() for b in self.bufs.values() for t in set(b))
+        return 4 * n
+
+    def _stream(self):
+        return C.c_void_p(_lib.current_stream_ptr())
+
+    # ---- layout --------------------------------------------------------------------------------------------------------
+    def _fits(self, slot: _Slot, w_end: int, new_hi) -> bool:
+        if not slot.placed or w_end - slot.w0 > slot.w_cap:
+            return False
+        return all(h - ps.a0 <= cap for h, ps, cap in zip(new_hi, slot.st.passes, slot.a_cap))
+
+    def _compact(self, before, keep_w, new_hi, w_end, table: list):
+        """Lay every live slot out anew in a fresh state buffer: windows from `keep_w` on, accumulators from the emitted
+        position on, each with room for at least as much again (rooms never shrink, so a steady stream stops moving them).
+        Appends the copy rows to `table`; returns (new buffer, first row, rows, longest row)."""
+        g = self.g
+        C_ = g.audio_channels
+        rows, total, longest = [], 0, 1
+        stats_vals = []
+        for key, slot in self.slots.items():
+            st = slot.st
+            w0 = keep_w[key]
+            live_w = before[key] - w0 if slot.placed else 0
+            w_cap = max(slot.w_cap, 2 * (w_end[key] - w0) + self.pad)
+            for c in range(C_):
+                src = slot.w_base + c * slot.w_cap + (w0 - slot.w0)
+                rows.append((src if live_w > 0 else 0, total + c * w_cap, max(0, live_w), w_cap))
+            slot.w_base, slot.w_cap, slot.w0 = total, w_cap, w0
+            total += C_ * w_cap
+            longest = max(longest, w_cap)
+            for pi, ps in enumerate(st.passes):
+                m = st.members[ps.member]
+                a0 = st.emitted - ps.origin
+                hi = max(ps.hi, new_hi[key][pi])
+                live = ps.hi - a0 if slot.placed else 0
+                cap = max(slot.a_cap[pi], 2 * max(0, hi - a0) + m.SL)
+                for r in range(m.rows):
+                    src = slot.a_base[pi] + r * slot.a_cap[pi] + (a0 - ps.a0)
+                    rows.append((src if live > 0 else 0, total + r * cap, max(0, live), cap))
+                slot.a_base[pi], slot.a_cap[pi] = total, cap
+                ps.a0 = a0
+                total += m.rows * cap
+                longest = max(longest, cap)
+            if st.affine is not None:
+                slot.stats = len(stats_vals) // 2
+                stats_vals += list(st.affine)
+            else:
+                slot.stats = -1
+            slot.placed = True
+        first = len(table) // COMPACT_COLS
+        for r in rows:
+            table += r
+        self.dead = False
+        self.n_stats = len(stats_vals) // 2
+        if stats_vals != self.stats_vals:
+            self.stats_vals = stats_vals
+            self.stats = _upload(stats_vals or [0.0, 0.0], torch.float32, g.device)
+        return torch.empty(total, device=g.device, dtype=torch.float32), first, len(rows), longest
+
+    # ---- forwards ------------------------------------------------------------------------------------------------------
+    def _plan(self, units):
+        """Pool the ready units of all streams into forwards [(member, valid, [(key, pass index, offset, n)])]: per member,
+        HTDemucs in stream / pass / offset order, up to max_batch per forward; HDemucs one chunk length per forward, longest
+        first (lengths never grow along a pass, so every accumulator still receives its segments in ascending order)."""
+        g = self.g
+        plan = []
+        for e, m in enumerate(g.members):
+            mine = [(key, pi, o, n) for key, us in units for pi, o, n in us if self.slots[key].st.passes[pi].member == e]
+            for key, us in units:
+                st = self.slots[key].st
+                st._dispatch_draw(st.members[e], sum(1 for pi, _, _ in us if st.passes[pi].member == e))
+            if not mine:
+                continue
+            B = m.model.max_batch
+            if m.kind == "ht":
+                plan += [(e, m.V, mine[i:i + B]) for i in range(0, len(mine), B)]
+                continue
+            for n in sorted({u[3] for u in mine}, reverse=True):
+                same = [u for u in mine if u[3] == n]
+                plan += [(e, n, same[i:i + B]) for i in range(0, len(same), B)]
+        return plan
+
+    def _forward_tables(self, e, valid, fw, table: list):
+        g = self.g
+        m = g.members[e]
+        items, tiles, groups = [], [], []
+        for k, (key, pi, o, n) in enumerate(fw):
+            slot = self.slots[key]
+            ps = slot.st.passes[pi]
+            trim = (valid - n) // 2 if m.kind == "ht" else 0
+            items += [slot.w_base, slot.w_cap, ps.origin + o - trim - slot.w0, slot.a_base[pi], slot.a_cap[pi], o - ps.a0, n, trim]
+            if groups and groups[-1][0] == (key, pi):
+                groups[-1][2] = k + 1
+            else:
+                groups.append([(key, pi), k, k + 1])
+        for (key, pi), i0, i1 in groups:
+            slot = self.slots[key]
+            ps = slot.st.passes[pi]
+            us = fw[i0:i1]
+            lo = max(0, min(o - ps.a0 for _, _, o, _ in us))
+            hi = min(slot.a_cap[pi], max(o + n - ps.a0 for _, _, o, n in us))
+            for pos in range(lo, hi, TILE_SPAN):
+                tiles += [slot.a_base[pi], slot.a_cap[pi], pos, i0, i1, self.w_offs[e], m.SL]
+        at = len(table)
+        table += items + tiles
+        return at, len(tiles) // TILE_COLS
+
+    def _forward(self, e, valid, fw, t_items, n_tiles, keep):
+        g = self.g
+        m = g.members[e]
+        sub = m.model
+        dev = g.device
+        nb = len(fw)
+        channels = g.audio_channels
+
+        def gather(seg):
+            _lib.check(self.lib.mi_segments_gather_packed(self.state.data_ptr(), self.state.numel(), channels, C.c_void_p(t_items),
+                                                          nb, valid, seg.data_ptr(), seg.numel(), self._stream()),
+                       "mi_segments_gather_packed")
+
+        if m.kind == "ht":
+            SL = sub.segment_length
+            if e not in self.bufs:
+                B = sub.max_batch
+                seg_buf = torch.zeros(B, channels, SL, device=dev, dtype=torch.float32)
+                cut_buf = torch.empty(B, channels, valid, device=dev, dtype=torch.float32) if valid < SL else seg_buf
+                self.bufs[e] = (seg_buf, cut_buf, torch.empty(B, len(sub.sources), channels, SL, device=dev, dtype=torch.float32))
+            seg_buf, cut_buf, out_buf = self.bufs[e]
+            gather(cut_buf[:nb])
+            if valid < SL:
+                seg_buf[:nb, :, :valid] = cut_buf[:nb]          # right zero padding, as HTDemucs.forward
+            out = out_buf[:nb]
+            sub.forward_segments(seg_buf[:nb], out)
+            out_valid = SL
+        else:
+            seg = torch.empty(nb, channels, valid, device=dev, dtype=torch.float32)
+            gather(seg)
+            side = nb == 1 and valid < m.SL and valid >= _HDEMUCS_MIN_LENGTH     # a lone tail: the single-item side engine
+            out = sub(seg, aux=True) if side else sub(seg)
+            out_valid = valid
+            keep.append(out)
+        if n_tiles:
+            _lib.check(self.lib.mi_ola_accumulate_packed(self.state.data_ptr(), self.state.numel(), m.rows, out.data_ptr(), out_valid,
+                                                         out.numel(), C.c_void_p(t_items), nb, C.c_void_p(t_items + 8 * ITEM_COLS * nb),
+                                                         n_tiles, self.weights.data_ptr(), self.weights.numel(), self._stream()),
+                       "mi_ola_accumulate_packed")
+
+    # ---- one call --------------------------------------------------------------------------------------------------------
+    def _step(self, work, final: bool) -> dict:
+        """work: [(key, stream, block or None)] in call order."""
+        g = self.g
+        dev = g.device
+        S, C_ = len(g.sources), g.audio_channels
+        keep = []
+        with torch.cuda.device(dev):
+            # 1. the streams' own scheduling: windows to keep, new samples, ready segments, what becomes final
+            for key, st, _ in work:
+                if key not in self.slots:
+                    self.slots[key] = _Slot(st)
+                    st.device = dev
+            # the first window position a pending segment can read, before this call dispatches any (as ModelStream's append)
+            before = {key: slot.st.pushed for key, slot in self.slots.items()}
+            keep_w = {key: slot.st._keep_from() for key, slot in self.slots.items()}
+            units, blocks = [], []
+            for key, st, block in work:
+                if block is not None:
+                    st.pushed += block.shape[1]
+                    st._out_device = block.device
+                    blocks.append((key, self.slots[key], block))
+                else:
+                    st.finished = True
+            for key, st, _ in work:
+                units.append((key, st._ready(final=final)))
+            w_end = {key: slot.st.pushed for key, slot in self.slots.items()}
+            new_hi = {key: [ps.hi for ps in slot.st.passes] for key, slot in self.slots.items()}
+            for key, us in units:
+                for pi, o, n in us:
+                    new_hi[key][pi] = max(new_hi[key][pi], o + n)
+            # 2. one int64 table for the whole call: compaction rows, append rows, every forward's items and tiles, the emit
+            table = []
+            compact = None
+            if self.dead or not all(self._fits(s, w_end[k], new_hi[k]) for k, s in self.slots.items()):
+                compact = self._compact(before, keep_w, new_hi, w_end, table)
+            for key, us in units:
+                slot = self.slots[key]
+                for pi, o, n in us:
+                    ps = slot.st.passes[pi]
+                    ps.hi = max(ps.hi, o + n)
+            append, staged = self._append_rows(blocks, table, keep)
+            plan = [(e, valid, fw, *self._forward_tables(e, valid, fw, table)) for e, valid, fw in self._plan(units)]
+            emit = self._emit_rows(work, table)
+            base = self._upload(table, staged, keep)
+            # 3. device work
+            if compact is not None:
+                state, first, n_rows, longest = compact
+                # nothing to copy from an empty buffer: any live pointer, capacity 0
+                old, old_cap = (self.state, self.state.numel()) if self.state.numel() else (self.weights, 0)
+                for r0 in range(0, n_rows, 65535):
+                    nr = min(65535, n_rows - r0)
+                    _lib.check(self.lib.mi_streams_compact(state.data_ptr(), state.numel(), old.data_ptr(), old_cap,
+                                                           C.c_void_p(base + 8 * COMPACT_COLS * (first + r0)), nr, longest,
+                                                           self._stream()), "mi_streams_compact")
+                self.state = state
+            if append is not None:
+                at, n_rows, longest = append
+                _lib.check(self.lib.mi_streams_append(self.state.data_ptr(), self.state.numel(), C_, C.c_void_p(base + 8 * at), n_rows,
+                                                      longest, self.stats.data_ptr(), self.n_stats, self._stream()),
+                           "mi_streams_append")
+            for e, valid, fw, at, n_tiles in plan:
+                self._forward(e, valid, fw, base + 8 * at, n_tiles, keep)
+            outs = self._emit(emit, base)
+            if final:
+                for m in g.members:
+                    if m.kind == "h":
+                        m.model.check()      # a time-out of the LAST forward's recurrence would otherwise pass unnoticed
+                for key, _, _ in work:
+                    del self.slots[key]
+                    self.dead = True
+                if not self.slots:
+                    self.state = torch.zeros(0, device=dev)
+            return outs
+
+    def _append_rows(self, blocks, table, keep):
+        """mi_streams_append's rows.  Device blocks are read where they are; a host block's source is named once the call's
+        upload buffer exists (`_upload`).  Returns ((first row, rows, longest block) or None, [(table index, float offset, block)])."""
+        g = self.g
+        live = [(key, slot, b) for key, slot, b in blocks if b.shape[1] > 0]
+        if not live:
+            return None, []
+        at = len(table)
+        longest, staged, off = 1, [], 0
+        for key, slot, b in live:
+            n = b.shape[1]
+            if b.device.type == "cpu":
+                staged.append((len(table), off, b))
+                off += b.numel()
+                src = 0
+            else:
+                d = b.to(device=g.device, dtype=torch.float32).contiguous()
+                keep.append(d)
+                src = d.data_ptr()
+            table += [src, n, slot.w_base, slot.w_cap, slot.st.pushed - n - slot.w0, slot.stats]
+            longest = max(longest, n)
+        return (at, len(live), longest), staged
+
+    def _upload(self, table, staged, keep) -> int:
+        """The call's int64 table and its host blocks (float32) in one pinned buffer, down in ONE H2D.  Returns the table's
+        device address."""
+        T = max(1, len(table))
+        f_at = -(-8 * T // 16) * 16
+        n_floats = sum(b.numel() for _, _, b in staged)
+        nbytes = f_at + 4 * n_floats
+        dev_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.g.device)
+        base = dev_buf.data_ptr()
+        for pos, off, _ in staged:
+            table[pos] = base + f_at + 4 * off
+        host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        np.frombuffer(host.numpy(), dtype=np.int64, count=T)[:] = table or [0]
+        if staged:
+            floats = host[f_at:].view(torch.float32)
+            for _, off, b in staged:
+                floats[off:off + b.numel()].view(b.shape).copy_(b)
+        dev_buf.copy_(host, non_blocking=True)
+        keep += [host, dev_buf]
+        return base
+
+    def _emit_rows(self, work, table):
+        """mi_streams_emit's tables for every stream of the call with new final samples; host-bound stems first."""
+        g = self.g
+        S, C_ = len(g.sources), g.audio_channels
+        spans = []
+        for key, st, _ in work:
+            t0, t1 = st.emitted, st._emit_limit()
+            dev = st._out_device
+            spans.append((key, st, t0, t1, dev is not None and torch.device(dev).type == "cpu"))
+        spans.sort(key=lambda s: not s[4])
+        streams, passes, segs = [], [], []
+        off, host_n, longest = 0, 0, 1
+        layout = {}
+        for key, st, t0, t1, to_host in spans:
+            n = t1 - t0
+            layout[key] = (off, n)
+            if n > 0:
+                slot = self.slots[key]
+                p_lo, s_lo = len(passes) // 8, len(segs) // 2
+                for pi, ps in enumerate(st.passes):
+                    q0, q1 = t0 - ps.origin, t1 - ps.origin
+                    g_lo = len(segs) // 2
+                    for o, sn in st._segments_covering(ps, q0, q1):
+                        segs += [o - ps.a0, sn]
+                    e = ps.member
+                    passes += [slot.a_base[pi], slot.a_cap[pi], q0 - ps.a0, g_lo, len(segs) // 2, self.w_offs[e], g.members[e].SL, e]
+                streams += [p_lo, len(passes) // 8, s_lo, len(segs) // 2, slot.stats, off, n]
+                longest = max(longest, n)
+            off += S * C_ * n
+            if to_host:
+                host_n = off
+            st.emitted = t1
+        at = len(table)
+        table += streams + passes + (segs or [0, 0])
+        return dict(at=at, n_streams=len(streams) // STREAMS_EMIT_COLS, n_passes=len(passes) // 8, n_segs=len(segs) // 2,
+                    total=off, host_n=host_n, longest=longest, layout=layout, order=[k for k, _, _ in work],
+                    streams={k: st for k, st, _ in work})
+
+    def _emit(self, emit, base) -> dict:
+        g = self.g
+        dev = g.device
+        S, C_ = len(g.sources), g.audio_channels
+        out = torch.empty(emit["total"], device=dev, dtype=torch.float32) if emit["total"] else None
+        if emit["n_streams"]:
+            at = base + 8 * emit["at"]
+            t_streams = at
+            t_passes = t_streams + 8 * STREAMS_EMIT_COLS * emit["n_streams"]
+            t_segs = t_passes + 8 * EMIT_PASS_COLS * emit["n_passes"]
+            _lib.check(self.lib.mi_streams_emit(self.state.data_ptr(), self.state.numel(), S, C_, C.c_void_p(t_streams),
+                                                emit["n_streams"], emit["longest"], C.c_void_p(t_passes), emit["n_passes"],
+                                                C.c_void_p(t_segs), emit["n_segs"], self.weights.data_ptr(), self.weights.numel(),
+                                                self.scales.data_ptr(), len(g.members), g._kw["shifts"],
+                                                int(g.bag_weights is not None), self.stats.data_ptr(), self.n_stats, out.data_ptr(),
+                                                out.numel(), self._stream()), "mi_streams_emit")
+        host = None
+        if emit["host_n"]:
+            host = torch.empty(emit["host_n"], dtype=torch.float32, pin_memory=True)
+            host.copy_(out[:emit["host_n"]], non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+        res = {}
+        for key in emit["order"]:
+            off, n = emit["layout"][key]
+            st = emit["streams"][key]
+            to = st._out_device
+            if n == 0:
+                res[key] = torch.empty(S, C_, 0, dtype=torch.float32, device=to)
+            elif host is not None and off < emit["host_n"]:
+                res[key] = host[off:off + S * C_ * n].view(S, C_, n)
+            else:
+                res[key] = st._result(out[off:off + S * C_ * n].view(S, C_, n))
+        return res
+
+    def push(self, items) -> dict:
+        return self._step(items, final=False)
+
+    def finish(self, items) -> dict:
+        return self._step([(k, st, None) for k, st in items], final=True)

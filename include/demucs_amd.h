@@ -262,6 +262,49 @@ int mi_stream_emit(const float *acc_dev, int64_t acc_capacity, int32_t n_sources
                    const float *scales_dev, int32_t n_members, int32_t shifts, int32_t bag, const float *stats_dev, int64_t n,
                    float *out_dev, int64_t out_capacity, void *stream);
 
+/* ---- stream groups: many streams as one unit of work per push (demucs_amd/stream.py, StreamGroup) ---------------------------
+ * All tables are int64 DEVICE arrays; every read and write of a buffer is clamped to its declared capacity (floats) or table size.
+ *
+ * mi_streams_emit: mi_stream_emit for every stream of a table in ONE launch, each stream's (row, sample) the same float32 chain.
+ *   Stream table (n_streams rows of MI_STREAMS_EMIT_COLS): the stream's rows [pass_lo, pass_hi) of the pass table (MI_EMIT_*
+ *   columns, its accumulators in acc_dev), the range [seg_lo, seg_hi) of segs_dev its pass rows' segment ranges are clamped to,
+ *   the index of its (mean, std + 1e-8) pair in stats_dev (n_stats pairs; negative: no affine), and its stems (S, channels, n) at
+ *   float offset out_off of out_dev.  max_n >= every n (grid size); rows with n = 0 write nothing.
+ * mi_streams_append: row s of the table (MI_APPEND_COLS) writes the stream's new block, (channels, n) float32 at the DEVICE
+ *   address `src` (row stride n), into columns [col, col + n) of its window (channels, dst_len) at float offset dst_off of win_dev,
+ *   as `(x - mean) / s` (mi_track_affine inverse = 0) when its stats index names a pair of stats_dev.  `src` is trusted: the
+ *   caller names live blocks of at least channels * n floats; the writes are clamped to the window.
+ * mi_streams_compact: row r of the table (MI_COMPACT_COLS) copies n floats from float offset src_off of src_dev to dst_off of
+ *   dst_dev and writes zeros after them up to len floats (src_dev and dst_dev must not overlap); max_len >= every len. */
+#define MI_STREAMS_EMIT_PASS_LO 0
+#define MI_STREAMS_EMIT_PASS_HI 1
+#define MI_STREAMS_EMIT_SEG_LO 2
+#define MI_STREAMS_EMIT_SEG_HI 3
+#define MI_STREAMS_EMIT_STATS 4
+#define MI_STREAMS_EMIT_OUT_OFF 5
+#define MI_STREAMS_EMIT_N 6
+#define MI_STREAMS_EMIT_COLS 7
+#define MI_APPEND_SRC 0
+#define MI_APPEND_N 1
+#define MI_APPEND_DST_OFF 2
+#define MI_APPEND_DST_LEN 3
+#define MI_APPEND_COL 4
+#define MI_APPEND_STATS 5
+#define MI_APPEND_COLS 6
+#define MI_COMPACT_SRC_OFF 0
+#define MI_COMPACT_DST_OFF 1
+#define MI_COMPACT_N 2
+#define MI_COMPACT_LEN 3
+#define MI_COMPACT_COLS 4
+int mi_streams_emit(const float *acc_dev, int64_t acc_capacity, int32_t n_sources, int32_t channels, const int64_t *streams_dev,
+                    int32_t n_streams, int64_t max_n, const int64_t *passes_dev, int32_t n_passes, const int64_t *segs_dev, int32_t n_segs,
+                    const float *weights_dev, int64_t weights_capacity, const float *scales_dev, int32_t n_members, int32_t shifts,
+                    int32_t bag, const float *stats_dev, int32_t n_stats, float *out_dev, int64_t out_capacity, void *stream);
+int mi_streams_append(float *win_dev, int64_t win_capacity, int32_t channels, const int64_t *table_dev, int32_t n_streams, int64_t max_n,
+                      const float *stats_dev, int32_t n_stats, void *stream);
+int mi_streams_compact(float *dst_dev, int64_t dst_capacity, const float *src_dev, int64_t src_capacity, const int64_t *table_dev,
+                       int32_t n_rows, int64_t max_len, void *stream);
+
 /* mi_resample_frac: `julius.resample_frac` as called by `demucs.audio.convert_audio` (demucs/audio.py:169-172), the step
  *   `Separator.separate_tensor` runs first when the input sample rate differs from the model's (demucs/api.py:265-266).
  *   old_sr / new_sr already divided by their gcd; table_dev (new_sr, 2*width + old_sr) is julius' windowed-sinc kernel bank
