@@ -132,7 +132,7 @@ class Separator:
             return [self._restore_on_device(st, out[None], device) for st, out in zip(states, outs)]
 
     def separate_stream(self, mean: Optional[float] = None, std: Optional[float] = None, sr: Optional[int] = None,
-                        length: Optional[int] = None) -> "SeparatorStream":
+                        length: Optional[int] = None, convert: bool = False, channels: Optional[int] = None) -> "SeparatorStream":
         """`separate_tensor` for a track that arrives block by block (demucs_amd/stream.py): `push(block)` takes (channels, n)
         float32 and returns `{source: (channels, m)}` of the newly final samples, `finish()` the rest.
 
@@ -140,25 +140,60 @@ class Separator:
         them (from an earlier analysis pass, or `mi_mono_stats` on a prefix): blocks become `(x - mean) / s` and stems
         `x * s + mean`, s = float32(std) + 1e-8 in float32, and with the track's own statistics the concatenated stems equal
         `separate_tensor`'s bit for bit.  Without them nothing is normalised, which differs from `separate_tensor`.  `length`
-        is `apply_model_stream`'s.  The input must already be at the model's sample rate and channel count."""
-        if sr is not None and sr != self._samplerate:
-            raise ValueError(f"separate_stream: input sample rate {sr} is not the model's {self._samplerate}; a stream does not "
-                             "resample")
+        is `apply_model_stream`'s.
+
+        Without `convert=True` the input must already be at the model's sample rate and channel count.  With it, blocks are
+        (`channels` or the model's, n) at `sr` and pass through `convert_audio` on the device first (`audio.ConvertStream`:
+        mono to the model's channels or the first channels, then the resampler), so the concatenated stems equal
+        `separate_tensor(wav, sr)`'s bit for bit; `mean` / `std` are those of the CONVERTED track, `length` counts input samples
+        at `sr`, stems come back at the model's rate, and `input_latency` bounds the lag in input samples."""
+        if not convert:
+            if channels is not None and channels != self._audio_channels:
+                raise ValueError(f"separate_stream: {channels} input channels are not the model's {self._audio_channels}; pass "
+                                 "convert=True to convert the channel layout on the stream")
+            if sr is not None and sr != self._samplerate:
+                raise ValueError(f"separate_stream: input sample rate {sr} is not the model's {self._samplerate}; a stream does not "
+                                 "resample unless convert=True")
         if (mean is None) != (std is None):
             raise ValueError("separate_stream: give both mean and std, or neither")
+        plan = self._convert_plan(sr, channels) if convert else None
+        if plan is not None and length is not None:
+            if int(length) < 0:
+                raise ValueError(f"length must be >= 0, got {length}")
+            in_length, length = int(length), plan.final_count(int(length))
         st = ModelStream(self._model, shifts=self._shifts, overlap=self._overlap, segment=self._segment, split=self._split,
                          device=self._device, length=length, progress=self._progress, callback=self._callback,
                          affine=None if mean is None else (mean, std))
-        return SeparatorStream(st, self._model.sources)
+        if plan is None:
+            return SeparatorStream(st, self._model.sources)
+        return ConvertingSeparatorStream(st, self._model.sources, plan, channels or self._audio_channels,
+                                         in_length if length is not None else None, self._device_index)
+
+    def _convert_plan(self, sr: Optional[int], channels: Optional[int]):
+        """The refusals of a converting stream (before any device work or RNG call) and its `audio.ConvertPlan`; None when the
+        input is already what the model takes."""
+        from .audio import ConvertPlan, check_stream_channels
+        sr = self._samplerate if sr is None else sr
+        src_channels = self._audio_channels if channels is None else channels
+        if int(sr) != sr or sr <= 0:
+            raise ValueError(f"separate_stream: the sample rate must be a positive integer, got {sr}")
+        check_stream_channels(int(src_channels), self._audio_channels)
+        if int(sr) == self._samplerate and src_channels == self._audio_channels:
+            return None
+        if not _is_engine(self._model) or torch.device(self._device).type != "cuda":
+            raise ValueError("separate_stream: convert=True runs on the GPU engines (HTDemucs / HDemucs on a cuda device); there is "
+                             "no CPU resampler in this package")
+        return ConvertPlan(int(sr), self._samplerate)
 
     def separate_stream_group(self) -> "SeparatorStreamGroup":
         """Many `separate_stream`s of this separator's model at once (demucs_amd/stream.py, `StreamGroup`): `open(mean, std,
-        length)` starts a stream with `separate_stream`'s normalisation rule and returns its key, `push({key: block})` and
-        `finish(keys)` return `{key: {source: (channels, m)}}`.  The input must already be at the model's sample rate and channel
-        count."""
+        length, sr, channels)` starts a stream with `separate_stream`'s normalisation rule and returns its key,
+        `push({key: block})` and `finish(keys)` return `{key: {source: (channels, m)}}`.  A stream opened with an `sr` or a
+        channel count that is not the model's converts on the device as `separate_stream(convert=True)` does, each stream with
+        its own rate; the others must already be at the model's sample rate and channel count."""
         g = StreamGroup(self._model, shifts=self._shifts, overlap=self._overlap, segment=self._segment, split=self._split,
                         device=self._device, progress=self._progress, callback=self._callback)
-        return SeparatorStreamGroup(g, self._model.sources)
+        return SeparatorStreamGroup(g, self._model.sources, self)
 
     def _device_index(self) -> torch.device:
         device = torch.device(self._device)
@@ -251,16 +286,75 @@ class SeparatorStream:
         return self.stream.latency
 
 
+class ConvertingSeparatorStream(SeparatorStream):
+    """`Separator.separate_stream(convert=True)`: an `audio.ConvertStream` on the device in front of the model's stream.
+    `emitted` and `latency` count samples at the model's rate, `pushed_input` and `input_latency` input samples:
+    after every push `pushed_input - ceil(emitted * old / new) <= input_latency = width + old - 1 + floor(latency * old / new)`
+    (old / new the rates divided by their gcd): the converter holds back at most `width + old - 1` input samples and the model's
+    stream `latency` of its own; a push that meets both bounds at once reaches it."""
+
+    def __init__(self, stream, sources, plan, src_channels, in_length, device_index):
+        super().__init__(stream, sources)
+        self.plan, self.src_channels, self.in_length = plan, int(src_channels), in_length
+        self.input_latency = plan.width + plan.old - 1 + stream.latency * plan.old // plan.new
+        self.pushed_input = 0
+        self._device_index = device_index
+        self._cv = None
+
+    def push(self, block: torch.Tensor) -> Dict[str, torch.Tensor]:
+        if self.stream.finished:
+            raise RuntimeError("push after finish()")
+        if not isinstance(block, torch.Tensor) or block.dim() != 2 or block.shape[0] != self.src_channels:
+            shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
+            raise ValueError(f"expected a ({self.src_channels}, n) block, got {shape}")
+        if self.in_length is not None and self.pushed_input + block.shape[1] > self.in_length:
+            raise ValueError(f"pushed {self.pushed_input + block.shape[1]} samples, more than the declared length {self.in_length}")
+        if self._cv is None:
+            from .audio import ConvertStream
+            self._cv = ConvertStream(None, None, self.stream.audio_channels, device=self._device_index(), plan=self.plan)
+        y = self._cv.push(block, on_device=True)
+        self.pushed_input = self._cv.pushed
+        return self._stems(self.stream.push(y), block.device)
+
+    def finish(self) -> Dict[str, torch.Tensor]:
+        if self.stream.finished:
+            raise RuntimeError("finish() called twice")
+        if self.in_length is not None and self.pushed_input != self.in_length:
+            raise ValueError(f"the stream ended after {self.pushed_input} samples, but length={self.in_length} was declared")
+        if self._cv is None or self.pushed_input == 0:
+            raise ValueError("the stream ended before any sample was pushed")
+        to = self._cv._out_device
+        y = self._cv.finish(on_device=True)
+        parts = [self.stream.push(y)] if y.shape[1] else []
+        parts.append(self.stream.finish())
+        return self._stems(parts[0] if len(parts) == 1 else torch.cat(parts, -1), to)
+
+    def _stems(self, out: torch.Tensor, to) -> Dict[str, torch.Tensor]:
+        if to is not None and torch.device(to).type == "cpu":
+            out = _to_host(out, out.device)
+        return dict(zip(self.sources, out))
+
+    def device_bytes(self) -> int:
+        return self.stream.device_bytes() + (0 if self._cv is None else self._cv.device_bytes())
+
+
 class SeparatorStreamGroup:
     """What `Separator.separate_stream_group` returns: every stream's stems as `{key: {source: (channels, m)}}`."""
 
-    def __init__(self, group, sources):
-        self.group, self.sources = group, list(sources)
+    def __init__(self, group, sources, separator=None):
+        self.group, self.sources, self.separator = group, list(sources), separator
 
-    def open(self, mean: Optional[float] = None, std: Optional[float] = None, length: Optional[int] = None):
+    def open(self, mean: Optional[float] = None, std: Optional[float] = None, length: Optional[int] = None,
+             sr: Optional[int] = None, channels: Optional[int] = None):
+        """`length`, `sr` and `channels` describe the stream's INPUT, as for `separate_stream(convert=True)`."""
         if (mean is None) != (std is None):
             raise ValueError("separate_stream_group: give both mean and std, or neither")
-        return self.group.open(length=length, affine=None if mean is None else (mean, std))
+        convert = None
+        if sr is not None or channels is not None:
+            plan = self.separator._convert_plan(sr, channels)
+            if plan is not None:
+                convert = (plan, int(channels or self.separator.audio_channels))
+        return self.group.open(length=length, affine=None if mean is None else (mean, std), convert=convert)
 
     def push(self, blocks) -> Dict[object, Dict[str, torch.Tensor]]:
         return {k: dict(zip(self.sources, v)) for k, v in self.group.push(blocks).items()}

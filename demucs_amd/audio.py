@@ -82,6 +82,202 @@ def convert_audio(wav: torch.Tensor, from_samplerate: int, to_samplerate: int, c
     return resample_frac(wav, from_samplerate, to_samplerate, device)
 
 
+# ---- convert_audio for a stream: the same float32 chain per output, whatever the partition of the input ------------------
+CVT_COLS = 20                      # include/demucs_amd.h: MI_CVT_*
+CVT_LDS_FLOATS = 16384             # MI_CVT_LDS_FLOATS: the kernel's LDS staging area (64 KiB)
+CVT_FRAMES, CVT_SUBRUNS, CVT_COPY_SPAN = 8, 4, 1024
+
+
+def check_stream_channels(src_channels: int, channels: int) -> None:
+    """`convert_audio_channels`' cases that a stream takes: the three per-sample ones."""
+    if src_channels < 1:
+        raise ValueError(f"a block needs at least one channel, got {src_channels}")
+    if src_channels == channels or src_channels == 1:
+        return
+    if channels == 1:
+        raise ValueError("a stream does not down-mix to mono (the mean over channels): convert the input before pushing it")
+    if src_channels < channels:
+        raise ValueError('The audio file has less channels than requested but is not mono.')
+
+
+class ConvertPlan:
+    """The arithmetic of a streaming `resample_frac` (no device work).  For old / new = the rates divided by their gcd, `width`
+    and klen = 2 * width + old as `sinc_bank` builds them, output n * new + i reads inputs clamp(n * old - width + k), k < klen.
+    Frame n (its `new` outputs) is final iff its last tap is pushed: n * old + width + old <= P."""
+
+    def __init__(self, from_samplerate: int, to_samplerate: int, zeros: int = ZEROS, rolloff: float = ROLLOFF):
+        from_samplerate, to_samplerate = int(from_samplerate), int(to_samplerate)
+        if from_samplerate <= 0 or to_samplerate <= 0:
+            raise ValueError(f"sample rates must be positive, got {from_samplerate} -> {to_samplerate}")
+        gcd = math.gcd(from_samplerate, to_samplerate)
+        self.old, self.new = from_samplerate // gcd, to_samplerate // gcd
+        self.copy = self.old == self.new                                   # equal rates: no filter, nothing is held back
+        self.width = 0 if self.copy else math.ceil(zeros * self.old / (min(self.new, self.old) * rolloff))   # sinc_bank's
+        self.klen = 2 * self.width + self.old
+        if not self.copy and CVT_FRAMES * self.old + 2 * self.width > CVT_LDS_FLOATS:
+            raise ValueError(f"the rate pair {from_samplerate} -> {to_samplerate} reduces to {self.old}:{self.new}: a frame of "
+                             f"{self.old} input samples is too long for the stream kernel; resample the whole track instead")
+        # floor(new * P / old) - ready(P) is largest one sample before a frame completes: P = width + old - 1 (+ a multiple of old)
+        self.hold = 0 if self.copy else self.new * (self.width + self.old - 1) // self.old
+        self.carry = 0 if self.copy else self.klen - 1                    # most input samples kept between two pushes
+
+    def ready(self, pushed: int) -> int:
+        """Outputs that are final after `pushed` input samples."""
+        if self.copy:
+            return pushed
+        return self.new * max(0, (pushed - self.width - self.old) // self.old + 1)
+
+    def final_count(self, total: int) -> int:
+        """The whole track's output length (`resample_frac`'s default)."""
+        return self.new * total // self.old
+
+    def carry_start(self, pushed: int) -> int:
+        """First input sample the first frame that is not ready reads (the left clamp keeps sample 0 while it is needed)."""
+        if self.copy:
+            return pushed
+        return max(0, self.ready(pushed) // self.new * self.old - self.width)
+
+    def subruns(self) -> int:
+        """8-frame runs a workgroup of the kernel takes (convert_stream.hip)."""
+        return min(CVT_SUBRUNS, (CVT_LDS_FLOATS - 2 * self.width) // (CVT_FRAMES * self.old))
+
+    def groups(self, n_out: int) -> int:
+        """Workgroups per row for `n_out` outputs."""
+        if self.copy:
+            return max(1, -(-n_out // CVT_COPY_SPAN))
+        return max(1, -(-(-(-n_out // self.new)) // (CVT_FRAMES * self.subruns())))
+
+    def lds_floats(self) -> int:
+        return 1 if self.copy else CVT_FRAMES * self.subruns() * self.old + 2 * self.width
+
+    def step(self, pushed: int, n_in: int, final: bool):
+        """One call: (first output, outputs to write, carried start for the next call or -1 when final)."""
+        total = pushed + n_in
+        out0 = self.ready(pushed)
+        if final:
+            return out0, self.final_count(total) - out0, -1
+        return out0, self.ready(total) - out0, self.carry_start(total)
+
+
+class _BankArena:
+    """Every rate pair's transposed kernel bank ([klen][new]: a tap's coefficients of all phases side by side) in one device
+    buffer per device, built once per pair.  Offsets never move; a grown buffer is a new tensor (calls in flight keep theirs)."""
+    _arenas = {}
+
+    def __init__(self, dev):
+        self.dev, self.buf, self.offs = dev, torch.zeros(0, device=dev), {}
+
+    @classmethod
+    def get(cls, dev) -> "_BankArena":
+        dev = torch.device(dev)
+        if dev not in cls._arenas:
+            cls._arenas[dev] = cls(dev)
+        return cls._arenas[dev]
+
+    def offset(self, plan: ConvertPlan) -> int:
+        key = (plan.old, plan.new)
+        if plan.copy:
+            return 0
+        if key not in self.offs:
+            width, bank = sinc_bank(plan.old, plan.new)
+            assert width == plan.width and bank.shape == (plan.new, plan.klen)
+            self.offs[key] = self.buf.numel()
+            self.buf = torch.cat([self.buf, bank.t().contiguous().reshape(-1).to(self.dev)])
+        return self.offs[key]
+
+
+def convert_audio_stream(from_samplerate: int, to_samplerate: int, channels: int, device="cuda", affine=None) -> "ConvertStream":
+    """`convert_audio` for a track that arrives block by block: `torch.cat([*pushes, finish], -1)` equals
+    `convert_audio(full, from_samplerate, to_samplerate, channels)` bit for bit for every partition of the input."""
+    return ConvertStream(from_samplerate, to_samplerate, channels, device=device, affine=affine)
+
+
+class ConvertStream:
+    """`push(block)` takes (source channels, n) float32 on the host or a device and returns the (channels, m) outputs that became
+    final, on the block's device; `finish()` returns the rest.  `pushed` counts input samples, `emitted` output samples;
+    `floor(new * pushed / old) - emitted <= hold`, and some push reaches it.  The source channel count is the first block's.
+    `affine=(mean, s)` writes `(y - mean) / s` instead (mi_track_affine inverse = 0 on the converted samples).
+    Device state: two sides of (channels, klen - 1) carried input samples, whatever the stream's duration."""
+
+    def __init__(self, from_samplerate, to_samplerate, channels: int, device="cuda", affine=None, plan=None):
+        self.plan = plan if plan is not None else ConvertPlan(from_samplerate, to_samplerate)
+        self.channels = int(channels)
+        if self.channels < 1:
+            raise ValueError(f"channels must be >= 1, got {channels}")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.EngineError("demucs_amd.audio.convert_audio_stream only runs on a GPU device (MI355X)")
+        self.device = dev
+        self.hold = self.plan.hold
+        self.pushed = self.emitted = 0
+        self.src_channels = None
+        self.finished = False
+        self.affine = None if affine is None else tuple(float(v) for v in affine)
+        self._hist = self._stats = None
+        self._side = 0
+        self._h0 = 0
+        self._out_device = None
+
+    def device_bytes(self) -> int:
+        return sum(4 * t.numel() for t in (self._hist, self._stats) if t is not None)
+
+    def _call(self, block, final: bool, on_device: bool = False) -> torch.Tensor:
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        plan, dev, ch = self.plan, self.device, self.channels
+        n_in = 0 if block is None else block.shape[1]
+        out0, n_out, nxt = plan.step(self.pushed, n_in, final)
+        with torch.cuda.device(dev):
+            out = torch.empty(ch, n_out, device=dev, dtype=torch.float32)
+            if n_in or n_out:
+                if self._hist is None and not plan.copy:
+                    self._hist = torch.zeros(2, ch, plan.carry, device=dev)
+                if self._stats is None and self.affine is not None:
+                    self._stats = torch.tensor(self.affine, dtype=torch.float32).to(dev)
+                src = block.to(device=dev, dtype=torch.float32).contiguous() if n_in else None
+                arena = _BankArena.get(dev)
+                bank_off = arena.offset(plan)
+                bank, hist, stats = arena.buf, self._hist, self._stats
+                h_len = plan.carry
+                side = ch * h_len
+                row = [src.data_ptr() if n_in else 0, self.src_channels or 1, n_in, self.pushed, h_len, self._side * side,
+                       (1 - self._side) * side, self._h0, nxt, out0, n_out, self.pushed + n_in if final else -1, plan.old, plan.new,
+                       plan.width, bank_off, 0, n_out, 0, 0 if stats is not None else -1]
+                table = torch.tensor(row, dtype=torch.int64).to(dev)
+                win = out if n_out else table              # nothing is written when n_out == 0: any live pointer
+                _lib.check(_lib.load().mi_streams_convert_append(
+                    win.data_ptr(), max(1, out.numel()), ch, table.data_ptr(), 1, plan.groups(n_out),
+                    bank.data_ptr() if bank.numel() else None, bank.numel(), hist.data_ptr() if hist is not None else None,
+                    0 if hist is None else hist.numel(), stats.data_ptr() if stats is not None else None, int(stats is not None),
+                    plan.lds_floats(), C.c_void_p(_lib.current_stream_ptr())), "mi_streams_convert_append")
+                if not final and not plan.copy:
+                    self._side, self._h0 = 1 - self._side, nxt
+        self.pushed += n_in
+        self.emitted += n_out
+        to = None if on_device else self._out_device
+        return out if to is None or out.device == torch.device(to) else out.to(to)
+
+    def push(self, block: torch.Tensor, on_device: bool = False) -> torch.Tensor:
+        """`on_device=True` leaves the output on the stream's device whatever the block's."""
+        if self.finished:
+            raise RuntimeError("push after finish()")
+        if not isinstance(block, torch.Tensor) or block.dim() != 2:
+            raise ValueError(f"expected a (channels, n) block, got {tuple(getattr(block, 'shape', ()))}")
+        if self.src_channels is None:
+            check_stream_channels(block.shape[0], self.channels)
+            self.src_channels = block.shape[0]
+        elif block.shape[0] != self.src_channels:
+            raise ValueError(f"expected a ({self.src_channels}, n) block, got {tuple(block.shape)}")
+        self._out_device = block.device
+        return self._call(block, final=False, on_device=on_device)
+
+    def finish(self, on_device: bool = False) -> torch.Tensor:
+        if self.finished:
+            raise RuntimeError("finish() called twice")
+        self.finished = True
+        return self._call(None, final=True, on_device=on_device)
+
+
 # ---- after the separation: what demucs.separate does with the stems before any encoder sees them ----------------------
 _CLIP_MODES = {"rescale": 1, "clamp": 2, "tanh": 3}
 

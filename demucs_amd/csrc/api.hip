@@ -306,6 +306,17 @@ int mi_streams_append(float *win_dev, int64_t win_capacity, int32_t channels, co
     return launch_streams_append(win_dev, win_capacity, channels, table_dev, n_streams, max_n, stats_dev, n_stats, (hipStream_t)stream);
 }
 
+int mi_streams_convert_append(float *win_dev, int64_t win_capacity, int32_t channels, const int64_t *table_dev, int32_t n_streams,
+                              int64_t max_groups, const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity,
+                              const float *stats_dev, int32_t n_stats, int32_t lds_floats, void *stream) {
+    MI_REQUIRE(win_dev && table_dev && channels > 0 && n_streams > 0 && (int64_t)n_streams * channels <= 65535 && max_groups >= 1 &&
+               max_groups <= INT32_MAX && win_capacity > 0 && bank_capacity >= 0 && (bank_capacity == 0 || bank_dev) &&
+               hist_capacity >= 0 && (hist_capacity == 0 || hist_dev) && n_stats >= 0 && (n_stats == 0 || stats_dev) &&
+               lds_floats >= 1 && lds_floats <= MI_CVT_LDS_FLOATS, "mi_streams_convert_append: bad argument");
+    return launch_streams_convert_append(win_dev, win_capacity, channels, table_dev, n_streams, max_groups, bank_dev, bank_capacity,
+                                         hist_dev, hist_capacity, stats_dev, n_stats, lds_floats, (hipStream_t)stream);
+}
+
 int mi_streams_compact(float *dst_dev, int64_t dst_capacity, const float *src_dev, int64_t src_capacity, const int64_t *table_dev,
                        int32_t n_rows, int64_t max_len, void *stream) {
     MI_REQUIRE(dst_dev && src_dev && table_dev && dst_dev != src_dev && n_rows > 0 && n_rows <= 65535 && max_len >= 1 && dst_capacity > 0 &&

@@ -156,6 +156,11 @@ int launch_ola_finish_packed(float *acc, int64_t acc_cap, int rows, const int64_
 int launch_resample_frac(const float *x, int rows, int64_t L, const float *table, int old_sr, int new_sr, int width, float *y,
                          int64_t Lout, hipStream_t st);
 
+// convert_stream.hip: the streaming convert_audio fused with the append (mi_streams_convert_append)
+int launch_streams_convert_append(float *win, int64_t win_cap, int channels, const int64_t *table, int n_streams, int64_t max_groups,
+                                  const float *bank, int64_t bank_cap, float *hist, int64_t hist_cap, const float *stats, int n_stats,
+                                  int lds_floats, hipStream_t st);
+
 const void *conv_zero_page();      // gemm_conv.hip: 256 bytes of device zeros
 // attention_heads.hip: half modes, per-head token-major 16-bit operands (MI_FLAG_HEADS), LDS-DMA ring
 int launch_attention_heads(const void *q, const void *k, const void *v, const void *zero_page, int B, int heads, int Tq, int Tk, int Tq_pitch,

@@ -657,7 +657,10 @@ class StreamGroup:
     On the engines a call is a fixed amount of device work whatever the number of streams: one H2D of the call's int64 table
     together with its host blocks, one `mi_streams_append`, the pooled forwards (each a gather, the forward and an overlap-add
     driven by that table), one `mi_streams_emit` and one D2H of the host-bound stems, plus one `mi_streams_compact` when a
-    stream outgrows its room in the state buffer (every stream's window and accumulators).
+    stream outgrows its room in the state buffer (every stream's window and accumulators).  Streams opened with `convert=`
+    take blocks at another sample rate or channel count: one `mi_streams_convert_append` per call runs the streaming
+    `convert_audio` (demucs_amd/audio.py, `ConvertPlan`) for all of them into their windows, and what the converter has made
+    final is what the stream's scheduler sees as pushed.
     Other models run the same scheduler one segment at a time on the plain-torch route."""
 
     def __init__(self, model, shifts=1, overlap=0.25, transition_power=1.0, segment=None, device=None, split=True,
@@ -676,9 +679,26 @@ class StreamGroup:
         self._exec = None
 
     # ---- public --------------------------------------------------------------------------------------------------------
-    def open(self, length: Optional[int] = None, affine=None):
-        """A new stream; makes the RNG calls `ModelStream(..., length=length)` makes.  Returns its key."""
+    def open(self, length: Optional[int] = None, affine=None, convert=None):
+        """A new stream; makes the RNG calls `ModelStream(..., length=length)` makes.  Returns its key.
+
+        `convert=(audio.ConvertPlan, source channels)`: the stream's blocks are (source channels, n) at the plan's input rate and
+        pass through the streaming `convert_audio` into its window (one `mi_streams_convert_append` for all such streams of a
+        call); `length` then counts input samples, and the RNG calls are those of the converted length."""
+        conv = None
+        if convert is not None:
+            from .audio import check_stream_channels
+            plan, src_channels = convert
+            check_stream_channels(int(src_channels), self.audio_channels)
+            if any(m.kind == "generic" for m in self.members) or (self.device is not None and self.device.type != "cuda"):
+                raise ValueError("a converting stream runs on the GPU engines (HTDemucs / HDemucs on a cuda device); there is no "
+                                 "CPU resampler in this package")
+            if length is not None and int(length) < 0:
+                raise ValueError(f"length must be >= 0, got {length}")
+            conv = _Conv(plan, int(src_channels), None if length is None else int(length))
+            length = None if length is None else plan.final_count(int(length))
         st = ModelStream(self.model, device=self.device, length=length, affine=affine, **self._kw)
+        st.convert = conv
         key = self._next
         self._next += 1
         self._streams[key] = st
@@ -703,6 +723,14 @@ class StreamGroup:
         items = list(blocks.items())
         for key, block in items:
             st = self._stream(key)
+            cv = getattr(st, "convert", None)
+            if cv is not None:
+                if not isinstance(block, torch.Tensor) or block.dim() != 2 or block.shape[0] != cv.src_channels:
+                    shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
+                    raise ValueError(f"expected a ({cv.src_channels}, n) block, got {shape}")
+                if cv.length is not None and cv.pushed + block.shape[1] > cv.length:
+                    raise ValueError(f"pushed {cv.pushed + block.shape[1]} samples, more than the declared length {cv.length}")
+                continue
             if not isinstance(block, torch.Tensor) or block.dim() != 2 or block.shape[0] != self.audio_channels:
                 shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
                 raise ValueError(f"expected a ({self.audio_channels}, n) block, got {shape}: a stream converts no channel layout")
@@ -720,12 +748,21 @@ class StreamGroup:
             raise ValueError("finish: a stream key is listed twice")
         for key in keys:
             st = self._stream(key)
+            cv = getattr(st, "convert", None)
+            if cv is not None:
+                if cv.length is not None and cv.pushed != cv.length:
+                    raise ValueError(f"the stream ended after {cv.pushed} samples, but length={cv.length} was declared")
+                if cv.plan.final_count(cv.pushed) == 0:
+                    raise ValueError("the stream ended before any sample was pushed")
+                continue
             if st.length is not None and st.pushed != st.length:
                 raise ValueError(f"the stream ended after {st.pushed} samples, but length={st.length} was declared")
             if st.pushed == 0:
                 raise ValueError("the stream ended before any sample was pushed")
         if not keys:
             return {}
+        if self._exec is None:                     # converting streams whose pushes were all empty
+            raise ValueError("the stream ended before any sample was pushed")
         out = self._exec.finish([(k, self._streams[k]) for k in keys])
         for key in keys:
             del self._streams[key]
@@ -782,6 +819,18 @@ class _GroupTorchExec:
         return {key: self.execs.pop(key).finish() for key, _ in items}
 
 
+class _Conv:
+    """The converter of one stream of a group: its `audio.ConvertPlan`, the input samples pushed, and where its carried input
+    lives in the group's history buffer (two sides of (channels, plan.carry) floats from `off`; `side` is the one to read, whose
+    first sample is input `h0`)."""
+
+    def __init__(self, plan, src_channels: int, length):
+        self.plan, self.src_channels, self.length = plan, src_channels, length
+        self.pushed = 0
+        self.off = None
+        self.side = self.h0 = 0
+
+
 class _Slot:
     """A stream's room in the group's state buffer: its window (channels, w_cap) at w_base, column 0 = track position w0, and
     per pass an accumulator (rows, cap) at base, column 0 = the pass's `a0`.  Columns past what was written hold zeros."""
@@ -816,10 +865,31 @@ class _GroupEngineExec:
         self.dead = False
         self.bufs = {}
         self.pad = max(m.V for m in g.members)
+        # converting streams: every stream's carried input in one buffer (doubled when an opened stream finds no room; regions of
+        # finished streams are reused), so its size follows the number of open streams and never a stream's duration
+        self.hist = None
+        self.hist_used = 0
+        self.hist_free = {}
 
     def device_bytes(self) -> int:
         n = self.state.numel() + self.stats.numel() + sum(t.numel() for b in self.bufs.values() for t in set(b))
-        return 4 * n
+        return 4 * (n + (0 if self.hist is None else self.hist.numel()))
+
+    def _hist_region(self, cv: _Conv) -> None:
+        size = 2 * self.g.audio_channels * cv.plan.carry
+        if cv.off is not None or size == 0:
+            return
+        if self.hist_free.get(size):
+            cv.off = self.hist_free[size].pop()
+            return
+        have = 0 if self.hist is None else self.hist.numel()
+        if self.hist_used + size > have:
+            grown = torch.zeros(max(2 * have, self.hist_used + size, 4096), device=self.g.device, dtype=torch.float32)
+            if have:
+                grown[:have] = self.hist
+            self.hist = grown
+        cv.off = self.hist_used
+        self.hist_used += size
 
     def _stream(self):
         return C.c_void_p(_lib.current_stream_ptr())
@@ -982,9 +1052,21 @@ class _GroupEngineExec:
             # the first window position a pending segment can read, before this call dispatches any (as ModelStream's append)
             before = {key: slot.st.pushed for key, slot in self.slots.items()}
             keep_w = {key: slot.st._keep_from() for key, slot in self.slots.items()}
-            units, blocks = [], []
+            units, blocks, jobs = [], [], []
             for key, st, block in work:
-                if block is not None:
+                cv = getattr(st, "convert", None)
+                if cv is not None:
+                    # the converter decides how many samples at the model's rate this call adds to the window
+                    n_in = 0 if block is None else block.shape[1]
+                    out0, n_out, nxt = cv.plan.step(cv.pushed, n_in, block is None)
+                    jobs.append((self.slots[key], cv, block, n_in, out0, n_out, nxt))
+                    st.pushed += n_out
+                    cv.pushed += n_in
+                    if block is not None:
+                        st._out_device = block.device
+                    else:
+                        st.finished = True
+                elif block is not None:
                     st.pushed += block.shape[1]
                     st._out_device = block.device
                     blocks.append((key, self.slots[key], block))
@@ -1008,6 +1090,7 @@ class _GroupEngineExec:
                     ps = slot.st.passes[pi]
                     ps.hi = max(ps.hi, o + n)
             append, staged = self._append_rows(blocks, table, keep)
+            convert = self._convert_rows(jobs, table, keep, staged)
             plan = [(e, valid, fw, *self._forward_tables(e, valid, fw, table)) for e, valid, fw in self._plan(units)]
             emit = self._emit_rows(work, table)
             base = self._upload(table, staged, keep)
@@ -1027,6 +1110,15 @@ class _GroupEngineExec:
                 _lib.check(self.lib.mi_streams_append(self.state.data_ptr(), self.state.numel(), C_, C.c_void_p(base + 8 * at), n_rows,
                                                       longest, self.stats.data_ptr(), self.n_stats, self._stream()),
                            "mi_streams_append")
+            if convert is not None:
+                from .audio import _BankArena
+                at, n_rows, groups, lds_floats = convert
+                bank, hist = _BankArena.get(dev).buf, self.hist
+                _lib.check(self.lib.mi_streams_convert_append(self.state.data_ptr(), self.state.numel(), C_, C.c_void_p(base + 8 * at),
+                                                              n_rows, groups, bank.data_ptr() if bank.numel() else None, bank.numel(),
+                                                              hist.data_ptr() if hist is not None else None,
+                                                              0 if hist is None else hist.numel(), self.stats.data_ptr(), self.n_stats,
+                                                              lds_floats, self._stream()), "mi_streams_convert_append")
             for e, valid, fw, at, n_tiles in plan:
                 self._forward(e, valid, fw, base + 8 * at, n_tiles, keep)
             outs = self._emit(emit, base)
@@ -1034,7 +1126,11 @@ class _GroupEngineExec:
                 for m in g.members:
                     if m.kind == "h":
                         m.model.check()      # a time-out of the LAST forward's recurrence would otherwise pass unnoticed
-                for key, _, _ in work:
+                for key, st, _ in work:
+                    cv = getattr(st, "convert", None)
+                    if cv is not None and cv.off is not None:
+                        self.hist_free.setdefault(2 * C_ * cv.plan.carry, []).append(cv.off)
+                        cv.off = None
                     del self.slots[key]
                     self.dead = True
                 if not self.slots:
@@ -1063,6 +1159,43 @@ class _GroupEngineExec:
             table += [src, n, slot.w_base, slot.w_cap, slot.st.pushed - n - slot.w0, slot.stats]
             longest = max(longest, n)
         return (at, len(live), longest), staged
+
+    def _convert_rows(self, jobs, table, keep, staged):
+        """mi_streams_convert_append's rows (MI_CVT_*) for the converting streams of the call with a block or final outputs; host
+        blocks join `staged`.  Flips every such stream's history side.  Returns (first index, rows, workgroups per row, LDS
+        floats) or None."""
+        from .audio import CVT_COLS, _BankArena
+        g = self.g
+        C_ = g.audio_channels
+        live = [j for j in jobs if j[3] > 0 or j[5] > 0]
+        if not live:
+            return None
+        arena = _BankArena.get(g.device)
+        at = len(table)
+        groups, lds_floats = 1, 1
+        off = sum(b.numel() for _, _, b in staged)
+        for slot, cv, b, n_in, out0, n_out, nxt in live:
+            plan, final = cv.plan, b is None
+            self._hist_region(cv)
+            src = 0
+            if n_in and b.device.type == "cpu":
+                staged.append((len(table), off, b))
+                off += b.numel()
+            elif n_in:
+                d = b.to(device=g.device, dtype=torch.float32).contiguous()
+                keep.append(d)
+                src = d.data_ptr()
+            side = C_ * plan.carry
+            base = cv.off or 0
+            table += [src, cv.src_channels, n_in, cv.pushed - n_in, plan.carry, base + cv.side * side, base + (1 - cv.side) * side,
+                      cv.h0, nxt, out0, n_out, cv.pushed if final else -1, plan.old, plan.new, plan.width, arena.offset(plan),
+                      slot.w_base, slot.w_cap, slot.st.pushed - n_out - slot.w0, slot.stats]
+            if not final and not plan.copy:
+                cv.side, cv.h0 = 1 - cv.side, nxt
+            groups = max(groups, plan.groups(n_out))
+            lds_floats = max(lds_floats, plan.lds_floats())
+        assert (len(table) - at) == CVT_COLS * len(live)
+        return at, len(live), groups, lds_floats
 
     def _upload(self, table, staged, keep) -> int:
         """The call's int64 table and its host blocks (float32) in one pinned buffer, down in ONE H2D.  Returns the table's

@@ -264,6 +264,8 @@ int mi_stream_emit(const float *acc_dev, int64_t acc_capacity, int32_t n_sources
 
 /* ---- stream groups: many streams as one unit of work per push (demucs_amd/stream.py, StreamGroup) ---------------------------
  * All tables are int64 DEVICE arrays; every read and write of a buffer is clamped to its declared capacity (floats) or table size.
+ * A stream whose input is at another sample rate or channel count is appended by mi_streams_convert_append (below) instead of
+ * mi_streams_append: the streaming convert_audio, bit-identical to mi_resample_frac on the whole track.
  *
  * mi_streams_emit: mi_stream_emit for every stream of a table in ONE launch, each stream's (row, sample) the same float32 chain.
  *   Stream table (n_streams rows of MI_STREAMS_EMIT_COLS): the stream's rows [pass_lo, pass_hi) of the pass table (MI_EMIT_*
@@ -304,6 +306,62 @@ int mi_streams_append(float *win_dev, int64_t win_capacity, int32_t channels, co
                       const float *stats_dev, int32_t n_stats, void *stream);
 int mi_streams_compact(float *dst_dev, int64_t dst_capacity, const float *src_dev, int64_t src_capacity, const int64_t *table_dev,
                        int32_t n_rows, int64_t max_len, void *stream);
+
+/* mi_streams_convert_append: `convert_audio` (channel map + julius.resample_frac, demucs/audio.py:169-172) for streams, fused with
+ *   mi_streams_append's write: the concatenation of what a stream's calls write equals mi_resample_frac on the whole row bit for
+ *   bit, for every partition of the input.  With old / new the rates divided by their gcd, width and klen = 2 * width + old as for
+ *   mi_resample_frac, every output y[n * new + i] is the same chain (acc = 0; k ascending; acc = fmaf(kernel[i][k],
+ *   x[clamp(n * old - width + k, 0, L - 1)], acc)).  Frame n (outputs n * new .. n * new + new - 1) is final once
+ *   n * old + width + old <= pushed, so after P input samples ready(P) = new * max(0, (P - width - old) / old + 1) outputs exist;
+ *   the final call (total >= 0) writes the rest up to floor(new * total / old) with the right taps clamped to x[total - 1].
+ *   Row s of the table (MI_CVT_COLS int64) is one stream of the call:
+ *     SRC, SRC_CH, N_IN   its new block (src_ch, n_in) float32 at the DEVICE address src (row stride n_in; trusted as in
+ *                         mi_streams_append).  Output row c reads source row 0 when src_ch == 1, else row min(c, src_ch - 1);
+ *     BEFORE              input samples pushed before this block;
+ *     HIST_LEN, HIST_RD, HIST_WR, HIST_START, HIST_NEXT
+ *                         the carried input: (channels, hist_len) floats at float offset hist_rd of hist_dev hold inputs
+ *                         [hist_start, before) of every output row; the call writes inputs [hist_next, before + n_in) (at most
+ *                         hist_len of them) at float offset hist_wr.  The two sides must differ: one launch reads one and writes
+ *                         the other.  hist_next = max(0, n * old - width) for the first frame n that is not ready, so
+ *                         before + n_in - hist_next <= klen - 1; hist_next < 0: nothing is written (the final call);
+ *     OUT0, N_OUT         the first output index (a multiple of new) and the number of outputs to write;
+ *     TOTAL               the total input length when this is the stream's final call, else negative;
+ *     OLD, NEW, WIDTH, BANK_OFF
+ *                         its rate entry; the kernel bank TRANSPOSED, (klen, new) float32, at float offset bank_off of bank_dev.
+ *                         width == 0 (equal rates): outputs are the inputs OUT0 .. through the channel map, no filter, no history;
+ *     DST_OFF, DST_LEN, COL, STATS
+ *                         outputs go to columns [col, col + n_out) of the (channels, dst_len) window at float offset dst_off of
+ *                         win_dev, as `(y - mean) / s` (mi_track_affine inverse = 0) when stats names a pair of stats_dev.
+ *   A workgroup takes 8 * G consecutive frames of one (stream, channel) row, G = min(4, (lds_floats - 2 * width) / (8 * old)) >= 1
+ *   (1024 samples when width == 0); max_groups >= every row's number of such runs (grid size); lds_floats <= MI_CVT_LDS_FLOATS is
+ *   the staging area, >= 8 * old + 2 * width for every row.  Reads and writes of win_dev / hist_dev / bank_dev are clamped to the
+ *   declared capacities (floats): a wrong table changes results, never memory outside the buffers.  A one-row table with a plain
+ *   (channels, n_out) output buffer as the window serves a single stream. */
+#define MI_CVT_SRC 0
+#define MI_CVT_SRC_CH 1
+#define MI_CVT_N_IN 2
+#define MI_CVT_BEFORE 3
+#define MI_CVT_HIST_LEN 4
+#define MI_CVT_HIST_RD 5
+#define MI_CVT_HIST_WR 6
+#define MI_CVT_HIST_START 7
+#define MI_CVT_HIST_NEXT 8
+#define MI_CVT_OUT0 9
+#define MI_CVT_N_OUT 10
+#define MI_CVT_TOTAL 11
+#define MI_CVT_OLD 12
+#define MI_CVT_NEW 13
+#define MI_CVT_WIDTH 14
+#define MI_CVT_BANK_OFF 15
+#define MI_CVT_DST_OFF 16
+#define MI_CVT_DST_LEN 17
+#define MI_CVT_COL 18
+#define MI_CVT_STATS 19
+#define MI_CVT_COLS 20
+#define MI_CVT_LDS_FLOATS 16384
+int mi_streams_convert_append(float *win_dev, int64_t win_capacity, int32_t channels, const int64_t *table_dev, int32_t n_streams,
+                              int64_t max_groups, const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity,
+                              const float *stats_dev, int32_t n_stats, int32_t lds_floats, void *stream);
 
 /* mi_resample_frac: `julius.resample_frac` as called by `demucs.audio.convert_audio` (demucs/audio.py:169-172), the step
  *   `Separator.separate_tensor` runs first when the input sample rate differs from the model's (demucs/api.py:265-266).

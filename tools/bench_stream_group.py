@@ -8,6 +8,9 @@ finishes the streams that have reached their end.  The group does a round as one
 per side: aggregate real-time factor (audio seconds of all streams / wall seconds, finishes included), median and p99 wall time
 of a round's pushes, the number of forwards and their mean batch size (counted at `mi_model_forward`).  The group and the solo
 run alternate in one process (group, solo, group, solo) after one warm-up of each; each side reports its faster run.
+`--sr RATE` pushes the same audio duration as stereo blocks at RATE: the group's streams are opened converting
+(`SeparatorStreamGroup.open(sr=RATE)`, one `mi_streams_convert_append` per round) and the solo side is
+`Separator.separate_stream(sr=RATE, convert=True)`.
 Prints ONE JSON line (and writes it to --out when given).
 
     python tools/bench_stream_group.py --out profiles/stream_group_bench.json
@@ -42,9 +45,9 @@ def model(mode: str) -> HTDemucs:
     return m.to("cuda").eval()
 
 
-def rounds(n_streams: int, length: int, block: int, staggered: bool):
+def rounds(n_streams: int, length: int, block: int, staggered: bool, sr: int = SR):
     """[(opens, pushes {i: (pos, n)}, finishes)] per round."""
-    start = [int(((i * 0.37) % 6.0) * SR) // block if staggered else 0 for i in range(n_streams)]
+    start = [int(((i * 0.37) % 6.0) * sr) // block if staggered else 0 for i in range(n_streams)]
     n_blocks = -(-length // block)
     out = []
     for r in range(max(start) + n_blocks):
@@ -73,17 +76,21 @@ class ForwardCounter:
         self.lib.mi_model_forward = self.real
 
 
-def run(m, audio, plan, grouped: bool):
+def run(m, audio, plan, grouped: bool, sr: int = SR):
     times = []
+    sep = None
+    if sr != SR:
+        from demucs_amd.api import Separator
+        sep = Separator(m, device="cuda", shifts=1)
     with ForwardCounter() as fc:
         torch.cuda.synchronize()
         t_all = time.perf_counter()
         if grouped:
-            g = apply_model_stream_group(m, shifts=1, device="cuda")
+            g = apply_model_stream_group(m, shifts=1, device="cuda") if sep is None else sep.separate_stream_group()
             keys = {}
             for opens, pushes, ends in plan:
                 for i in opens:
-                    keys[i] = g.open()
+                    keys[i] = g.open() if sep is None else g.open(sr=sr)
                 t0 = time.perf_counter()
                 g.push({keys[i]: audio[:, p:p + n] for i, (p, n) in pushes.items()})
                 torch.cuda.synchronize()
@@ -94,7 +101,8 @@ def run(m, audio, plan, grouped: bool):
             streams = {}
             for opens, pushes, ends in plan:
                 for i in opens:
-                    streams[i] = apply_model_stream(m, shifts=1, device="cuda")
+                    streams[i] = apply_model_stream(m, shifts=1, device="cuda") if sep is None else \
+                        sep.separate_stream(sr=sr, convert=True)
                 t0 = time.perf_counter()
                 for i, (p, n) in pushes.items():
                     streams[i].push(audio[:, p:p + n])
@@ -121,25 +129,28 @@ def main():
     ap.add_argument("--streams", default="1,8,32,64")
     ap.add_argument("--blocks", default="0.1,1")
     ap.add_argument("--modes", default="f32,bf16")
+    ap.add_argument("--sr", type=int, default=SR, help="sample rate of the pushed blocks (converted on the streams when not 44100)")
+    ap.add_argument("--starts", default="lockstep,staggered")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    length = int(args.seconds * SR)
+    sr = args.sr
+    length = int(args.seconds * sr)
     audio = torch.from_numpy(synth_mix(1, length, "tones"))
     result = {"what": "apply_model_stream_group vs solo apply_model_stream, htdemucs, shifts=1, max_batch=8, host blocks",
-              "device": torch.cuda.get_device_name(0), "stream_seconds": args.seconds, "reps": args.reps, "runs": {}}
+              "device": torch.cuda.get_device_name(0), "stream_seconds": args.seconds, "input_sr": sr, "reps": args.reps, "runs": {}}
     for mode in args.modes.split(","):
         m = model(mode)
-        warm = rounds(2, 10 * SR, SR, False)
-        run(m, audio, warm, True)
-        run(m, audio, warm, False)
+        warm = rounds(2, 10 * sr, sr, False, sr)
+        run(m, audio, warm, True, sr)
+        run(m, audio, warm, False, sr)
         for n_streams in (int(x) for x in args.streams.split(",")):
             for block_s in (float(x) for x in args.blocks.split(",")):
-                for staggered in (False, True):
-                    plan = rounds(n_streams, length, int(block_s * SR), staggered)
+                for staggered in [x == "staggered" for x in args.starts.split(",")]:
+                    plan = rounds(n_streams, length, int(block_s * sr), staggered, sr)
                     grps, solos = [], []
                     for _ in range(args.reps):
-                        grps.append(run(m, audio, plan, True))
-                        solos.append(run(m, audio, plan, False))
+                        grps.append(run(m, audio, plan, True, sr))
+                        solos.append(run(m, audio, plan, False, sr))
                     grp = min(grps, key=lambda r: r["wall_s"])
                     solo = min(solos, key=lambda r: r["wall_s"])
                     audio_s = n_streams * args.seconds
