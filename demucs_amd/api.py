@@ -24,9 +24,9 @@ import torch
 from . import _lib
 from .audio import convert_audio
 from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
-from .stream import ModelStream, StreamGroup
+from .stream import Delivery, ModelStream, StreamGroup
 
-__all__ = ["Separator", "SeparatorStream", "LoadModelError", "list_models"]
+__all__ = ["Separator", "SeparatorStream", "Delivery", "LoadModelError", "list_models"]
 
 
 class LoadModelError(Exception):
@@ -132,7 +132,8 @@ class Separator:
             return [self._restore_on_device(st, out[None], device) for st, out in zip(states, outs)]
 
     def separate_stream(self, mean: Optional[float] = None, std: Optional[float] = None, sr: Optional[int] = None,
-                        length: Optional[int] = None, convert: bool = False, channels: Optional[int] = None) -> "SeparatorStream":
+                        length: Optional[int] = None, convert: bool = False, channels: Optional[int] = None,
+                        deliver: Optional[Delivery] = None) -> "SeparatorStream":
         """`separate_tensor` for a track that arrives block by block (demucs_amd/stream.py): `push(block)` takes (channels, n)
         float32 and returns `{source: (channels, m)}` of the newly final samples, `finish()` the rest.
 
@@ -146,7 +147,12 @@ class Separator:
         (`channels` or the model's, n) at `sr` and pass through `convert_audio` on the device first (`audio.ConvertStream`:
         mono to the model's channels or the first channels, then the resampler), so the concatenated stems equal
         `separate_tensor(wav, sr)`'s bit for bit; `mean` / `std` are those of the CONVERTED track, `length` counts input samples
-        at `sr`, stems come back at the model's rate, and `input_latency` bounds the lag in input samples."""
+        at `sr`, stems come back at the model's rate, and `input_latency` bounds the lag in input samples.
+
+        With `deliver=Delivery(...)` (demucs_amd/stream.py) `push` / `finish` return what the reference would write to its files
+        for those samples instead: `{name: (m, channels) frames}` in the order of its save loop, after `prevent_clip` and as
+        int16 PCM or float32 with interleaved channels -- `audio.deliver`'s chain on the stems above, by one more launch per
+        push.  A stream refuses clip="rescale" and other_method="minus", which need the whole track."""
         if not convert:
             if channels is not None and channels != self._audio_channels:
                 raise ValueError(f"separate_stream: {channels} input channels are not the model's {self._audio_channels}; pass "
@@ -163,7 +169,7 @@ class Separator:
             in_length, length = int(length), plan.final_count(int(length))
         st = ModelStream(self._model, shifts=self._shifts, overlap=self._overlap, segment=self._segment, split=self._split,
                          device=self._device, length=length, progress=self._progress, callback=self._callback,
-                         affine=None if mean is None else (mean, std))
+                         affine=None if mean is None else (mean, std), deliver=deliver)
         if plan is None:
             return SeparatorStream(st, self._model.sources)
         return ConvertingSeparatorStream(st, self._model.sources, plan, channels or self._audio_channels,
@@ -265,6 +271,11 @@ class Separator:
         return self._model
 
 
+def _named(sources, out) -> Dict[str, torch.Tensor]:
+    """A stream's stems by source name; a delivering stream's result already is `{name: frames}`."""
+    return out if isinstance(out, dict) else dict(zip(sources, out))
+
+
 class SeparatorStream:
     """What `Separator.separate_stream` returns: the stream's stems as `{source: (channels, m)}`."""
 
@@ -272,10 +283,10 @@ class SeparatorStream:
         self.stream, self.sources = stream, list(sources)
 
     def push(self, block: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return dict(zip(self.sources, self.stream.push(block)))
+        return _named(self.sources, self.stream.push(block))
 
     def finish(self) -> Dict[str, torch.Tensor]:
-        return dict(zip(self.sources, self.stream.finish()))
+        return _named(self.sources, self.stream.finish())
 
     @property
     def emitted(self) -> int:
@@ -327,10 +338,15 @@ class ConvertingSeparatorStream(SeparatorStream):
         y = self._cv.finish(on_device=True)
         parts = [self.stream.push(y)] if y.shape[1] else []
         parts.append(self.stream.finish())
+        if isinstance(parts[0], dict):                      # delivered frames: (m, channels) per name
+            return self._stems({k: torch.cat([p[k] for p in parts], 0) for k in parts[0]}, to)
         return self._stems(parts[0] if len(parts) == 1 else torch.cat(parts, -1), to)
 
-    def _stems(self, out: torch.Tensor, to) -> Dict[str, torch.Tensor]:
-        if to is not None and torch.device(to).type == "cpu":
+    def _stems(self, out, to) -> Dict[str, torch.Tensor]:
+        host = to is not None and torch.device(to).type == "cpu"
+        if isinstance(out, dict):
+            return out if to is None else {k: v.to(to) for k, v in out.items()}
+        if host:
             out = _to_host(out, out.device)
         return dict(zip(self.sources, out))
 
@@ -345,8 +361,9 @@ class SeparatorStreamGroup:
         self.group, self.sources, self.separator = group, list(sources), separator
 
     def open(self, mean: Optional[float] = None, std: Optional[float] = None, length: Optional[int] = None,
-             sr: Optional[int] = None, channels: Optional[int] = None):
-        """`length`, `sr` and `channels` describe the stream's INPUT, as for `separate_stream(convert=True)`."""
+             sr: Optional[int] = None, channels: Optional[int] = None, deliver: Optional[Delivery] = None):
+        """`length`, `sr` and `channels` describe the stream's INPUT, as for `separate_stream(convert=True)`; `deliver` is
+        `separate_stream`'s, each stream with its own."""
         if (mean is None) != (std is None):
             raise ValueError("separate_stream_group: give both mean and std, or neither")
         convert = None
@@ -354,13 +371,13 @@ class SeparatorStreamGroup:
             plan = self.separator._convert_plan(sr, channels)
             if plan is not None:
                 convert = (plan, int(channels or self.separator.audio_channels))
-        return self.group.open(length=length, affine=None if mean is None else (mean, std), convert=convert)
+        return self.group.open(length=length, affine=None if mean is None else (mean, std), convert=convert, deliver=deliver)
 
     def push(self, blocks) -> Dict[object, Dict[str, torch.Tensor]]:
-        return {k: dict(zip(self.sources, v)) for k, v in self.group.push(blocks).items()}
+        return {k: _named(self.sources, v) for k, v in self.group.push(blocks).items()}
 
     def finish(self, keys) -> Dict[object, Dict[str, torch.Tensor]]:
-        return {k: dict(zip(self.sources, v)) for k, v in self.group.finish(keys).items()}
+        return {k: _named(self.sources, v) for k, v in self.group.finish(keys).items()}
 
     def emitted(self, key) -> int:
         return self.group.emitted(key)

@@ -354,3 +354,153 @@ def two_stems(origin: torch.Tensor, stems: dict, stem: str, other_method: str = 
     if other_method == "add":
         out["no_" + stem] = y
     return out
+
+
+# ---- delivery: every output of the reference's save loop, clipped, converted and interleaved by one kernel pair -----------
+DELIVER_COLS = 9                                  # include/demucs_amd.h: MI_DELIVER_*
+DELIVER_STEM, DELIVER_ADD, DELIVER_MINUS = 0, 1, 2
+_FORMATS = {"i16": (0, torch.int16, 2), "f32": (1, torch.float32, 4)}       # MI_DELIVER_I16 / _F32, dtype, bytes per sample
+
+
+def clip_code(clip) -> int:
+    """`prevent_clip`'s mode as mi_deliver_pcm's CLIP column (0: none)."""
+    if clip is None or clip == "none":
+        return 0
+    if clip not in _CLIP_MODES:
+        raise ValueError(f"Invalid mode {clip}")
+    return _CLIP_MODES[clip]
+
+
+def delivery_outputs(sources, stem=None, other_method="add") -> list:
+    """[(name, KIND, SEL)] in the order demucs/separate.py:178-218 saves its files: every source without `stem`; with it
+    "minus_STEM" (other_method "minus"), STEM, "no_STEM" ("add")."""
+    sources = list(sources)
+    if other_method not in ("add", "minus", "none"):
+        raise ValueError(f"Invalid other_method {other_method}")
+    if stem is None:
+        return [(name, DELIVER_STEM, k) for k, name in enumerate(sources)]
+    if stem not in sources:
+        raise ValueError(f"stem {stem!r} is not in the separated sources {sources}")
+    sel = sources.index(stem)
+    outs = [("minus_" + stem, DELIVER_MINUS, sel)] if other_method == "minus" else []
+    outs.append((stem, DELIVER_STEM, sel))
+    if other_method == "add":
+        outs.append(("no_" + stem, DELIVER_ADD, sel))
+    return outs
+
+
+def deliver_layout(outputs, frames: int, channels: int, fmt: str, at: int = 0):
+    """Byte offsets of `outputs`' (frames, channels) blocks from `at` on, each on a 16-byte boundary (the kernel's widest store),
+    and the end of the last."""
+    if fmt not in _FORMATS:
+        raise ValueError(f"Invalid format {fmt!r}: 'i16' or 'f32'")
+    size = frames * channels * _FORMATS[fmt][2]
+    offs = []
+    for _ in outputs:
+        at = -(-at // 16) * 16
+        offs.append(at)
+        at += size
+    return offs, at
+
+
+def deliver_views(buf: torch.Tensor, outputs, offs, frames: int, channels: int, fmt: str) -> dict:
+    """{name: (frames, channels) int16 / float32 view} of the byte buffer `buf` mi_deliver_pcm filled."""
+    _, dtype, width = _FORMATS[fmt]
+    size = frames * channels * width
+    return {name: buf[off:off + size].view(dtype).view(frames, channels) for (name, _, _), off in zip(outputs, offs)}
+
+
+def _stems_block(tensors, dev: torch.device) -> torch.Tensor:
+    """The stems as one contiguous float32 (S, channels, n) tensor on `dev`: read in place when they already are the rows of one
+    (what `Separator.separate_tensor` returns for a device mix), else stacked once (host stems: stacked, then one H2D)."""
+    first = tensors[0]
+    step = first.numel() * 4
+    if (first.device == dev and step and
+            all(t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and t.shape == first.shape and
+                t.untyped_storage().data_ptr() == first.untyped_storage().data_ptr() and
+                t.data_ptr() == first.data_ptr() + k * step for k, t in enumerate(tensors))):
+        return torch.as_strided(first, (len(tensors), *first.shape), (first.numel(), *first.stride()))
+    return torch.stack([t.to(torch.float32) for t in tensors]).to(dev).contiguous()
+
+
+def deliver(origin: torch.Tensor, stems: dict, stem=None, other_method: str = "add", clip="rescale", fmt: str = "i16") -> dict:
+    """What demucs/separate.py:178-218 hands to its encoders, for one separated track: `{name: (n, channels) frames}` in the
+    order of the reference's save loop -- every source, or with `stem` the `--two-stems` outputs `two_stems` names -- each after
+    `prevent_clip(·, clip)` (the peak of "rescale" is per output, as `save_audio` is called per output) and `i16_pcm` (fmt "i16")
+    or as float32 ("f32"), channels interleaved per frame.  All outputs of the track take ONE `mi_deliver_peaks` launch (only
+    for "rescale") and ONE `mi_deliver_pcm` launch; host stems come back on the host by one D2H of the byte buffer."""
+    names = list(stems)
+    outputs = delivery_outputs(names, stem, other_method)
+    code = clip_code(clip)
+    if fmt not in _FORMATS:
+        raise ValueError(f"Invalid format {fmt!r}: 'i16' or 'f32'")
+    tensors = [stems[k] for k in names]
+    for t in tensors:
+        if not t.dtype.is_floating_point:
+            raise TypeError(f"deliver: a floating-point tensor is expected, got {t.dtype}")
+        if t.dim() != 2 or t.shape != tensors[0].shape:
+            raise ValueError(f"deliver: every stem is (channels, n), got {[tuple(x.shape) for x in tensors]}")
+    channels, n = tensors[0].shape
+    home = tensors[0].device
+    dtype = _FORMATS[fmt][1]
+    if n == 0 or channels == 0:
+        return {name: torch.empty(n, channels, dtype=dtype, device=home) for name, _, _ in outputs}
+    dev = _engine_device(*tensors)
+    minus = any(kind == DELIVER_MINUS for _, kind, _ in outputs)
+    with torch.cuda.device(dev):
+        block = _stems_block(tensors, dev)
+        org = _stage(origin, dev, "deliver") if minus else None
+        if org is not None and org.shape != (channels, n):
+            raise ValueError(f"deliver: the mix is {tuple(org.shape)}, the stems are {(channels, n)}")
+        offs, total = deliver_layout(outputs, n, channels, fmt)
+        rows = []
+        for i, ((_, kind, sel), off) in enumerate(zip(outputs, offs)):
+            rows += [block.data_ptr(), org.data_ptr() if kind == DELIVER_MINUS else 0, n, kind, sel, code, i, _FORMATS[fmt][0], off]
+        table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        buf = torch.empty(total, dtype=torch.uint8, device=dev)
+        lib, stream = _lib.load(), C.c_void_p(_lib.current_stream_ptr())
+        peaks = None
+        if code == _CLIP_MODES["rescale"]:
+            peaks = torch.empty(len(outputs), dtype=torch.int32, device=dev)
+            _lib.check(lib.mi_deliver_peaks(table.data_ptr(), len(outputs), n, len(names), channels, peaks.data_ptr(), len(outputs),
+                                            total, stream), "mi_deliver_peaks")
+        _lib.check(lib.mi_deliver_pcm(table.data_ptr(), len(outputs), n, len(names), channels,
+                                      peaks.data_ptr() if peaks is not None else None, 0 if peaks is None else len(outputs),
+                                      buf.data_ptr(), total, stream), "mi_deliver_pcm")
+        if home.type == "cpu":
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            host.copy_(buf, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            buf = host
+        elif home != dev:
+            buf = buf.to(home)
+    return deliver_views(buf, outputs, offs, n, channels, fmt)
+
+
+def wav_header(frames, samplerate: int, channels: int, fmt: str = "i16") -> bytes:
+    """The RIFF / WAVE header in front of `deliver`'s frames: 44 bytes of PCM header for "i16"; format tag 3 (IEEE float) with
+    the `fact` chunk that format needs for "f32".  `frames=None` writes 0xFFFFFFFF sizes, for a live stream of unknown length."""
+    import struct
+    if fmt not in _FORMATS:
+        raise ValueError(f"Invalid format {fmt!r}: 'i16' or 'f32'")
+    samplerate, channels = int(samplerate), int(channels)
+    if samplerate <= 0 or not 1 <= channels <= 65535:
+        raise ValueError(f"wav_header: sample rate {samplerate} and {channels} channels do not fit a WAVE header")
+    width = _FORMATS[fmt][2]
+    align = channels * width
+    head = 58 if fmt == "f32" else 44
+    if frames is None:
+        data = riff = count = 0xFFFFFFFF
+    else:
+        count = int(frames)
+        data = count * align
+        riff = head - 8 + data
+        if count < 0 or riff > 0xFFFFFFFF:
+            raise ValueError(f"wav_header: {frames} frames do not fit a WAVE file's 32-bit sizes")
+    if fmt == "i16":
+        return (b"RIFF" + struct.pack("<I", riff) + b"WAVEfmt " +
+                struct.pack("<IHHIIHH", 16, 1, channels, samplerate, samplerate * align, align, 16) +
+                b"data" + struct.pack("<I", data))
+    return (b"RIFF" + struct.pack("<I", riff) + b"WAVEfmt " +
+            struct.pack("<IHHIIHHH", 18, 3, channels, samplerate, samplerate * align, align, 32, 0) +
+            b"fact" + struct.pack("<II", 4, count) + b"data" + struct.pack("<I", data))

@@ -1,0 +1,151 @@
+// Delivery of the stems as the reference saves them (demucs/separate.py:178-218 through save_audio, demucs/audio.py:236-265):
+// per output the `--two-stems` value, prevent_clip, i16_pcm (or float32) and the interleaving of channels per frame, for EVERY
+// output of a call in one table-driven launch (include/demucs_amd.h, MI_DELIVER_*).  Both kernels are memory-bound elementwise
+// passes; the arithmetic is post_ops.h's, shared with mi_prevent_clip / mi_two_stems, each step a separately rounded float32
+// operation in the reference's order.  Nothing here synchronises with the host and there is no scratch.
+#include "common.h"
+#include "kernels.h"
+#include "post_ops.h"
+
+namespace mi {
+
+struct DeliverRow {
+    const float *src, *origin;
+    int64_t n, dst_off;
+    int kind, sel, clip, fmt, peak;
+    bool ok, vec;
+};
+
+// One row of the table, with every rule under which it is skipped; both kernels read a row through this, so they agree on it
+__device__ __forceinline__ DeliverRow deliver_row(const int64_t *__restrict__ t, int n_sources, int channels, int n_peaks, int64_t dst_cap) {
+    DeliverRow r;
+    r.src = reinterpret_cast<const float *>(static_cast<uintptr_t>(t[MI_DELIVER_SRC]));
+    r.origin = reinterpret_cast<const float *>(static_cast<uintptr_t>(t[MI_DELIVER_ORIGIN]));
+    r.n = t[MI_DELIVER_N];
+    r.dst_off = t[MI_DELIVER_DST_OFF];
+    const int64_t kind = t[MI_DELIVER_KIND], sel = t[MI_DELIVER_SEL], clip = t[MI_DELIVER_CLIP], fmt = t[MI_DELIVER_FMT];
+    const int64_t peak = t[MI_DELIVER_PEAK];
+    r.ok = r.src && r.n > 0 && kind >= MI_DELIVER_STEM && kind <= MI_DELIVER_MINUS && sel >= 0 && sel < n_sources && clip >= 0 &&
+           clip <= MI_CLIP_TANH && fmt >= MI_DELIVER_I16 && fmt <= MI_DELIVER_F32 && (clip != MI_CLIP_RESCALE || (peak >= 0 && peak < n_peaks)) &&
+           (kind != MI_DELIVER_MINUS || r.origin) && r.dst_off >= 0 && (r.dst_off & 3) == 0;
+    r.kind = (int)kind; r.sel = (int)sel; r.clip = (int)clip; r.fmt = (int)fmt; r.peak = (int)peak;
+    if (r.ok) {
+        const int64_t frame = (int64_t)channels * (r.fmt == MI_DELIVER_F32 ? 4 : 2);        // bytes
+        r.ok = r.n <= dst_cap / frame && r.dst_off <= dst_cap - r.n * frame;
+    }
+    // 16-byte loads: every (source, channel) row starts at a multiple of 4 floats from an aligned base
+    r.vec = (r.n & 3) == 0 && (reinterpret_cast<uintptr_t>(r.src) & 15) == 0 &&
+            (r.kind != MI_DELIVER_MINUS || (reinterpret_cast<uintptr_t>(r.origin) & 15) == 0);
+    return r;
+}
+
+// four consecutive samples from j0 of a row of n; positions past n read nothing and give 0
+__device__ __forceinline__ void load4(const float *__restrict__ p, int64_t j0, int64_t n, bool vec, float (&v)[4]) {
+    if (vec) {
+        const float4 q = *reinterpret_cast<const float4 *>(p + j0);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = j0 + e < n ? p[j0 + e] : 0.f;
+    }
+}
+
+// step 1, the value: frames j0 .. j0 + 3 of channel c of the row's output, before clipping
+__device__ __forceinline__ void row_values(const DeliverRow &r, int n_sources, int channels, int c, int64_t j0, float (&v)[4]) {
+    const int64_t stem_stride = (int64_t)channels * r.n;
+    const float *base = r.src + (int64_t)c * r.n;                  // stem k's channel c at base + k * stem_stride
+    if (r.kind == MI_DELIVER_STEM) {
+        load4(base + r.sel * stem_stride, j0, r.n, r.vec, v);
+    } else if (r.kind == MI_DELIVER_MINUS) {
+        float o[4], s[4];
+        load4(r.origin + (int64_t)c * r.n, j0, r.n, r.vec, o);
+        load4(base + r.sel * stem_stride, j0, r.n, r.vec, s);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = two_stems_minus(o[e], s[e]);
+    } else {
+        two_stems_add<4>(n_sources, r.sel, [&](int k, float (&s)[4]) { load4(base + k * stem_stride, j0, r.n, r.vec, s); }, v);
+    }
+}
+
+// mi_deliver_peaks: grid (ceil(max_n / 1024), n_rows); a thread takes four consecutive frames of every channel of its row
+__global__ __launch_bounds__(256) void deliver_peaks_kernel(const int64_t *__restrict__ table, int n_sources, int channels,
+                                                            unsigned *__restrict__ peaks, int n_peaks, int64_t dst_cap) {
+    const DeliverRow r = deliver_row(table + (size_t)blockIdx.y * MI_DELIVER_COLS, n_sources, channels, n_peaks, dst_cap);
+    if (!r.ok || r.clip != MI_CLIP_RESCALE) return;                // the same for the whole block
+    const int64_t j0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    unsigned m = 0u;
+    if (j0 < r.n) {
+        for (int c = 0; c < channels; ++c) {
+            float v[4];
+            row_values(r, n_sources, channels, c, j0, v);          // positions past n give 0, which changes no maximum
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m = max(m, abs_bits(v[e]));
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(peaks + r.peak, m);
+}
+
+// mi_deliver_pcm: the same grid and thread assignment.  Stores: one 16-byte store of four frames for int16 stereo when all four
+// exist and their address is 16-byte aligned; else one 4-byte store per int16 stereo frame; else element by element
+__global__ __launch_bounds__(256) void deliver_pcm_kernel(const int64_t *__restrict__ table, int n_sources, int channels,
+                                                          const unsigned *__restrict__ peaks, int n_peaks, unsigned char *__restrict__ dst,
+                                                          int64_t dst_cap) {
+    const DeliverRow r = deliver_row(table + (size_t)blockIdx.y * MI_DELIVER_COLS, n_sources, channels, n_peaks, dst_cap);
+    if (!r.ok) return;
+    const int64_t j0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (j0 >= r.n) return;
+    const float d = r.clip == MI_CLIP_RESCALE ? clip_divisor(peaks[r.peak]) : 0.f;
+    unsigned char *out = dst + r.dst_off;                          // frames [0, n) of the row: inside dst_cap by deliver_row
+    if (channels == 2 && r.fmt == MI_DELIVER_I16) {
+        float a[4], b[4];
+        row_values(r, n_sources, channels, 0, j0, a);
+        row_values(r, n_sources, channels, 1, j0, b);
+        unsigned w[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned lo = (unsigned short)pcm_i16(clip_sample(a[e], r.clip, d)), hi = (unsigned short)pcm_i16(clip_sample(b[e], r.clip, d));
+            w[e] = lo | (hi << 16);
+        }
+        unsigned *frames = reinterpret_cast<unsigned *>(out) + j0;  // 4-byte aligned: dst is, and DST_OFF is a multiple of 4
+        if (j0 + 4 <= r.n && (reinterpret_cast<uintptr_t>(frames) & 15) == 0) {
+            *reinterpret_cast<uint4 *>(frames) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (j0 + e < r.n) frames[e] = w[e];
+        }
+        return;
+    }
+    for (int c = 0; c < channels; ++c) {
+        float v[4];
+        row_values(r, n_sources, channels, c, j0, v);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (j0 + e >= r.n) continue;
+            const float y = clip_sample(v[e], r.clip, d);
+            const int64_t at = (j0 + e) * channels + c;
+            if (r.fmt == MI_DELIVER_I16) reinterpret_cast<short *>(out)[at] = pcm_i16(y);
+            else reinterpret_cast<float *>(out)[at] = y;
+        }
+    }
+}
+
+int launch_deliver_peaks(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks, int n_peaks,
+                         int64_t dst_cap, hipStream_t st) {
+    MI_HIP(hipMemsetAsync(peaks, 0, sizeof(unsigned) * (size_t)n_peaks, st));
+    hipLaunchKernelGGL(deliver_peaks_kernel, dim3(ceil_div(max_n, 1024), n_rows), dim3(256), 0, st, table, n_sources, channels, peaks,
+                       n_peaks, dst_cap);
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}
+
+int launch_deliver_pcm(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, const unsigned *peaks, int n_peaks,
+                       unsigned char *dst, int64_t dst_cap, hipStream_t st) {
+    hipLaunchKernelGGL(deliver_pcm_kernel, dim3(ceil_div(max_n, 1024), n_rows), dim3(256), 0, st, table, n_sources, channels, peaks,
+                       n_peaks, dst, dst_cap);
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}
+
+}  // namespace mi

@@ -184,4 +184,10 @@ int launch_track_affine(float *x, int64_t n, const float *stats, int mode, hipSt
 int launch_prevent_clip(const float *x, int64_t n, int mode, unsigned *peak, float *y, hipStream_t st);
 int launch_two_stems(const float *const *stems, int S, int sel, const float *origin, int mode, int64_t n, float *y, hipStream_t st);
 
+// deliver.hip: two-stems value, clip prevention, PCM conversion and interleaving of every output of a call in one launch
+int launch_deliver_peaks(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks, int n_peaks,
+                         int64_t dst_cap, hipStream_t st);
+int launch_deliver_pcm(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, const unsigned *peaks, int n_peaks,
+                       unsigned char *dst, int64_t dst_cap, hipStream_t st);
+
 }  // namespace mi

@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "post_ops.h"
 
 namespace mi {
 
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void track_affine_kernel(float *__restrict__ x
 // reduction runs on the bit patterns: |NaN| orders above +inf, so a NaN sample reaches `peak` as torch's abs().max() propagates it
 __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ x, int64_t n, unsigned *__restrict__ peak) {
     unsigned m = 0u;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = max(m, __float_as_uint(fabsf(x[i])));
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = max(m, abs_bits(x[i]));
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
     if ((threadIdx.x & 63) == 0) atomicMax(peak, m);
 }
@@ -87,17 +88,7 @@ __global__ __launch_bounds__(256) void prevent_clip_kernel(const float *__restri
                                                            float *__restrict__ y) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float v = x[i];
-    float r;
-    if (mode == 1) {
-        const float d = __fmul_rn(__uint_as_float(*peak), 1.01f);
-        r = (d > 1.0f || d != d) ? __fdiv_rn(v, d) : v;       // a NaN peak divides everything (python's max(nan_tensor, 1) keeps the NaN)
-    } else if (mode == 2) {
-        r = fminf(fmaxf(v, -0.99f), 0.99f);
-    } else {
-        r = tanhf(v);
-    }
-    y[i] = r;
+    y[i] = clip_sample(x[i], mode, mode == 1 ? clip_divisor(*peak) : 0.f);      // post_ops.h, shared with deliver.hip
 }
 
 struct StemPtrs { const float *p[8]; };
@@ -108,11 +99,10 @@ __global__ __launch_bounds__(256) void two_stems_kernel(StemPtrs stems, int S, i
                                                         float *__restrict__ y) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    if (mode == 1) { y[i] = __fsub_rn(origin[i], stems.p[sel][i]); return; }
-    float a = 0.f;
-    for (int k = 0; k < S; ++k)
-        if (k != sel) a = __fadd_rn(a, stems.p[k][i]);
-    y[i] = a;
+    if (mode == 1) { y[i] = two_stems_minus(origin[i], stems.p[sel][i]); return; }
+    float a[1];
+    two_stems_add<1>(S, sel, [&](int k, float (&s)[1]) { s[0] = stems.p[k][i]; }, a);      // post_ops.h, shared with deliver.hip
+    y[i] = a[0];
 }
 
 int post_stats_scratch_bytes() { return kPostBlocks * 2 * (int)sizeof(double); }

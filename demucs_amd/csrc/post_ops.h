@@ -1,0 +1,49 @@
+// Per-sample arithmetic of the stem post-processing, shared by post.hip (mi_prevent_clip, mi_two_stems: one output per call) and
+// deliver.hip (mi_deliver_peaks / mi_deliver_pcm: every output of a call in one launch), so both routes run the same float32
+// sequence.  Every step is a separately rounded operation (the library builds with -ffp-contract=off).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace mi {
+
+// "add" of `--two-stems` (demucs/separate.py:207-210): zeros_like, then += every stem but `sel` in index order, for W samples
+// side by side.  stem(k, s) fills s[0 .. W-1] with stem k's samples
+template <int W, class Stem>
+__device__ __forceinline__ void two_stems_add(int S, int sel, Stem stem, float (&a)[W]) {
+#pragma unroll
+    for (int e = 0; e < W; ++e) a[e] = 0.f;
+    for (int k = 0; k < S; ++k) {
+        if (k == sel) continue;
+        float s[W];
+        stem(k, s);
+#pragma unroll
+        for (int e = 0; e < W; ++e) a[e] = __fadd_rn(a[e], s[e]);
+    }
+}
+
+// "minus" (separate.py:197): origin - stem
+__device__ __forceinline__ float two_stems_minus(float origin, float stem) { return __fsub_rn(origin, stem); }
+
+// the divisor of "rescale" from the peak's bit pattern: 1.01 * wav.abs().max() (demucs/audio.py:226)
+__device__ __forceinline__ float clip_divisor(unsigned peak_bits) { return __fmul_rn(__uint_as_float(peak_bits), 1.01f); }
+
+// mode 1 "rescale": v / max(d, 1); 2 "clamp": clamp(v, -0.99, 0.99); 3 "tanh"; anything else: v   (audio.py:225-231)
+__device__ __forceinline__ float clip_sample(float v, int mode, float d) {
+    if (mode == 1) return (d > 1.0f || d != d) ? __fdiv_rn(v, d) : v;   // a NaN peak divides everything (python's max(nan_tensor, 1) keeps the NaN)
+    if (mode == 2) return v != v ? v : fminf(fmaxf(v, -0.99f), 0.99f);   // torch's clamp keeps a NaN; fmaxf / fminf alone would drop it
+    if (mode == 3) return tanhf(v);
+    return v;
+}
+
+// the unsigned bit pattern of |v|: unsigned order == float order for non-negative floats, and |NaN| orders above +inf, so a max
+// over these reaches the peak as torch's abs().max() propagates a NaN
+__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(fabsf(v)); }
+
+// `i16_pcm` (audio.py:178): (wav.clamp_(-1, 1) * (2**15 - 1)).short(); the conversion truncates toward zero.  A NaN passes the
+// clamp and the product; C leaves its conversion undefined, torch on x86 gives 0: that is the rule here
+__device__ __forceinline__ short pcm_i16(float v) {
+    if (v != v) return 0;
+    return (short)(int)__fmul_rn(fminf(fmaxf(v, -1.0f), 1.0f), 32767.0f);
+}
+
+}  // namespace mi

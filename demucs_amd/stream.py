@@ -45,20 +45,67 @@ from . import _lib
 from .hdemucs import HDemucs, MIN_LENGTH as _HDEMUCS_MIN_LENGTH
 from .htdemucs import HTDemucs
 
-__all__ = ["apply_model_stream", "apply_model_stream_group", "ModelStream", "StreamGroup", "EMIT_PASS_COLS"]
+__all__ = ["apply_model_stream", "apply_model_stream_group", "ModelStream", "StreamGroup", "Delivery", "EMIT_PASS_COLS"]
 
 # column layout of mi_stream_emit's pass table (include/demucs_amd.h, MI_EMIT_*)
 EMIT_PASS_COLS = 8
 TILE_COLS, TILE_SPAN = 7, 1024                 # packed tile table (MI_PACK_*)
 
 
+class Delivery:
+    """How a stream hands its stems over (`audio.deliver`'s arguments): with one, `push` / `finish` return `{name: (m, channels)
+    frames}` -- every source, or with `stem` the `--two-stems` outputs -- after `prevent_clip(·, clip)`, as int16 PCM ("i16") or
+    float32 ("f32") with the channels interleaved per frame, instead of the float32 (S, channels, m) stems."""
+
+    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16"):
+        from .audio import clip_code, deliver_layout
+        if other_method not in ("add", "minus", "none"):
+            raise ValueError(f"Invalid other_method {other_method}")
+        self.stem, self.other_method, self.clip, self.fmt = stem, other_method, clip, fmt
+        self.clip_code = clip_code(clip)
+        deliver_layout([], 0, 1, fmt)                       # refuses an unknown format
+
+    def __repr__(self):
+        return f"Delivery(stem={self.stem!r}, other_method={self.other_method!r}, clip={self.clip!r}, fmt={self.fmt!r})"
+
+    def outputs(self, sources) -> list:
+        """[(name, KIND, SEL)] in the reference's save order (`audio.delivery_outputs`)."""
+        from .audio import delivery_outputs
+        return delivery_outputs(sources, self.stem, self.other_method)
+
+    def for_stream(self, sources, engine: bool) -> list:
+        """The refusals of a delivering stream (no device work, no RNG call) and its outputs."""
+        if self.clip == "rescale":
+            raise ValueError("a stream cannot deliver with clip='rescale': the divisor is the whole track's peak per output; use "
+                             "'clamp', 'tanh' or None")
+        if self.stem is not None and self.other_method == "minus":
+            raise ValueError("a stream cannot deliver other_method='minus': it keeps no copy of its input behind the emit point; "
+                             "use 'add' or 'none'")
+        outs = self.outputs(sources)
+        if not engine:
+            raise ValueError("a delivering stream runs on the GPU engines (HTDemucs / HDemucs on a cuda device); there is no CPU "
+                             "implementation of the delivery kernels in this package")
+        return outs
+
+
+def _deliver_rows(outputs, dl: Delivery, src: int, n: int, offs) -> list:
+    """mi_deliver_pcm's rows (MI_DELIVER_*) for one stream's outputs on a push: `n` frames of the stems at device address `src`."""
+    from .audio import _FORMATS
+    rows = []
+    for (_, kind, sel), off in zip(outputs, offs):
+        rows += [src, 0, n, kind, sel, dl.clip_code, 0, _FORMATS[dl.fmt][0], off]
+    return rows
+
+
 def apply_model_stream(model, shifts: int = 1, overlap: float = 0.25, transition_power: float = 1.0, segment=None,
                        device=None, length: Optional[int] = None, split: bool = True, progress: bool = False,
-                       callback=None) -> "ModelStream":
+                       callback=None, deliver: Optional[Delivery] = None) -> "ModelStream":
     """Start a stream; see the module docstring.  `st.push(block)` takes (channels, n) float32 on the host or a device and
-    returns the newly final stems (S, channels, m); `st.finish()` returns the rest.  `device` defaults to the first block's."""
+    returns the newly final stems (S, channels, m); `st.finish()` returns the rest.  `device` defaults to the first block's.
+    With `deliver=Delivery(...)` both return `{name: (m, channels) frames}` instead (one more launch per push, `mi_deliver_pcm`
+    on the emitted span; host blocks get the frames by one D2H of their bytes and no float stems leave the device)."""
     return ModelStream(model, shifts=shifts, overlap=overlap, transition_power=transition_power, segment=segment, device=device,
-                       length=length, split=split, progress=progress, callback=callback)
+                       length=length, split=split, progress=progress, callback=callback, deliver=deliver)
 
 
 class _Member:
@@ -105,7 +152,7 @@ class ModelStream:
     """One stream.  Attributes: `emitted` (samples returned so far), `pushed`, `latency` (see the module docstring)."""
 
     def __init__(self, model, shifts=1, overlap=0.25, transition_power=1.0, segment=None, device=None, length=None,
-                 split=True, progress=False, callback=None, affine=None):
+                 split=True, progress=False, callback=None, affine=None, deliver=None):
         from .apply import BagOfModels
         from . import distributed
         if not split:
@@ -134,6 +181,10 @@ class ModelStream:
         self.finished = False
         self._exec = None
         self._out_device = None
+        self.deliver, self.outputs = deliver, None
+        if deliver is not None:
+            engine = all(m.kind != "generic" for m in self.members) and (self.device is None or self.device.type == "cuda")
+            self.outputs = deliver.for_stream(self.sources, engine)
         # Separator.separate_stream: blocks are normalised `(x - mean) / s` and stems restored `x * s + mean`, s = std + 1e-8
         self.affine = None
         if affine is not None:
@@ -573,6 +624,7 @@ class _EngineExec:
         t0 = st.emitted
         S, channels = len(st.sources), st.audio_channels
         out = torch.empty(S, channels, t1 - t0, device=st.device, dtype=torch.float32)
+        dl, frames = st.deliver, None
         if t1 > t0:
             passes, segs = [], []
             for pi, ps in enumerate(st.passes):
@@ -582,6 +634,12 @@ class _EngineExec:
                     segs += [o - ps.a0, n]
                 e = ps.member
                 passes += [self.bases[pi], ps.hi - ps.a0, q0 - ps.a0, s_lo, len(segs) // 2, self.w_offs[e], st.members[e].SL, e]
+            if dl is not None:              # the delivery rows ride behind the pass table, in its upload
+                from .audio import deliver_layout
+                offs, total = deliver_layout(st.outputs, t1 - t0, channels, dl.fmt)
+                d_at = len(passes)
+                passes = passes + _deliver_rows(st.outputs, dl, out.data_ptr(), t1 - t0, offs)
+                frames = (torch.empty(total, dtype=torch.uint8, device=st.device), offs)
             t_passes = _upload(passes, torch.int64, st.device)
             t_segs = _upload(segs or [0, 0], torch.int64, st.device)
             keep += [t_passes, t_segs]
@@ -591,15 +649,40 @@ class _EngineExec:
                                                int(st.bag_weights is not None),
                                                self.stats.data_ptr() if self.stats is not None else None,
                                                t1 - t0, out.data_ptr(), out.numel(), self._stream()), "mi_stream_emit")
+            if dl is not None:
+                keep.append(out)
+                _lib.check(self.lib.mi_deliver_pcm(C.c_void_p(t_passes.data_ptr() + 8 * d_at), len(st.outputs), t1 - t0, S, channels,
+                                                   None, 0, frames[0].data_ptr(), frames[0].numel(), self._stream()),
+                           "mi_deliver_pcm")
         st.emitted = t1
-        return out
+        return out if dl is None else (frames, t1 - t0)
 
-    def _host(self, out: torch.Tensor) -> torch.Tensor:
+    def _host(self, out):
+        if self.st.deliver is not None:
+            return self._frames(*out)
         dev = self.st._out_device
         if dev is None or torch.device(dev).type != "cpu":
             return self.st._result(out)
-        host = torch.empty(out.shape, dtype=torch.float32, pin_memory=True)
+        host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
         host.copy_(out, non_blocking=True)
+        torch.cuda.current_stream(self.st.device).synchronize()
+        return host
+
+    def _frames(self, frames, n: int) -> dict:
+        """`{name: (n, channels) frames}` of a delivering stream, on the pushed block's device (host: ONE D2H of the bytes)."""
+        from .audio import _FORMATS, deliver_views
+        st = self.st
+        to = st._out_device if st._out_device is not None else st.device
+        if frames is None:
+            dtype = _FORMATS[st.deliver.fmt][1]
+            return {name: torch.empty(0, st.audio_channels, dtype=dtype, device=to) for name, _, _ in st.outputs}
+        buf, offs = frames
+        buf = self._host_bytes(buf) if torch.device(to).type == "cpu" else st._result(buf)
+        return deliver_views(buf, st.outputs, offs, n, st.audio_channels, st.deliver.fmt)
+
+    def _host_bytes(self, buf: torch.Tensor) -> torch.Tensor:
+        host = torch.empty(buf.shape, dtype=buf.dtype, pin_memory=True)
+        host.copy_(buf, non_blocking=True)
         torch.cuda.current_stream(self.st.device).synchronize()
         return host
 
@@ -636,6 +719,7 @@ class _EngineExec:
 # stream groups: many streams, one unit of work per push
 # ------------------------------------------------------------------------------------------------------------------------
 STREAMS_EMIT_COLS, APPEND_COLS, COMPACT_COLS = 7, 6, 4     # include/demucs_amd.h: MI_STREAMS_EMIT_*, MI_APPEND_*, MI_COMPACT_*
+DELIVER_COLS = 9                                            # MI_DELIVER_COLS
 ITEM_COLS = 8                                               # MI_PACK_ITEM_COLS
 
 
@@ -657,7 +741,9 @@ class StreamGroup:
     On the engines a call is a fixed amount of device work whatever the number of streams: one H2D of the call's int64 table
     together with its host blocks, one `mi_streams_append`, the pooled forwards (each a gather, the forward and an overlap-add
     driven by that table), one `mi_streams_emit` and one D2H of the host-bound stems, plus one `mi_streams_compact` when a
-    stream outgrows its room in the state buffer (every stream's window and accumulators).  Streams opened with `convert=`
+    stream outgrows its room in the state buffer (every stream's window and accumulators).  Streams opened with `deliver=` add one
+    `mi_deliver_pcm` for all of them behind the emit; their host-bound frames leave in one D2H of the byte buffer, and their float
+    stems never do.  Streams opened with `convert=`
     take blocks at another sample rate or channel count: one `mi_streams_convert_append` per call runs the streaming
     `convert_audio` (demucs_amd/audio.py, `ConvertPlan`) for all of them into their windows, and what the converter has made
     final is what the stream's scheduler sees as pushed.
@@ -679,12 +765,18 @@ class StreamGroup:
         self._exec = None
 
     # ---- public --------------------------------------------------------------------------------------------------------
-    def open(self, length: Optional[int] = None, affine=None, convert=None):
+    def open(self, length: Optional[int] = None, affine=None, convert=None, deliver: Optional[Delivery] = None):
         """A new stream; makes the RNG calls `ModelStream(..., length=length)` makes.  Returns its key.
+
+        `deliver=Delivery(...)`: the stream's results are `{name: (m, channels) frames}` (see `Delivery`), each stream of a group
+        with its own; one `mi_deliver_pcm` launch per call serves all of them, its rows in the call's table.
 
         `convert=(audio.ConvertPlan, source channels)`: the stream's blocks are (source channels, n) at the plan's input rate and
         pass through the streaming `convert_audio` into its window (one `mi_streams_convert_append` for all such streams of a
         call); `length` then counts input samples, and the RNG calls are those of the converted length."""
+        if deliver is not None:             # refused here, before any RNG call
+            deliver.for_stream(self.sources, all(m.kind != "generic" for m in self.members) and
+                               (self.device is None or self.device.type == "cuda"))
         conv = None
         if convert is not None:
             from .audio import check_stream_channels
@@ -697,7 +789,7 @@ class StreamGroup:
                 raise ValueError(f"length must be >= 0, got {length}")
             conv = _Conv(plan, int(src_channels), None if length is None else int(length))
             length = None if length is None else plan.final_count(int(length))
-        st = ModelStream(self.model, device=self.device, length=length, affine=affine, **self._kw)
+        st = ModelStream(self.model, device=self.device, length=length, affine=affine, deliver=deliver, **self._kw)
         st.convert = conv
         key = self._next
         self._next += 1
@@ -719,7 +811,8 @@ class StreamGroup:
         return 0 if self._exec is None else self._exec.device_bytes()
 
     def push(self, blocks) -> dict:
-        """`{key: (channels, n) block}` -> `{key: (S, channels, m) newly final stems}`, the streams taken in the mapping's order."""
+        """`{key: (channels, n) block}` -> `{key: (S, channels, m) newly final stems}` (a delivering stream: `{name: (m, channels)
+        frames}`), the streams taken in the mapping's order."""
         items = list(blocks.items())
         for key, block in items:
             st = self._stream(key)
@@ -1221,13 +1314,15 @@ class _GroupEngineExec:
     def _emit_rows(self, work, table):
         """mi_streams_emit's tables for every stream of the call with new final samples; host-bound stems first."""
         g = self.g
+        from .audio import deliver_layout
         S, C_ = len(g.sources), g.audio_channels
         spans = []
         for key, st, _ in work:
             t0, t1 = st.emitted, st._emit_limit()
             dev = st._out_device
             spans.append((key, st, t0, t1, dev is not None and torch.device(dev).type == "cpu"))
-        spans.sort(key=lambda s: not s[4])
+        # float stems that go to the host first; a delivering stream's stay on the device, so they sort with the device-bound
+        spans.sort(key=lambda s: not (s[4] and s[1].deliver is None))
         streams, passes, segs = [], [], []
         off, host_n, longest = 0, 0, 1
         layout = {}
@@ -1247,20 +1342,37 @@ class _GroupEngineExec:
                 streams += [p_lo, len(passes) // 8, s_lo, len(segs) // 2, slot.stats, off, n]
                 longest = max(longest, n)
             off += S * C_ * n
-            if to_host:
+            if to_host and st.deliver is None:
                 host_n = off
             st.emitted = t1
         at = len(table)
         table += streams + passes + (segs or [0, 0])
+        # the float stems of the call (allocated here: a delivery row names its stream's) and the delivered frames, one byte
+        # buffer with the host-bound streams first
+        out = torch.empty(off, device=g.device, dtype=torch.float32) if off else None
+        d_rows, d_layout, d_off, d_host, d_longest = [], {}, 0, 0, 1
+        for key, st, _, _, to_host in sorted(spans, key=lambda s: not s[4]):
+            f_off, n = layout[key]
+            if st.deliver is None or n == 0:
+                continue
+            offs, d_off = deliver_layout(st.outputs, n, C_, st.deliver.fmt, d_off)
+            d_rows += _deliver_rows(st.outputs, st.deliver, out.data_ptr() + 4 * f_off, n, offs)
+            d_layout[key] = offs
+            d_longest = max(d_longest, n)
+            if to_host:
+                d_host = d_off
+        d_at = len(table)
+        table += d_rows
         return dict(at=at, n_streams=len(streams) // STREAMS_EMIT_COLS, n_passes=len(passes) // 8, n_segs=len(segs) // 2,
                     total=off, host_n=host_n, longest=longest, layout=layout, order=[k for k, _, _ in work],
-                    streams={k: st for k, st, _ in work})
+                    streams={k: st for k, st, _ in work}, out=out, d_at=d_at, d_rows=len(d_rows) // DELIVER_COLS, d_total=d_off,
+                    d_host=d_host, d_longest=d_longest, d_layout=d_layout)
 
     def _emit(self, emit, base) -> dict:
         g = self.g
         dev = g.device
         S, C_ = len(g.sources), g.audio_channels
-        out = torch.empty(emit["total"], device=dev, dtype=torch.float32) if emit["total"] else None
+        out = emit["out"]
         if emit["n_streams"]:
             at = base + 8 * emit["at"]
             t_streams = at
@@ -1272,23 +1384,47 @@ class _GroupEngineExec:
                                                 self.scales.data_ptr(), len(g.members), g._kw["shifts"],
                                                 int(g.bag_weights is not None), self.stats.data_ptr(), self.n_stats, out.data_ptr(),
                                                 out.numel(), self._stream()), "mi_streams_emit")
-        host = None
+        frames = None
+        if emit["d_rows"]:
+            frames = torch.empty(emit["d_total"], dtype=torch.uint8, device=dev)
+            _lib.check(self.lib.mi_deliver_pcm(C.c_void_p(base + 8 * emit["d_at"]), emit["d_rows"], emit["d_longest"], S, C_, None, 0,
+                                               frames.data_ptr(), frames.numel(), self._stream()), "mi_deliver_pcm")
+        host = host_frames = None
         if emit["host_n"]:
             host = torch.empty(emit["host_n"], dtype=torch.float32, pin_memory=True)
             host.copy_(out[:emit["host_n"]], non_blocking=True)
+        if emit["d_host"]:
+            host_frames = torch.empty(emit["d_host"], dtype=torch.uint8, pin_memory=True)
+            host_frames.copy_(frames[:emit["d_host"]], non_blocking=True)
+        if host is not None or host_frames is not None:
             torch.cuda.current_stream(dev).synchronize()
         res = {}
         for key in emit["order"]:
             off, n = emit["layout"][key]
             st = emit["streams"][key]
             to = st._out_device
-            if n == 0:
+            if st.deliver is not None:
+                res[key] = self._frames(st, n, emit["d_layout"].get(key), frames, host_frames, emit["d_host"])
+            elif n == 0:
                 res[key] = torch.empty(S, C_, 0, dtype=torch.float32, device=to)
             elif host is not None and off < emit["host_n"]:
                 res[key] = host[off:off + S * C_ * n].view(S, C_, n)
             else:
                 res[key] = st._result(out[off:off + S * C_ * n].view(S, C_, n))
         return res
+
+    def _frames(self, st: ModelStream, n: int, offs, frames, host_frames, d_host: int) -> dict:
+        """`{name: (n, channels) frames}` of a delivering stream, on its last block's device."""
+        from .audio import _FORMATS, deliver_views
+        C_ = self.g.audio_channels
+        to = st._out_device if st._out_device is not None else self.g.device
+        if offs is None:
+            dtype = _FORMATS[st.deliver.fmt][1]
+            return {name: torch.empty(0, C_, dtype=dtype, device=to) for name, _, _ in st.outputs}
+        if host_frames is not None and offs[0] < d_host:
+            return deliver_views(host_frames, st.outputs, offs, n, C_, st.deliver.fmt)
+        views = deliver_views(frames, st.outputs, offs, n, C_, st.deliver.fmt)
+        return {name: st._result(v) for name, v in views.items()}
 
     def push(self, items) -> dict:
         return self._step(items, final=False)

@@ -392,6 +392,51 @@ int mi_prevent_clip(const float *x_dev, int64_t numel, int32_t mode, void *peak_
 int mi_two_stems(const float *const *stems_dev, int32_t n_stems, int32_t selected, const float *origin_dev, int32_t minus, int64_t numel,
                  float *y_dev, void *stream);
 
+/* ---- delivery: the stems as the reference saves them, every output of a call in ONE launch -----------------------------------
+ * The reference's save loop (demucs/separate.py:178-218) forms the `--two-stems` outputs and hands each to `save_audio`
+ * (demucs/audio.py:236-265): `prevent_clip` (audio.py:218-234), then `i16_pcm` (audio.py:175-181) or float32, channels
+ * interleaved per frame.  Row r of the table (MI_DELIVER_COLS int64, a DEVICE array) is ONE such output:
+ *     SRC       DEVICE address of the contiguous float32 (n_sources, channels, n) stems (trusted, as MI_APPEND_SRC is);
+ *     ORIGIN    DEVICE address of the (channels, n) float32 mix, or 0 (needed by KIND 2 only; trusted);
+ *     N         frames;
+ *     KIND      MI_DELIVER_STEM: stem SEL; MI_DELIVER_ADD: 0 + every stem but SEL in index order (separate.py:207-210, the
+ *               "no_STEM" file); MI_DELIVER_MINUS: origin - stem SEL (separate.py:197, the "minus_STEM" file);
+ *     SEL       source index;
+ *     CLIP      0 (none) or MI_CLIP_*, as mi_prevent_clip;
+ *     PEAK      the row's slot in peaks_dev (n_peaks uint32 bit patterns; read only by MI_CLIP_RESCALE rows);
+ *     FMT       MI_DELIVER_I16: clamp to [-1, 1], times 32767.f, truncated toward zero (a NaN becomes 0); MI_DELIVER_F32: the
+ *               clipped value as it is;
+ *     DST_OFF   byte offset of the row's (n, channels) interleaved frames in dst_dev: channel c of frame j at
+ *               DST_OFF + (j * channels + c) * (2 or 4).
+ *   Every step is a separately rounded float32 operation in the reference's order, by the device functions mi_prevent_clip and
+ *   mi_two_stems are built from.  A row is skipped (nothing of it is read or written) when its frames leave dst_capacity (bytes),
+ *   DST_OFF is negative or no multiple of 4, N <= 0, SRC is 0, KIND / SEL / CLIP / FMT is out of range, a MI_CLIP_RESCALE row's PEAK is
+ *   not in [0, n_peaks), or a MI_DELIVER_MINUS row has no ORIGIN.  dst_dev is 4-byte aligned; max_n >= every N (grid size).
+ * mi_deliver_peaks: zeroes peaks_dev (one memset) and reduces max |value| of every MI_CLIP_RESCALE row into its slot, on the
+ *   unsigned bit patterns as mi_prevent_clip does (a NaN sample makes the row's peak NaN, as torch's abs().max()).  The peak is
+ *   per row, as the reference calls save_audio per output.  Call it before mi_deliver_pcm on the same stream when a row rescales;
+ *   nothing synchronises with the host.
+ * mi_deliver_pcm: writes every row's frames.  peaks_dev may be null when n_peaks == 0 (rescaling rows are then skipped). */
+#define MI_DELIVER_SRC 0
+#define MI_DELIVER_ORIGIN 1
+#define MI_DELIVER_N 2
+#define MI_DELIVER_KIND 3
+#define MI_DELIVER_SEL 4
+#define MI_DELIVER_CLIP 5
+#define MI_DELIVER_PEAK 6
+#define MI_DELIVER_FMT 7
+#define MI_DELIVER_DST_OFF 8
+#define MI_DELIVER_COLS 9
+#define MI_DELIVER_STEM 0
+#define MI_DELIVER_ADD 1
+#define MI_DELIVER_MINUS 2
+#define MI_DELIVER_I16 0
+#define MI_DELIVER_F32 1
+int mi_deliver_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels, void *peaks_dev,
+                     int32_t n_peaks, int64_t dst_capacity, void *stream);
+int mi_deliver_pcm(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels, const void *peaks_dev,
+                   int32_t n_peaks, void *dst_dev, int64_t dst_capacity, void *stream);
+
 /* ---- kernel-level entry points (parity tests; same kernels the forward uses) --------------
  * mi_stft_cac: `_magnitude(_spec(mix))` (demucs/htdemucs.py:420-461, demucs/spec.py:11-27):
  *   mix_dev (B,2,L) -> cac_dev (B,4,2048,ceil(L/1024)), channel order [c0.re,c0.im,c1.re,c1.im]. */
