@@ -152,7 +152,14 @@ class Separator:
         With `deliver=Delivery(...)` (demucs_amd/stream.py) `push` / `finish` return what the reference would write to its files
         for those samples instead: `{name: (m, channels) frames}` in the order of its save loop, after `prevent_clip` and as
         int16 PCM or float32 with interleaved channels -- `audio.deliver`'s chain on the stems above, by one more launch per
-        push.  A stream refuses clip="rescale" and other_method="minus", which need the whole track."""
+        push.  A stream refuses clip="rescale" and other_method="minus", which need the whole track.
+
+        `Delivery(..., samplerate=R)` returns the frames at R Hz instead of the model's rate M, resampled on the device:
+        `audio.deliver(..., samplerate=(M, R))` on the whole track, bit for bit.  A push returns the resampler frames whose last
+        tap the stream has emitted (`delivered` counts them, at most `output_hold` behind floor(new * emitted / old)), `finish()`
+        the rest, floor(new * L / old) in all for L samples at M.  With `convert=True` and `samplerate=sr` a feed gets its stems back
+        at its own rate; the length then is floor(new' * floor(new * N / old) / old') for N input samples (sr -> M reduces to
+        old:new, M -> sr to old':new'), which can be a sample or two short of N: nothing is padded."""
         if not convert:
             if channels is not None and channels != self._audio_channels:
                 raise ValueError(f"separate_stream: {channels} input channels are not the model's {self._audio_channels}; pass "
@@ -296,6 +303,16 @@ class SeparatorStream:
     def latency(self) -> int:
         return self.stream.latency
 
+    @property
+    def delivered(self) -> int:
+        """Frames returned so far by a stream that delivers at another sample rate (`Delivery(samplerate=R)`), at R."""
+        return self.stream.delivered
+
+    @property
+    def output_hold(self) -> int:
+        """Bound of floor(new * emitted / old) - delivered for such a stream; some push reaches it."""
+        return self.stream.output_hold
+
 
 class ConvertingSeparatorStream(SeparatorStream):
     """`Separator.separate_stream(convert=True)`: an `audio.ConvertStream` on the device in front of the model's stream.
@@ -381,6 +398,9 @@ class SeparatorStreamGroup:
 
     def emitted(self, key) -> int:
         return self.group.emitted(key)
+
+    def delivered(self, key) -> int:
+        return self.group.delivered(key)
 
     @property
     def latency(self) -> int:

@@ -423,12 +423,111 @@ def _stems_block(tensors, dev: torch.device) -> torch.Tensor:
     return torch.stack([t.to(torch.float32) for t in tensors]).to(dev).contiguous()
 
 
-def deliver(origin: torch.Tensor, stems: dict, stem=None, other_method: str = "add", clip="rescale", fmt: str = "i16") -> dict:
+# ---- delivery at another sample rate (mi_deliver_resample_pcm, demucs_amd/csrc/deliver_resample.hip) -------------------------
+RATE_COLS = 20                     # include/demucs_amd.h: MI_RATE_*
+RATE_LDS_FLOATS = 16384            # MI_RATE_LDS_FLOATS: the kernel's LDS staging area (64 KiB), shared by all channels
+RATE_FRAMES, RATE_SUBRUNS = 8, 4
+
+
+def rate_subruns(plan: ConvertPlan, channels: int) -> int:
+    """8-frame runs a workgroup of the kernel takes: what the staging area holds for all channels (deliver_resample.hip)."""
+    return min(RATE_SUBRUNS, (RATE_LDS_FLOATS // channels - 2 * plan.width) // (RATE_FRAMES * plan.old))
+
+
+def rate_groups(plan: ConvertPlan, channels: int, n_out: int) -> int:
+    """Workgroups per row for `n_out` output frames."""
+    return max(1, -(-(-(-n_out // plan.new)) // (RATE_FRAMES * rate_subruns(plan, channels))))
+
+
+def rate_lds_floats(plan: ConvertPlan, channels: int) -> int:
+    return channels * (RATE_FRAMES * rate_subruns(plan, channels) * plan.old + 2 * plan.width)
+
+
+def delivery_rate_plan(model_rate: int, samplerate, channels: int):
+    """The `ConvertPlan(model_rate, samplerate)` of a stream that delivers at `samplerate`, None when that is the model's rate (or
+    None): the refusals of such a stream, without any device work."""
+    if samplerate is None:
+        return None
+    if int(samplerate) != samplerate or samplerate <= 0:
+        raise ValueError(f"the delivered sample rate must be a positive integer, got {samplerate}")
+    if int(samplerate) == int(model_rate):
+        return None
+    try:
+        plan = ConvertPlan(int(model_rate), int(samplerate))
+    except ValueError as exc:
+        raise ValueError(f"a stream cannot deliver at {samplerate} Hz from the model's {model_rate} Hz: {exc}") from None
+    if rate_subruns(plan, channels) < 1:
+        raise ValueError(f"a stream cannot deliver at {samplerate} Hz from the model's {model_rate} Hz: the rate pair {model_rate} -> "
+                         f"{samplerate} reduces to {plan.old}:{plan.new}, and a frame of {plan.old} samples of {channels} channels is "
+                         "too long for the delivery kernel; deliver at the model's rate and resample the whole track instead")
+    return plan
+
+
+def _deliver_resampled(origin, stems: dict, stem, other_method, clip, fmt, rates) -> dict:
+    """`deliver` at another sample rate, for a whole track: per output the `two_stems` value, `resample_frac`, then the delivery
+    kernels on the resampled values as plain rows (the peak of "rescale" is that of the resampled value)."""
+    old_rate, new_rate = (int(r) for r in rates)
+    names = list(stems)
+    outputs = delivery_outputs(names, stem, other_method)
+    code = clip_code(clip)
+    if fmt not in _FORMATS:
+        raise ValueError(f"Invalid format {fmt!r}: 'i16' or 'f32'")
+    for t in stems.values():
+        if not t.dtype.is_floating_point:
+            raise TypeError(f"deliver: a floating-point tensor is expected, got {t.dtype}")
+        if t.dim() != 2 or t.shape != stems[names[0]].shape:
+            raise ValueError(f"deliver: every stem is (channels, n), got {[tuple(x.shape) for x in stems.values()]}")
+    values = dict(stems) if stem is None else two_stems(origin, stems, stem, other_method)
+    assert list(values) == [name for name, _, _ in outputs]
+    first = next(iter(values.values()))
+    home = first.device
+    dev = _engine_device(*values.values())
+    with torch.cuda.device(dev):
+        block = torch.stack([_stage(v, dev, "deliver") for v in values.values()])
+        block = resample_frac(block, old_rate, new_rate, device=dev).contiguous()
+        _, channels, n = block.shape
+        if n == 0 or channels == 0:
+            return {name: torch.empty(n, channels, dtype=_FORMATS[fmt][1], device=home) for name in values}
+        plain = [(name, DELIVER_STEM, i) for i, name in enumerate(values)]
+        offs, total = deliver_layout(plain, n, channels, fmt)
+        rows = []
+        for (_, kind, sel), off in zip(plain, offs):
+            rows += [block.data_ptr(), 0, n, kind, sel, code, sel, _FORMATS[fmt][0], off]
+        table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        buf = torch.empty(total, dtype=torch.uint8, device=dev)
+        lib, stream = _lib.load(), C.c_void_p(_lib.current_stream_ptr())
+        peaks = None
+        if code == _CLIP_MODES["rescale"]:
+            peaks = torch.empty(len(plain), dtype=torch.int32, device=dev)
+            _lib.check(lib.mi_deliver_peaks(table.data_ptr(), len(plain), n, len(plain), channels, peaks.data_ptr(), len(plain), total,
+                                            stream), "mi_deliver_peaks")
+        _lib.check(lib.mi_deliver_pcm(table.data_ptr(), len(plain), n, len(plain), channels,
+                                      peaks.data_ptr() if peaks is not None else None, 0 if peaks is None else len(plain),
+                                      buf.data_ptr(), total, stream), "mi_deliver_pcm")
+        if home.type == "cpu":
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            host.copy_(buf, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            buf = host
+        elif home != dev:
+            buf = buf.to(home)
+    return deliver_views(buf, plain, offs, n, channels, fmt)
+
+
+def deliver(origin: torch.Tensor, stems: dict, stem=None, other_method: str = "add", clip="rescale", fmt: str = "i16",
+            samplerate=None) -> dict:
     """What demucs/separate.py:178-218 hands to its encoders, for one separated track: `{name: (n, channels) frames}` in the
     order of the reference's save loop -- every source, or with `stem` the `--two-stems` outputs `two_stems` names -- each after
     `prevent_clip(·, clip)` (the peak of "rescale" is per output, as `save_audio` is called per output) and `i16_pcm` (fmt "i16")
     or as float32 ("f32"), channels interleaved per frame.  All outputs of the track take ONE `mi_deliver_peaks` launch (only
-    for "rescale") and ONE `mi_deliver_pcm` launch; host stems come back on the host by one D2H of the byte buffer."""
+    for "rescale") and ONE `mi_deliver_pcm` launch; host stems come back on the host by one D2H of the byte buffer.
+
+    `samplerate=(M, R)` delivers at R what was separated at M: per output `resample_frac(value, M, R)` between the two-stems value
+    and `prevent_clip`, i.e. `save_audio(julius.resample_frac(v, M, R), path, samplerate=R, clip=clip)`; the frames number
+    floor(R' * n / M') (the rates divided by their gcd).  It is the whole-track counterpart of `Delivery(samplerate=R)` on a
+    stream, and takes `two_stems`' and `resample_frac`'s launches before the two above."""
+    if samplerate is not None and int(samplerate[0]) != int(samplerate[1]):
+        return _deliver_resampled(origin, stems, stem, other_method, clip, fmt, samplerate)
     names = list(stems)
     outputs = delivery_outputs(names, stem, other_method)
     code = clip_code(clip)

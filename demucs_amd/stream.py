@@ -55,25 +55,42 @@ TILE_COLS, TILE_SPAN = 7, 1024                 # packed tile table (MI_PACK_*)
 class Delivery:
     """How a stream hands its stems over (`audio.deliver`'s arguments): with one, `push` / `finish` return `{name: (m, channels)
     frames}` -- every source, or with `stem` the `--two-stems` outputs -- after `prevent_clip(·, clip)`, as int16 PCM ("i16") or
-    float32 ("f32") with the channels interleaved per frame, instead of the float32 (S, channels, m) stems."""
+    float32 ("f32") with the channels interleaved per frame, instead of the float32 (S, channels, m) stems.
 
-    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16"):
+    `samplerate=R` delivers at R Hz instead of the model's M: the frames are those of `prevent_clip(resample_frac(v, M, R), clip)`
+    per output value v, i.e. `audio.deliver(..., samplerate=(M, R))` on the whole track, bit for bit for every partition of the
+    input.  A resampler frame is final once the stream has emitted its last tap, so after `emitted` model-rate samples
+    `ConvertPlan(M, R).ready(emitted)` frames have been returned (`stream.delivered`), at most `stream.output_hold` fewer than
+    floor(new * emitted / old); `finish()` returns the rest, floor(new * L / old) in all.  None, or the model's own rate, changes
+    nothing."""
+
+    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16", samplerate=None):
         from .audio import clip_code, deliver_layout
         if other_method not in ("add", "minus", "none"):
             raise ValueError(f"Invalid other_method {other_method}")
         self.stem, self.other_method, self.clip, self.fmt = stem, other_method, clip, fmt
+        if samplerate is not None and (int(samplerate) != samplerate or samplerate <= 0):
+            raise ValueError(f"the delivered sample rate must be a positive integer, got {samplerate}")
+        self.samplerate = None if samplerate is None else int(samplerate)
         self.clip_code = clip_code(clip)
         deliver_layout([], 0, 1, fmt)                       # refuses an unknown format
 
     def __repr__(self):
-        return f"Delivery(stem={self.stem!r}, other_method={self.other_method!r}, clip={self.clip!r}, fmt={self.fmt!r})"
+        return (f"Delivery(stem={self.stem!r}, other_method={self.other_method!r}, clip={self.clip!r}, fmt={self.fmt!r}, "
+                f"samplerate={self.samplerate!r})")
 
     def outputs(self, sources) -> list:
         """[(name, KIND, SEL)] in the reference's save order (`audio.delivery_outputs`)."""
         from .audio import delivery_outputs
         return delivery_outputs(sources, self.stem, self.other_method)
 
-    def for_stream(self, sources, engine: bool) -> list:
+    def rate_plan(self, model_rate: int, channels: int):
+        """The `audio.ConvertPlan(model_rate, samplerate)` of a stream that resamples its frames, None when it delivers at the
+        model's rate; refuses a rate pair the delivery kernel cannot take."""
+        from .audio import delivery_rate_plan
+        return delivery_rate_plan(model_rate, self.samplerate, channels)
+
+    def for_stream(self, sources, engine: bool, model_rate=None, channels: int = 2) -> list:
         """The refusals of a delivering stream (no device work, no RNG call) and its outputs."""
         if self.clip == "rescale":
             raise ValueError("a stream cannot deliver with clip='rescale': the divisor is the whole track's peak per output; use "
@@ -85,6 +102,8 @@ class Delivery:
         if not engine:
             raise ValueError("a delivering stream runs on the GPU engines (HTDemucs / HDemucs on a cuda device); there is no CPU "
                              "implementation of the delivery kernels in this package")
+        if model_rate is not None:
+            self.rate_plan(model_rate, channels)
         return outs
 
 
@@ -97,13 +116,43 @@ def _deliver_rows(outputs, dl: Delivery, src: int, n: int, offs) -> list:
     return rows
 
 
+class _Rate:
+    """The resampler of one stream that delivers at another rate: its `audio.ConvertPlan(M, R)` and where its carried values
+    live -- (outputs, 2 sides, channels, plan.carry) floats from `off` of a history buffer; `side` is the one to read, whose first
+    value is model-rate position `h0`."""
+
+    def __init__(self, plan, n_outputs: int, channels: int):
+        self.plan, self.n_outputs, self.channels = plan, n_outputs, channels
+        self.size = n_outputs * 2 * channels * plan.carry
+        self.off = None
+        self.side = self.h0 = 0
+
+    def rows(self, outputs, dl: Delivery, src: int, n_in: int, t0: int, final: bool, bank_off: int, offs) -> list:
+        """mi_deliver_resample_pcm's rows (MI_RATE_*) for the stream's outputs on a call that emits `n_in` model-rate samples after
+        `t0`; flips the history side."""
+        from .audio import _FORMATS
+        plan = self.plan
+        out0, n_out, nxt = plan.step(t0, n_in, final)
+        side = self.channels * plan.carry
+        rows = []
+        for o, ((_, kind, sel), off) in enumerate(zip(outputs, offs)):
+            base = self.off + o * 2 * side
+            rows += [src if n_in else 0, n_in, t0, kind, sel, dl.clip_code, _FORMATS[dl.fmt][0], plan.old, plan.new, plan.width,
+                     bank_off, out0, n_out, t0 + n_in if final else -1, plan.carry, base + self.side * side,
+                     base + (1 - self.side) * side, self.h0, nxt, off]
+        if not final:
+            self.side, self.h0 = 1 - self.side, nxt
+        return rows
+
+
 def apply_model_stream(model, shifts: int = 1, overlap: float = 0.25, transition_power: float = 1.0, segment=None,
                        device=None, length: Optional[int] = None, split: bool = True, progress: bool = False,
                        callback=None, deliver: Optional[Delivery] = None) -> "ModelStream":
     """Start a stream; see the module docstring.  `st.push(block)` takes (channels, n) float32 on the host or a device and
     returns the newly final stems (S, channels, m); `st.finish()` returns the rest.  `device` defaults to the first block's.
     With `deliver=Delivery(...)` both return `{name: (m, channels) frames}` instead (one more launch per push, `mi_deliver_pcm`
-    on the emitted span; host blocks get the frames by one D2H of their bytes and no float stems leave the device)."""
+    on the emitted span; host blocks get the frames by one D2H of their bytes and no float stems leave the device).  With
+    `Delivery(samplerate=R)` the frames are at R Hz (`mi_deliver_resample_pcm` in that launch's place)."""
     return ModelStream(model, shifts=shifts, overlap=overlap, transition_power=transition_power, segment=segment, device=device,
                        length=length, split=split, progress=progress, callback=callback, deliver=deliver)
 
@@ -149,7 +198,9 @@ class _Pass:
 
 
 class ModelStream:
-    """One stream.  Attributes: `emitted` (samples returned so far), `pushed`, `latency` (see the module docstring)."""
+    """One stream.  Attributes: `emitted` (samples returned so far), `pushed`, `latency` (see the module docstring); with a
+    `Delivery(samplerate=R)` also `delivered` (frames at R returned so far) and `output_hold`:
+    floor(new * emitted / old) - delivered <= output_hold, and some push reaches it."""
 
     def __init__(self, model, shifts=1, overlap=0.25, transition_power=1.0, segment=None, device=None, length=None,
                  split=True, progress=False, callback=None, affine=None, deliver=None):
@@ -181,10 +232,15 @@ class ModelStream:
         self.finished = False
         self._exec = None
         self._out_device = None
-        self.deliver, self.outputs = deliver, None
+        self.deliver, self.outputs, self.rate = deliver, None, None
+        self.delivered = self.output_hold = 0
         if deliver is not None:
             engine = all(m.kind != "generic" for m in self.members) and (self.device is None or self.device.type == "cuda")
-            self.outputs = deliver.for_stream(self.sources, engine)
+            self.outputs = deliver.for_stream(self.sources, engine, self.samplerate, self.audio_channels)
+            plan = deliver.rate_plan(self.samplerate, self.audio_channels)
+            if plan is not None:
+                self.rate = _Rate(plan, len(self.outputs), self.audio_channels)
+                self.output_hold = plan.hold
         # Separator.separate_stream: blocks are normalised `(x - mean) / s` and stems restored `x * s + mean`, s = std + 1e-8
         self.affine = None
         if affine is not None:
@@ -485,10 +541,11 @@ class _EngineExec:
         self.win0 = 0
         self.bases = [0] * len(st.passes)
         self.bufs = {}
+        self.rate_hist = None              # a resampling delivery's carried values (`_Rate`)
 
     def device_bytes(self) -> int:
         n = self.win.numel() + self.acc.numel() + sum(t.numel() for b in self.bufs.values() for t in set(b))
-        return 4 * n
+        return 4 * (n + (0 if self.rate_hist is None else self.rate_hist.numel()))
 
     def _stream(self):
         return C.c_void_p(_lib.current_stream_ptr())
@@ -624,10 +681,12 @@ class _EngineExec:
         t0 = st.emitted
         S, channels = len(st.sources), st.audio_channels
         out = torch.empty(S, channels, t1 - t0, device=st.device, dtype=torch.float32)
-        dl, frames = st.deliver, None
-        if t1 > t0:
+        dl, rt, frames = st.deliver, st.rate, None
+        # a resampling delivery returns the frames whose last tap is emitted; its finish() has a tail even when nothing is emitted
+        n_frames = t1 - t0 if rt is None else rt.plan.step(t0, t1 - t0, st.finished)[1]
+        if t1 > t0 or (rt is not None and n_frames > 0):
             passes, segs = [], []
-            for pi, ps in enumerate(st.passes):
+            for pi, ps in enumerate(st.passes if t1 > t0 else []):
                 q0, q1 = t0 - ps.origin, t1 - ps.origin
                 s_lo = len(segs) // 2
                 for o, n in st._segments_covering(ps, q0, q1):
@@ -635,27 +694,45 @@ class _EngineExec:
                 e = ps.member
                 passes += [self.bases[pi], ps.hi - ps.a0, q0 - ps.a0, s_lo, len(segs) // 2, self.w_offs[e], st.members[e].SL, e]
             if dl is not None:              # the delivery rows ride behind the pass table, in its upload
-                from .audio import deliver_layout
-                offs, total = deliver_layout(st.outputs, t1 - t0, channels, dl.fmt)
+                from .audio import _BankArena, deliver_layout, rate_groups, rate_lds_floats
+                offs, total = deliver_layout(st.outputs, n_frames, channels, dl.fmt)
                 d_at = len(passes)
-                passes = passes + _deliver_rows(st.outputs, dl, out.data_ptr(), t1 - t0, offs)
+                if rt is None:
+                    passes = passes + _deliver_rows(st.outputs, dl, out.data_ptr(), t1 - t0, offs)
+                else:
+                    arena = _BankArena.get(st.device)
+                    if self.rate_hist is None:
+                        self.rate_hist, rt.off = torch.zeros(rt.size, device=st.device, dtype=torch.float32), 0
+                    passes = passes + rt.rows(st.outputs, dl, out.data_ptr(), t1 - t0, t0, st.finished, arena.offset(rt.plan), offs)
+                    total = max(total, 16)                     # a call that only carries values still names a destination
                 frames = (torch.empty(total, dtype=torch.uint8, device=st.device), offs)
             t_passes = _upload(passes, torch.int64, st.device)
-            t_segs = _upload(segs or [0, 0], torch.int64, st.device)
-            keep += [t_passes, t_segs]
-            _lib.check(self.lib.mi_stream_emit(self.acc.data_ptr(), self.acc.numel(), S, channels, t_passes.data_ptr(),
-                                               len(st.passes), t_segs.data_ptr(), len(segs) // 2, self.weights.data_ptr(),
-                                               self.weights.numel(), self.scales.data_ptr(), len(st.members), st.shifts,
-                                               int(st.bag_weights is not None),
-                                               self.stats.data_ptr() if self.stats is not None else None,
-                                               t1 - t0, out.data_ptr(), out.numel(), self._stream()), "mi_stream_emit")
-            if dl is not None:
+            keep.append(t_passes)
+            if t1 > t0:
+                t_segs = _upload(segs or [0, 0], torch.int64, st.device)
+                keep.append(t_segs)
+                _lib.check(self.lib.mi_stream_emit(self.acc.data_ptr(), self.acc.numel(), S, channels, t_passes.data_ptr(),
+                                                   len(st.passes), t_segs.data_ptr(), len(segs) // 2, self.weights.data_ptr(),
+                                                   self.weights.numel(), self.scales.data_ptr(), len(st.members), st.shifts,
+                                                   int(st.bag_weights is not None),
+                                                   self.stats.data_ptr() if self.stats is not None else None,
+                                                   t1 - t0, out.data_ptr(), out.numel(), self._stream()), "mi_stream_emit")
+            if dl is not None and rt is None:
                 keep.append(out)
                 _lib.check(self.lib.mi_deliver_pcm(C.c_void_p(t_passes.data_ptr() + 8 * d_at), len(st.outputs), t1 - t0, S, channels,
                                                    None, 0, frames[0].data_ptr(), frames[0].numel(), self._stream()),
                            "mi_deliver_pcm")
+            elif dl is not None:
+                keep.append(out)
+                bank, hist = arena.buf, self.rate_hist
+                _lib.check(self.lib.mi_deliver_resample_pcm(C.c_void_p(t_passes.data_ptr() + 8 * d_at), len(st.outputs),
+                                                            rate_groups(rt.plan, channels, n_frames), S, channels, bank.data_ptr(),
+                                                            bank.numel(), hist.data_ptr() if hist.numel() else None, hist.numel(),
+                                                            rate_lds_floats(rt.plan, channels), frames[0].data_ptr(),
+                                                            frames[0].numel(), self._stream()), "mi_deliver_resample_pcm")
+                st.delivered += n_frames
         st.emitted = t1
-        return out if dl is None else (frames, t1 - t0)
+        return out if dl is None else (frames, n_frames)
 
     def _host(self, out):
         if self.st.deliver is not None:
@@ -743,7 +820,9 @@ class StreamGroup:
     driven by that table), one `mi_streams_emit` and one D2H of the host-bound stems, plus one `mi_streams_compact` when a
     stream outgrows its room in the state buffer (every stream's window and accumulators).  Streams opened with `deliver=` add one
     `mi_deliver_pcm` for all of them behind the emit; their host-bound frames leave in one D2H of the byte buffer, and their float
-    stems never do.  Streams opened with `convert=`
+    stems never do.  Those whose `Delivery` names another sample rate share one `mi_deliver_resample_pcm` instead (so a call has at
+    most one launch more, whatever the number of streams), their frames in the same byte buffer and their carried values in the
+    group's history buffer.  Streams opened with `convert=`
     take blocks at another sample rate or channel count: one `mi_streams_convert_append` per call runs the streaming
     `convert_audio` (demucs_amd/audio.py, `ConvertPlan`) for all of them into their windows, and what the converter has made
     final is what the stream's scheduler sees as pushed.
@@ -776,7 +855,7 @@ class StreamGroup:
         call); `length` then counts input samples, and the RNG calls are those of the converted length."""
         if deliver is not None:             # refused here, before any RNG call
             deliver.for_stream(self.sources, all(m.kind != "generic" for m in self.members) and
-                               (self.device is None or self.device.type == "cuda"))
+                               (self.device is None or self.device.type == "cuda"), self.samplerate, self.audio_channels)
         conv = None
         if convert is not None:
             from .audio import check_stream_channels
@@ -802,6 +881,10 @@ class StreamGroup:
 
     def emitted(self, key) -> int:
         return self._stream(key).emitted
+
+    def delivered(self, key) -> int:
+        """Frames a stream with `Delivery(samplerate=R)` has returned so far (at R)."""
+        return self._stream(key).delivered
 
     def pushed(self, key) -> int:
         return self._stream(key).pushed
@@ -958,8 +1041,9 @@ class _GroupEngineExec:
         self.dead = False
         self.bufs = {}
         self.pad = max(m.V for m in g.members)
-        # converting streams: every stream's carried input in one buffer (doubled when an opened stream finds no room; regions of
-        # finished streams are reused), so its size follows the number of open streams and never a stream's duration
+        # converting streams and streams that deliver at another rate: every stream's carried samples in one buffer (doubled when
+        # an opened stream finds no room; regions of finished streams are reused), so its size follows the number of open streams
+        # and never a stream's duration
         self.hist = None
         self.hist_used = 0
         self.hist_free = {}
@@ -968,8 +1052,9 @@ class _GroupEngineExec:
         n = self.state.numel() + self.stats.numel() + sum(t.numel() for b in self.bufs.values() for t in set(b))
         return 4 * (n + (0 if self.hist is None else self.hist.numel()))
 
-    def _hist_region(self, cv: _Conv) -> None:
-        size = 2 * self.g.audio_channels * cv.plan.carry
+    def _hist_region(self, cv, size=None) -> None:
+        """Room for `cv`'s carried samples (a `_Conv`'s input, a `_Rate`'s values) in the history buffer."""
+        size = 2 * self.g.audio_channels * cv.plan.carry if size is None else size
         if cv.off is not None or size == 0:
             return
         if self.hist_free.get(size):
@@ -1224,6 +1309,9 @@ class _GroupEngineExec:
                     if cv is not None and cv.off is not None:
                         self.hist_free.setdefault(2 * C_ * cv.plan.carry, []).append(cv.off)
                         cv.off = None
+                    if st.rate is not None and st.rate.off is not None:
+                        self.hist_free.setdefault(st.rate.size, []).append(st.rate.off)
+                        st.rate.off = None
                     del self.slots[key]
                     self.dead = True
                 if not self.slots:
@@ -1312,9 +1400,10 @@ class _GroupEngineExec:
         return base
 
     def _emit_rows(self, work, table):
-        """mi_streams_emit's tables for every stream of the call with new final samples; host-bound stems first."""
+        """mi_streams_emit's tables for every stream of the call with new final samples; host-bound stems first.  Behind them the
+        rows of the delivering streams: mi_deliver_pcm's, then mi_deliver_resample_pcm's for those that deliver at another rate."""
         g = self.g
-        from .audio import deliver_layout
+        from .audio import RATE_COLS, _BankArena, deliver_layout, rate_groups, rate_lds_floats
         S, C_ = len(g.sources), g.audio_channels
         spans = []
         for key, st, _ in work:
@@ -1351,22 +1440,41 @@ class _GroupEngineExec:
         # buffer with the host-bound streams first
         out = torch.empty(off, device=g.device, dtype=torch.float32) if off else None
         d_rows, d_layout, d_off, d_host, d_longest = [], {}, 0, 0, 1
-        for key, st, _, _, to_host in sorted(spans, key=lambda s: not s[4]):
+        r_rows, r_groups, r_lds, d_count = [], 1, 1, {}
+        for key, st, t0, _, to_host in sorted(spans, key=lambda s: not s[4]):
             f_off, n = layout[key]
-            if st.deliver is None or n == 0:
+            rt = st.rate
+            if st.deliver is None or (n == 0 and rt is None):
                 continue
-            offs, d_off = deliver_layout(st.outputs, n, C_, st.deliver.fmt, d_off)
-            d_rows += _deliver_rows(st.outputs, st.deliver, out.data_ptr() + 4 * f_off, n, offs)
-            d_layout[key] = offs
-            d_longest = max(d_longest, n)
+            if rt is not None:
+                # the frames whose last tap is emitted; a finishing stream has a tail even when it emits nothing
+                n_out = rt.plan.step(t0, n, st.finished)[1]
+                if n == 0 and n_out == 0:
+                    continue
+                self._hist_region(rt, rt.size)
+                offs, d_off = deliver_layout(st.outputs, n_out, C_, st.deliver.fmt, d_off)
+                r_rows += rt.rows(st.outputs, st.deliver, out.data_ptr() + 4 * f_off if n else 0, n, t0, st.finished,
+                                  _BankArena.get(g.device).offset(rt.plan), offs)
+                r_groups = max(r_groups, rate_groups(rt.plan, C_, n_out))
+                r_lds = max(r_lds, rate_lds_floats(rt.plan, C_))
+                st.delivered += n_out
+                d_layout[key], d_count[key] = offs, n_out
+            else:
+                offs, d_off = deliver_layout(st.outputs, n, C_, st.deliver.fmt, d_off)
+                d_rows += _deliver_rows(st.outputs, st.deliver, out.data_ptr() + 4 * f_off, n, offs)
+                d_layout[key], d_count[key] = offs, n
+                d_longest = max(d_longest, n)
             if to_host:
                 d_host = d_off
         d_at = len(table)
         table += d_rows
+        r_at = len(table)
+        table += r_rows
         return dict(at=at, n_streams=len(streams) // STREAMS_EMIT_COLS, n_passes=len(passes) // 8, n_segs=len(segs) // 2,
                     total=off, host_n=host_n, longest=longest, layout=layout, order=[k for k, _, _ in work],
                     streams={k: st for k, st, _ in work}, out=out, d_at=d_at, d_rows=len(d_rows) // DELIVER_COLS, d_total=d_off,
-                    d_host=d_host, d_longest=d_longest, d_layout=d_layout)
+                    d_host=d_host, d_longest=d_longest, d_layout=d_layout, d_count=d_count, r_at=r_at,
+                    r_rows=len(r_rows) // RATE_COLS, r_groups=r_groups, r_lds=r_lds)
 
     def _emit(self, emit, base) -> dict:
         g = self.g
@@ -1385,10 +1493,19 @@ class _GroupEngineExec:
                                                 int(g.bag_weights is not None), self.stats.data_ptr(), self.n_stats, out.data_ptr(),
                                                 out.numel(), self._stream()), "mi_streams_emit")
         frames = None
+        if emit["d_rows"] or emit["r_rows"]:
+            # at least 16 bytes: a call on which resampling streams only carry values still names a destination
+            frames = torch.empty(max(emit["d_total"], 16), dtype=torch.uint8, device=dev)
         if emit["d_rows"]:
-            frames = torch.empty(emit["d_total"], dtype=torch.uint8, device=dev)
             _lib.check(self.lib.mi_deliver_pcm(C.c_void_p(base + 8 * emit["d_at"]), emit["d_rows"], emit["d_longest"], S, C_, None, 0,
                                                frames.data_ptr(), frames.numel(), self._stream()), "mi_deliver_pcm")
+        if emit["r_rows"]:
+            from .audio import _BankArena
+            bank, hist = _BankArena.get(dev).buf, self.hist
+            _lib.check(self.lib.mi_deliver_resample_pcm(C.c_void_p(base + 8 * emit["r_at"]), emit["r_rows"], emit["r_groups"], S, C_,
+                                                        bank.data_ptr(), bank.numel(), hist.data_ptr(), hist.numel(), emit["r_lds"],
+                                                        frames.data_ptr(), frames.numel(), self._stream()),
+                       "mi_deliver_resample_pcm")
         host = host_frames = None
         if emit["host_n"]:
             host = torch.empty(emit["host_n"], dtype=torch.float32, pin_memory=True)
@@ -1404,7 +1521,8 @@ class _GroupEngineExec:
             st = emit["streams"][key]
             to = st._out_device
             if st.deliver is not None:
-                res[key] = self._frames(st, n, emit["d_layout"].get(key), frames, host_frames, emit["d_host"])
+                res[key] = self._frames(st, emit["d_count"].get(key, 0), emit["d_layout"].get(key), frames, host_frames,
+                                        emit["d_host"])
             elif n == 0:
                 res[key] = torch.empty(S, C_, 0, dtype=torch.float32, device=to)
             elif host is not None and off < emit["host_n"]:

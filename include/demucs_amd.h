@@ -437,6 +437,64 @@ int mi_deliver_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_n, in
 int mi_deliver_pcm(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels, const void *peaks_dev,
                    int32_t n_peaks, void *dst_dev, int64_t dst_capacity, void *stream);
 
+/* mi_deliver_resample_pcm: delivery of a STREAM's outputs at another sample rate R than the model's M, what a user of the reference
+ *   writes as `save_audio(julius.resample_frac(v, M, R), path, samplerate=R, clip=...)` for each output v of the save loop
+ *   (demucs/audio.py:169-172,175-181,218-265 on the outputs of demucs/separate.py:178-218): the `--two-stems` value of
+ *   mi_deliver_pcm, then mi_resample_frac's chain on it (old / new = M / R divided by their gcd; acc = 0; k ascending;
+ *   acc = fmaf(kernel[i][k], v[clamp(n * old - width + k, 0, L - 1)], acc) for output n * new + i), then prevent_clip and i16_pcm or
+ *   float32, channels interleaved.  The concatenation of what a stream's calls write equals that chain on the whole track bit for
+ *   bit, for every partition: frame n is written once n * old + width + old <= emitted (mi_streams_convert_append's `ready` rule
+ *   with the model-rate samples the stream has emitted as the input), the final call (TOTAL >= 0) writes the rest up to
+ *   floor(new * total / old) with the right taps clamped to v[total - 1].
+ *   Row r of the table (MI_RATE_COLS int64, a DEVICE array) is ONE output of one stream on one call:
+ *     SRC, N_IN           DEVICE address of the stream's newly emitted float32 stems (n_sources, channels, n_in) (trusted, as
+ *                         MI_DELIVER_SRC; may be 0 when n_in == 0);
+ *     BEFORE              model-rate samples emitted before this call;
+ *     KIND, SEL, CLIP, FMT  as MI_DELIVER_*: KIND is MI_DELIVER_STEM or MI_DELIVER_ADD, CLIP 0, MI_CLIP_CLAMP or MI_CLIP_TANH (the
+ *                         whole-track modes "minus" and "rescale" do not exist on a stream);
+ *     OLD, NEW, WIDTH, BANK_OFF   the rate entry as MI_CVT_*: the kernel bank TRANSPOSED, (klen, new) float32, at float offset bank_off
+ *                         of bank_dev; width >= 1 (equal rates are mi_deliver_pcm's);
+ *     OUT0, N_OUT         the first output frame (a multiple of new) and the number of frames to write;
+ *     TOTAL               before + n_in when this is the stream's final call, else negative;
+ *     HIST_LEN, HIST_RD, HIST_WR, HIST_START, HIST_NEXT
+ *                         the carried VALUES of this output, as MI_CVT_HIST_*: (channels, hist_len) floats at float offset hist_rd
+ *                         of hist_dev hold positions [hist_start, before); the call writes positions [hist_next, before + n_in) (at
+ *                         most hist_len, <= klen - 1 by the same rule) at float offset hist_wr, a side apart from the read one;
+ *                         hist_next < 0: nothing is written (the final call).  hist_len == 0: no history, for a stream whose only
+ *                         call is its final one (before == 0, hist_next < 0);
+ *     DST_OFF             byte offset of the row's (n_out, channels) interleaved frames in dst_dev (a multiple of 4).
+ *   A workgroup takes 8 * G consecutive frames of one row for all channels, G = min(4, (lds_floats / channels - 2 * width) / (8 * old))
+ *   >= 1; max_groups >= every row's number of such runs (grid size); lds_floats <= MI_RATE_LDS_FLOATS is the staging area,
+ *   >= channels * (8 * old + 2 * width) for every row.  A row is skipped whole (nothing of it is read or written, its history
+ *   included) when its frames leave dst_capacity (bytes), DST_OFF is negative or no multiple of 4, a history side or the bank leaves
+ *   its capacity (floats) or the sides overlap, KIND / SEL / CLIP / FMT / OLD / NEW / WIDTH is out of range, OUT0 is no multiple
+ *   of NEW, TOTAL >= 0 differs from before + n_in, or the staging area is too small for it.  dst_dev is 4-byte aligned. */
+#define MI_RATE_SRC 0
+#define MI_RATE_N_IN 1
+#define MI_RATE_BEFORE 2
+#define MI_RATE_KIND 3
+#define MI_RATE_SEL 4
+#define MI_RATE_CLIP 5
+#define MI_RATE_FMT 6
+#define MI_RATE_OLD 7
+#define MI_RATE_NEW 8
+#define MI_RATE_WIDTH 9
+#define MI_RATE_BANK_OFF 10
+#define MI_RATE_OUT0 11
+#define MI_RATE_N_OUT 12
+#define MI_RATE_TOTAL 13
+#define MI_RATE_HIST_LEN 14
+#define MI_RATE_HIST_RD 15
+#define MI_RATE_HIST_WR 16
+#define MI_RATE_HIST_START 17
+#define MI_RATE_HIST_NEXT 18
+#define MI_RATE_DST_OFF 19
+#define MI_RATE_COLS 20
+#define MI_RATE_LDS_FLOATS 16384
+int mi_deliver_resample_pcm(const int64_t *table_dev, int32_t n_rows, int64_t max_groups, int32_t n_sources, int32_t channels,
+                            const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity, int32_t lds_floats,
+                            void *dst_dev, int64_t dst_capacity, void *stream);
+
 /* ---- kernel-level entry points (parity tests; same kernels the forward uses) --------------
  * mi_stft_cac: `_magnitude(_spec(mix))` (demucs/htdemucs.py:420-461, demucs/spec.py:11-27):
  *   mix_dev (B,2,L) -> cac_dev (B,4,2048,ceil(L/1024)), channel order [c0.re,c0.im,c1.re,c1.im]. */

@@ -14,6 +14,12 @@ route's own pairs, the yardstick for "not slower": delivered_median >= float_med
 Prints ONE JSON line (and writes it to --out when given).
 
     python tools/bench_deliver.py --out profiles/deliver_bench.json
+
+With `--out-sr R` the pair is instead the delivered route at the model's rate (`Delivery("vocals")`, the run of record) and the
+same route at R Hz (`Delivery("vocals", samplerate=R)`: `mi_deliver_resample_pcm` in `mi_deliver_pcm`'s place), by the same
+method; `rate_over_model` is the ratio of their median real-time factors.  No speed is claimed for it.
+
+    python tools/bench_deliver.py --out-sr 48000 --out profiles/deliver_rate_bench.json
 """
 from __future__ import annotations
 
@@ -84,7 +90,10 @@ def main():
     ap.add_argument("--block", type=float, default=1.0)
     ap.add_argument("--modes", default="f32,bf16")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--out-sr", type=int, default=None, help="compare delivery at the model's rate with delivery at this rate")
     args = ap.parse_args()
+    if args.out_sr is not None:
+        return rate_main(args)
     length = int(args.seconds * SR)
     audio = torch.from_numpy(synth_mix(1, length, "tones"))
     karaoke = Delivery("vocals")
@@ -112,6 +121,37 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def rate_main(args):
+    length = int(args.seconds * SR)
+    audio = torch.from_numpy(synth_mix(1, length, "tones"))
+    at_model, at_rate = Delivery("vocals"), Delivery("vocals", samplerate=args.out_sr)
+    result = {"what": f"stream group, htdemucs, shifts=1, max_batch=8, lockstep host blocks: Delivery('vocals') int16 at the model's "
+                      f"{SR} Hz vs at {args.out_sr} Hz",
+              "device": torch.cuda.get_device_name(0), "stream_seconds": args.seconds, "block_seconds": args.block,
+              "pairs": args.pairs, "out_sr": args.out_sr, "runs": {}}
+    for mode in args.modes.split(","):
+        sep = Separator(model(mode), device="cuda", shifts=1)
+        warm = audio[:, :10 * SR]
+        run(sep, warm, 2, SR, at_model)
+        run(sep, warm, 2, SR, at_rate)
+        for n_streams in (int(x) for x in args.streams.split(",")):
+            plain, rated = [], []
+            for _ in range(args.pairs):
+                plain.append(run(sep, audio, n_streams, int(args.block * SR), at_model))
+                rated.append(run(sep, audio, n_streams, int(args.block * SR), at_rate))
+            a, b = summary(plain, n_streams * args.seconds), summary(rated, n_streams * args.seconds)
+            name = f"{mode}_n{n_streams}"
+            result["runs"][name] = {"model_rate": a, "out_rate": b,
+                                    "rate_over_model": round(b["realtime_factor_median"] / a["realtime_factor_median"], 3)}
+            print(name, result["runs"][name], file=sys.stderr, flush=True)
+    line = json.dumps(result)
+    print(line)
+    out = args.out or os.path.join(ROOT, "profiles", "deliver_rate_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(line + "\n")
 
 
 if __name__ == "__main__":
