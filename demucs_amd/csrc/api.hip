@@ -58,6 +58,12 @@ extern "C" {
 const char *mi_last_error(void) { return last_error_buf(); }
 void mi_debug_set_post_launch_hook(void (*hook)(void *stream)) { g_post_launch_hook = hook; }
 int mi_debug_last_conv_route(void) { return g_last_conv_route; }
+int mi_debug_conv_route(const struct mi_conv_desc *desc, int *tile) {
+    if (!desc) return -1;
+    const ConvRoute r = conv_route(*desc);
+    if (tile) *tile = r.tile;
+    return r.route;
+}
 const char *mi_version(void) { return "demucs_amd 0.1 gfx950"; }
 
 int mi_model_create(const mi_config *cfg, const mi_tensor_desc *weights, size_t n_weights, void **handle) {

@@ -6,8 +6,6 @@
 // (lane l: row/col l&31, k = l>>5) is one conflict-free ds_read_b32 per operand.
 // Arithmetic is exact fp32 (v_mfma_f32_32x32x2_f32 == k-ordered fmaf chain): the <=1e-4 parity
 // target against the fp32 CPU reference leaves no room for bf16 operands.
-#include <vector>
-
 #include "gemm_tile.h"
 
 namespace mi {
@@ -384,29 +382,12 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_dmatap_kernel(const mi_conv_
     conv_epilogue<TM, TN, EPI, 0>(d, acc, m0, n0, wm, wn, N, P, o2v);
 }
 
-// float32, stride-1 k x k conv with K2 = 3 whose geometry the descriptor states (ntaps, tap_k2, tap_pad*): the DMA loop above,
-// or, for a layer with a split weight image (`split`), the same shifted-run loader in front of the split-bf16 main loop (gemm_x6.hip
-// conv_tap_x6_kernel; GLU only)
-static bool dmatap_eligible(const mi_conv_desc &d, int tile, bool split = false) {
-    static const bool off = getenv("MI_NO_DMA_TAP") != nullptr;
-    const int ld = d.x_ld ? d.x_ld : d.D2;
-    static const bool off_dconv = getenv("MI_NO_DMA_DCONV") != nullptr;      // A/B switch for the BIAS_STATS kind alone
-    if (off_dconv && d.epi == MI_EPI_BIAS_STATS) return false;
-    const int dil = d.tap_dil2 ? d.tap_dil2 : 1;
-    // GLU: the decoders' 3 x 3 / k = 3 rewrite convs (96- / 128-row tiles); BIAS_STATS: the DConv blocks' dilated k = 3 convs (32- / 64-row)
-    const bool kind = (d.epi == MI_EPI_GLU && (tile == 96 || tile == 128) && (d.ntaps == 9 || d.ntaps == 3) && dil == 1) ||
-                      (d.epi == MI_EPI_BIAS_STATS && (tile == 32 || tile == 64) && d.ntaps == 3 && (dil == 1 || dil == 2) && d.flags == 0);
-    return !off && !d.half && (split ? d.wx && d.epi == MI_EPI_GLU : !d.wx) && kind && d.tap_k2 == 3 && d.Mpad % tile == 0 &&
-           d.K % d.ntaps == 0 && d.S1 == 1 && d.S2 == 1 && d.O1 == d.D1 && d.O2 == ld && ld % 4 == 0 && d.tap_pad2 == dil &&
-           d.tap_pad1 == (d.ntaps / 3 - 1) / 2 && !(d.flags & (MI_FLAG_IMG | MI_FLAG_IMG4)) && d.x_bstride == (int64_t)(d.K / d.ntaps) * d.D1 * ld;
-}
 template <int EPI>
 static int launch_dmatap(const mi_conv_desc &d, int tile, hipStream_t st) {
     const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
     MI_REQUIRE(N64 < (1ll << 31) - 256 && d.Mpad % tile == 0, "conv: DMA tap route: %lld positions, Mpad %d", (long long)N64, d.Mpad);
     const int N = (int)N64, MT = d.Mpad / tile, NT = ceil_div(N, BN);
     const unsigned grid = grouped_grid(MT, NT, 1);
-    g_last_conv_route = 2;
     if constexpr (EPI == MI_EPI_BIAS_STATS) {
         const bool d2 = d.tap_dil2 == 2;
         if (tile == 64 && d2) hipLaunchKernelGGL((conv_gemm_dmatap_kernel<64, EPI, 3, 2>), dim3(grid), dim3(256), 0, st, d, N, MT, 1);
@@ -548,30 +529,12 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_dmarow_kernel(const mi_conv_
     conv_epilogue<TM, TN, EPI, LFLAGS>(d, acc, m0, n0, wm, wn, N, P, o2v);
 }
 
-// float32 layer with row taps only (the caller vouches for the table: `dma_rows`; a plain layer's table is the identity): see above.
-// `split`: such a layer with a split weight image -- a strided encoder conv (LINEAR + GELU) or transposed conv on a 96- / 128-row
-// tile, a 1 x 1 + GLU layer on a 128-row tile -- takes the same row loader in front of the split-bf16 main loop (gemm_x6.hip
-// conv_rows_x6_kernel); MI_NO_DMA_ROWS=1 turns both off
-static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain, bool split = false) {
-    static const bool off = getenv("MI_NO_DMA_ROWS") != nullptr;
-    const int ld = d.x_ld ? d.x_ld : d.D2;
-    const int lf = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS | MI_FLAG_IMG | MI_FLAG_IMG4 | MI_FLAG_HEADS);
-    // 1x1 + GLU / GroupNorm-GLU: 128-row tiles only -- the 96-row ones are the level-0 / 1 rewrites (K = 48 / 96: three or six K steps,
-    // bound by their output), where the register-staged kernel's four workgroups per CU measured 3 % faster (476 vs 490 us)
-    const bool epi_ok = (d.epi == MI_EPI_LINEAR && lf == MI_FLAG_GELU && !plain) || d.epi == MI_EPI_CONVTR ||
-                        ((d.epi == MI_EPI_GLU || d.epi == MI_EPI_GN_GLU) && plain && tile == 128 && !(d.flags & (MI_FLAG_IMG | MI_FLAG_IMG4)));
-    if (split && (d.epi == MI_EPI_GN_GLU || tile == 64)) return false;
-    return !off && !d.half && (split ? d.wx != nullptr : !d.wx) && d.ktab && epi_ok && (plain || d.dma_rows) && (tile == 64 || tile == 96 || tile == 128) &&
-           d.Mpad % tile == 0 && d.S2 == 1 && d.O2 == ld && ld % 4 == 0 && ((uintptr_t)d.x & 3) == 0 && ((uintptr_t)d.ktab & 63) == 0 &&
-           (d.epi == MI_EPI_CONVTR || tile != 64 || d.epi == MI_EPI_LINEAR);
-}
 template <int EPI, int LFLAGS>
 static int launch_dmarow(const mi_conv_desc &d, int tile, hipStream_t st) {
     const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
     MI_REQUIRE(N64 < (1ll << 31) - 256 && d.Mpad % tile == 0, "conv: DMA row route: %lld positions, Mpad %d", (long long)N64, d.Mpad);
     const int N = (int)N64, MT = d.Mpad / tile, NT = ceil_div(N, BN);
     const unsigned grid = grouped_grid(MT, NT, 1);
-    g_last_conv_route = 3;
     if (tile == 128) hipLaunchKernelGGL((conv_gemm_dmarow_kernel<128, EPI, LFLAGS>), dim3(grid), dim3(256), 0, st, d, N, MT, 1);
     else if constexpr (EPI == MI_EPI_LINEAR || EPI == MI_EPI_CONVTR) {
         if (tile == 96) hipLaunchKernelGGL((conv_gemm_dmarow_kernel<96, EPI, LFLAGS>), dim3(grid), dim3(256), 0, st, d, N, MT, 1);
@@ -582,8 +545,9 @@ static int launch_dmarow(const mi_conv_desc &d, int tile, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// `dma` (route MI_ROUTE_DMA): the LDS-DMA linear tile instead of the register-staged loader -- a plain LINEAR layer on the 128-row tile
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN>
-static int launch_cfg(const mi_conv_desc &d, hipStream_t st) {
+static int launch_cfg(const mi_conv_desc &d, bool dma, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
     const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
     MI_REQUIRE(N64 < (1ll << 31) - 256, "conv: too many output positions (%lld)", (long long)N64);
@@ -592,40 +556,28 @@ static int launch_cfg(const mi_conv_desc &d, hipStream_t st) {
     // M groups (gemm_tile.h) halve this kernel's L2 misses on the 4 MiB weight matrices (TCC hit rate 48 % -> 74 %) but
     // the misses were Infinity-Cache hits: no time is gained and every activation tile is then fetched from HBM by
     // several XCDs (+10 % HBM bytes), so the fp32 path keeps one group unless MI_MGROUPS=1.
-    static const bool groups = getenv("MI_MGROUPS") != nullptr;
-    const int Gm = groups ? pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 4) : 1;
+    const int Gm = conv_switches().mgroups ? pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 4) : 1;
     const unsigned grid = grouped_grid(MT, NT, Gm);
     if constexpr (PLAIN && BM == 128 && EPI == MI_EPI_LINEAR) {
-        static const bool use_dma = getenv("MI_NO_DMA") == nullptr;
-        if (use_dma) {
-            g_last_conv_route = 1;
+        if (dma) {
             hipLaunchKernelGGL((conv_gemm_dma_kernel<EPI, LFLAGS>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
             MI_CHECK_LAUNCH();
             return MI_OK;
         }
     }
-    g_last_conv_route = 0;
+    MI_REQUIRE(!dma, "conv: the LDS-DMA linear tile takes a plain LINEAR layer on the 128-row tile");
     hipLaunchKernelGGL((conv_gemm_kernel<WM, WN, TM, TN, EPI, LFLAGS, PLAIN>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }
 
 template <int EPI, int LFLAGS, bool PLAIN>
-static int launch_tile(const mi_conv_desc &d, int tile, hipStream_t st) {
-    if constexpr (PLAIN && EPI == MI_EPI_LINEAR) {
-        // Small batches: a plain linear layer whose 128-row tiles give fewer workgroups than the chip has CUs (B = 1: M = 512 and
-        // 2 688 tokens -> 84) runs on 64-row tiles instead -- twice the workgroups at a lower per-workgroup rate.  MI_SMALL_TILE=0: off
-        static const int small = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
-        if (small && tile == 128 && d.Mpad % 64 == 0) {
-            const int64_t wgs = (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN);
-            if (wgs < 200) tile = 64;
-        }
-    }
+static int launch_tile(const mi_conv_desc &d, int tile, bool dma, hipStream_t st) {
     switch (tile) {
-        case 128: return launch_cfg<2, 2, 2, 2, EPI, LFLAGS, PLAIN>(d, st);
-        case 96: return launch_cfg<1, 4, 3, 1, EPI, LFLAGS, PLAIN>(d, st);
-        case 64: return launch_cfg<1, 4, 2, 1, EPI, LFLAGS, PLAIN>(d, st);
-        case 32: return launch_cfg<1, 4, 1, 1, EPI, LFLAGS, PLAIN>(d, st);
+        case 128: return launch_cfg<2, 2, 2, 2, EPI, LFLAGS, PLAIN>(d, dma, st);
+        case 96: return launch_cfg<1, 4, 3, 1, EPI, LFLAGS, PLAIN>(d, dma, st);
+        case 64: return launch_cfg<1, 4, 2, 1, EPI, LFLAGS, PLAIN>(d, dma, st);
+        case 32: return launch_cfg<1, 4, 1, 1, EPI, LFLAGS, PLAIN>(d, dma, st);
     }
     return set_error(MI_EINVAL, "conv: unsupported tile_m %d", tile);
 }
@@ -658,88 +610,95 @@ const void *conv_zero_page() {
 }
 
 // ---------------------------------------------------------------------------------------------
-// MI_X6_VERIFY=1 (debugging aid for the split-bf16 path): every x6 launch is followed, on the same stream and with no
-// host synchronisation, by the fp32 kernel of the same layer into a scratch copy of the output and a comparison whose
-// verdict goes to a device-side log; the log is printed when the process exits.
-struct X6VerifyRec { unsigned bad, maxdiff_bits; int bmin, bmax, mmin, mmax, pmin, pmax; };
-struct X6VerifyInfo { int M, K, N, epi, flags, tile, plain, B, O1, O2, o2v; long long ybs, ycs; };
-static X6VerifyRec *g_vlog = nullptr;
-static std::vector<X6VerifyInfo> g_vinfo;
-static float *g_vscratch = nullptr;
-static size_t g_vscratch_elems = 0;
-constexpr int kVerifyMax = 1 << 16;
-
-__global__ void x6_verify_kernel(const float *__restrict__ a, const float *__restrict__ b, long long n, long long ybs, long long ycs,
-                                 X6VerifyRec *rec) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float x = a[i], y = b[i];
-        const float dlt = fabsf(x - y);
-        if (dlt > 1e-3f * (1.f + fabsf(y)) || (x != x) != (y != y)) {
-            atomicAdd(&rec->bad, 1u);
-            atomicMax(&rec->maxdiff_bits, __float_as_uint(dlt == dlt ? dlt : 3.0e38f));
-            const int bb = (int)(i / ybs), m = (int)((i % ybs) / ycs), p = (int)(i % ycs);
-            atomicMin(&rec->bmin, bb); atomicMax(&rec->bmax, bb);
-            atomicMin(&rec->mmin, m); atomicMax(&rec->mmax, m);
-            atomicMin(&rec->pmin, p); atomicMax(&rec->pmax, p);
-        }
-    }
-}
-
-static void x6_verify_dump() {
-    if (!g_vlog || g_vinfo.empty()) return;
-    (void)hipDeviceSynchronize();
-    std::vector<X6VerifyRec> h(g_vinfo.size());
-    if (hipMemcpy(h.data(), g_vlog, h.size() * sizeof(X6VerifyRec), hipMemcpyDeviceToHost) != hipSuccess) return;
-    size_t nbad = 0;
-    for (size_t i = 0; i < h.size(); ++i) {
-        if (!h[i].bad) continue;
-        const X6VerifyInfo &f = g_vinfo[i];
-        if (++nbad <= 40)
-            fprintf(stderr, "[x6 verify] launch %zu: M %d K %d N %d epi %d flags %d tile %d plain %d B %d O1 %d O2 %d o2v %d | %u bad, max %.3e, "
-                    "b %d-%d  m %d-%d  p %d-%d (col tiles %d-%d)\n", i, f.M, f.K, f.N, f.epi, f.flags, f.tile, f.plain, f.B, f.O1, f.O2, f.o2v,
-                    h[i].bad, __builtin_bit_cast(float, h[i].maxdiff_bits), h[i].bmin, h[i].bmax, h[i].mmin, h[i].mmax, h[i].pmin, h[i].pmax,
-                    h[i].pmin / BN, h[i].pmax / BN);
-    }
-    fprintf(stderr, "[x6 verify] %zu launches checked, %zu with mismatches\n", h.size(), nbad);
-}
-
-static int launch_conv_fp32_only(const mi_conv_desc &d, hipStream_t st);
-
-// loader: 0 plain / gather table (launch_conv_x6), 1 shifted-run taps (launch_conv_tap_x6), 2 row taps (launch_conv_rows_x6)
-static int x6_verified_launch(const mi_conv_desc &d, int tile, bool plain, hipStream_t st, int loader = 0) {
-    auto launch_x6 = [&]() {
-        return loader == 1 ? launch_conv_tap_x6(d, tile, st) : loader == 2 ? launch_conv_rows_x6(d, tile, st) : launch_conv_x6(d, tile, plain, st);
-    };
-    const bool checkable = d.epi != MI_EPI_STATS_ONLY && d.epi != MI_EPI_BIAS_STATS && d.res != d.y && (int)g_vinfo.size() < kVerifyMax;
-    if (!checkable) return launch_x6();
-    if (!g_vlog) {
-        MI_HIP(hipMalloc((void **)&g_vlog, kVerifyMax * sizeof(X6VerifyRec)));
-        std::vector<X6VerifyRec> init(kVerifyMax, X6VerifyRec{0, 0, 1 << 30, -1, 1 << 30, -1, 1 << 30, -1});
-        MI_HIP(hipMemcpy(g_vlog, init.data(), init.size() * sizeof(X6VerifyRec), hipMemcpyHostToDevice));
-        atexit(x6_verify_dump);
-    }
-    const size_t elems = (size_t)d.B * (size_t)d.y_bstride;
-    if (elems > g_vscratch_elems) {
-        MI_HIP(hipStreamSynchronize(st));
-        if (g_vscratch) (void)hipFree(g_vscratch);
-        MI_HIP(hipMalloc((void **)&g_vscratch, elems * sizeof(float)));
-        g_vscratch_elems = elems;
-    }
-    MI_HIP(hipMemcpyAsync(g_vscratch, d.y, elems * sizeof(float), hipMemcpyDeviceToDevice, st));     // unwritten positions compare equal
-    MI_TRY(launch_x6());
-    mi_conv_desc e = d;
-    e.wx = nullptr; e.y = g_vscratch;
-    MI_TRY(launch_conv_fp32_only(e, st));
-    const int id = (int)g_vinfo.size();
-    g_vinfo.push_back(X6VerifyInfo{d.M, d.K, d.B * d.O1 * d.O2, d.epi, d.flags, tile, plain ? 1 : 0, d.B, d.O1, d.O2, d.o2_valid, d.y_bstride, d.y_cstride});
-    hipLaunchKernelGGL(x6_verify_kernel, dim3(1024), dim3(256), 0, st, d.y, g_vscratch, (long long)elems, (long long)d.y_bstride, (long long)d.y_cstride, g_vlog + id);
-    MI_CHECK_LAUNCH();
-    return MI_OK;
-}
+// Which kernel a float32 layer runs: the environment switches, the eligibility of the loaders and conv_route, which turns them
+// into one value.  Nothing below this line and above launch_conv touches the GPU.
 
 // process-wide switch of the split-bf16 main loops (mi_set_split_bf16): 0 ignores every split weight image
 int g_split_bf16 = 1;
 
+const ConvSwitches &conv_switches() {
+    static const ConvSwitches s = {
+        getenv("MI_NO_DMA") != nullptr,
+        getenv("MI_NO_DMA_TAP") != nullptr,
+        getenv("MI_NO_DMA_ROWS") != nullptr,
+        getenv("MI_NO_DMA_DCONV") != nullptr,
+        getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) != 0 : true,
+        getenv("MI_MGROUPS") != nullptr,
+        getenv("MI_X6_MODE") ? atoi(getenv("MI_X6_MODE")) == 1 : false,
+    };
+    return s;
+}
+
+// Small batches: a layer whose 128-row tiles give fewer workgroups than the chip has CUs (B = 1: M = 512 and 2 688 tokens -> 84;
+// a k x k GLU conv: 6 x 21) runs on a smaller tile instead -- more workgroups at a lower per-workgroup rate.  Which tile that is
+// depends on the route (conv_route).  MI_SMALL_TILE=0: off
+static bool under_filled(const mi_conv_desc &d) {
+    return (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200;
+}
+
+// float32, stride-1 k x k conv with K2 = 3 whose geometry the descriptor states (ntaps, tap_k2, tap_pad*): the DMA loop above,
+// or, for a layer with a usable split weight image (`has_image`) when asked for it (`split`), the same shifted-run loader in front of the split-bf16 main loop (gemm_x6.hip
+// conv_tap_x6_kernel; GLU only)
+static bool dmatap_eligible(const mi_conv_desc &d, int tile, bool has_image, bool split = false) {
+    const bool off = conv_switches().no_dma_tap;
+    const int ld = d.x_ld ? d.x_ld : d.D2;
+    if (conv_switches().no_dma_dconv && d.epi == MI_EPI_BIAS_STATS) return false;      // A/B switch for the BIAS_STATS kind alone
+    const int dil = d.tap_dil2 ? d.tap_dil2 : 1;
+    // GLU: the decoders' 3 x 3 / k = 3 rewrite convs (96- / 128-row tiles); BIAS_STATS: the DConv blocks' dilated k = 3 convs (32- / 64-row)
+    const bool kind = (d.epi == MI_EPI_GLU && (tile == 96 || tile == 128) && (d.ntaps == 9 || d.ntaps == 3) && dil == 1) ||
+                      (d.epi == MI_EPI_BIAS_STATS && (tile == 32 || tile == 64) && d.ntaps == 3 && (dil == 1 || dil == 2) && d.flags == 0);
+    return !off && !d.half && (split ? has_image && d.epi == MI_EPI_GLU : !has_image) && kind && d.tap_k2 == 3 && d.Mpad % tile == 0 &&
+           d.K % d.ntaps == 0 && d.S1 == 1 && d.S2 == 1 && d.O1 == d.D1 && d.O2 == ld && ld % 4 == 0 && d.tap_pad2 == dil &&
+           d.tap_pad1 == (d.ntaps / 3 - 1) / 2 && !(d.flags & (MI_FLAG_IMG | MI_FLAG_IMG4)) && d.x_bstride == (int64_t)(d.K / d.ntaps) * d.D1 * ld;
+}
+// float32 layer with row taps only (the caller vouches for the table: `dma_rows`; a plain layer's table is the identity): see above.
+// `split`: such a layer with a split weight image -- a strided encoder conv (LINEAR + GELU) or transposed conv on a 96- / 128-row
+// tile, a 1 x 1 + GLU layer on a 128-row tile -- takes the same row loader in front of the split-bf16 main loop (gemm_x6.hip
+// conv_rows_x6_kernel); MI_NO_DMA_ROWS=1 turns both off
+static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain, bool has_image, bool split = false) {
+    const bool off = conv_switches().no_dma_rows;
+    const int ld = d.x_ld ? d.x_ld : d.D2;
+    const int lf = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS | MI_FLAG_IMG | MI_FLAG_IMG4 | MI_FLAG_HEADS);
+    // 1x1 + GLU / GroupNorm-GLU: 128-row tiles only -- the 96-row ones are the level-0 / 1 rewrites (K = 48 / 96: three or six K steps,
+    // bound by their output), where the register-staged kernel's four workgroups per CU measured 3 % faster (476 vs 490 us)
+    const bool epi_ok = (d.epi == MI_EPI_LINEAR && lf == MI_FLAG_GELU && !plain) || d.epi == MI_EPI_CONVTR ||
+                        ((d.epi == MI_EPI_GLU || d.epi == MI_EPI_GN_GLU) && plain && tile == 128 && !(d.flags & (MI_FLAG_IMG | MI_FLAG_IMG4)));
+    if (split && (d.epi == MI_EPI_GN_GLU || tile == 64)) return false;
+    return !off && !d.half && (split ? has_image : !has_image) && d.ktab && epi_ok && (plain || d.dma_rows) && (tile == 64 || tile == 96 || tile == 128) &&
+           d.Mpad % tile == 0 && d.S2 == 1 && d.O2 == ld && ld % 4 == 0 && ((uintptr_t)d.x & 3) == 0 && ((uintptr_t)d.ktab & 63) == 0 &&
+           (d.epi == MI_EPI_CONVTR || tile != 64 || d.epi == MI_EPI_LINEAR);
+}
+
+// The decision, top to bottom; the first test that holds wins (kernels.h ConvRoute)
+ConvRoute conv_route(const mi_conv_desc &d) {
+    const bool image = d.wx && g_split_bf16;                // mi_set_split_bf16(0): native fp32 MFMA kernels only
+    const ConvSwitches &sw = conv_switches();
+    const int tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M);
+    // plain fast path: a 1x1 / linear layer whose gather is the identity
+    const int64_t P = (int64_t)d.O1 * d.O2;
+    const bool plain = d.plain && d.K == d.Kpad && P % 4 == 0 && d.x_bstride % 4 == 0 && ((uintptr_t)d.x & 15) == 0 &&
+                       d.S1 == 1 && d.S2 == 1 && d.D1 == d.O1 && (d.x_ld ? d.x_ld : d.D2) == d.O2;
+    if (d.wtap) return {MI_ROUTE_TAP_HALF, tile, plain};
+    if (d.half) return {MI_ROUTE_HALF, tile, plain};
+    const bool small = sw.small_tile && tile == 128 && under_filled(d), small_linear = small && plain && d.epi == MI_EPI_LINEAR;
+    // Split weight image.  An under-filled layer takes the 64-row tile that reads the 128-row image: bit-identical to the 128-row
+    // tile, no second image.  The decoders' 3 x 3 / k = 3 rewrite convs: shifted-run DMA taps in front of the split-bf16 main loop
+    if (!plain && !sw.x6_plain_only && dmatap_eligible(d, tile, image, true)) return {MI_ROUTE_TAP_X6, small ? 64 : tile, plain};
+    // the frequency branch's encoder / transposed convs and the 1 x 1 + GLU rewrites: the DMA row loader in front of it
+    if (!sw.x6_plain_only && dmarow_eligible(d, tile, plain, image, true)) return {MI_ROUTE_ROWS_X6, small ? 64 : tile, plain};
+    // native DMA taps: an under-filled k x k GLU conv takes 96-row tiles
+    const int ktile = small && !plain && d.epi == MI_EPI_GLU && d.Mpad % 96 == 0 ? 96 : tile;
+    if (!plain && dmatap_eligible(d, ktile, image)) return {MI_ROUTE_DMATAP, ktile, plain};
+    if (dmarow_eligible(d, tile, plain, image)) return {MI_ROUTE_DMAROW, tile, plain};
+    // the split-bf16 main loop behind the plain loader or the gather table (MI_X6_MODE=1: plain layers only)
+    if (image && conv_x6_supported(tile) && (!sw.x6_plain_only || plain)) return {MI_ROUTE_X6, small_linear ? 64 : tile, plain};
+    // native fp32 kernels: an under-filled plain linear layer takes 64-row tiles
+    const int ntile = small_linear && d.Mpad % 64 == 0 ? 64 : tile;
+    const bool dma = plain && ntile == 128 && d.epi == MI_EPI_LINEAR && !sw.no_dma;
+    return {dma ? MI_ROUTE_DMA : MI_ROUTE_TABLE, ntile, plain};
+}
+
+// validate, decide (conv_route), launch
 int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     mi_conv_desc d = din;
     if (!d.sink) d.sink = conv_sink();
@@ -749,19 +708,14 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     MI_REQUIRE(d.Mpad % 4 == 0, "conv: Mpad %d must be a multiple of 4", d.Mpad);
     MI_REQUIRE(d.O2 >= 32 || d.row_mode == 0 || (d.epi != MI_EPI_BIAS_STATS && d.epi != MI_EPI_STATS_ONLY),
                "conv: statistics epilogue needs O2 >= 32");
-    const int tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M);
     MI_REQUIRE(d.pro == 0, "conv: the fused GroupNorm+GELU prologue was replaced by launch_gn_gelu");
     MI_REQUIRE(!(d.flags & MI_FLAG_IMG4) || (d.epi == MI_EPI_GLU && d.half && d.yh && d.yh_pq > 0 && d.yh_n >= (int64_t)d.B * d.yh_pq && d.M % 32 == 0 &&
                                              ((uintptr_t)d.yh & 15) == 0),
                "conv: MI_FLAG_IMG4 needs a half-mode GLU layer with M %% 32 == 0 and an aligned phase image of >= B * yh_pq positions per plane");
     MI_REQUIRE(!(d.flags & MI_FLAG_STATS) || (d.epi == MI_EPI_LINEAR && d.stats && d.O2 >= 32 && d.row_mode == 0),
                "conv: MI_FLAG_STATS needs a LINEAR layer, a statistics buffer and O2 >= 32");
-    if (!g_split_bf16) d.wx = nullptr;                      // mi_set_split_bf16(0): native fp32 MFMA kernels only
     MI_REQUIRE(!(d.flags & MI_FLAG_LN) || (d.pro_stats && d.scale && d.epi == MI_EPI_LINEAR), "conv: MI_FLAG_LN needs pro_stats and scale");
-    // plain fast path: a 1x1 / linear layer whose gather is the identity
     const int64_t P = (int64_t)d.O1 * d.O2;
-    const bool plain = d.plain && d.K == d.Kpad && P % 4 == 0 && d.x_bstride % 4 == 0 && ((uintptr_t)d.x & 15) == 0 &&
-                       d.S1 == 1 && d.S2 == 1 && d.D1 == d.O1 && (d.x_ld ? d.x_ld : d.D2) == d.O2;
     MI_REQUIRE(!(d.flags & MI_FLAG_IMG) || d.epi == MI_EPI_CONVTR ||
                (d.half && d.yh && d.epi == MI_EPI_LINEAR && d.M % 8 == 0 && d.yh_n >= (int64_t)d.B * P && ((uintptr_t)d.yh & 15) == 0) ||
                (d.half && d.yh && d.epi == MI_EPI_GLU && d.M % 32 == 0 && !(d.flags & (MI_FLAG_IMG4 | MI_FLAG_EMB)) && d.yh_n >= (int64_t)d.B * P &&
@@ -779,76 +733,39 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     MI_REQUIRE(!(d.flags & MI_FLAG_IMG) || d.epi != MI_EPI_CONVTR ||
                (d.half && d.yh && d.yh_n >= (int64_t)d.B * d.y_cstride && ((uintptr_t)d.yh & 15) == 0),
                "conv: MI_FLAG_IMG on a transposed conv needs a half mode and an output image of >= B * y_cstride positions");
-    if (d.wtap) { MI_REQUIRE(d.half && d.xh, "conv: tap-ordered weights need a half mode and an operand-image input"); g_last_conv_route = 6; return launch_conv_tap(d, tile, st); }
-    MI_REQUIRE(!(d.flags & MI_FLAG_HEADS) || (d.half && d.yh && d.epi == MI_EPI_LINEAR && d.M % 512 == 0 && d.O1 == 1 && d.yh_n >= d.O2 &&
-                                              ((uintptr_t)d.yh & 15) == 0 && !(d.flags & MI_FLAG_IMG)),
+    MI_REQUIRE(!d.wtap || (d.half && d.xh), "conv: tap-ordered weights need a half mode and an operand-image input");
+    // (a layer with tap-ordered weights answers to the check above alone)
+    MI_REQUIRE(d.wtap || !(d.flags & MI_FLAG_HEADS) || (d.half && d.yh && d.epi == MI_EPI_LINEAR && d.M % 512 == 0 && d.O1 == 1 && d.yh_n >= d.O2 &&
+                                                        ((uintptr_t)d.yh & 15) == 0 && !(d.flags & MI_FLAG_IMG)),
                "conv: MI_FLAG_HEADS needs a half-precision LINEAR layer on tokens (O1 = 1) with M %% 512 == 0 and an aligned output");
     MI_REQUIRE(!d.xh || d.half, "conv: an operand-image input needs a half-precision layer");
-    if (d.half) { g_last_conv_route = 5; return launch_conv_half(d, tile, plain, st); }
-    static const int x6_mode = getenv("MI_X6_MODE") ? atoi(getenv("MI_X6_MODE")) : 0;   // bisecting: 1 plain only, 2 gather only
-    static const int x6_class = getenv("MI_X6_CLASS") ? atoi(getenv("MI_X6_CLASS")) : -1;   // bisecting: one kernel class only
-    const bool x6_class_ok = x6_class < 0 || x6_class == d.epi * 8 + (tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3) * 2 + (plain ? 1 : 0);
-    // the decoders' 3 x 3 / k = 3 rewrite convs with a split image: shifted-run DMA taps in front of the split-bf16 main loop (its
-    // own small-batch tile: launch_conv_tap_x6)
-    static const bool x6_verify = getenv("MI_X6_VERIFY") != nullptr;
-    if (!plain && x6_mode == 0 && x6_class_ok && dmatap_eligible(d, tile, true))
-        return x6_verify ? x6_verified_launch(d, tile, false, st, 1) : launch_conv_tap_x6(d, tile, st);
-    // the frequency branch's encoder / transposed convs and the 1 x 1 + GLU rewrites with a split image: the DMA row loader in front
-    // of the split-bf16 main loop
-    if (x6_mode == 0 && x6_class_ok && dmarow_eligible(d, tile, plain, true))
-        return x6_verify ? x6_verified_launch(d, tile, false, st, 2) : launch_conv_rows_x6(d, tile, st);
-    // small batches: a k x k GLU conv whose 128-row tiles under-fill the chip (B = 1: 6 x 21 workgroups) takes 96-row tiles
-    static const int small_tile = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
-    int ktile = tile;
-    if (small_tile && !plain && d.epi == MI_EPI_GLU && tile == 128 && d.Mpad % 96 == 0 &&
-        (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200)
-        ktile = 96;
-    if (!plain && dmatap_eligible(d, ktile))
-        return d.epi == MI_EPI_GLU ? launch_dmatap<MI_EPI_GLU>(d, ktile, st) : launch_dmatap<MI_EPI_BIAS_STATS>(d, ktile, st);
-    if (dmarow_eligible(d, tile, plain)) {
-        switch (d.epi) {
-            case MI_EPI_LINEAR: return launch_dmarow<MI_EPI_LINEAR, MI_FLAG_GELU>(d, tile, st);
-            case MI_EPI_CONVTR: return launch_dmarow<MI_EPI_CONVTR, 0>(d, tile, st);
-            case MI_EPI_GLU: return launch_dmarow<MI_EPI_GLU, 0>(d, tile, st);
-            case MI_EPI_GN_GLU: return launch_dmarow<MI_EPI_GN_GLU, 0>(d, tile, st);
-        }
-    }
-    if (!x6_class_ok) d.wx = nullptr;
-    if (d.wx && conv_x6_supported(tile) && x6_mode == 3) return launch_conv_x6(d, tile, false, st);      // 3: table loader for all
-    if (d.wx && conv_x6_supported(tile) && (x6_mode == 0 || (x6_mode == 1) == plain))
-        return x6_verify ? x6_verified_launch(d, tile, plain, st) : launch_conv_x6(d, tile, plain, st);
-#define MI_DISPATCH(E)                                              \
-    case E: return plain ? launch_tile<E, 0, true>(d, tile, st) : launch_tile<E, 0, false>(d, tile, st)
-#define MI_LINEAR(F)                                                \
-    case F: return plain ? launch_tile<MI_EPI_LINEAR, F, true>(d, tile, st) : launch_tile<MI_EPI_LINEAR, F, false>(d, tile, st)
-    if (d.epi == MI_EPI_LINEAR) {
-        switch (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) {
-            MI_LINEAR(0);
-            MI_LINEAR(MI_FLAG_GELU);
-            MI_LINEAR(MI_FLAG_RES);
-            MI_LINEAR(MI_FLAG_SCALE | MI_FLAG_RES);
-            MI_LINEAR(MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS);
-            MI_LINEAR(MI_FLAG_LN);
-            MI_LINEAR(MI_FLAG_LN | MI_FLAG_GELU);
-        }
-        return set_error(MI_EINVAL, "conv: unsupported LINEAR flag combination %d", d.flags);
-    }
-#undef MI_LINEAR
-    switch (d.epi) {
-        MI_DISPATCH(MI_EPI_GLU);
-        MI_DISPATCH(MI_EPI_BIAS_STATS);
-        MI_DISPATCH(MI_EPI_STATS_ONLY);
-        MI_DISPATCH(MI_EPI_GN_GLU);
-        MI_DISPATCH(MI_EPI_CONVTR);
-    }
-#undef MI_DISPATCH
-    return set_error(MI_EINVAL, "conv: unsupported epilogue %d", d.epi);
-}
 
-static int launch_conv_fp32_only(const mi_conv_desc &d, hipStream_t st) {
-    mi_conv_desc e = d;
-    e.wx = nullptr;
-    return launch_conv(e, st);
+    const ConvRoute r = conv_route(d);
+    const int image_tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M);       // the tile the layer's weight images were packed for
+    g_last_conv_route = r.route;
+    switch (r.route) {
+        case MI_ROUTE_TAP_HALF: return launch_conv_tap(d, r.tile, st);
+        case MI_ROUTE_HALF: return launch_conv_half(d, r.tile, r.plain, st);
+        case MI_ROUTE_TAP_X6: return launch_conv_tap_x6(d, r.tile, image_tile, st);
+        case MI_ROUTE_ROWS_X6: return launch_conv_rows_x6(d, r.tile, image_tile, st);
+        case MI_ROUTE_X6: return launch_conv_x6(d, r.tile, image_tile, r.plain, st);
+        case MI_ROUTE_DMATAP:
+            return d.epi == MI_EPI_GLU ? launch_dmatap<MI_EPI_GLU>(d, r.tile, st) : launch_dmatap<MI_EPI_BIAS_STATS>(d, r.tile, st);
+        case MI_ROUTE_DMAROW:
+            switch (d.epi) {
+                case MI_EPI_LINEAR: return launch_dmarow<MI_EPI_LINEAR, MI_FLAG_GELU>(d, r.tile, st);
+                case MI_EPI_CONVTR: return launch_dmarow<MI_EPI_CONVTR, 0>(d, r.tile, st);
+                case MI_EPI_GLU: return launch_dmarow<MI_EPI_GLU, 0>(d, r.tile, st);
+                case MI_EPI_GN_GLU: return launch_dmarow<MI_EPI_GN_GLU, 0>(d, r.tile, st);
+            }
+            return set_error(MI_EINVAL, "conv: DMA row route has no epilogue %d", d.epi);
+    }
+    // MI_ROUTE_TABLE, MI_ROUTE_DMA: the native fp32 kernels
+    const bool dma = r.route == MI_ROUTE_DMA;
+    return dispatch_epilogue(d, [&](auto epi, auto lflags) {
+        constexpr int E = decltype(epi)::value, F = decltype(lflags)::value;
+        return r.plain ? launch_tile<E, F, true>(d, r.tile, dma, st) : launch_tile<E, F, false>(d, r.tile, dma, st);
+    });
 }
 
 }  // namespace mi

@@ -1,6 +1,8 @@
 // Device-side pieces shared by the implicit-GEMM main loops (gemm_conv.hip: fp32 MFMA; gemm_x6.hip: split-bf16
 // MFMA): tile constants, output-column decomposition, the table-driven gather and the fused epilogues.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "gemm_conv.h"
 #include "kernels.h"
@@ -341,5 +343,34 @@ static inline int pick_m_groups(int MT, size_t weight_bytes) {
     return Gm;
 }
 static inline unsigned grouped_grid(int MT, int NT, int Gm) { return 8u * (MT / Gm) * ((NT + 8 / Gm - 1) / (8 / Gm)); }
+
+// Host side: the (epilogue, LINEAR flag set) combinations the float32 kernels are compiled for, as compile-time constants:
+// calls f(std::integral_constant<int, EPI>, std::integral_constant<int, LFLAGS>) for the descriptor's pair
+template <class F>
+static inline int dispatch_epilogue(const mi_conv_desc &d, F &&f) {
+    using std::integral_constant;
+    constexpr integral_constant<int, 0> none{};
+    if (d.epi == MI_EPI_LINEAR) {
+        constexpr integral_constant<int, MI_EPI_LINEAR> lin{};
+        switch (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) {
+            case 0: return f(lin, none);
+            case MI_FLAG_GELU: return f(lin, integral_constant<int, MI_FLAG_GELU>());
+            case MI_FLAG_RES: return f(lin, integral_constant<int, MI_FLAG_RES>());
+            case MI_FLAG_SCALE | MI_FLAG_RES: return f(lin, integral_constant<int, MI_FLAG_SCALE | MI_FLAG_RES>());
+            case MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS: return f(lin, integral_constant<int, MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS>());
+            case MI_FLAG_LN: return f(lin, integral_constant<int, MI_FLAG_LN>());
+            case MI_FLAG_LN | MI_FLAG_GELU: return f(lin, integral_constant<int, MI_FLAG_LN | MI_FLAG_GELU>());
+        }
+        return set_error(MI_EINVAL, "conv: unsupported LINEAR flag combination %d", d.flags);
+    }
+    switch (d.epi) {
+        case MI_EPI_GLU: return f(integral_constant<int, MI_EPI_GLU>(), none);
+        case MI_EPI_BIAS_STATS: return f(integral_constant<int, MI_EPI_BIAS_STATS>(), none);
+        case MI_EPI_STATS_ONLY: return f(integral_constant<int, MI_EPI_STATS_ONLY>(), none);
+        case MI_EPI_GN_GLU: return f(integral_constant<int, MI_EPI_GN_GLU>(), none);
+        case MI_EPI_CONVTR: return f(integral_constant<int, MI_EPI_CONVTR>(), none);
+    }
+    return set_error(MI_EINVAL, "conv: unsupported epilogue %d", d.epi);
+}
 
 }  // namespace mi

@@ -56,12 +56,8 @@ int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx,
 // a bare MFMA loop with no memory traffic is enough; fp32 MFMAs and bf16 MFMAs with AGPR accumulators -- what the
 // vendor GEMMs use -- are clean).  hipcc picks the VGPR form whenever the registers fit; one inline-asm AGPR operand in
 // the kernel makes it allocate AGPRs and place every MFMA accumulator there.
-#ifndef MI_X6_ABL
-#define MI_X6_ABL 0          /* victim-side bisect builds: 1 = one MFMA per K step instead of 24, 4 = no epilogue, 8 = zero operands,
-                                16 = 32 idle cycles after every MFMA, 32 = 64 idle cycles after every 4 MFMAs */
-#endif
 // HALF_IMG: a 64-row tile that reads its rows out of the 128-row weight image (the small-batch tile of the plain linear
-// layers and of the tap convs, launch_cfg_x6): the same fragments, products and k order as the 128-row tile, so both give
+// layers, of the tap and of the row-tap convs: gemm_conv.hip conv_route): the same fragments, products and k order as the 128-row tile, so both give
 // bit-identical results.
 // NT (taps, 9 or 3; 0 = none): the B loader of the float32 decoders' stride-1 3 x 3 / k = 3 rewrite convs (conv_tap_x6_kernel).
 // Row k = ci * NT + tap of the raw [16][128] activation tile is, for 128 consecutive output positions, a run of input row ci
@@ -263,22 +259,12 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int cur = 0;
-    bf16x8 keepa[TM][3], keepb[TN][3];       // MI_X6_ABL & 128 only
     for (int kt = 0; kt < nk; ++kt) {
         // All fragment reads of this K step are ISSUED before the loads of the next one: hipcc orders every ds_read
         // behind pending LDS-DMA with s_waitcnt vmcnt(0) (it cannot tell the ring stages apart), which would
         // otherwise make each step wait for the loads it has just issued.
         const unsigned char *As = smem + cur * STAGE, *Bs = As + A_BYTES;
         bf16x8 af[TM][3], bf[TN][3];
-        if ((MI_X6_ABL & 128) && kt > 0) {   // fragments fetched in the first step only: 24 MFMAs per step, (almost) no ds_read_b128
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                for (int a = 0; a < TM; ++a) af[a][p] = keepa[a][p];
-#pragma unroll
-                for (int b = 0; b < TN; ++b) bf[b][p] = keepb[b][p];
-            }
-        } else
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
 #pragma unroll
@@ -287,35 +273,6 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
 #pragma unroll
             for (int b = 0; b < TN; ++b)
                 bf[b][p] = *reinterpret_cast<const bf16x8 *>(Bs + (((p * 2 + lh) * BN) + (wn * TN + b) * 32 + li) * 16);
-        }
-        if (MI_X6_ABL & 128) {
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                for (int a = 0; a < TM; ++a) keepa[a][p] = af[a][p];
-#pragma unroll
-                for (int b = 0; b < TN; ++b) keepb[b][p] = bf[b][p];
-            }
-        }
-        if (MI_X6_ABL & 64) {                 // all fragment reads stay alive although only one MFMA consumes them
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                for (int a = 0; a < TM; ++a) { u32x4 z = __builtin_bit_cast(u32x4, af[a][p]); asm volatile("" : "+v"(z)); af[a][p] = __builtin_bit_cast(bf16x8, z); }
-#pragma unroll
-                for (int b = 0; b < TN; ++b) { u32x4 z = __builtin_bit_cast(u32x4, bf[b][p]); asm volatile("" : "+v"(z)); bf[b][p] = __builtin_bit_cast(bf16x8, z); }
-            }
-        }
-        if (MI_X6_ABL & 8) {                  // same instruction stream, all-zero operands (minimal switching power)
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                for (int a = 0; a < TM; ++a) { u32x4 z = {0u, 0u, 0u, 0u}; asm volatile("" : "+v"(z)); af[a][p] = __builtin_bit_cast(bf16x8, z); }
-#pragma unroll
-                for (int b = 0; b < TN; ++b) { u32x4 z = {0u, 0u, 0u, 0u}; asm volatile("" : "+v"(z)); bf[b][p] = __builtin_bit_cast(bf16x8, z); }
-            }
         }
         __builtin_amdgcn_sched_barrier(0);
         if (kt + 1 < nk) {
@@ -338,11 +295,7 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
             for (int a = 0; a < TM; ++a)
 #pragma unroll
                 for (int b = 0; b < TN; ++b)
-                    if (!(MI_X6_ABL & 1) || (q == 0 && a == 0 && b == 0)) {
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][PA[q]], bf[b][PB[q]], acc[a][b], 0, 0, 0);
-                        if (MI_X6_ABL & 16) asm volatile("s_nop 15\n\ts_nop 15");                     // gap after every MFMA
-                        if ((MI_X6_ABL & 32) && a == TM - 1 && b == TN - 1) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15");   // gap after each group
-                    }
+                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][PA[q]], bf[b][PB[q]], acc[a][b], 0, 0, 0);
         if (RAW || kt + 1 < nk) MI_B_STORE(cur ^ 1);
         if constexpr (RAW) {
             // the split of the next activation tile (~70 VALU) issues in the shadow of this step's MFMAs
@@ -372,12 +325,6 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
 #undef MI_ROW_LOADS
 #undef MI_B_STORE
 
-    if (MI_X6_ABL & 4) {                     // no epilogue: one store per thread keeps the loop alive
-        float s = 0.f;
-        for (int a = 0; a < TM; ++a) for (int b = 0; b < TN; ++b) for (int r = 0; r < 16; ++r) s += acc[a][b][r];
-        d.sink[threadIdx.x] = s;
-        return;
-    }
     conv_epilogue<TM, TN, EPI, LFLAGS>(d, acc, m0, n0, wm, wn, N, P, o2v);
 }
 
@@ -415,106 +362,62 @@ static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     return MI_OK;
 }
 
-template <int EPI, int LFLAGS, bool PLAIN>
-static int launch_tile_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
-    if constexpr (PLAIN && EPI == MI_EPI_LINEAR) {
-        // small batches, as in the fp32 kernels (gemm_conv.hip launch_tile): a plain linear layer whose 128-row tiles give fewer
-        // workgroups than the chip has CUs runs on 64-row tiles that read the 128-row image (MI_SMALL_TILE=0: off)
-        static const int small = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
-        if (small && tile == 128 && (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200)
-            return launch_cfg_x6<1, 4, 2, 1, EPI, LFLAGS, PLAIN, true>(d, st);
+// `tile` is the tile gemm_conv.hip conv_route decided, `image_tile` the one the split image was packed for: they differ for the
+// under-filled 128-row layers, which run 64-row tiles that read the 128-row image (bit-identical to the 128-row tile, no second
+// image).  NTAPS: the loader (0: plain / gather table, 9 or 3: shifted-run taps, kRowTaps: row taps)
+template <int EPI, int LFLAGS, bool PLAIN, int NTAPS>
+static int launch_tile_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st) {
+    if (tile != image_tile) {
+        if constexpr (NTAPS != 0 || (PLAIN && EPI == MI_EPI_LINEAR)) {
+            if (tile == 64 && image_tile == 128) return launch_cfg_x6<1, 4, 2, 1, EPI, LFLAGS, PLAIN, true, NTAPS>(d, st);
+        }
+        return set_error(MI_EINVAL, "conv x6: no %d-row tile on a %d-row image for epilogue %d", tile, image_tile, EPI);
     }
     switch (tile) {
-        case 128: return launch_cfg_x6<2, 2, 2, 2, EPI, LFLAGS, PLAIN>(d, st);
-        case 96: return launch_cfg_x6<1, 4, 3, 1, EPI, LFLAGS, PLAIN>(d, st);
-        case 64: return launch_cfg_x6<1, 4, 2, 1, EPI, LFLAGS, PLAIN>(d, st);
+        case 128: return launch_cfg_x6<2, 2, 2, 2, EPI, LFLAGS, PLAIN, false, NTAPS>(d, st);
+        case 96: return launch_cfg_x6<1, 4, 3, 1, EPI, LFLAGS, PLAIN, false, NTAPS>(d, st);
+        case 64:
+            if constexpr (NTAPS == 0) return launch_cfg_x6<1, 4, 2, 1, EPI, LFLAGS, PLAIN>(d, st);
     }
     return set_error(MI_EINVAL, "conv x6: unsupported tile_m %d", tile);
 }
 
 bool conv_x6_supported(int tile) { return tile == 128 || tile == 96 || tile == 64; }
 
-template <int NT>
-static int launch_tile_tap_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
-    // small batches, as in the fp32 route (gemm_conv.hip launch_conv): a 128-row layer with fewer than 200 workgroups runs on
-    // 64-row tiles that read the 128-row image -- bit-identical to the 128-row tile, no second image (MI_SMALL_TILE=0: off)
-    static const int small = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
-    if (small && tile == 128 && (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200)
-        return launch_cfg_x6<1, 4, 2, 1, MI_EPI_GLU, 0, false, true, NT>(d, st);
-    if (tile == 128) return launch_cfg_x6<2, 2, 2, 2, MI_EPI_GLU, 0, false, false, NT>(d, st);
-    return launch_cfg_x6<1, 4, 3, 1, MI_EPI_GLU, 0, false, false, NT>(d, st);
-}
-
 // d has been validated by launch_conv (gemm_conv.hip): a stride-1 GLU conv with K2 = 3, dilation 1, NT = 9 or 3 taps, its row
-// pitch a multiple of 4 and equal to O2, tile 96 or 128 (dmatap_eligible)
-int launch_conv_tap_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
-    g_last_conv_route = 7;
+// pitch a multiple of 4 and equal to O2, image tile 96 or 128 (dmatap_eligible)
+int launch_conv_tap_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st) {
     MI_REQUIRE(d.wx && ((uintptr_t)d.wx & 15) == 0, "conv tap x6: split weight image missing or misaligned");
-    MI_REQUIRE(d.epi == MI_EPI_GLU && (tile == 96 || tile == 128) && (d.ntaps == 9 || d.ntaps == 3),
-               "conv tap x6: GLU layer with 9 or 3 taps on a 96- or 128-row tile (epi %d, tile %d, ntaps %d)", d.epi, tile, d.ntaps);
-    return d.ntaps == 9 ? launch_tile_tap_x6<9>(d, tile, st) : launch_tile_tap_x6<3>(d, tile, st);
-}
-
-template <int EPI, int LFLAGS>
-static int launch_tile_rows_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
-    // small batches, as for the tap convs: a 128-row layer with fewer than 200 workgroups runs on 64-row tiles that read the
-    // 128-row image -- bit-identical to the 128-row tile (MI_SMALL_TILE=0: off)
-    static const int small = getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) : 1;
-    if (small && tile == 128 && (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200)
-        return launch_cfg_x6<1, 4, 2, 1, EPI, LFLAGS, false, true, kRowTaps>(d, st);
-    if (tile == 128) return launch_cfg_x6<2, 2, 2, 2, EPI, LFLAGS, false, false, kRowTaps>(d, st);
-    return launch_cfg_x6<1, 4, 3, 1, EPI, LFLAGS, false, false, kRowTaps>(d, st);
+    MI_REQUIRE(d.epi == MI_EPI_GLU && (image_tile == 96 || image_tile == 128) && (d.ntaps == 9 || d.ntaps == 3),
+               "conv tap x6: GLU layer with 9 or 3 taps on a 96- or 128-row tile (epi %d, tile %d, ntaps %d)", d.epi, image_tile, d.ntaps);
+    return d.ntaps == 9 ? launch_tile_x6<MI_EPI_GLU, 0, false, 9>(d, tile, image_tile, st) : launch_tile_x6<MI_EPI_GLU, 0, false, 3>(d, tile, image_tile, st);
 }
 
 // d has been validated by launch_conv (gemm_conv.hip): a float32 layer whose table moves its taps along rows only (dma_rows, or a
 // plain layer's identity table), row pitch a multiple of 4 and equal to O2, S2 = 1, a 64-byte-aligned table (dmarow_eligible):
 // LINEAR + GELU (the encoder convs) or CONVTR (the transposed convs; the epilogue reads its flag set at run time) on 96 or 128
 // rows, 1 x 1 + GLU (the encoders' rewrites) on 128 rows -- the epilogue instantiations of conv_gemm_dmarow_kernel
-int launch_conv_rows_x6(const mi_conv_desc &d, int tile, hipStream_t st) {
-    g_last_conv_route = 8;
+int launch_conv_rows_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st) {
     MI_REQUIRE(d.wx && ((uintptr_t)d.wx & 15) == 0, "conv rows x6: split weight image missing or misaligned");
     MI_REQUIRE(d.ktab && ((uintptr_t)d.ktab & 63) == 0, "conv rows x6: gather table missing or misaligned");
-    MI_REQUIRE(tile == 96 || tile == 128, "conv rows x6: 96- or 128-row tile (tile %d)", tile);
-    if (d.epi == MI_EPI_CONVTR) return launch_tile_rows_x6<MI_EPI_CONVTR, 0>(d, tile, st);
+    MI_REQUIRE(image_tile == 96 || image_tile == 128, "conv rows x6: 96- or 128-row tile (tile %d)", image_tile);
+    if (d.epi == MI_EPI_CONVTR) return launch_tile_x6<MI_EPI_CONVTR, 0, false, kRowTaps>(d, tile, image_tile, st);
     if (d.epi == MI_EPI_GLU) {
-        MI_REQUIRE(tile == 128, "conv rows x6: GLU on a 128-row tile (tile %d)", tile);
-        return launch_tile_rows_x6<MI_EPI_GLU, 0>(d, tile, st);
+        MI_REQUIRE(image_tile == 128, "conv rows x6: GLU on a 128-row tile (tile %d)", image_tile);
+        return launch_tile_x6<MI_EPI_GLU, 0, false, kRowTaps>(d, tile, image_tile, st);
     }
     MI_REQUIRE(d.epi == MI_EPI_LINEAR && (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) == MI_FLAG_GELU,
                "conv rows x6: LINEAR + GELU, CONVTR or GLU (epi %d, flags %d)", d.epi, d.flags);
-    return launch_tile_rows_x6<MI_EPI_LINEAR, MI_FLAG_GELU>(d, tile, st);
+    return launch_tile_x6<MI_EPI_LINEAR, MI_FLAG_GELU, false, kRowTaps>(d, tile, image_tile, st);
 }
 
-// d has been validated by launch_conv (gemm_conv.hip), which also decided `plain`
-int launch_conv_x6(const mi_conv_desc &d, int tile, bool plain, hipStream_t st) {
-    g_last_conv_route = 4;
+// d has been validated by launch_conv (gemm_conv.hip); `plain` is conv_route's
+int launch_conv_x6(const mi_conv_desc &d, int tile, int image_tile, bool plain, hipStream_t st) {
     MI_REQUIRE(d.wx && ((uintptr_t)d.wx & 15) == 0, "conv x6: split weight image missing or misaligned");
-#define MI_DISPATCH(E)                                              \
-    case E: return plain ? launch_tile_x6<E, 0, true>(d, tile, st) : launch_tile_x6<E, 0, false>(d, tile, st)
-#define MI_LINEAR(F)                                                \
-    case F: return plain ? launch_tile_x6<MI_EPI_LINEAR, F, true>(d, tile, st) : launch_tile_x6<MI_EPI_LINEAR, F, false>(d, tile, st)
-    if (d.epi == MI_EPI_LINEAR) {
-        switch (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) {
-            MI_LINEAR(0);
-            MI_LINEAR(MI_FLAG_GELU);
-            MI_LINEAR(MI_FLAG_RES);
-            MI_LINEAR(MI_FLAG_SCALE | MI_FLAG_RES);
-            MI_LINEAR(MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS);
-            MI_LINEAR(MI_FLAG_LN);
-            MI_LINEAR(MI_FLAG_LN | MI_FLAG_GELU);
-        }
-        return set_error(MI_EINVAL, "conv: unsupported LINEAR flag combination %d", d.flags);
-    }
-#undef MI_LINEAR
-    switch (d.epi) {
-        MI_DISPATCH(MI_EPI_GLU);
-        MI_DISPATCH(MI_EPI_BIAS_STATS);
-        MI_DISPATCH(MI_EPI_STATS_ONLY);
-        MI_DISPATCH(MI_EPI_GN_GLU);
-        MI_DISPATCH(MI_EPI_CONVTR);
-    }
-#undef MI_DISPATCH
-    return set_error(MI_EINVAL, "conv: unsupported epilogue %d", d.epi);
+    return dispatch_epilogue(d, [&](auto epi, auto lflags) {
+        constexpr int E = decltype(epi)::value, F = decltype(lflags)::value;
+        return plain ? launch_tile_x6<E, F, true, 0>(d, tile, image_tile, st) : launch_tile_x6<E, F, false, 0>(d, tile, image_tile, st);
+    });
 }
 
 }  // namespace mi

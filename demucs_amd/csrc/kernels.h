@@ -93,11 +93,27 @@ int launch_dconv_time_layer(const DConvTimeLayer &l, int C, int dil, int B, int 
 int launch_conv(const mi_conv_desc &d, hipStream_t st);
 int conv_pick_tile(int M);
 extern int g_split_bf16;     // 0 (mi_set_split_bf16): native fp32 MFMA kernels even where a split weight image exists
-// gemm_x6.hip
+// Which kernel launch_conv runs for a descriptor, decided from the descriptor alone (no HIP call, no pointer followed):
+// route: mi_conv_route (include/demucs_amd.h); tile: the rows of the tile that kernel runs, after every small-batch substitution
+// (routes 4, 7, 8: 64 under a 128-row layer = the 64-row tile that reads the 128-row image); plain: the 1x1 / linear fast path
+struct ConvRoute { int route; int tile; bool plain; };
+ConvRoute conv_route(const mi_conv_desc &d);
+// the environment switches of the float32 conv kernels, read once
+struct ConvSwitches {
+    bool no_dma;            // MI_NO_DMA: plain linear layers on the register-staged loader
+    bool no_dma_tap;        // MI_NO_DMA_TAP: no shifted-run DMA taps (routes 2 and 7)
+    bool no_dma_rows;       // MI_NO_DMA_ROWS: no DMA row taps (routes 3 and 8)
+    bool no_dma_dconv;      // MI_NO_DMA_DCONV: the DConv blocks' k = 3 convs off route 2
+    bool small_tile;        // MI_SMALL_TILE (default 1): smaller tiles for under-filled 128-row layers
+    bool mgroups;           // MI_MGROUPS: M-grouped tile order in the native fp32 kernels
+    bool x6_plain_only;     // MI_X6_MODE=1: the split-bf16 loop for plain layers only
+};
+const ConvSwitches &conv_switches();
+// gemm_x6.hip: `tile` as decided by conv_route, `image_tile` the tile the split image was packed for
 bool conv_x6_supported(int tile);
-int launch_conv_x6(const mi_conv_desc &d, int tile, bool plain, hipStream_t st);
-int launch_conv_tap_x6(const mi_conv_desc &d, int tile, hipStream_t st);      // stride-1 3 x 3 / k = 3 GLU convs (route 7)
-int launch_conv_rows_x6(const mi_conv_desc &d, int tile, hipStream_t st);     // row-tap encoder / transposed convs (route 8)
+int launch_conv_x6(const mi_conv_desc &d, int tile, int image_tile, bool plain, hipStream_t st);
+int launch_conv_tap_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);      // stride-1 3 x 3 / k = 3 GLU convs (route 7)
+int launch_conv_rows_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);     // row-tap encoder / transposed convs (route 8)
 int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx, hipStream_t st);
 
 // gemm_half.hip: bf16 / fp16 operand main loop (mi_config.dtype)

@@ -102,17 +102,19 @@ Profiler::~Profiler() {
 
 static const char *kEpiNames[6] = {"linear", "glu", "bias_stats", "stats_only", "gn_glu", "convtr"};
 
-// class id of a conv launch: epilogue x tile x prologue
-static int conv_class(const mi_conv_desc &d, int tile) {
-    const int ti = tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3;
-    const bool x6 = d.half || (d.wx && g_split_bf16 && conv_x6_supported(tile));   // bf16 / fp16 operand or split-bf16 main loops: own classes
-    return (x6 ? 48 : 0) + d.epi * 8 + ti * 2 + (d.plain ? 1 : 0);
-}
-
 int Model::conv(const mi_conv_desc &d, hipStream_t st) {
     if (!prof.on) return launch_conv(d, st);
-    const int tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M);
-    const int cls = conv_class(d, tile);
+    // The row of this launch: which main loop runs is conv_route's answer, asked before the launch.  Rows stay keyed by the layer's
+    // own tile (the one its weights are packed for) and the descriptor's `plain`, not by the small-batch tile the kernel runs
+    const int route = conv_route(d).route;
+    const int tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M), ti = tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3;
+    // bf16 / fp16 operand or split-bf16 main loops: classes of their own.  The split-bf16 tap convs (conv_tap_x6_kernel) and row-tap
+    // convs (conv_rows_x6_kernel: the frequency branch's encoder / transposed convs, the encoders' 1 x 1 + GLU rewrites): rows of
+    // their own, named after the kernel -- the conv_gemm_x6 rows stay the linears' ones
+    const bool tap_x6 = route == MI_ROUTE_TAP_X6, rows_x6 = route == MI_ROUTE_ROWS_X6;
+    const int cls = tap_x6    ? 105 + (d.ntaps == 9 ? 2 : 0) + (tile == 128 ? 1 : 0)
+                    : rows_x6 ? 109 + (d.epi == MI_EPI_CONVTR ? 4 : d.epi == MI_EPI_GLU ? 2 : 0) + (tile == 128 ? 1 : 0)
+                              : (route >= MI_ROUTE_X6 ? 48 : 0) + d.epi * 8 + ti * 2 + (d.plain ? 1 : 0);
     const double N = (double)d.B * d.O1 * d.O2;
     // algorithmic work: 2*M*K flops per output column; bytes = input tensor + output tensor + weights, once each
     const double in_bytes = 4.0 * (double)d.B * (double)d.x_bstride;
@@ -126,15 +128,8 @@ int Model::conv(const mi_conv_desc &d, hipStream_t st) {
     MI_HIP(hipEventRecord(p.a, st));
     const int r = launch_conv(d, st);
     MI_HIP(hipEventRecord(p.b, st));
-    // the split-bf16 tap convs (route 7, gemm_x6.hip conv_tap_x6_kernel): rows of their own, named after the kernel -- the
-    // conv_gemm_x6 rows stay the linears' ones
-    // ... and so do the split-bf16 row-tap convs (route 8, conv_rows_x6_kernel: the frequency branch's encoder / transposed convs,
-    // the encoders' 1 x 1 + GLU rewrites)
-    const bool tap_x6 = r == MI_OK && g_last_conv_route == 7, rows_x6 = r == MI_OK && g_last_conv_route == 8;
-    if (tap_x6) p.cls = 105 + (d.ntaps == 9 ? 2 : 0) + (tile == 128 ? 1 : 0);
-    if (rows_x6) p.cls = 109 + (d.epi == MI_EPI_CONVTR ? 4 : d.epi == MI_EPI_GLU ? 2 : 0) + (tile == 128 ? 1 : 0);
     prof.pending.push_back(p);
-    ProfRow &row = prof.rows[p.cls];
+    ProfRow &row = prof.rows[cls];
     if (!row.name[0] && tap_x6)
         snprintf(row.name, sizeof(row.name), "conv_tap_x6<%s,tile%d,taps%d>", kEpiNames[d.epi], tile, d.ntaps);
     else if (!row.name[0] && rows_x6)
@@ -210,7 +205,7 @@ int Model::attn_heads(const void *q, const void *k, const void *v, float *o, int
 // a device); one process per GPU is the supported deployment.
 int Model::pack_split(PackedConv *pc) {
     const int scope = x6_scope();                 // 0 none, 1 transformer linears + decoder rewrites + row-tap convs (float32), 2 all
-    static const bool no_rows = getenv("MI_NO_DMA_ROWS") != nullptr;
+    const bool no_rows = conv_switches().no_dma_rows;
     const bool want = scope == 2 || (scope == 1 && (split_linears || split_taps || (split_rows && !no_rows)) && cfg.dtype == MI_DTYPE_F32);
     if (!want || !conv_x6_supported(pc->tile)) return MI_OK;
     MI_TRY(dev_alloc(&pc->wx, (size_t)6 * pc->Kpad * pc->Mpad));

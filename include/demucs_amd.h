@@ -607,15 +607,31 @@ int mi_layernorm_cf(const float *x_dev, int32_t B, int32_t C, int32_t T, const f
  * tools/micro/poison_all.py to interleave a register / LDS poisoning kernel between the engine's kernels. */
 void mi_debug_set_post_launch_hook(void (*hook)(void *stream));
 
-/* Debug aid for the kernel tests: which main loop the LAST mi_conv_forward of this process took -- 0 table-driven gather /
- * register-staged loader (conv_gemm_kernel), 1 LDS-DMA plain linear tile (conv_gemm_dma_kernel), 2 LDS-DMA shifted-run taps
- * (conv_gemm_dmatap_kernel), 3 LDS-DMA row taps (conv_gemm_dmarow_kernel), 4 split-bf16 (gemm_x6.hip), 5 half-mode loops
- * (gemm_half.hip), 6 half-mode tap images (gemm_tap.hip), 7 split-bf16 with LDS-DMA shifted-run taps (gemm_x6.hip
- * conv_tap_x6_kernel: stride-1 3 x 3 / k = 3 GLU convs with a split image and the geometry of route 2), 8 split-bf16 with LDS-DMA
- * row taps (gemm_x6.hip conv_rows_x6_kernel: the row-tap layers of route 3 -- LINEAR + GELU or CONVTR, 96- / 128-row tiles -- with
- * a split image); -1 before any call.  A route is chosen from the descriptor alone, so a
- * test that compares two routes bit for bit also has to see that they WERE two routes.  Process-wide, not thread-safe. */
+/* The main loops a conv / linear layer can run on ("routes"): chosen from the descriptor alone, so a test that compares two
+ * routes bit for bit also has to see that they WERE two routes. */
+enum mi_conv_route {
+    MI_ROUTE_TABLE = 0,    /* table-driven gather / register-staged loader (conv_gemm_kernel) */
+    MI_ROUTE_DMA = 1,      /* LDS-DMA plain linear tile (conv_gemm_dma_kernel) */
+    MI_ROUTE_DMATAP = 2,   /* LDS-DMA shifted-run taps (conv_gemm_dmatap_kernel) */
+    MI_ROUTE_DMAROW = 3,   /* LDS-DMA row taps (conv_gemm_dmarow_kernel) */
+    MI_ROUTE_X6 = 4,       /* split-bf16 (gemm_x6.hip conv_gemm_x6_kernel) */
+    MI_ROUTE_HALF = 5,     /* half-mode loops (gemm_half.hip) */
+    MI_ROUTE_TAP_HALF = 6, /* half-mode tap images (gemm_tap.hip) */
+    MI_ROUTE_TAP_X6 = 7,   /* split-bf16 with LDS-DMA shifted-run taps (gemm_x6.hip conv_tap_x6_kernel: stride-1 3 x 3 / k = 3 GLU
+                              convs with a split image and the geometry of route 2) */
+    MI_ROUTE_ROWS_X6 = 8   /* split-bf16 with LDS-DMA row taps (gemm_x6.hip conv_rows_x6_kernel: the row-tap layers of route 3 --
+                              LINEAR + GELU or CONVTR on 96- / 128-row tiles, 1 x 1 + GLU on 128-row tiles -- with a split image) */
+};
+
+/* Debug aid for the kernel tests: the route the LAST mi_conv_forward of this process took; -1 before any call.  Process-wide,
+ * not thread-safe. */
 int mi_debug_last_conv_route(void);
+
+/* Debug aid: the route mi_conv_forward WOULD take for `desc` (under the environment switches and mi_set_split_bf16 as they
+ * stand) and, in *tile (may be NULL), the rows of the tile that kernel runs, after every small-batch substitution: for the
+ * split-bf16 routes 64 under a 128-row layer means the 64-row tile that reads the 128-row image.  Host code only: launches
+ * nothing, follows no pointer of the descriptor, works in a process that never touches the GPU.  Returns -1 for desc == NULL. */
+int mi_debug_conv_route(const struct mi_conv_desc *desc, int *tile);
 
 const char *mi_last_error(void);
 /* "demucs_amd <version> gfx950" */

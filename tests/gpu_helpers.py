@@ -67,8 +67,8 @@ def ktab(Cin, K1, K2, dil1, dil2, pad1, pad2, chan_stride, D2, Kpad):
     return torch.from_numpy(t).cuda()
 
 
-def conv_call(**kw):
-    """Fill a MiConvDesc from keyword arguments (tensors -> data_ptr) and launch."""
+def conv_desc(**kw):
+    """Fill a MiConvDesc from keyword arguments (tensors -> data_ptr) -> (descriptor, the tensors it points to)."""
     d = _lib.MiConvDesc()
     keep = []
     mode = kw.pop("x6", False)
@@ -94,6 +94,12 @@ def conv_call(**kw):
             keep.append(v)
             v = v.data_ptr()
         setattr(d, name, v if v is not None else 0)
+    return d, keep
+
+
+def conv_call(**kw):
+    """Fill a MiConvDesc from keyword arguments and launch."""
+    d, keep = conv_desc(**kw)
     _lib.check(_lib.load().mi_conv_forward(C.byref(d), C.c_void_p(_lib.current_stream_ptr())), "mi_conv_forward")
     torch.cuda.synchronize()
     return keep
