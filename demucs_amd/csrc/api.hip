@@ -495,9 +495,23 @@ int mi_gn_gelu(float *x_dev, int32_t B, int32_t C, int32_t C_alloc, int32_t D1, 
 int32_t mi_gram_order(int32_t h) { return gram_hp(h); }
 
 int mi_lstm_seq(const float *gx_dev, const float *whh_host, int32_t N, int32_t H, int32_t W, float *out_dev, int32_t mode, void *stream) {
-    MI_REQUIRE(gx_dev && whh_host && out_dev && N > 0 && W > 0 && (H == 192 || H == 384), "mi_lstm_seq: bad argument (H must be 192 or 384)");
-    MI_REQUIRE(mode == 0 || mode == 1, "mi_lstm_seq: mode 0 (one launch per step) or 1 (persistent kernel)");
+    MI_REQUIRE(mode == 0 || mode == 1 || mode == 2, "mi_lstm_seq: mode 0 (one launch per step), 1 (persistent kernel) or 2 (generic small kernel)");
     hipStream_t st = (hipStream_t)stream;
+    if (mode == 2) {                 // the generic kernel reads W_hh in its natural order: upload, launch, wait
+        MI_REQUIRE(gx_dev && whh_host && out_dev && N > 0 && N <= 65535 && W > 0 && H >= 1 && H <= 64,
+                   "mi_lstm_seq: bad argument (mode 2 needs 1 <= H <= 64)");
+        const size_t bytes = (size_t)2 * 4 * H * H * sizeof(float);
+        float *wn = nullptr;
+        MI_HIP(hipMalloc((void **)&wn, bytes));
+        int rs = MI_OK;
+        if (hipMemcpyAsync(wn, whh_host, bytes, hipMemcpyHostToDevice, st) != hipSuccess) rs = set_error(MI_EHIP, "mi_lstm_seq: hipMemcpyAsync failed");
+        if (rs == MI_OK) rs = launch_lstm_small(gx_dev, wn, N, H, W, out_dev, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        if (es != hipSuccess && rs == MI_OK) rs = set_error(MI_EHIP, "mi_lstm_seq: hipStreamSynchronize: %s", hipGetErrorString(es));
+        (void)hipFree(wn);
+        return rs;
+    }
+    MI_REQUIRE(gx_dev && whh_host && out_dev && N > 0 && W > 0 && (H == 192 || H == 384), "mi_lstm_seq: bad argument (H must be 192 or 384)");
     std::vector<float> packed((size_t)2 * 4 * H * H);
     pack_lstm_whh(whh_host, H, packed.data());
     float *wd = nullptr, *state = nullptr;
@@ -559,6 +573,71 @@ int mi_layernorm_cf(const float *x_dev, int32_t B, int32_t C, int32_t T, const f
                     const float *add_dev, float *y_dev, void *stream) {
     MI_REQUIRE(x_dev && w_dev && b_dev && y_dev, "mi_layernorm_cf: null argument");
     return launch_layernorm_cf(x_dev, B, C, T, w_dev, b_dev, add_dev, y_dev, nullptr, (hipStream_t)stream);
+}
+
+// ---- test entries of the hdemucs_mmi kernels (hkernels.hip) and of the token kernel (norms.hip): argument checks + the launcher
+int mi_token_norm(int32_t mode, const float *x_dev, int32_t B, int32_t C, int32_t T, const float *w_dev, const float *b_dev,
+                  const float *pe_dev, const float *gstat_dev, float *y_dev, float *ostat_dev, void *img_dev, int64_t img_n,
+                  int32_t img_dtype, void *stream) {
+    MI_REQUIRE(mode >= 0 && mode <= 2, "mi_token_norm: mode %d (0 LayerNorm, 1 statistics, 2 GroupNorm(1) apply)", mode);
+    MI_REQUIRE(x_dev && B > 0 && B <= 65535 && C > 0 && T > 0, "mi_token_norm: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 1) {
+        MI_REQUIRE(ostat_dev, "mi_token_norm: mode 1 writes only the statistics, ostat_dev is NULL");
+        return launch_token_stats(x_dev, B, C, T, (float2 *)ostat_dev, st, img_dev, img_n, img_dtype);
+    }
+    MI_REQUIRE(w_dev && b_dev && y_dev, "mi_token_norm: mode %d needs w_dev, b_dev and y_dev", mode);
+    if (mode == 0) return launch_layernorm_cf(x_dev, B, C, T, w_dev, b_dev, pe_dev, y_dev, (float2 *)ostat_dev, st, img_dev, img_n, img_dtype);
+    MI_REQUIRE(gstat_dev, "mi_token_norm: mode 2 needs gstat_dev");
+    return launch_gn_apply_tokstats(x_dev, B, C, T, (const float2 *)gstat_dev, w_dev, b_dev, y_dev, (float2 *)ostat_dev, st, img_dev, img_n,
+                                    img_dtype);
+}
+
+int mi_local_attn(const float *qkc_dev, int32_t B, int32_t C, int32_t T, int32_t ld, float *out_dev, int32_t ld_o, void *stream) {
+    MI_REQUIRE(qkc_dev && out_dev && B > 0 && B <= 65535 && C > 0 && T > 0, "mi_local_attn: bad argument");
+    MI_REQUIRE(ld_o >= T, "mi_local_attn: output pitch %d < T = %d", ld_o, T);
+    return launch_local_attn(qkc_dev, B, C, T, ld, out_dev, ld_o, (hipStream_t)stream);
+}
+
+int mi_group_norm_apply(const float *x_dev, int32_t B, int32_t Cin, int32_t G, int32_t in_pitch, int32_t in_len, int32_t off,
+                        const float *w_dev, const float *b_dev, int32_t glu, int32_t gelu, const float *scale_dev, const float *res_dev,
+                        int32_t res_pitch, float *y_dev, int32_t Cout, int32_t out_len, int32_t out_pitch, int32_t chan_div,
+                        double *stats_ws_dev, float *stats_out_dev, void *stream) {
+    MI_REQUIRE(x_dev && w_dev && b_dev && y_dev && stats_ws_dev && stats_out_dev, "mi_group_norm_apply: null argument");
+    MI_REQUIRE(B > 0 && B <= 65535 && Cin > 0 && G > 0 && (int64_t)B * G <= 65535 && Cin % G == 0 && Cout > 0 && Cout <= 65535 && in_len > 0 && out_len > 0 &&
+               chan_div >= 1 && Cin % chan_div == 0, "mi_group_norm_apply: bad sizes");
+    MI_REQUIRE(in_pitch == in_len, "mi_group_norm_apply: statistics need contiguous channel rows (in_pitch %d != in_len %d)", in_pitch, in_len);
+    MI_REQUIRE(off >= 0 && (int64_t)off + out_len <= in_len, "mi_group_norm_apply: window [%d, %d + %d) outside the %d input columns", off, off,
+               out_len, in_len);
+    MI_REQUIRE(out_pitch >= out_len && (!res_dev || res_pitch >= out_len), "mi_group_norm_apply: a row pitch below out_len = %d", out_len);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t cnt = (int64_t)(Cin / G) * in_len;
+    MI_TRY(launch_row_stats(x_dev, B * G, cnt, cnt, stats_ws_dev, st));
+    MI_TRY(launch_finalize_stats(stats_ws_dev, B * G, (double)cnt, 1e-5f, 0, (float2 *)stats_out_dev, nullptr, st));
+    return launch_gn_apply(x_dev, B, Cin, G, in_pitch, off, (const float2 *)stats_out_dev, w_dev, b_dev, glu ? 1 : 0, gelu ? 1 : 0, scale_dev,
+                           res_dev, res_pitch, y_dev, Cout, out_len, out_pitch, st, chan_div);
+}
+
+int mi_blstm_unfold(const float *x_dev, int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t S, float *frames_dev, void *stream) {
+    MI_REQUIRE(x_dev && frames_dev && B > 0 && C > 0 && C <= 65535 && T > 0 && F > 0 && (int64_t)B * F <= 65535 && W > 0 && S > 0,
+               "mi_blstm_unfold: bad argument");
+    return launch_unfold_frames(x_dev, B, C, T, F, W, S, frames_dev, (hipStream_t)stream);
+}
+
+int mi_blstm_restitch(const float *frames_dev, int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t S, const float *skip_dev,
+                      float *y_dev, void *stream) {
+    MI_REQUIRE(frames_dev && y_dev && B > 0 && B <= 65535 && C > 0 && C <= 65535 && T > 0 && F > 0 && W > 0 && S > 0,
+               "mi_blstm_restitch: bad argument");
+    const int64_t per = (int64_t)W - 2 * (S / 2);
+    MI_REQUIRE(per > 0 && T <= W + (F - 1) * per, "mi_blstm_restitch: %d frames of %d columns every %d do not cover T = %d", F, W, S, T);
+    return launch_restitch_frames(frames_dev, B, C, T, F, W, S, skip_dev, y_dev, (hipStream_t)stream);
+}
+
+int mi_row_affine_pitch(const float *x_dev, int32_t B, int32_t C, int32_t L, int32_t out_pitch, const float *norm_dev, float *y_dev,
+                        void *stream) {
+    MI_REQUIRE(x_dev && norm_dev && y_dev && B > 0 && C > 0 && (int64_t)B * C <= 65535 && L > 0 && out_pitch >= L,
+               "mi_row_affine_pitch: bad argument");
+    return launch_row_affine_pitch(x_dev, B, C, L, out_pitch, (const float2 *)norm_dev, y_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

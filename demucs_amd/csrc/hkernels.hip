@@ -225,7 +225,11 @@ __global__ __launch_bounds__(256) void lstm_small_kernel(const float *__restrict
 
 int launch_lstm_small(const float *gx, const float *whh_natural, int N, int H, int W, float *out, hipStream_t st) {
     MI_REQUIRE(H >= 1 && H <= 64, "lstm: hidden size %d has no kernel (192 / 384: matrix-pipe kernels; <= 64: the generic one)", H);
-    hipLaunchKernelGGL(lstm_small_kernel, dim3(N, 2), dim3(256), (size_t)(4 * H * H + 5 * H) * sizeof(float), st, gx, whh_natural, out, N, H, W);
+    const size_t lds = (size_t)(4 * H * H + 5 * H) * sizeof(float);
+    // H = 64 asks for 66 816 bytes with the launch (H = 63: 64 764): above 64 KiB of dynamic LDS a kernel opts in first, the
+    // runtime's default per-kernel limit (hipDeviceProp_t.sharedMemPerBlock against sharedMemPerBlockOptin) is not assumed to cover it
+    if (lds > 64 * 1024) MI_HIP(hipFuncSetAttribute((const void *)lstm_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(lstm_small_kernel, dim3(N, 2), dim3(256), lds, st, gx, whh_natural, out, N, H, W);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }

@@ -30,7 +30,17 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float *__restrict_
     const int64_t per = (count + gridDim.x - 1) / gridDim.x;
     const int64_t lo = (int64_t)blockIdx.x * per, hi = min(count, lo + per);
     double s1 = 0.0, s2 = 0.0;
-    for (int64_t base = lo; base < hi; base += 256 * 16) {      // fp32 partials over <=16 elements, fp64 across
+    if (gridDim.x == 1) {
+        // a row that one workgroup covers (<= 4096 elements): squares and sums in float64.  A float32 square is rounded at 6e-8 of
+        // mean^2 + var and  s2 - s1 * mean  divides that by var: rows of two elements with |mean| >> std lost five digits of rstd
+        // (tests/test_gpu_hkernels.py).  One workgroup, one atomic per row: the result does not depend on any ordering.
+        for (int64_t i = lo + threadIdx.x; i < hi; i += 256) { const double d = p[i]; s1 += d; s2 += d * d; }
+    } else
+    // rows spread over workgroups: fp32 partials over <=16 elements, fp64 across.  The float-valued partials keep the float64 sums
+    // (near) exact, so the order in which the workgroups' atomics land does not show in the result; float64 squares would make it
+    // show (a side engine running beside the main one must reproduce its own forward bit for bit), and over this many elements
+    // the squares' rounding averages out
+    for (int64_t base = lo; base < hi; base += 256 * 16) {
         float a = 0.f, q = 0.f;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -87,7 +97,9 @@ __global__ __launch_bounds__(256) void row_affine_kernel(const float *__restrict
 //   MODE 0  LayerNorm (+ optional additive table pe[C][T]) -> y, and (mean, rstd) of y over channels -> ostat
 //   MODE 1  per-token (mean, rstd) of x only -> ostat                      (LayerNorm folded into the next GEMM)
 //   MODE 2  GroupNorm(1) apply y = (x - gm[b]) * gr[b] * w[c] + b[c] -> y, and (mean, rstd) of y -> ostat
-// Variances use sums shifted by the token's first value (no cancellation), float32.
+// Variances come from float64 sums of v - v0 and (v - v0)^2, v0 the token's first value.  The sums were float32 once: a first
+// channel far from the others (1e3 against a spread of 3) then left  s2 / C - (s1 / C)^2  with three digits, and the LayerNorm output
+// 2e-3 off (tests/test_gpu_token_norm.py); the shift alone does not prevent the cancellation, the wider sums do.
 // Half modes: `img` (optional) receives the tensor the NEXT matrix product reads -- y for MODE 0 / 2, x for MODE 1 -- as that
 // product's 16-bit operand image [C / 8][img_n][8] (column b T + t; gemm_half.hip): one coalesced 16-byte store per eight
 // channels and token, so that the projection moves it global -> LDS by DMA instead of loading and converting float32.
@@ -96,24 +108,24 @@ __global__ __launch_bounds__(256) void token_tile_kernel(const float *__restrict
                                                          const float *__restrict__ bvec, const float *__restrict__ pe,
                                                          const float2 *__restrict__ gstat, float eps, float *__restrict__ y,
                                                          float2 *__restrict__ ostat, uint4 *__restrict__ img, int64_t img_n, int img_dtype) {
-    __shared__ float red[4][64][2];
+    __shared__ double red[4][64][2];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave-uniform: w[c], b[c] become scalar loads
     const int t = blockIdx.x * 64 + lane;
     const bool ok = t < T;
     const size_t base = (size_t)blockIdx.y * C * T + (ok ? t : 0);
     const int cw = C / 4, c0 = wv * cw;
-    const float inv_c = 1.0f / (float)C;
+    const double inv_c = 1.0 / (double)C;
     float mean = 0.f, rstd = 1.f;
     if (MODE == 0 || MODE == 1) {                     // statistics of the input over channels
         const float x0 = x[base];
-        float s1 = 0.f, s2 = 0.f;
+        double s1 = 0.0, s2 = 0.0;
         if (MODE == 1 && img) {
             for (int c = c0; c < c0 + cw; c += 8) {
                 float q[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     q[e] = x[base + (size_t)(c + e) * T];
-                    const float v = q[e] - x0;
+                    const double v = (double)q[e] - (double)x0;
                     s1 += v; s2 += v * v;
                 }
                 if (ok) img[(size_t)(c >> 3) * img_n + (size_t)blockIdx.y * T + t] =
@@ -122,16 +134,16 @@ __global__ __launch_bounds__(256) void token_tile_kernel(const float *__restrict
             }
         } else
         for (int c = c0; c < c0 + cw; ++c) {
-            const float v = x[base + (size_t)c * T] - x0;
+            const double v = (double)x[base + (size_t)c * T] - (double)x0;
             s1 += v; s2 += v * v;
         }
         red[wv][lane][0] = s1; red[wv][lane][1] = s2;
         __syncthreads();
         s1 = red[0][lane][0] + red[1][lane][0] + red[2][lane][0] + red[3][lane][0];
         s2 = red[0][lane][1] + red[1][lane][1] + red[2][lane][1] + red[3][lane][1];
-        const float dm = s1 * inv_c;
-        mean = x0 + dm;
-        rstd = 1.0f / sqrtf(fmaxf(s2 * inv_c - dm * dm, 0.f) + eps);
+        const double dm = s1 * inv_c;
+        mean = (float)((double)x0 + dm);
+        rstd = 1.0f / sqrtf((float)fmax(s2 * inv_c - dm * dm, 0.0) + eps);
         if (MODE == 1) {
             if (ok && wv == 0) ostat[(size_t)blockIdx.y * T + t] = make_float2(mean, rstd);
             return;
@@ -148,7 +160,7 @@ __global__ __launch_bounds__(256) void token_tile_kernel(const float *__restrict
         if (MODE == 0 && pe) v += pe[ok ? t : 0];
         y0 = v;
     }
-    float s1 = 0.f, s2 = 0.f;
+    double s1 = 0.0, s2 = 0.0;
     // eight channels per trip: their loads are issued together (one channel per trip left ONE load in flight per wave: the trip
     // waited for x, w[c] and b[c] before the next address was formed); same per-element arithmetic and summation order
     int c = c0;
@@ -165,7 +177,7 @@ __global__ __launch_bounds__(256) void token_tile_kernel(const float *__restrict
             float v = (xv[e] - mean) * rstd * w[c + e] + bvec[c + e];
             if (MODE == 0 && pe) v += pv[e];
             if (ok) y[base + (size_t)(c + e) * T] = v;
-            const float dv = v - y0;
+            const double dv = (double)v - (double)y0;
             s1 += dv; s2 += dv * dv;
             q8[e] = v;
         }
@@ -178,7 +190,7 @@ __global__ __launch_bounds__(256) void token_tile_kernel(const float *__restrict
         float v = (x[base + (size_t)c * T] - mean) * rstd * w[c] + bvec[c];
         if (MODE == 0 && pe) v += pe[(size_t)c * T + (ok ? t : 0)];
         if (ok) y[base + (size_t)c * T] = v;
-        const float dv = v - y0;
+        const double dv = (double)v - (double)y0;
         s1 += dv; s2 += dv * dv;
     }
     if (!ostat) return;
@@ -187,8 +199,8 @@ __global__ __launch_bounds__(256) void token_tile_kernel(const float *__restrict
     if (ok && wv == 0) {
         s1 = red[0][lane][0] + red[1][lane][0] + red[2][lane][0] + red[3][lane][0];
         s2 = red[0][lane][1] + red[1][lane][1] + red[2][lane][1] + red[3][lane][1];
-        const float dm = s1 * inv_c;
-        ostat[(size_t)blockIdx.y * T + t] = make_float2(y0 + dm, 1.0f / sqrtf(fmaxf(s2 * inv_c - dm * dm, 0.f) + eps));
+        const double dm = s1 * inv_c;
+        ostat[(size_t)blockIdx.y * T + t] = make_float2((float)((double)y0 + dm), 1.0f / sqrtf((float)fmax(s2 * inv_c - dm * dm, 0.0) + eps));
     }
 }
 

@@ -592,9 +592,10 @@ int mi_gram_finalize(double *gram_dev, int32_t rows, int32_t h, int32_t slots, c
 /* The recurrence of one bidirectional nn.LSTM layer as the BLSTM of demucs/demucs.py:20-67 runs it (zero initial state, gate order
  *   i, f, g, o): gx_dev (N, 2 directions, 4H, W) = W_ih x_t + b_ih + b_hh for every step (a GEMM done before), whh_host = the HOST
  *   array (2, 4H, H) of weight_hh_l{k} / weight_hh_l{k}_reverse; out_dev (N, 2H, W): forward hidden states in channels [0, H), backward
- *   ones in [H, 2H).  H = 192 or 384 (hdemucs_mmi's layers 4 / 5).  mode 0: one launch per time step; mode 1: the persistent kernel
- *   the engine uses (hidden state exchanged between workgroups as self-validating 4-byte values whose least significant mantissa bit
- *   carries a step tag, bounded waits).  Synchronous (test entry). */
+ *   ones in [H, 2H).  mode 0: one launch per time step; mode 1: the persistent kernel the engine uses (hidden state exchanged between
+ *   workgroups as self-validating 4-byte values whose least significant mantissa bit carries a step tag, bounded waits); both for
+ *   H = 192 or 384 (hdemucs_mmi's layers 4 / 5).  mode 2: the generic kernel the engine runs for every other hidden size (one
+ *   workgroup per sequence and direction, W_hh in LDS in its natural order), 1 <= H <= 64.  Synchronous (test entry). */
 int mi_lstm_seq(const float *gx_dev, const float *whh_host, int32_t N, int32_t H, int32_t W, float *out_dev, int32_t mode, void *stream);
 
 /* LayerNorm over the channel axis of channel-first tokens x (B, C, T), optional additive table
@@ -602,6 +603,54 @@ int mi_lstm_seq(const float *gx_dev, const float *whh_host, int32_t N, int32_t H
  *   embedding add :655-663). */
 int mi_layernorm_cf(const float *x_dev, int32_t B, int32_t C, int32_t T, const float *w_dev, const float *b_dev,
                     const float *add_dev, float *y_dev, void *stream);
+
+/* ---- Kernel-level test entries of the remaining hand-written kernels (hkernels.hip, norms.hip): each validates its arguments and
+ * calls the launcher the engine calls, nothing else.  Asynchronous on `stream`. ---- */
+
+/* The token kernel of the transformer (norms.hip token_tile_kernel) on channel-first tokens x (B, C, T), C % 4 == 0:
+ *   mode 0  LayerNorm over channels (eps 1e-5) with affine w, b (C) plus the optional additive table pe (C, T) -> y (B, C, T)
+ *   mode 1  statistics only: nothing but ostat (and img) is written; w, b, pe, gstat, y are ignored (y_dev may be NULL)
+ *   mode 2  GroupNorm(1) apply y = (x - gstat[b].mean) * gstat[b].rstd * w[c] + b[c], gstat_dev = B (mean, rstd) float pairs
+ * ostat_dev (B * T (mean, rstd) float pairs, NULL = not wanted in modes 0 / 2, required in mode 1): per token, mean over channels
+ * and 1 / sqrt(biased variance + 1e-5) of y (modes 0, 2) or of x (mode 1) -- what the next GEMM's folded LayerNorm consumes.
+ * img_dev (may be NULL): the same tensor (y, or x in mode 1) as a 16-bit operand image [C / 8][img_n][8], column b * T + t,
+ * img_dtype MI_DTYPE_BF16 / MI_DTYPE_F16, round to nearest even; needs C % 32 == 0, img_n >= B * T and 16-byte alignment. */
+int mi_token_norm(int32_t mode, const float *x_dev, int32_t B, int32_t C, int32_t T, const float *w_dev, const float *b_dev,
+                  const float *pe_dev, const float *gstat_dev, float *y_dev, float *ostat_dev, void *img_dev, int64_t img_n,
+                  int32_t img_dtype, void *stream);
+
+/* LocalState attention core (demucs/demucs.py:182-216; hkernels.hip): qkc_dev (B, 3C + 16, ld) holds per item C query rows, C key
+ *   rows, C content rows and 16 decay-logit rows (4 heads x 4), row pitch ld >= T, ld % 4 == 0, 16-byte aligned; out_dev (B, C, ld_o),
+ *   ld_o >= T.  C = 192 / 384: the matrix-pipe kernels; any other C % 4 == 0 with C / 4 <= 16: the generic kernel.  Columns past T of
+ *   either tensor are neither read nor written. */
+int mi_local_attn(const float *qkc_dev, int32_t B, int32_t C, int32_t T, int32_t ld, float *out_dev, int32_t ld_o, void *stream);
+
+/* GroupNorm(G, Cin) (eps 1e-5) of x (B, Cin, in_len) with contiguous rows (in_pitch == in_len) followed by the fused apply of the
+ *   hdemucs_mmi layers, as HModel::group_norm runs it (row statistics, their finalisation, the apply kernel):
+ *     y[b][co][p] = res[b][co][p] + scale[co'] * act(n(co, p + off) [* sigmoid(n(co + Cout, p + off)) if glu]),  0 <= p < out_len,
+ *     n(c, q) = (x[b][c][q] - mean) * rstd * w[c'] + b[c'],  c' = c / chan_div,  act = erf-GELU if gelu,
+ *   Cout = Cin / 2 with glu, Cin without; scale_dev / res_dev may be NULL; res rows have pitch res_pitch, y rows pitch out_pitch
+ *   (columns past out_len are not written).  chan_div > 1: the Cin rows are (channel, row) pairs of a (Cin / chan_div, chan_div, len)
+ *   tensor and w, b, scale hold Cin / chan_div values.
+ *   stats_ws_dev: B * G * 64 doubles (32 slots of (sum, sum of squares) per statistics row), ZERO on entry and zero again on return
+ *   (the finalisation cleans what it read); stats_out_dev: B * G (mean, rstd) float pairs, written. */
+int mi_group_norm_apply(const float *x_dev, int32_t B, int32_t Cin, int32_t G, int32_t in_pitch, int32_t in_len, int32_t off,
+                        const float *w_dev, const float *b_dev, int32_t glu, int32_t gelu, const float *scale_dev, const float *res_dev,
+                        int32_t res_pitch, float *y_dev, int32_t Cout, int32_t out_len, int32_t out_pitch, int32_t chan_div,
+                        double *stats_ws_dev, float *stats_out_dev, void *stream);
+
+/* BLSTM framing (demucs/utils.py:20-35, demucs/demucs.py:38-44,51-64).  unfold: x (B, C, T) -> frames (B * F, C, W), frame f =
+ *   columns [f * S, f * S + W) of x, zero past T.  restitch: frames (B * F, C, W) -> y (B, C, T) = skip (B, C, T, may be NULL) + the
+ *   kept part of every frame (frame 0 columns [0, W - S / 2), the last one [S / 2, W), the others [S / 2, W - S / 2)) concatenated and
+ *   cut to T; needs W > 2 (S / 2) and T <= W + (F - 1) (W - 2 (S / 2)). */
+int mi_blstm_unfold(const float *x_dev, int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t S, float *frames_dev, void *stream);
+int mi_blstm_restitch(const float *frames_dev, int32_t B, int32_t C, int32_t T, int32_t F, int32_t W, int32_t S, const float *skip_dev,
+                      float *y_dev, void *stream);
+
+/* y (B, C, out_pitch)[.., i] = (x (B, C, L)[.., i] - norm[b].x) * norm[b].y for i < L and exactly 0 for L <= i < out_pitch;
+ *   norm_dev = B (mean, 1 / (eps + std)) float pairs: the waveform branch's input normalisation into pitched rows. */
+int mi_row_affine_pitch(const float *x_dev, int32_t B, int32_t C, int32_t L, int32_t out_pitch, const float *norm_dev, float *y_dev,
+                        void *stream);
 
 /* Debug aid: `hook(stream)` is called after every kernel launch the library makes (NULL switches it off).  Used by
  * tools/micro/poison_all.py to interleave a register / LDS poisoning kernel between the engine's kernels. */

@@ -67,37 +67,53 @@ def blstm(sd: Dict[str, Tensor], p: str, x: Tensor) -> Tensor:
         x = torch.cat([fw, bw], dim=-1)
     x = F.linear(x, sd[f"{p}.linear.weight"], sd[f"{p}.linear.bias"]).permute(1, 2, 0)    # (N, C, T)
     if framed:
-        fr = x.reshape(B, -1, C, width)
-        limit = stride // 2
-        parts = []
-        for k in range(nframes):
-            if k == 0:
-                parts.append(fr[:, k, :, :-limit])
-            elif k == nframes - 1:
-                parts.append(fr[:, k, :, limit:])
-            else:
-                parts.append(fr[:, k, :, limit:-limit])
-        x = torch.cat(parts, -1)[..., :T]
+        x = restitch(x.reshape(B, -1, C, width), stride, T)
     return x + y
+
+
+def restitch(fr: Tensor, stride: int, length: int) -> Tensor:
+    """demucs/demucs.py:51-64: frames (B, F, C, width) -> (B, C, length).  Every frame drops stride // 2 columns on the sides it
+    shares with a neighbour (the first keeps its start, the last its end); the kept parts are concatenated and cut."""
+    nframes = fr.shape[1]
+    limit = stride // 2
+    parts = []
+    for k in range(nframes):
+        if k == 0:
+            parts.append(fr[:, k, :, :-limit])
+        elif k == nframes - 1:
+            parts.append(fr[:, k, :, limit:])
+        else:
+            parts.append(fr[:, k, :, limit:-limit])
+    return torch.cat(parts, -1)[..., :length]
+
+
+def local_attention(q: Tensor, k: Tensor, content: Tensor, decay_logits: Tensor) -> Tensor:
+    """The attention core of LocalState (demucs/demucs.py:196-214): q, k, content (B, heads, dh, T), decay_logits
+    (B, heads, ndecay, T) -> (B, heads * dh, T).  score[key t, query s] = k_t . q_s / sqrt(dh) - |t - s| * sum_f (f + 1) *
+    (sigmoid(d_f[s]) / 2) / sqrt(ndecay), the diagonal FILLED with -100 (not removed), softmax over the keys."""
+    B, heads, dh, T = q.shape
+    ndecay = decay_logits.shape[2]
+    idx = torch.arange(T, dtype=q.dtype)
+    delta = idx[:, None] - idx[None, :]                           # left index keys, right index queries
+    dots = torch.einsum("bhct,bhcs->bhts", k, q) / dh ** 0.5
+    decays = torch.arange(1, ndecay + 1, dtype=q.dtype)
+    dq = torch.sigmoid(decay_logits) / 2
+    kernel = -decays.view(-1, 1, 1) * delta.abs() / ndecay ** 0.5
+    dots = dots + torch.einsum("fts,bhfs->bhts", kernel, dq)
+    dots = dots.masked_fill(torch.eye(T, dtype=torch.bool), -100)
+    w = torch.softmax(dots, dim=2)
+    return torch.einsum("bhts,bhct->bhcs", w, content).reshape(B, -1, T)
 
 
 def local_state(sd: Dict[str, Tensor], p: str, x: Tensor, heads: int = 4, ndecay: int = 4) -> Tensor:
     """LocalState(channels, heads=4, ndecay=4) (demucs/demucs.py:182-216): attention over keys t for every query s with
     a per-query decay penalty on |t - s| and the diagonal masked to -100."""
     B, C, T = x.shape
-    idx = torch.arange(T, dtype=x.dtype)
-    delta = idx[:, None] - idx[None, :]                           # left index keys, right index queries
     q = F.conv1d(x, sd[f"{p}.query.weight"], sd[f"{p}.query.bias"]).view(B, heads, -1, T)
     k = F.conv1d(x, sd[f"{p}.key.weight"], sd[f"{p}.key.bias"]).view(B, heads, -1, T)
-    dots = torch.einsum("bhct,bhcs->bhts", k, q) / k.shape[2] ** 0.5
-    decays = torch.arange(1, ndecay + 1, dtype=x.dtype)
-    dq = torch.sigmoid(F.conv1d(x, sd[f"{p}.query_decay.weight"], sd[f"{p}.query_decay.bias"]).view(B, heads, -1, T)) / 2
-    kernel = -decays.view(-1, 1, 1) * delta.abs() / ndecay ** 0.5
-    dots = dots + torch.einsum("fts,bhfs->bhts", kernel, dq)
-    dots = dots.masked_fill(torch.eye(T, dtype=torch.bool), -100)
-    w = torch.softmax(dots, dim=2)
+    dl = F.conv1d(x, sd[f"{p}.query_decay.weight"], sd[f"{p}.query_decay.bias"]).view(B, heads, ndecay, T)
     content = F.conv1d(x, sd[f"{p}.content.weight"], sd[f"{p}.content.bias"]).view(B, heads, -1, T)
-    res = torch.einsum("bhts,bhct->bhcs", w, content).reshape(B, -1, T)
+    res = local_attention(q, k, content, dl)
     return x + F.conv1d(res, sd[f"{p}.proj.weight"], sd[f"{p}.proj.bias"])
 
 

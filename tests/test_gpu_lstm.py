@@ -2,7 +2,9 @@
 through the C ABI (`mi_lstm_seq`): the persistent kernel the engine uses (lstm.hip: one launch for all time steps, hidden state
 exchanged between workgroups as tagged granules) and the one-launch-per-step chain, against torch's own nn.LSTM in float64 fed
 with the same pre-activations -- at the sizes the 44-second chunks produce (95 / 50 sequences of 200 steps), at ragged sizes
-(sequence counts that are not multiples of 16, one step, several launches of sequence tiles) and bit for bit against each other."""
+(sequence counts that are not multiples of 16, one step, several launches of sequence tiles) and bit for bit against each other.
+Mode 2 is the generic kernel the engine runs for every other hidden size (H <= 64: W_hh in LDS in its natural order), which no
+model but `demucs_unittest` (H = 16 / 32) reaches."""
 import ctypes as C
 
 import numpy as np
@@ -57,6 +59,29 @@ def test_persistent_recurrence_matches_float64_and_the_step_chain(H, N, W):
           f"{float((fast - slow).abs().max()):.2e}")
     assert err <= 2e-5 and float((slow.double() - want).abs().max()) <= 2e-5
     assert torch.equal(fast, slow)              # same products, same summation order: bit-identical
+
+
+@pytest.mark.parametrize("H,N,W", [(16, 5, 200), (32, 3, 37), (48, 2, 9), (1, 1, 1), (64, 2, 9)])
+def test_small_recurrence_matches_float64(H, N, W):
+    """`lstm_small_kernel` (mode 2): the unittest model's sizes, one that is no power of two, the smallest, and H = 64, the
+    launcher's upper bound, whose 66 816 bytes of dynamic LDS exceed 64 KiB (the launcher opts in for it)."""
+    gen = torch.Generator().manual_seed(H + 7 * N + W)
+    gx = torch.randn(N, 2, 4 * H, W, generator=gen)
+    whh = torch.randn(2, 4 * H, H, generator=gen) * (1.5 / H ** 0.5)
+    want = reference(gx, whh, H)
+    got = run(gx, whh, H, 2)
+    assert bool(torch.isfinite(got).all())
+    err = float((got.double() - want).abs().max())
+    print(f"lstm H={H} N={N} W={W}: generic kernel vs float64 {err:.2e}")
+    assert err <= 2e-5
+
+
+def test_small_recurrence_refuses_other_sizes():
+    gx, whh = torch.zeros(1, 2, 4 * 65, 1), torch.zeros(2, 4 * 65, 65)
+    with pytest.raises(_lib.EngineError):
+        run(gx, whh, 65, 2)
+    with pytest.raises(_lib.EngineError):
+        run(torch.zeros(1, 2, 4 * 16, 1), torch.zeros(2, 4 * 16, 16), 16, 0)        # modes 0 / 1 keep their sizes
 
 
 def test_back_to_back_calls_reuse_the_granule_buffers():
