@@ -23,7 +23,6 @@ bookkeeping around `model(padded)`), which is also what the CPU host-logic tests
 from __future__ import annotations
 
 import ctypes as C
-import os
 import random
 from concurrent.futures import CancelledError, ThreadPoolExecutor
 from threading import Lock
@@ -33,7 +32,7 @@ import torch
 from torch.nn import functional as F
 
 from . import _lib
-from .hdemucs import HDemucs, MIN_LENGTH as _HDEMUCS_MIN_LENGTH
+from .hdemucs import HDemucs, MIN_LENGTH as _HDEMUCS_MIN_LENGTH, tail_overlap_enabled
 from .htdemucs import HTDemucs
 
 __all__ = ["apply_model", "apply_model_many", "apply_model_stream", "apply_model_stream_group", "BagOfModels", "TensorChunk", "tensor_chunk", "center_trim", "DummyPoolExecutor"]
@@ -539,7 +538,7 @@ def ragged_split_accumulate(model: HDemucs, base: torch.Tensor, chunk_offset: in
         side = None
         n_main = len(offsets)
         if (on_start is None and on_end is None and len(offsets) >= 2 and lens[-1] < lens[-2]
-                and lens[-1] >= hdemucs_min_length() and os.environ.get("MI_NO_TAIL_OVERLAP") is None):
+                and lens[-1] >= hdemucs_min_length() and tail_overlap_enabled()):
             main_stream, side = torch.cuda.current_stream(dev), model.side_stream()
             side.wait_stream(main_stream)                 # `base` and whatever produced it
             with torch.cuda.stream(side):

@@ -33,15 +33,12 @@ struct Tables {
 static int get_tables(FftTables *out) {
     static Tables tb;
     if (!tb.ready) {
-        std::vector<float> win(4096), env(1024);
-        const std::vector<float2> tw = fft_twiddle_table();
-        for (int i = 0; i < 4096; ++i) win[i] = 0.5f - 0.5f * cosf((float)i * (float)(2.0 * M_PI / 4096.0));
-        for (int r = 0; r < 1024; ++r) { float e = 0.f; for (int j = 3; j >= 0; --j) e += win[r + 1024 * j] * win[r + 1024 * j]; env[r] = e; }
+        const FftHostTables h = fft_host_tables();
         float *dw, *de; float2 *dt;
-        MI_HIP(hipMalloc((void **)&dw, 4096 * 4)); MI_HIP(hipMalloc((void **)&dt, tw.size() * 8)); MI_HIP(hipMalloc((void **)&de, 1024 * 4));
-        MI_HIP(hipMemcpy(dw, win.data(), 4096 * 4, hipMemcpyHostToDevice));
-        MI_HIP(hipMemcpy(dt, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
-        MI_HIP(hipMemcpy(de, env.data(), 1024 * 4, hipMemcpyHostToDevice));
+        MI_HIP(hipMalloc((void **)&dw, 4096 * 4)); MI_HIP(hipMalloc((void **)&dt, h.twiddle.size() * 8)); MI_HIP(hipMalloc((void **)&de, 1024 * 4));
+        MI_HIP(hipMemcpy(dw, h.window.data(), 4096 * 4, hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(dt, h.twiddle.data(), h.twiddle.size() * 8, hipMemcpyHostToDevice));
+        MI_HIP(hipMemcpy(de, h.envelope.data(), 1024 * 4, hipMemcpyHostToDevice));
         tb.t = FftTables{dw, dt, de};
         tb.ready = true;
     }
@@ -529,7 +526,7 @@ int mi_lstm_seq(const float *gx_dev, const float *whh_host, int32_t N, int32_t H
         if (r == MI_OK) r = mode ? launch_lstm_persist(gx_dev, wd, N, H, W, out_dev, scratch, flag, st) : launch_lstm_seq(gx_dev, wd, N, H, W, out_dev, state, st);
         fail(hipStreamSynchronize(st), "hipStreamSynchronize");
         if (r == MI_OK && *(volatile unsigned *)flag) r = set_error(MI_EHIP, "mi_lstm_seq: the persistent kernel timed out waiting for its hidden-state exchange");
-        if (r == MI_OK && mode && getenv("MI_LSTM_DEBUG")) {
+        if (r == MI_OK && mode && switches().lstm_debug) {
                         unsigned dbg[16] = {};
             (void)hipMemcpy(dbg, (char *)scratch + lstm_persist_ctl_offset(), sizeof(dbg), hipMemcpyDeviceToHost);
             fprintf(stderr, "[lstm] H %d N %d W %d: block 0 / wave 1 spent %.1f us gathering h in %u poll passes (%.2f us, %.2f passes per step); "

@@ -479,7 +479,7 @@ int launch_dconv_row(const DConvRowArgs &a, int C, int rows, hipStream_t st) {
     // C = 96: 8-wave workgroups (102 KiB: one per CU, two waves per SIMD as the 200 registers allow)
     // MI_DCONV_ROW=lds selects the LDS-resident kernel (1.0x the algorithmic HBM bytes, but 1.87 ms per level-0 launch against
     // 1.19 ms: one wave per SIMD exposes every LDS / barrier latency, and statistics + GELU are repeated in all four waves)
-    static const bool lds_row = [] { const char *e = getenv("MI_DCONV_ROW"); return e && e[0] == 'l'; }();
+    const bool lds_row = switches().dconv_row_lds;
     if (C == 48 && lds_row && a.T <= kRowLdsT) {
         hipLaunchKernelGGL((dconv_rowlds_kernel<48, 6>), dim3(std::min(rows, cus)), dim3(256), 0, st, a, rows);
     } else if (C == 48) {

@@ -384,13 +384,7 @@ __global__ __launch_bounds__(256) void spec_transpose_strip_kernel(const float *
 }
 
 // bit 0: one-frame-per-workgroup STFT, bit 1: tile cac_transpose, bit 2: tile spec_transpose (mi_set_transpose_tiles(1) sets all three)
-static int transpose_tiles_from_env() {
-    const char *e = getenv("MI_TRANSPOSE_TILES");
-    if (!e) return 0;
-    const int v = atoi(e);
-    return v > 1 ? (v & 7) : 7;
-}
-int g_transpose_tiles = transpose_tiles_from_env();
+int g_transpose_tiles = switches().transpose_tiles;
 
 // ---------------------------------------------------------------------------------------------
 // iSTFT.  (1) y[b][S*4][2048][T] (decoder output, CaC) -> frame-major yt[b][s][t][4][2048] with
@@ -585,7 +579,7 @@ __global__ __launch_bounds__(256, 3) void istft_fused_kernel(const float *__rest
     }
 }
 
-int g_istft_fused = getenv("MI_ISTFT_SPLIT") == nullptr ? 1 : 0;
+int g_istft_fused = switches().istft_split ? 0 : 1;
 
 // ---------------------------------------------------------------------------------------------
 // host-side launchers

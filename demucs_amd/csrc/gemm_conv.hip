@@ -556,7 +556,7 @@ static int launch_cfg(const mi_conv_desc &d, bool dma, hipStream_t st) {
     // M groups (gemm_tile.h) halve this kernel's L2 misses on the 4 MiB weight matrices (TCC hit rate 48 % -> 74 %) but
     // the misses were Infinity-Cache hits: no time is gained and every activation tile is then fetched from HBM by
     // several XCDs (+10 % HBM bytes), so the fp32 path keeps one group unless MI_MGROUPS=1.
-    const int Gm = conv_switches().mgroups ? pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 4) : 1;
+    const int Gm = switches().mgroups ? pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 4) : 1;
     const unsigned grid = grouped_grid(MT, NT, Gm);
     if constexpr (PLAIN && BM == 128 && EPI == MI_EPI_LINEAR) {
         if (dma) {
@@ -616,19 +616,6 @@ const void *conv_zero_page() {
 // process-wide switch of the split-bf16 main loops (mi_set_split_bf16): 0 ignores every split weight image
 int g_split_bf16 = 1;
 
-const ConvSwitches &conv_switches() {
-    static const ConvSwitches s = {
-        getenv("MI_NO_DMA") != nullptr,
-        getenv("MI_NO_DMA_TAP") != nullptr,
-        getenv("MI_NO_DMA_ROWS") != nullptr,
-        getenv("MI_NO_DMA_DCONV") != nullptr,
-        getenv("MI_SMALL_TILE") ? atoi(getenv("MI_SMALL_TILE")) != 0 : true,
-        getenv("MI_MGROUPS") != nullptr,
-        getenv("MI_X6_MODE") ? atoi(getenv("MI_X6_MODE")) == 1 : false,
-    };
-    return s;
-}
-
 // Small batches: a layer whose 128-row tiles give fewer workgroups than the chip has CUs (B = 1: M = 512 and 2 688 tokens -> 84;
 // a k x k GLU conv: 6 x 21) runs on a smaller tile instead -- more workgroups at a lower per-workgroup rate.  Which tile that is
 // depends on the route (conv_route).  MI_SMALL_TILE=0: off
@@ -640,9 +627,9 @@ static bool under_filled(const mi_conv_desc &d) {
 // or, for a layer with a usable split weight image (`has_image`) when asked for it (`split`), the same shifted-run loader in front of the split-bf16 main loop (gemm_x6.hip
 // conv_tap_x6_kernel; GLU only)
 static bool dmatap_eligible(const mi_conv_desc &d, int tile, bool has_image, bool split = false) {
-    const bool off = conv_switches().no_dma_tap;
+    const bool off = switches().no_dma_tap;
     const int ld = d.x_ld ? d.x_ld : d.D2;
-    if (conv_switches().no_dma_dconv && d.epi == MI_EPI_BIAS_STATS) return false;      // A/B switch for the BIAS_STATS kind alone
+    if (switches().no_dma_dconv && d.epi == MI_EPI_BIAS_STATS) return false;      // A/B switch for the BIAS_STATS kind alone
     const int dil = d.tap_dil2 ? d.tap_dil2 : 1;
     // GLU: the decoders' 3 x 3 / k = 3 rewrite convs (96- / 128-row tiles); BIAS_STATS: the DConv blocks' dilated k = 3 convs (32- / 64-row)
     const bool kind = (d.epi == MI_EPI_GLU && (tile == 96 || tile == 128) && (d.ntaps == 9 || d.ntaps == 3) && dil == 1) ||
@@ -656,7 +643,7 @@ static bool dmatap_eligible(const mi_conv_desc &d, int tile, bool has_image, boo
 // tile, a 1 x 1 + GLU layer on a 128-row tile -- takes the same row loader in front of the split-bf16 main loop (gemm_x6.hip
 // conv_rows_x6_kernel); MI_NO_DMA_ROWS=1 turns both off
 static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain, bool has_image, bool split = false) {
-    const bool off = conv_switches().no_dma_rows;
+    const bool off = switches().no_dma_rows;
     const int ld = d.x_ld ? d.x_ld : d.D2;
     const int lf = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS | MI_FLAG_IMG | MI_FLAG_IMG4 | MI_FLAG_HEADS);
     // 1x1 + GLU / GroupNorm-GLU: 128-row tiles only -- the 96-row ones are the level-0 / 1 rewrites (K = 48 / 96: three or six K steps,
@@ -672,7 +659,7 @@ static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain, bool ha
 // The decision, top to bottom; the first test that holds wins (kernels.h ConvRoute)
 ConvRoute conv_route(const mi_conv_desc &d) {
     const bool image = d.wx && g_split_bf16;                // mi_set_split_bf16(0): native fp32 MFMA kernels only
-    const ConvSwitches &sw = conv_switches();
+    const Switches &sw = switches();
     const int tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M);
     // plain fast path: a 1x1 / linear layer whose gather is the identity
     const int64_t P = (int64_t)d.O1 * d.O2;

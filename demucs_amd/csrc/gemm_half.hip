@@ -505,7 +505,7 @@ static int launch_conv_half_t(const mi_conv_desc &d, int tile, bool plain, hipSt
         // residual epilogues (out_proj, lin2: 340 MB of float32 residual read + output write per launch) keep the 256 x 128 tile
         // at two workgroups per CU, whose epilogues overlap each other's main loops: measured 9.63 ms against 9.79 for the
         // linear class with the 256 x 256 tile here (MI_IMG256=1: A/B switch)
-        static const bool img256 = [] { const char *e = getenv("MI_IMG256"); return e && atoi(e) != 0; }();
+        const bool img256 = switches().img256;
         if (f == (MI_FLAG_SCALE | MI_FLAG_RES)) {
             if (img256 && d.Mpad % 256 == 0) return launch_half_img256<HT, MI_FLAG_SCALE | MI_FLAG_RES>(d, st);
             return d.Mpad % 256 == 0 ? launch_half_img<HT, 4, MI_FLAG_SCALE | MI_FLAG_RES>(d, st) : launch_half_img<HT, 2, MI_FLAG_SCALE | MI_FLAG_RES>(d, st);
@@ -549,7 +549,7 @@ int launch_conv_half(const mi_conv_desc &d, int tile, bool plain, hipStream_t st
     MI_REQUIRE(d.wh && ((uintptr_t)d.wh & 15) == 0, "conv half: weight image missing or misaligned");
     MI_REQUIRE(plain || d.ktab_len >= (d.Kpad + HK - 1) / HK * HK, "conv half: gather table has %d entries, the K step of %d needs %d",
                d.ktab_len, HK, (d.Kpad + HK - 1) / HK * HK);
-    static const bool wide = [] { const char *e = getenv("MI_HALF_TILE256"); return !e || atoi(e) != 0; }();
+    const bool wide = switches().half_tile256;
     if (wide && plain && tile == 128 && d.epi == MI_EPI_LINEAR && d.Mpad % 256 == 0) tile = 256;
     if (d.half == MI_DTYPE_BF16) return launch_conv_half_t<MI_DTYPE_BF16>(d, tile, plain, st);
     if (d.half == MI_DTYPE_F16) return launch_conv_half_t<MI_DTYPE_F16>(d, tile, plain, st);

@@ -34,6 +34,14 @@ struct HGeo {                   // everything that depends on the input length
 };
 
 struct HModel : Model {
+    // As Model::plan: decided once, at the end of hinit, from cfg.dtype, switches() and what was packed and allocated
+    struct HPlan {
+        bool deep_tap = false;      // half modes: the k = 3 convs of layers 4 / 5 and decoders 0 / 1 read tap images (where they have the weights)
+        bool enc_img = false;       // half modes: encoder levels 1-3 read phase-split images of the previous level's output
+        bool tap_img = false;       // half modes: the tensors between decoder layers 2-5 exist only as operand images
+        bool last_tap = false;      // ... the outermost transposed conv's input included
+        bool two_streams = false;   // the waveform branch may run on the side stream (with mi_set_two_streams)
+    } hplan;
     int Lmax = 0, Tmax = 0;
     int hCh[7] = {};             // layer widths: channels << level (48 ... 3 072 for hdemucs_mmi; 4 ... 256 for demucs_unittest)
     HEncW henc[6], htenc[5];

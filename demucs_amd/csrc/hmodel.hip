@@ -34,12 +34,6 @@ HModel::~HModel() {
     if (lstm_timeout) (void)hipHostFree(lstm_timeout);
 }
 
-// MI_LSTM_STEPS=1: the round-3 recurrence (one launch per time step, hkernels.hip) instead of the persistent kernel of lstm.hip
-static bool lstm_step_chain() {
-    static const bool on = getenv("MI_LSTM_STEPS") != nullptr && atoi(getenv("MI_LSTM_STEPS")) != 0;
-    return on;
-}
-
 int HModel::load_norm(const WeightTable &wt, const std::string &name, int C, float **w, float **b) {
     const float *pw, *pb;
     MI_TRY(wt.get(name + ".weight", C, &pw)); MI_TRY(wt.get(name + ".bias", C, &pb));
@@ -122,15 +116,7 @@ int HModel::hinit(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         for (int i = 0; i < 7; ++i) hCh[i] = (int)c0 << i;
     }
     const int C0 = hCh[0], C3 = hCh[3], C4 = hCh[4], C5 = hCh[5], C6 = hCh[6];
-    {   // FFT tables (as in Model::init)
-        std::vector<float> win(4096), env(1024);
-        const std::vector<float2> tw = fft_twiddle_table();
-        for (int i = 0; i < 4096; ++i) win[i] = 0.5f - 0.5f * cosf((float)i * (float)(2.0 * M_PI / 4096.0));
-        for (int r = 0; r < 1024; ++r) { float e = 0.f; for (int j = 3; j >= 0; --j) e += win[r + 1024 * j] * win[r + 1024 * j]; env[r] = e; }
-        float *dw, *de; float2 *dt;
-        MI_TRY(upload(win, &dw)); MI_TRY(upload(tw, &dt)); MI_TRY(upload(env, &de));
-        fft = FftTables{dw, dt, de};
-    }
+    MI_TRY(upload_fft_tables());
     const float *w, *b, *rw, *rb;
     for (int i = 0; i < 4; ++i) {                         // layers 0-3: both branches, htdemucs-shaped (DConv hidden C/4)
         const int Cin = i ? hCh[i - 1] : 4, Cint = i ? hCh[i - 1] : 2, C = hCh[i];
@@ -268,6 +254,18 @@ int HModel::hinit(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
     MI_TRY(halloc((void **)&x_st1t, max_rows * sizeof(float2))); MI_TRY(halloc((void **)&x_st2t, max_rows * sizeof(float2)));
     MI_TRY(halloc((void **)&x_nf, B * sizeof(float2))); MI_TRY(halloc((void **)&x_df, B * sizeof(float2)));
     MI_TRY(halloc((void **)&x_nt, B * sizeof(float2))); MI_TRY(halloc((void **)&x_dt, B * sizeof(float2)));
+    {   // the forward's plan
+        const Switches &sw = switches();
+        const bool half = cfg.dtype != MI_DTYPE_F32;
+        hplan.deep_tap = half && !sw.h_no_deep_tap;
+        hplan.enc_img = half && x_eimg[0][0];
+        for (int i = 1; i < 4 && hplan.enc_img; ++i) hplan.enc_img = henc[i].conv.wtap && htenc[i].conv.wtap && hCh[i - 1] % 16 == 0;
+        hplan.tap_img = half && x_gimg;
+        for (int j = 2; j < 6 && hplan.tap_img; ++j)        // every level has its tap-ordered weights (widths that are multiples of 8)
+            hplan.tap_img = hdec[j].rewrite.wtap && htdec[j - 1].rewrite.wtap && hdec[j].convtr.wtap && htdec[j - 1].convtr.wtap;
+        hplan.last_tap = !sw.h_no_last_tap;
+        hplan.two_streams = !sw.h_one_stream;
+    }
     MI_HIP(hipDeviceSynchronize());
     return MI_OK;
 }
@@ -357,7 +355,8 @@ int HModel::group_norm(const float *x, int B, int C, int G, int in_pitch, int in
 
 int HModel::run_lstm(const float *gx, const float *whh, int N, int H, int W, float *out, hipStream_t st) {
     if (H != 192 && H != 384) return launch_lstm_small(gx, whh, N, H, W, out, st);
-    if (lstm_step_chain()) return launch_lstm_seq(gx, whh, N, H, W, out, x_lstm, st);
+    // MI_LSTM_STEPS=1: the round-3 recurrence (one launch per time step, hkernels.hip) instead of the persistent kernel of lstm.hip
+    if (switches().lstm_steps) return launch_lstm_seq(gx, whh, N, H, W, out, x_lstm, st);
     return launch_lstm_persist(gx, whh, N, H, W, out, x_lstm_scratch, lstm_timeout, st);
 }
 
@@ -367,8 +366,6 @@ int HModel::run_deep(HGeo &g, HEncW &e, int C, int Tn, int B, float *x, float *t
     const Geo gt{B, 1, Tn, 0};
     // half modes: the k = 3 convs of layers 4 / 5 and of decoders 0 / 1 (K up to 4 608) on the tap-DMA route of gemm_tap.hip, their
     // float32 inputs converted to operand images by one streaming pass each (MI_H_NO_DEEP_TAP=1: table-driven gathers)
-    static const bool no_deep_tap = getenv("MI_H_NO_DEEP_TAP") != nullptr;
-    const bool deep_tap = cfg.dtype != MI_DTYPE_F32 && !no_deep_tap;
     float *src = x, *dst = tmp;
     for (int d = 0; d < 2; ++d) {
         const HDeepLayerW &l = e.deep[d];
@@ -377,7 +374,7 @@ int HModel::run_deep(HGeo &g, HEncW &e, int C, int Tn, int B, float *x, float *t
         MI_TRY(ktab(g, Gather{C, 1, 3, 1, dil, 0, dil, (int64_t)Tn, Tn}, l.conv3.Kpad, &k));
         mi_conv_desc c3 = base_desc(l.conv3, k, src, (int64_t)C * Tn, gt);
         c3.epi = MI_EPI_LINEAR; c3.y = x_dh; c3.y_bstride = (int64_t)H * Tn; c3.y_cstride = Tn;
-        if (deep_tap && l.conv3.wtap) {          // K = 3 C = 2 304 / 4 608: the taps of a 16-bit image of the layer input, by LDS-DMA
+        if (hplan.deep_tap && l.conv3.wtap) {          // K = 3 C = 2 304 / 4 608: the taps of a 16-bit image of the layer input, by LDS-DMA
             MI_TRY(launch_f32_to_image(src, B, C, Tn, cfg.dtype, x_zB, st));
             c3.xh = x_zB; c3.xh_n = (int64_t)B * Tn; c3.wtap = l.conv3.wtap; c3.ntaps = 3; c3.tap_k2 = 3; c3.tap_pad2 = dil; c3.tap_dil2 = dil;
         }
@@ -395,16 +392,11 @@ int HModel::run_deep(HGeo &g, HEncW &e, int C, int Tn, int B, float *x, float *t
             mi_conv_desc gi = base_desc(l.ih[layer], k, layer ? x_o0 : xin, (int64_t)Kin * W, gs);
             gi.plain = 1; gi.epi = MI_EPI_LINEAR; gi.y = x_gx; gi.y_bstride = (int64_t)8 * H * W; gi.y_cstride = W;
             MI_TRY(conv(gi, st));
-            if (prof.on) {         // the LSTM recurrence: W dependent launches timed as one span (bench.py's latency roofline of the mode)
-                const int cls = 103;         // own row: 101 is Model::run_dconv's dconv_row_kernel
-                Profiler::Pending p{cls, prof.get(), prof.get(), (double)W * 2.0 * 8.0 * H * H * N, (double)W * (8.0 * H * H + 8.0 * H * N) * 4.0, W};
-                MI_HIP(hipEventRecord(p.a, st));
-                MI_TRY(run_lstm(x_gx, l.whhT[layer], N, H, W, layer ? x_o1 : x_o0, st));
-                MI_HIP(hipEventRecord(p.b, st));
-                prof.pending.push_back(p);
-                snprintf(prof.rows[cls].name, sizeof(prof.rows[cls].name), lstm_step_chain() ? "lstm_step_kernel" : "lstm_persist_kernel");
-            } else
-            MI_TRY(run_lstm(x_gx, l.whhT[layer], N, H, W, layer ? x_o1 : x_o0, st));
+            // the LSTM recurrence: W dependent launches timed as one span (bench.py's latency roofline of the mode); row 103 is its own
+            // (101 is Model::run_dconv's dconv_row_kernel)
+            MI_TRY(prof.timed(103, switches().lstm_steps ? "lstm_step_kernel" : "lstm_persist_kernel", (double)W * 2.0 * 8.0 * H * H * N,
+                              (double)W * (8.0 * H * H + 8.0 * H * N) * 4.0, st,
+                              [&] { return run_lstm(x_gx, l.whhT[layer], N, H, W, layer ? x_o1 : x_o0, st); }, W));
         }
         MI_TRY(ktab(g, Gather{2 * H, 1, 1, 1, 1, 0, 0, (int64_t)W, W}, l.lin.Kpad, &k));
         mi_conv_desc li = base_desc(l.lin, k, x_o1, (int64_t)2 * H * W, gs);
@@ -475,8 +467,7 @@ int HModel::hforward_impl(const float *mix, float *out, int B, int L, hipStream_
     // track): the forward was paced by 1 600 dependent LSTM step launches that more concurrent kernels only lengthened.  With the
     // recurrence in one persistent launch per sequence (lstm.hip) the side stream pays: 37.8-38.1 against 39.3-39.5 ms.
     // MI_H_ONE_STREAM=1 keeps everything on the caller's stream (A/B, profiling).
-    static const bool h_two = getenv("MI_H_ONE_STREAM") == nullptr;
-    const bool two = h_two && g_two_streams && side_streams() == MI_OK;
+    const bool two = hplan.two_streams && g_two_streams && side_streams() == MI_OK;
     hipStream_t stt = two ? side_st : st;
     auto fork = [&]() -> int {
         if (!two) return MI_OK;
@@ -503,8 +494,7 @@ int HModel::hforward_impl(const float *mix, float *out, int B, int L, hipStream_
     // the 1x1 + GLU epilogue beside the float32 skip tensor (gemm_conv.h MI_FLAG_IMG4); the conv is then a stride-1 two-tap conv
     // whose taps gemm_tap.hip fetches by LDS-DMA.  The image slots no epilogue writes are the conv's zero padding: they depend
     // on the geometry (length, batch), so the images are re-zeroed when it changes.
-    bool encimg = cfg.dtype != MI_DTYPE_F32 && x_eimg[0][0];
-    for (int i = 1; i < 4 && encimg; ++i) encimg = henc[i].conv.wtap && htenc[i].conv.wtap && hCh[i - 1] % 16 == 0;
+    const bool encimg = hplan.enc_img;
     if (encimg && (eimg_L != L || eimg_B != B)) {
         for (int br = 0; br < 2; ++br)
             for (int i = 0; i < 3; ++i) MI_HIP(hipMemsetAsync(x_eimg[br][i], 0, x_eimg_floats[br][i] * sizeof(float), st));
@@ -609,8 +599,7 @@ int HModel::hforward_impl(const float *mix, float *out, int B, int L, hipStream_
         MI_TRY(ktab(g, Gather{C5, 1, 3, 1, 1, 0, 1, (int64_t)T5, T5}, hdec[0].rewrite.Kpad, &k));
         mi_conv_desc r = base_desc(hdec[0].rewrite, k, x_skip[5], (int64_t)C5 * T5, Geo{B, 1, T5, 0});
         r.epi = MI_EPI_LINEAR; r.y = x_zA; r.y_bstride = (int64_t)C6 * T5; r.y_cstride = T5;
-        static const bool no_deep_tap = getenv("MI_H_NO_DEEP_TAP") != nullptr;
-        if (cfg.dtype != MI_DTYPE_F32 && !no_deep_tap && hdec[0].rewrite.wtap) {
+        if (hplan.deep_tap && hdec[0].rewrite.wtap) {
             MI_TRY(launch_f32_to_image(x_skip[5], B, C5, T5, cfg.dtype, x_zB, st));
             r.xh = x_zB; r.xh_n = (int64_t)B * T5; r.wtap = hdec[0].rewrite.wtap; r.ntaps = 3; r.tap_k2 = 3; r.tap_pad2 = 1;
         }
@@ -631,8 +620,7 @@ int HModel::hforward_impl(const float *mix, float *out, int B, int L, hipStream_
         MI_TRY(ktab(g, Gather{C4, 1, 3, 1, 1, 0, 1, (int64_t)T, T}, hdec[1].rewrite.Kpad, &k));
         mi_conv_desc r = base_desc(hdec[1].rewrite, k, x_dec[0], (int64_t)C4 * T, Geo{B, 1, T, 0});
         r.epi = MI_EPI_LINEAR; r.y = x_zA; r.y_bstride = (int64_t)C5 * T; r.y_cstride = T;
-        static const bool no_deep_tap = getenv("MI_H_NO_DEEP_TAP") != nullptr;
-        if (cfg.dtype != MI_DTYPE_F32 && !no_deep_tap && hdec[1].rewrite.wtap) {
+        if (hplan.deep_tap && hdec[1].rewrite.wtap) {
             MI_TRY(launch_f32_to_image(x_dec[0], B, C4, T, cfg.dtype, x_zB, st));
             r.xh = x_zB; r.xh_n = (int64_t)B * T; r.wtap = hdec[1].rewrite.wtap; r.ntaps = 3; r.tap_k2 = 3; r.tap_pad2 = 1;
         }
@@ -661,12 +649,10 @@ int HModel::hforward_impl(const float *mix, float *out, int B, int L, hipStream_
     // previous transposed conv's GELU + skip epilogue; for the first layer converted from GroupNorm's float32 output), and the
     // GLU output (written by the rewrite conv's epilogue, MI_FLAG_IMG) -- and both convs gather their taps by LDS-DMA
     // (gemm_tap.hip) instead of walking a table over float32 tensors.  MI_NO_TAP_IMAGE=1 restores the table-driven route.
-    bool tapimg = cfg.dtype != MI_DTYPE_F32 && x_gimg;
-    for (int j = 2; j < 6 && tapimg; ++j)        // every level has its tap-ordered weights (widths that are multiples of 8)
-        tapimg = hdec[j].rewrite.wtap && htdec[j - 1].rewrite.wtap && hdec[j].convtr.wtap && htdec[j - 1].convtr.wtap;
+    const bool tapimg = hplan.tap_img;
     // the outermost transposed conv (K = 96, bound by its output) on the image route too: no conversion pass is needed here (the GLU
     // epilogue writes the image), 38.6-38.9 against 39.3-39.5 ms; MI_H_NO_LAST_TAP=1: table-driven gather over float32
-    static const bool last_tap = getenv("MI_H_NO_LAST_TAP") == nullptr;
+    const bool last_tap = hplan.last_tap;
     MI_TRY(fork());
     if (tapimg) {
         MI_TRY(launch_f32_to_image(x_dec[1], B, C3, (int64_t)8 * Tp, cfg.dtype, x_b, st));

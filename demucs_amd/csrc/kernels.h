@@ -11,15 +11,26 @@ namespace mi {
 
 struct FftTables {
     const float *window;    // [4096] periodic Hann, float32 like th.hann_window
-    const float2 *twiddle;  // [2048] fft_twiddle_table(): exp(-2 pi i n / 4096)
+    const float2 *twiddle;  // [2048] exp(-2 pi i n / 4096)
     const float *envelope;  // [1024] sum_j window^2[r + 1024 j]
 };
-// W^n = exp(-2 pi i n / 4096) for n < 2048 (W^(n + 2048) = -W^n), float32 of the float64 value: one builder for both engines and the
-// handle-free entry points
-static inline std::vector<float2> fft_twiddle_table() {
-    std::vector<float2> tw(2048);
-    for (int i = 0; i < 2048; ++i) { const double a = -2.0 * M_PI * i / 4096.0; tw[i] = make_float2((float)cos(a), (float)sin(a)); }
-    return tw;
+// The three tables on the host, one builder for both engines and the handle-free entry points (each uploads with its own
+// allocator): the window and its overlap envelope in float32 arithmetic like th.hann_window (spec.py:19,41), the envelope summed in
+// ascending frame order; W^n = exp(-2 pi i n / 4096) for n < 2048 (W^(n + 2048) = -W^n) as the float32 of the float64 value
+struct FftHostTables {
+    std::vector<float> window, envelope;
+    std::vector<float2> twiddle;
+};
+static inline FftHostTables fft_host_tables() {
+    FftHostTables t{std::vector<float>(4096), std::vector<float>(1024), std::vector<float2>(2048)};
+    for (int i = 0; i < 4096; ++i) t.window[i] = 0.5f - 0.5f * cosf((float)i * (float)(2.0 * M_PI / 4096.0));
+    for (int r = 0; r < 1024; ++r) {
+        float e = 0.f;
+        for (int j = 3; j >= 0; --j) e += t.window[r + 1024 * j] * t.window[r + 1024 * j];
+        t.envelope[r] = e;
+    }
+    for (int i = 0; i < 2048; ++i) { const double a = -2.0 * M_PI * i / 4096.0; t.twiddle[i] = make_float2((float)cos(a), (float)sin(a)); }
+    return t;
 }
 
 // fft.hip
@@ -98,8 +109,10 @@ extern int g_split_bf16;     // 0 (mi_set_split_bf16): native fp32 MFMA kernels 
 // (routes 4, 7, 8: 64 under a 128-row layer = the 64-row tile that reads the 128-row image); plain: the 1x1 / linear fast path
 struct ConvRoute { int route; int tile; bool plain; };
 ConvRoute conv_route(const mi_conv_desc &d);
-// the environment switches of the float32 conv kernels, read once
-struct ConvSwitches {
+// Every environment switch of the engine (INTEGRATION.md has the table), parsed once, when the library is loaded (switches.hip:
+// the only file that looks at the environment).  The values are the parsed meanings, not the strings.
+struct Switches {
+    // ---- the float32 conv kernels (conv_route) ----
     bool no_dma;            // MI_NO_DMA: plain linear layers on the register-staged loader
     bool no_dma_tap;        // MI_NO_DMA_TAP: no shifted-run DMA taps (routes 2 and 7)
     bool no_dma_rows;       // MI_NO_DMA_ROWS: no DMA row taps (routes 3 and 8)
@@ -107,8 +120,32 @@ struct ConvSwitches {
     bool small_tile;        // MI_SMALL_TILE (default 1): smaller tiles for under-filled 128-row layers
     bool mgroups;           // MI_MGROUPS: M-grouped tile order in the native fp32 kernels
     bool x6_plain_only;     // MI_X6_MODE=1: the split-bf16 loop for plain layers only
+    // ---- packing and schedule of both engines ----
+    int x6_scope;           // MI_X6: which layers get a split-bf16 weight image: unset 1 = the default scope (Model::pack_split), 0 = none, anything else 2 = every layer
+    bool no_tap_image;      // MI_NO_TAP_IMAGE: half modes, no tap-ordered weight images: the k x k convs walk gather tables over float32 tensors
+    bool no_enc_image;      // MI_NO_ENC_IMAGE: half modes, no phase-split images in front of the strided encoder convs
+    bool no_dconv_time;     // MI_NO_DCONV_TIME: the time branch's DConv blocks on the implicit-GEMM route, not dconv_time.hip
+    bool no_lin2_stats;     // MI_NO_LIN2_STATS: norm_out's statistics by a separate pass, not by lin2's epilogue
+    bool no_ffn_image;      // MI_NO_FFN_IMAGE: half modes, attention output and FFN hidden tensor as float32, not as operand images
+    bool no_qkv_heads;      // MI_NO_QKV_HEADS: half modes, Q / K / V as float32 tensors, not as per-head 16-bit ones
+    bool no_input_image;    // MI_NO_INPUT_IMAGE: half modes, the projections read their float32 inputs, not operand images of them
+    bool one_stream;        // MI_ONE_STREAM: HTDemucs, both branches on the caller's stream
+    bool debug_sync;        // MI_DEBUG_SYNC: HTDemucs synchronises after every stage and names it on stderr (one stream)
+    int side_prio;          // MI_SIDE_PRIO: the side stream's priority: unset 0 = normal, first letter l -1 = the device's least, else 1 = its greatest
+    bool h_no_deep_tap;     // MI_H_NO_DEEP_TAP: HDemucs half modes, the k = 3 convs of layers 4 / 5 and decoders 0 / 1 on table-driven gathers
+    bool h_no_last_tap;     // MI_H_NO_LAST_TAP: HDemucs half modes, the outermost transposed conv on the table-driven gather over float32
+    bool h_one_stream;      // MI_H_ONE_STREAM: HDemucs, both branches on the caller's stream
+    bool lstm_steps;        // MI_LSTM_STEPS (a non-zero number): one launch per LSTM time step, not the persistent kernel
+    // ---- single kernels ----
+    bool lstm_write_through;    // MI_LSTM_WRITE_THROUGH: the persistent LSTM kernel never uses the same-XCD plain-store path
+    bool lstm_debug;        // MI_LSTM_DEBUG: mi_lstm_seq prints the persistent kernel's cycle counters
+    int transpose_tiles;    // MI_TRANSPOSE_TILES: initial g_transpose_tiles mask (bit 0 STFT frames, 1 cac_transpose, 2 spec_transpose): unset 0, a number above 1 its low three bits, anything else 7
+    bool istft_split;       // MI_ISTFT_SPLIT: g_istft_fused starts at 0 (inverse transform and overlap-add as two kernels)
+    bool dconv_row_lds;     // MI_DCONV_ROW (first letter l): the LDS-resident DConv row kernel for C = 48
+    bool img256;            // MI_IMG256 (a non-zero number): the 256 x 256 tile for the half modes' residual epilogues on image inputs
+    bool half_tile256;      // MI_HALF_TILE256 (default 1): the half modes' 256-row tile for plain linear layers
 };
-const ConvSwitches &conv_switches();
+const Switches &switches();
 // gemm_x6.hip: `tile` as decided by conv_route, `image_tile` the tile the split image was packed for
 bool conv_x6_supported(int tile);
 int launch_conv_x6(const mi_conv_desc &d, int tile, int image_tile, bool plain, hipStream_t st);

@@ -302,7 +302,7 @@ static int launch_one(const float *gx, const float *whh, float *out, unsigned *h
                       int n0, int G, hipStream_t st) {
     constexpr int members = H / (4 * MT);
     const int gpx = ceil_div(G, 8);
-    static const int force_wt = getenv("MI_LSTM_WRITE_THROUGH") != nullptr;      // A/B: never use the same-XCD plain-store path
+    const int force_wt = switches().lstm_write_through;      // A/B: never use the same-XCD plain-store path
     hipLaunchKernelGGL((lstm_persist_kernel<H, MT>), dim3(8 * gpx * members), dim3(256), 0, st, gx, whh, out, hx, xcc, ctl, ctl_host, N, W, n0, G, gpx,
                        force_wt);
     MI_CHECK_LAUNCH();

@@ -73,6 +73,19 @@ struct Profiler {
     std::vector<hipEvent_t> pool;
     ProfRow rows[128];
     hipEvent_t get();
+    // Runs fn (one launch, or `launches` of them timed as one span) between two events on its stream and books the span under
+    // row `cls`; `name`, when given, names the row.  While the profiler is off: fn alone.
+    template <typename Fn>
+    int timed(int cls, const char *name, double flops, double bytes, hipStream_t st, Fn &&fn, long long launches = 1) {
+        if (!on) return fn();
+        Pending p{cls, get(), get(), flops, bytes, launches};
+        MI_HIP(hipEventRecord(p.a, st));
+        const int r = fn();
+        MI_HIP(hipEventRecord(p.b, st));
+        pending.push_back(p);
+        if (name) snprintf(rows[cls].name, sizeof(rows[cls].name), "%s", name);
+        return r;
+    }
     void begin();
     int end(hipStream_t st);
     ~Profiler();
@@ -113,8 +126,27 @@ struct Workspace : WorkspacePtrs {
     ~Workspace();
 };
 
+// Which layers get a split-bf16 weight image (pack_split), stated by the call that packs the layer.  MI_X6=0 gives none of them
+// one, MI_X6=1 all of them; in between (the default) the float32 engine gives one to:
+enum SplitScope {
+    SPLIT_OPT_IN,      // no layer of this kind
+    SPLIT_DEFAULT,     // the transformer linears and the decoders' 3 x 3 / k = 3 rewrite convs
+    SPLIT_ROWS,        // the row-tap layers of the DMA row route: like SPLIT_DEFAULT, unless MI_NO_DMA_ROWS keeps them on the table routes
+};
+
 struct Model : WorkspacePtrs {
     mi_config cfg{};
+    // What a forward of this handle writes as 16-bit images and which statistics route it takes: decided once, at the end of init,
+    // from cfg.dtype, switches() and what was packed and allocated; the forward only reads it.  All false in the float32 mode
+    // except lin2_stats.
+    struct Plan {
+        bool ffn_img = false;      // attention output and FFN hidden tensor exist only as the next product's operand image
+        bool qkv_heads = false;    // Q / K / V exist only as per-head 16-bit tensors (attention_heads.hip)
+        bool in_img = false;       // the layer inputs and x1 exist as operand images too: the in-projections and lin1 read those
+        bool lin2_stats = false;   // norm_out's statistics come from lin2's epilogue
+        bool tap_img = false;      // the decoder inputs exist only as their rewrite conv's operand image
+        bool enc_img[2][4] = {};   // [branch][level i]: encoder conv i reads the phase-split image of level i - 1's output
+    } plan;
     Profiler prof;
     int conv(const mi_conv_desc &d, hipStream_t st);
     int attn(const float *q, const float *k, const float *v, float *o, int B, int Tq, int Tk, int64_t q_bs, int64_t kv_bs,
@@ -150,27 +182,25 @@ struct Model : WorkspacePtrs {
    protected:
     int dev_alloc(void **p, size_t bytes);
     template <typename T> int upload(const std::vector<T> &h, T **dptr);
-    int pack_split(PackedConv *pc);
+    int upload_fft_tables();         // fills `fft`
+    int pack_split(PackedConv *pc, SplitScope scope);
     int pack_half(PackedConv *pc);
-    int pack_conv(const float *W, const float *bias, int M, int K, bool glu, PackedConv *pc, int ntaps = 0);
+    int pack_conv(const float *W, const float *bias, int M, int K, bool glu, PackedConv *pc, int ntaps = 0, SplitScope scope = SPLIT_OPT_IN);
     int pack_tap(PackedConv *pc, int ntaps);
     int pack_enc_tap(const float *W, int Cin, PackedConv *pc);
-    int pack_convtr(const float *W, const float *bias, int Cin, int Cout, PackedConv *pc, int stride = 4);
+    int pack_convtr(const float *W, const float *bias, int Cin, int Cout, PackedConv *pc, int stride = 4, SplitScope scope = SPLIT_OPT_IN);
     int pack_vec(const float *v, int n, int npad, bool glu, float **out);
     int pack_linear_ln(const float *W, const float *bias, const float *ln_w, const float *ln_b, int M, int K, PackedConv *pc,
-                       float **c1);
+                       float **c1, SplitScope scope);
     int make_ktab(const Gather &g, int Kpad, mi_ktab_entry **out);
     int load_dconv(const WeightTable &wt, const std::string &prefix, int C, int64_t chan_stride, int D2, bool freq, DConvW *dw, int comp = 8);
     int alloc_workspace();
     int fill_workspace(Workspace &w);
-    bool split_linears = false;  // set while the transformer linears are packed: pack_split's default scope
-    bool split_taps = false;     // ... and while the decoders' 3 x 3 / k = 3 rewrite convs are packed
-    bool split_rows = false;     // ... and while the frequency branch's encoder convs (levels 1-3), transposed convs (j = 0-2) and 128-row 1 x 1 + GLU rewrites are packed
     bool dconv_tap_dma = false;  // run_dconv may state the k = 3 convs' geometry (DMA tap route): only when x / tmp carry 128 bytes of slack
     int run_dconv(const DConvW &w, int C, const Geo &g, float *x, float *tmp, float *hidden, double *stats, float2 *st1, float2 *st2,
                   hipStream_t st, double *gram2 = nullptr, size_t gram2_cap = 0);
     int run_tr_layer(int br, int k, int B, const float *x, const float2 *xstat, const float *other, const float2 *ostat, float *out,
-                     float2 *outstat, hipStream_t st, const void *ximg = nullptr, const void *oimg = nullptr, void *outimg = nullptr);
+                     float2 *outstat, hipStream_t st, const void *ximg, const void *oimg, void *outimg);
 };
 
 }  // namespace mi

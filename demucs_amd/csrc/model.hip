@@ -42,6 +42,14 @@ int Model::upload(const std::vector<T> &h, T **dptr) {
     return MI_OK;
 }
 
+int Model::upload_fft_tables() {
+    const FftHostTables h = fft_host_tables();
+    float *dw, *de; float2 *dt;
+    MI_TRY(upload(h.window, &dw)); MI_TRY(upload(h.twiddle, &dt)); MI_TRY(upload(h.envelope, &de));
+    fft = FftTables{dw, dt, de};
+    return MI_OK;
+}
+
 Model::~Model() {
     for (void *p : allocs) (void)hipFree(p);
     if (side_st) (void)hipStreamDestroy(side_st);
@@ -57,11 +65,11 @@ int g_two_streams = 1;
 int Model::side_streams() {
     if (side_st) return MI_OK;
     // MI_SIDE_PRIO=low / high: the side stream at the device's least / greatest priority (A/B switch; default: normal priority)
-    const char *prio = getenv("MI_SIDE_PRIO");
+    const int prio = switches().side_prio;
     if (prio) {
         int least = 0, greatest = 0;
         MI_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        MI_HIP(hipStreamCreateWithPriority(&side_st, hipStreamNonBlocking, prio[0] == 'l' ? least : greatest));
+        MI_HIP(hipStreamCreateWithPriority(&side_st, hipStreamNonBlocking, prio < 0 ? least : greatest));
     } else
         MI_HIP(hipStreamCreateWithFlags(&side_st, hipStreamNonBlocking));
     MI_HIP(hipEventCreateWithFlags(&ev_main, hipEventDisableTiming));
@@ -124,27 +132,16 @@ int Model::conv(const mi_conv_desc &d, hipStream_t st) {
     if (d.epi == MI_EPI_STATS_ONLY) out_rows = 0;
     double bytes = in_bytes + 4.0 * out_rows * N + 4.0 * (double)d.M * d.K;
     if (d.flags & MI_FLAG_RES || d.epi == MI_EPI_GN_GLU) bytes += 4.0 * out_rows * N;
-    Profiler::Pending p{cls, prof.get(), prof.get(), 2.0 * d.M * (double)d.K * N, bytes};
-    MI_HIP(hipEventRecord(p.a, st));
-    const int r = launch_conv(d, st);
-    MI_HIP(hipEventRecord(p.b, st));
-    prof.pending.push_back(p);
-    ProfRow &row = prof.rows[cls];
-    if (!row.name[0] && tap_x6)
-        snprintf(row.name, sizeof(row.name), "conv_tap_x6<%s,tile%d,taps%d>", kEpiNames[d.epi], tile, d.ntaps);
-    else if (!row.name[0] && rows_x6)
-        snprintf(row.name, sizeof(row.name), "conv_rows_x6<%s,tile%d>", kEpiNames[d.epi], tile);
-    else if (!row.name[0])
-        snprintf(row.name, sizeof(row.name), "conv_gemm%s<%s,tile%d%s>", d.half == MI_DTYPE_BF16 ? "_bf16" : d.half == MI_DTYPE_F16 ? "_f16" : cls >= 48 ? "_x6" : "",
+    char name[sizeof(ProfRow::name)];
+    const bool unnamed = !prof.rows[cls].name[0];        // a row keeps the name its first launch gave it
+    if (unnamed && tap_x6)
+        snprintf(name, sizeof(name), "conv_tap_x6<%s,tile%d,taps%d>", kEpiNames[d.epi], tile, d.ntaps);
+    else if (unnamed && rows_x6)
+        snprintf(name, sizeof(name), "conv_rows_x6<%s,tile%d>", kEpiNames[d.epi], tile);
+    else if (unnamed)
+        snprintf(name, sizeof(name), "conv_gemm%s<%s,tile%d%s>", d.half == MI_DTYPE_BF16 ? "_bf16" : d.half == MI_DTYPE_F16 ? "_f16" : cls >= 48 ? "_x6" : "",
                  kEpiNames[d.epi], tile, d.plain ? ",1x1" : "");
-    return r;
-}
-
-// MI_X6: 0 no split-bf16 kernels (A/B runs), unset the default scope, non-zero every layer with a split main loop (pack_split)
-static int x6_scope() {
-    static const char *env = getenv("MI_X6");
-    static const int scope = env ? (atoi(env) != 0 ? 2 : 0) : 1;      // 0 none, 1 default, 2 all
-    return scope;
+    return prof.timed(cls, unnamed ? name : nullptr, 2.0 * d.M * (double)d.K * N, bytes, st, [&] { return launch_conv(d, st); });
 }
 
 // The float32 engine's attention core runs on the split-bf16 kernel (attention_x6.hip) in the scope of the split linears:
@@ -153,23 +150,15 @@ int Model::attn(const float *q, const float *k, const float *v, float *o, int B,
                 int64_t o_bs, hipStream_t st, bool image) {
     void *oh = image ? (void *)o : nullptr;               // the image takes the place (half the bytes) of the float32 tensor
     const int64_t oh_n = (int64_t)B * Tq;
-    const bool x6 = cfg.dtype == MI_DTYPE_F32 && !image && g_split_bf16 && x6_scope() != 0;
+    const bool x6 = cfg.dtype == MI_DTYPE_F32 && !image && g_split_bf16 && switches().x6_scope != 0;
     auto launch = [&]() {
         return x6 ? launch_attention_x6(q, k, v, o, B, 8, Tq, Tk, q_bs, kv_bs, o_bs, st)
                   : launch_attention(q, k, v, o, B, 8, Tq, Tk, q_bs, kv_bs, o_bs, cfg.dtype, st, oh, oh_n);
     };
-    if (!prof.on) return launch();
     const int cls = x6 ? 104 : 100;          // 101-103 are the DConv and LSTM rows
+    const char *name = x6 ? "attention_x6_kernel" : cfg.dtype == MI_DTYPE_BF16 ? "attention_bf16_kernel" : cfg.dtype == MI_DTYPE_F16 ? "attention_f16_kernel" : "attention_kernel";
     // QK^T and PV: 2 * 2 * Tq * Tk * 64 flops per head (fp32-equivalent on the split kernel); bytes = q, k, v read once + o written
-    Profiler::Pending p{cls, prof.get(), prof.get(), 4.0 * B * 8 * (double)Tq * Tk * 64.0,
-                        4.0 * B * 512.0 * (2.0 * Tq + 2.0 * Tk)};
-    MI_HIP(hipEventRecord(p.a, st));
-    const int r = launch();
-    MI_HIP(hipEventRecord(p.b, st));
-    prof.pending.push_back(p);
-    snprintf(prof.rows[cls].name, sizeof(prof.rows[cls].name), "attention%s_kernel",
-             x6 ? "_x6" : cfg.dtype == MI_DTYPE_BF16 ? "_bf16" : cfg.dtype == MI_DTYPE_F16 ? "_f16" : "");
-    return r;
+    return prof.timed(cls, name, 4.0 * B * 8 * (double)Tq * Tk * 64.0, 4.0 * B * 512.0 * (2.0 * Tq + 2.0 * Tk), st, launch);
 }
 
 // half modes: per-head 16-bit operands [B][8][T][64] (written by the projections' MI_FLAG_HEADS epilogue); the output is always
@@ -178,35 +167,30 @@ int Model::attn_heads(const void *q, const void *k, const void *v, float *o, int
     const int64_t oh_n = (int64_t)B * Tq;
     const void *zero = conv_zero_page();
     MI_REQUIRE(zero, "attention: could not allocate the zero page");
-    if (!prof.on) return launch_attention_heads(q, k, v, zero, B, 8, Tq, Tk, Tq, Tk, cfg.dtype, o, oh_n, nullptr, 0, st);
-    const int cls = 100;
-    Profiler::Pending p{cls, prof.get(), prof.get(), 4.0 * B * 8 * (double)Tq * Tk * 64.0, 2.0 * B * 512.0 * (2.0 * Tq + 2.0 * Tk)};
-    MI_HIP(hipEventRecord(p.a, st));
-    const int r = launch_attention_heads(q, k, v, zero, B, 8, Tq, Tk, Tq, Tk, cfg.dtype, o, oh_n, nullptr, 0, st);
-    MI_HIP(hipEventRecord(p.b, st));
-    prof.pending.push_back(p);
-    snprintf(prof.rows[cls].name, sizeof(prof.rows[cls].name), "attention_heads%s_kernel", cfg.dtype == MI_DTYPE_BF16 ? "_bf16" : "_f16");
-    return r;
+    return prof.timed(100, cfg.dtype == MI_DTYPE_BF16 ? "attention_heads_bf16_kernel" : "attention_heads_f16_kernel",
+                      4.0 * B * 8 * (double)Tq * Tk * 64.0, 2.0 * B * 512.0 * (2.0 * Tq + 2.0 * Tk), st,
+                      [&] { return launch_attention_heads(q, k, v, zero, B, 8, Tq, Tk, Tq, Tk, cfg.dtype, o, oh_n, nullptr, 0, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
 // weight lookup and packing
 // ------------------------------------------------------------------------------------------------
 // Second copy of the packed weights as exact 3-term bf16 tile images: selects the 6-product bf16 MFMA main loop
-// (gemm_x6.hip).  Scope: by default the float32 engine's 44 transformer linears (split_linears), where the split loop is
-// ~1.4x faster than the native fp32 MFMA kernels, and its eight decoder rewrite convs (split_taps: dec[j] 3 x 3, tdec[j] k = 3,
+// (gemm_x6.hip).  Scope (stated by the call that packs the layer, model.h SplitScope): by default the float32 engine's 44
+// transformer linears (SPLIT_DEFAULT), where the split loop is
+// ~1.4x faster than the native fp32 MFMA kernels, and its eight decoder rewrite convs (SPLIT_DEFAULT: dec[j] 3 x 3, tdec[j] k = 3,
 // + GLU), which the shifted-run DMA tap loader feeds (conv_tap_x6_kernel; the table-driven gather in front of the split loop had
-// measured slower than the native DMA tap loop), and the row-tap layers of the DMA row route (split_rows: enc[1..3].conv, k = 8,
+// measured slower than the native DMA tap loop), and the row-tap layers of the DMA row route (SPLIT_ROWS: enc[1..3].conv, k = 8,
 // s = 4, + GELU; dec[0..2].convtr; the 128-row 1 x 1 + GLU rewrites of enc / tenc[2..3]), which the DMA row loader feeds
 // (conv_rows_x6_kernel; not with MI_NO_DMA_ROWS=1, whose layers keep the native table routes); MI_X6=0 packs none (A/B runs), MI_X6=1 every layer whose tile has the split
 // loop.  When several PROCESSES share one GPU, split-loop results were
 // intermittently corrupted (tests/test_gpu_distributed.py, tools/micro/det3.py; cause not found), so such a process
 // selects the native kernels at run time (mi_set_split_bf16(0): demucs_amd/distributed.py does it for ranks that share
 // a device); one process per GPU is the supported deployment.
-int Model::pack_split(PackedConv *pc) {
-    const int scope = x6_scope();                 // 0 none, 1 transformer linears + decoder rewrites + row-tap convs (float32), 2 all
-    const bool no_rows = conv_switches().no_dma_rows;
-    const bool want = scope == 2 || (scope == 1 && (split_linears || split_taps || (split_rows && !no_rows)) && cfg.dtype == MI_DTYPE_F32);
+int Model::pack_split(PackedConv *pc, SplitScope scope) {
+    const Switches &sw = switches();
+    const bool in_default = scope == SPLIT_DEFAULT || (scope == SPLIT_ROWS && !sw.no_dma_rows);
+    const bool want = sw.x6_scope == 2 || (sw.x6_scope == 1 && in_default && cfg.dtype == MI_DTYPE_F32);
     if (!want || !conv_x6_supported(pc->tile)) return MI_OK;
     MI_TRY(dev_alloc(&pc->wx, (size_t)6 * pc->Kpad * pc->Mpad));
     MI_TRY(launch_pack_split(pc->wt, pc->Kpad, pc->Mpad, pc->tile, pc->wx, nullptr));
@@ -229,8 +213,7 @@ int Model::pack_half(PackedConv *pc) {
 // two GLU halves: packed row 2c = W[c], 2c+1 = W[c + M/2].
 // half modes, k x k stride-1 convs whose input is written as an operand image: third copy of the weights, tap-ordered
 int Model::pack_tap(PackedConv *pc, int ntaps) {
-    static const bool no_tap = getenv("MI_NO_TAP_IMAGE") != nullptr;
-    if (cfg.dtype == MI_DTYPE_F32 || no_tap || ntaps < 2 || pc->K % ntaps || (pc->K / ntaps) % 8) return MI_OK;
+    if (cfg.dtype == MI_DTYPE_F32 || switches().no_tap_image || ntaps < 2 || pc->K % ntaps || (pc->K / ntaps) % 8) return MI_OK;
     const int Cin = pc->K / ntaps;
     MI_TRY(dev_alloc(&pc->wtap, (size_t)16 * conv_tap_pairs_pad(Cin, ntaps) * pc->Mpad));
     pc->ntaps = ntaps;
@@ -242,8 +225,7 @@ int Model::pack_tap(PackedConv *pc, int ntaps) {
 // half modes, encoder convs (k = 8, s = 4, pad 2) fed by a phase-split image (gemm_conv.h MI_FLAG_IMG4): the same weights as a stride-1
 // two-tap conv over 4 Cin channels -- channel (octet, plane rho, ci % 8), tap j <-> original tap 4 (j - (rho >= 2)) + rho + 2
 int Model::pack_enc_tap(const float *W /* (M, Cin, 8) */, int Cin, PackedConv *pc) {
-    static const bool off = getenv("MI_NO_ENC_IMAGE") != nullptr || getenv("MI_NO_TAP_IMAGE") != nullptr;
-    if (cfg.dtype == MI_DTYPE_F32 || off || Cin % 8) return MI_OK;
+    if (cfg.dtype == MI_DTYPE_F32 || switches().no_enc_image || switches().no_tap_image || Cin % 8) return MI_OK;
     const int M = pc->M, K = 8 * Cin;
     std::vector<float> wt((size_t)K * pc->Mpad, 0.f);
     for (int m = 0; m < M; ++m)
@@ -264,7 +246,7 @@ int Model::pack_enc_tap(const float *W /* (M, Cin, 8) */, int Cin, PackedConv *p
     return r;
 }
 
-int Model::pack_conv(const float *W, const float *bias, int M, int K, bool glu, PackedConv *pc, int ntaps) {
+int Model::pack_conv(const float *W, const float *bias, int M, int K, bool glu, PackedConv *pc, int ntaps, SplitScope scope) {
     const int tile = conv_pick_tile(M);
     pc->M = M; pc->K = K; pc->Mpad = round_up(M, tile); pc->Kpad = round_up(K, 16); pc->tile = tile;
     std::vector<float> wt((size_t)pc->Kpad * pc->Mpad, 0.f), b(pc->Mpad, 0.f);
@@ -277,12 +259,12 @@ int Model::pack_conv(const float *W, const float *bias, int M, int K, bool glu, 
     MI_TRY(upload(b, &pc->bias));
     MI_TRY(pack_half(pc));
     MI_TRY(pack_tap(pc, ntaps));
-    return pack_split(pc);
+    return pack_split(pc, scope);
 }
 
 // ConvTranspose(k = 2s, stride s) weights W[Cin][Cout][2s] -> s-phase GEMM (s = 4: k = 8; s = 2: k = 4): row m = s*co + r,
 // k = 2*ci + j, tap = r + s*j (output index s*q + r - pad receives input q - j through tap r + s*j).
-int Model::pack_convtr(const float *W, const float *bias, int Cin, int Cout, PackedConv *pc, int stride) {
+int Model::pack_convtr(const float *W, const float *bias, int Cin, int Cout, PackedConv *pc, int stride, SplitScope scope) {
     const int M = stride * Cout, K = 2 * Cin, ks = 2 * stride;
     const int tile = conv_pick_tile(M);
     pc->M = M; pc->K = K; pc->Mpad = round_up(M, tile); pc->Kpad = round_up(K, 16); pc->tile = tile;
@@ -298,12 +280,12 @@ int Model::pack_convtr(const float *W, const float *bias, int Cin, int Cout, Pac
     MI_TRY(upload(b, &pc->bias));
     MI_TRY(pack_half(pc));
     MI_TRY(pack_tap(pc, 2));             // k = 2 ci + j is already (channel, tap) order
-    return pack_split(pc);
+    return pack_split(pc, scope);
 }
 
 // Linear layer applied to LayerNorm(x): fold the LayerNorm affine into the weights (MI_FLAG_LN in gemm_conv.h)
 int Model::pack_linear_ln(const float *W, const float *bias, const float *ln_w, const float *ln_b, int M, int K, PackedConv *pc,
-                          float **c1) {
+                          float **c1, SplitScope scope) {
     std::vector<float> wf((size_t)M * K), c2(M), c1h(M);
     for (int m = 0; m < M; ++m) {
         double s1 = 0.0, s2 = bias ? (double)bias[m] : 0.0;
@@ -315,7 +297,7 @@ int Model::pack_linear_ln(const float *W, const float *bias, const float *ln_w, 
         }
         c1h[m] = (float)s1; c2[m] = (float)s2;
     }
-    MI_TRY(pack_conv(wf.data(), c2.data(), M, K, false, pc));
+    MI_TRY(pack_conv(wf.data(), c2.data(), M, K, false, pc, 0, scope));
     return pack_vec(c1h.data(), M, pc->Mpad, false, c1);
 }
 
@@ -333,8 +315,8 @@ int Model::load_dconv(const WeightTable &wt, const std::string &prefix, int C, i
     const int h = C / comp;
     dw->h = h;
     dw->has_row = comp == 8 && freq && dconv_row_supported(C, D2);
-    static const bool no_time = getenv("MI_NO_DCONV_TIME") != nullptr;      // A/B switch: fall back to the implicit-GEMM route
-    dw->has_time = comp == 8 && !freq && !no_time && dconv_time_supported(C, D2);
+    // MI_NO_DCONV_TIME (A/B switch): fall back to the implicit-GEMM route
+    dw->has_time = comp == 8 && !freq && !switches().no_dconv_time && dconv_time_supported(C, D2);
     for (int d = 0; d < 2; ++d) {
         DConvLayerW &l = dw->l[d];
         const std::string p = prefix + ".dconv.layers." + std::to_string(d);
@@ -449,19 +431,7 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
     for (size_t i = 0; i < n; ++i) wt.t[weights[i].name] = {weights[i].data, weights[i].numel};
 
     // ---- FFT tables (window in float32 arithmetic like th.hann_window, spec.py:19,41) ------------
-    {
-        std::vector<float> win(4096), env(1024);
-        const std::vector<float2> tw = fft_twiddle_table();
-        for (int i = 0; i < 4096; ++i) win[i] = 0.5f - 0.5f * cosf((float)i * (float)(2.0 * M_PI / 4096.0));
-        for (int r = 0; r < 1024; ++r) {
-            float e = 0.f;
-            for (int j = 3; j >= 0; --j) e += win[r + 1024 * j] * win[r + 1024 * j];   // ascending frame order
-            env[r] = e;
-        }
-        float *dw, *de; float2 *dt;
-        MI_TRY(upload(win, &dw)); MI_TRY(upload(tw, &dt)); MI_TRY(upload(env, &de));
-        fft = FftTables{dw, dt, de};
-    }
+    MI_TRY(upload_fft_tables());
 
     // ---- encoders ---------------------------------------------------------------------------------
     for (int i = 0; i < 4; ++i) {
@@ -473,14 +443,12 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(wt.get(p + ".rewrite.weight", (int64_t)2 * C * C, &rw));
         MI_TRY(wt.get(p + ".rewrite.bias", 2 * C, &rb));
         EncW &e = enc[i];
-        split_rows = i > 0;              // level 0 (K = 32) is bound by its output: native
-        MI_TRY(pack_conv(w, b, C, Cin * 8, false, &e.conv));
-        split_rows = false;
+        // level 0 (K = 32) is bound by its output: native
+        MI_TRY(pack_conv(w, b, C, Cin * 8, false, &e.conv, 0, i > 0 ? SPLIT_ROWS : SPLIT_OPT_IN));
         if (i) MI_TRY(pack_enc_tap(w, Cin, &e.conv));
         MI_TRY(make_ktab(Gather{Cin, 8, 1, 1, 1, 2, 0, (int64_t)kFr[i] * T, T}, e.conv.Kpad, &e.ktab_conv));
-        split_rows = i >= 2;             // 128-row rewrites; levels 0 / 1 (96 rows, K = 48 / 96) are bound by their output
-        MI_TRY(pack_conv(rw, rb, 2 * C, C, true, &e.rewrite));
-        split_rows = false;
+        // 128-row rewrites; levels 0 / 1 (96 rows, K = 48 / 96) are bound by their output
+        MI_TRY(pack_conv(rw, rb, 2 * C, C, true, &e.rewrite, 0, i >= 2 ? SPLIT_ROWS : SPLIT_OPT_IN));
         MI_TRY(make_ktab(Gather{C, 1, 1, 1, 1, 0, 0, (int64_t)kFr[i + 1] * T, T}, e.rewrite.Kpad, &e.ktab_rw));
         MI_TRY(load_dconv(wt, p, C, (int64_t)kFr[i + 1] * T, T, true, &e.dconv));
 
@@ -494,9 +462,7 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(pack_conv(w, b, C, Cint * 8, false, &te.conv));
         if (i) MI_TRY(pack_enc_tap(w, Cint, &te.conv));
         MI_TRY(make_ktab(Gather{Cint, 1, 8, 1, 1, 0, 2, (int64_t)Lp[i], Lp[i]}, te.conv.Kpad, &te.ktab_conv));
-        split_rows = i >= 2;
-        MI_TRY(pack_conv(rw, rb, 2 * C, C, true, &te.rewrite));
-        split_rows = false;
+        MI_TRY(pack_conv(rw, rb, 2 * C, C, true, &te.rewrite, 0, i >= 2 ? SPLIT_ROWS : SPLIT_OPT_IN));
         MI_TRY(make_ktab(Gather{C, 1, 1, 1, 1, 0, 0, (int64_t)Lp[i + 1], Lp[i + 1]}, te.rewrite.Kpad, &te.ktab_rw));
         MI_TRY(load_dconv(wt, pt, C, (int64_t)Lp[i + 1], Lp[i + 1], false, &te.dconv));
     }
@@ -519,14 +485,11 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(wt.get(p + ".rewrite.weight", (int64_t)2 * C * C * 9, &rw));
         MI_TRY(wt.get(p + ".rewrite.bias", 2 * C, &rb));
         DecW &dd = dec[j];
-        split_taps = true;
-        MI_TRY(pack_conv(rw, rb, 2 * C, C * 9, true, &dd.rewrite, 9));
-        split_taps = false;
+        MI_TRY(pack_conv(rw, rb, 2 * C, C * 9, true, &dd.rewrite, 9, SPLIT_DEFAULT));
         MI_TRY(make_ktab(Gather{C, 3, 3, 1, 1, 1, 1, (int64_t)Fr * T, T}, dd.rewrite.Kpad, &dd.ktab_rw));
         MI_TRY(load_dconv(wt, p, C, (int64_t)Fr * T, T, true, &dd.dconv));
-        split_rows = j < 3;              // the outermost one (K = 96, 64-row tile) is bound by its output: native
-        MI_TRY(pack_convtr(w, b, C, Cout, &dd.convtr));
-        split_rows = false;
+        // the outermost one (K = 96, 64-row tile) is bound by its output: native
+        MI_TRY(pack_convtr(w, b, C, Cout, &dd.convtr, 4, j < 3 ? SPLIT_ROWS : SPLIT_OPT_IN));
         MI_TRY(make_ktab(Gather{C, 2, 1, -1, 1, 0, 0, (int64_t)Fr * T, T}, dd.convtr.Kpad, &dd.ktab_tr));
 
         const int L = Lp[4 - j];          // row pitch of this level's time-branch tensors
@@ -536,9 +499,7 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(wt.get(pt + ".rewrite.weight", (int64_t)2 * C * C * 3, &rw));
         MI_TRY(wt.get(pt + ".rewrite.bias", 2 * C, &rb));
         DecW &td = tdec[j];
-        split_taps = true;
-        MI_TRY(pack_conv(rw, rb, 2 * C, C * 3, true, &td.rewrite, 3));
-        split_taps = false;
+        MI_TRY(pack_conv(rw, rb, 2 * C, C * 3, true, &td.rewrite, 3, SPLIT_DEFAULT));
         MI_TRY(make_ktab(Gather{C, 1, 3, 1, 1, 0, 1, (int64_t)L, L}, td.rewrite.Kpad, &td.ktab_rw));
         MI_TRY(load_dconv(wt, pt, C, (int64_t)L, L, false, &td.dconv));
         MI_TRY(pack_convtr(w, b, C, Coutt, &td.convtr));
@@ -568,7 +529,6 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         const float *w, *b;
         MI_TRY(wt.get(ni + ".weight", 512, &w)); MI_TRY(wt.get(ni + ".bias", 512, &b));
         MI_TRY(pack_vec(w, 512, 512, false, &norm_in_w[br])); MI_TRY(pack_vec(b, 512, 512, false, &norm_in_b[br]));
-        split_linears = true;
         for (int k = 0; k < 5; ++k) {
             const std::string p = std::string("crosstransformer.") + (br ? "layers_t." : "layers.") + std::to_string(k);
             const bool cross = k & 1;
@@ -589,19 +549,18 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
             }
             MI_TRY(pack_vec(nw[3], 512, 512, false, &l.norm_w[3])); MI_TRY(pack_vec(nb[3], 512, 512, false, &l.norm_b[3]));
             if (cross) {     // q from norm1(own branch), k/v from norm2(other branch), FFN from norm3
-                MI_TRY(pack_linear_ln(ipw, ipb, nw[0], nb[0], 512, 512, &l.q_proj, &l.q_c1));
-                MI_TRY(pack_linear_ln(ipw + 512 * 512, ipb + 512, nw[1], nb[1], 1024, 512, &l.kv_proj, &l.kv_c1));
-                MI_TRY(pack_linear_ln(w1, b1, nw[2], nb[2], 2048, 512, &l.lin1, &l.lin1_c1));
+                MI_TRY(pack_linear_ln(ipw, ipb, nw[0], nb[0], 512, 512, &l.q_proj, &l.q_c1, SPLIT_DEFAULT));
+                MI_TRY(pack_linear_ln(ipw + 512 * 512, ipb + 512, nw[1], nb[1], 1024, 512, &l.kv_proj, &l.kv_c1, SPLIT_DEFAULT));
+                MI_TRY(pack_linear_ln(w1, b1, nw[2], nb[2], 2048, 512, &l.lin1, &l.lin1_c1, SPLIT_DEFAULT));
             } else {
-                MI_TRY(pack_linear_ln(ipw, ipb, nw[0], nb[0], 1536, 512, &l.qkv_proj, &l.qkv_c1));
-                MI_TRY(pack_linear_ln(w1, b1, nw[1], nb[1], 2048, 512, &l.lin1, &l.lin1_c1));
+                MI_TRY(pack_linear_ln(ipw, ipb, nw[0], nb[0], 1536, 512, &l.qkv_proj, &l.qkv_c1, SPLIT_DEFAULT));
+                MI_TRY(pack_linear_ln(w1, b1, nw[1], nb[1], 2048, 512, &l.lin1, &l.lin1_c1, SPLIT_DEFAULT));
             }
-            MI_TRY(pack_conv(ow, ob, 512, 512, false, &l.out_proj));
-            MI_TRY(pack_conv(w2, b2, 512, 2048, false, &l.lin2));
+            MI_TRY(pack_conv(ow, ob, 512, 512, false, &l.out_proj, 0, SPLIT_DEFAULT));
+            MI_TRY(pack_conv(w2, b2, 512, 2048, false, &l.lin2, 0, SPLIT_DEFAULT));
             MI_TRY(wt.get(p + ".gamma_1.scale", 512, &w)); MI_TRY(pack_vec(w, 512, 512, false, &l.gamma1));
             MI_TRY(wt.get(p + ".gamma_2.scale", 512, &w)); MI_TRY(pack_vec(w, 512, 512, false, &l.gamma2));
         }
-        split_linears = false;
     }
     {   // positional tables, float32 arithmetic like the reference (transformer.py:19-70), stored [512][tokens]
         std::vector<float> pe2((size_t)512 * Tf), pe1((size_t)512 * Tt);
@@ -629,6 +588,19 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(upload(pe2, &pos_emb[0])); MI_TRY(upload(pe1, &pos_emb[1]));
     }
     MI_TRY(alloc_workspace());
+    {   // the forward's plan: every fact below is decided here and only read afterwards
+        const Switches &sw = switches();
+        const bool half = cfg.dtype != MI_DTYPE_F32;
+        plan.ffn_img = half && !sw.no_ffn_image;
+        plan.qkv_heads = plan.ffn_img && !sw.no_qkv_heads;
+        plan.in_img = plan.qkv_heads && !sw.no_input_image;
+        plan.lin2_stats = !sw.no_lin2_stats;
+        plan.tap_img = half && dec[0].rewrite.wtap && tdec[0].rewrite.wtap;
+        for (int i = 1; i < 4; ++i) {
+            plan.enc_img[0][i] = enc[i].conv.wtap && w_eimg[0][i - 1];
+            plan.enc_img[1][i] = tenc[i].conv.wtap && w_eimg[1][i - 1];
+        }
+    }
     MI_HIP(hipDeviceSynchronize());
     return MI_OK;
 }
@@ -749,13 +721,9 @@ int Model::fill_workspace(Workspace &w) {
 }
 
 // MI_DEBUG_SYNC=1: synchronise after every stage and name it on stderr (locates a faulting kernel)
-static bool debug_sync() {
-    static const bool on = getenv("MI_DEBUG_SYNC") != nullptr;
-    return on;
-}
 #define MI_STAGE(name)                                                                        \
     do {                                                                                      \
-        if (debug_sync()) {                                                                   \
+        if (switches().debug_sync) {                                                          \
             hipError_t _e = hipStreamSynchronize(st);                                         \
             fprintf(stderr, "[mi] reached %s (%s)\n", name, hipGetErrorString(_e));          \
             fflush(stderr);                                                                   \
@@ -775,34 +743,18 @@ int Model::run_dconv(const DConvW &w, int C, const Geo &g, float *x, float *tmp,
     const int rows = g.row_mode ? g.B * g.D1 : g.B;
     if (w.has_row && g.row_mode == 1) {      // both layers in one LDS-resident pass, in place
         DConvRowArgs a{{w.tl[0], w.tl[1]}, x, x, g.D1, g.D2};
-        if (prof.on) {
-            Profiler::Pending p{101, prof.get(), prof.get(), 2.0 * 2.0 * (3.0 * C * h + 2.0 * 2 * C * h) * (double)rows * g.D2,
-                                2.0 * 4.0 * C * (double)rows * g.D2};
-            MI_HIP(hipEventRecord(p.a, st));
-            const int r = launch_dconv_row(a, C, rows, st);
-            MI_HIP(hipEventRecord(p.b, st));
-            prof.pending.push_back(p);
-            snprintf(prof.rows[101].name, sizeof(prof.rows[101].name), "dconv_row_kernel");
-            return r;
-        }
-        return launch_dconv_row(a, C, rows, st);
+        return prof.timed(101, "dconv_row_kernel", 2.0 * 2.0 * (3.0 * C * h + 2.0 * 2 * C * h) * (double)rows * g.D2,
+                          2.0 * 4.0 * C * (double)rows * g.D2, st, [&] { return launch_dconv_row(a, C, rows, st); });
     }
     if (w.has_time && g.row_mode == 0 && g.D1 == 1) {     // time branch, C = 48 / 96: three streaming VALU passes per layer
-        const bool timed = prof.on;
-        Profiler::Pending p{102, nullptr, nullptr, 2.0 * 2.0 * (3.0 * C * h + 2.0 * C * h) * (double)g.B * g.D2,
-                            2.0 * 4.0 * C * (double)g.B * g.D2};
-        if (timed) { p.a = prof.get(); p.b = prof.get(); MI_HIP(hipEventRecord(p.a, st)); }
-        float *s = x, *dd = tmp;
-        for (int dlayer = 0; dlayer < 2; ++dlayer) {
-            MI_TRY(launch_dconv_time_layer(w.tl[dlayer], C, 1 << dlayer, g.B, g.D2, g.pitch(), s, dd, hidden, stats, w_gram, st1, st2, st));
-            std::swap(s, dd);
-        }
-        if (timed) {
-            MI_HIP(hipEventRecord(p.b, st));
-            prof.pending.push_back(p);
-            snprintf(prof.rows[102].name, sizeof(prof.rows[102].name), "dconv_time_kernels");
-        }
-        return MI_OK;   // two layers: result is back in x
+        return prof.timed(102, "dconv_time_kernels", 2.0 * 2.0 * (3.0 * C * h + 2.0 * C * h) * (double)g.B * g.D2, 2.0 * 4.0 * C * (double)g.B * g.D2, st, [&] {
+            float *s = x, *dd = tmp;
+            for (int dlayer = 0; dlayer < 2; ++dlayer) {
+                MI_TRY(launch_dconv_time_layer(w.tl[dlayer], C, 1 << dlayer, g.B, g.D2, g.pitch(), s, dd, hidden, stats, w_gram, st1, st2, st));
+                std::swap(s, dd);
+            }
+            return (int)MI_OK;   // two layers: result is back in x
+        });
     }
     const double cnt_row = g.row_mode ? (double)g.D2 : (double)g.D1 * g.D2;
     float *src = x, *dst = tmp;
@@ -849,13 +801,10 @@ int Model::run_tr_layer(int br, int k, int B, const float *x, const float2 *xsta
     // 16-bit operand image, in place of the float32 tensor, and consumed by the LDS-DMA main loop of gemm_half.hip
     // norm_out's statistics come from lin2's epilogue (MI_FLAG_STATS): ten launches and 1.7 GB of reads fewer per batched forward;
     // time-neutral on the two-stream schedule, where the separate pass was hidden (MI_NO_LIN2_STATS=1 restores it for A/B runs)
-    static const bool lin2_stats = getenv("MI_NO_LIN2_STATS") == nullptr;
-    static const bool no_img = getenv("MI_NO_FFN_IMAGE") != nullptr;
-    const bool img = cfg.dtype != MI_DTYPE_F32 && !no_img;
     // half modes: Q, K, V feed nothing but the attention kernel, so the projections write them ONLY as 16-bit per-head token-major
-    // tensors (MI_FLAG_HEADS, no float32 copy) and attention_heads.hip moves K / V tiles global -> LDS by DMA
-    static const bool no_heads = getenv("MI_NO_QKV_HEADS") != nullptr;
-    const bool heads = img && !no_heads;
+    // tensors (MI_FLAG_HEADS, no float32 copy) and attention_heads.hip moves K / V tiles global -> LDS by DMA (MI_NO_QKV_HEADS=1,
+    // MI_NO_FFN_IMAGE=1: float32 tensors); with plan.in_img the layer inputs (ximg / oimg -> outimg) and x1 exist as operand images too
+    const bool img = plan.ffn_img, heads = plan.qkv_heads, in_img = plan.in_img, lin2_stats = plan.lin2_stats;
     unsigned short *qh = reinterpret_cast<unsigned short *>(qkv);
     const size_t plane_q = (size_t)B * 512 * Tq, plane_k = (size_t)B * 512 * Tk;        // 16-bit elements of one of Q / K / V
     if (!cross) {
@@ -863,7 +812,7 @@ int Model::run_tr_layer(int br, int k, int B, const float *x, const float2 *xsta
         d.plain = 1; d.epi = MI_EPI_LINEAR; d.flags = MI_FLAG_LN; d.scale = l.qkv_c1; d.pro_stats = (const float *)xstat;
         d.y = qkv; d.y_bstride = (int64_t)1536 * Tq; d.y_cstride = Tq;
         if (heads) { d.flags |= MI_FLAG_HEADS; d.yh = qh; d.yh_n = Tq; }
-        if (heads && ximg) { d.xh = ximg; d.xh_n = (int64_t)B * Tq; }
+        if (in_img) { d.xh = ximg; d.xh_n = (int64_t)B * Tq; }
         MI_TRY(conv(d, st));
         if (heads) MI_TRY(attn_heads(qh, qh + plane_q, qh + 2 * plane_q, att, B, Tq, Tq, st));
         else MI_TRY(attn(qkv, qkv + (size_t)512 * Tq, qkv + (size_t)1024 * Tq, att, B, Tq, Tq, (int64_t)1536 * Tq, (int64_t)1536 * Tq,
@@ -873,7 +822,7 @@ int Model::run_tr_layer(int br, int k, int B, const float *x, const float2 *xsta
         d.plain = 1; d.epi = MI_EPI_LINEAR; d.flags = MI_FLAG_LN; d.scale = l.q_c1; d.pro_stats = (const float *)xstat;
         d.y = qkv; d.y_bstride = (int64_t)512 * Tq; d.y_cstride = Tq;
         if (heads) { d.flags |= MI_FLAG_HEADS; d.yh = qh; d.yh_n = Tq; }
-        if (heads && ximg) { d.xh = ximg; d.xh_n = (int64_t)B * Tq; }
+        if (in_img) { d.xh = ximg; d.xh_n = (int64_t)B * Tq; }
         MI_TRY(conv(d, st));
         float *kv = qkv + (size_t)B * 512 * Tq;
         unsigned short *kvh = qh + plane_q;
@@ -881,7 +830,7 @@ int Model::run_tr_layer(int br, int k, int B, const float *x, const float2 *xsta
         e.plain = 1; e.epi = MI_EPI_LINEAR; e.flags = MI_FLAG_LN; e.scale = l.kv_c1; e.pro_stats = (const float *)ostat;
         e.y = kv; e.y_bstride = (int64_t)1024 * Tk; e.y_cstride = Tk;
         if (heads) { e.flags |= MI_FLAG_HEADS; e.yh = kvh; e.yh_n = Tk; }
-        if (heads && oimg) { e.xh = oimg; e.xh_n = (int64_t)B * Tk; }
+        if (in_img) { e.xh = oimg; e.xh_n = (int64_t)B * Tk; }
         MI_TRY(conv(e, st));
         if (heads) MI_TRY(attn_heads(qh, kvh, kvh + plane_k, att, B, Tq, Tk, st));
         else MI_TRY(attn(qkv, kv, kv + (size_t)512 * Tk, att, B, Tq, Tk, (int64_t)512 * Tq, (int64_t)1024 * Tk, (int64_t)512 * Tq, st, img));
@@ -893,7 +842,6 @@ int Model::run_tr_layer(int br, int k, int B, const float *x, const float2 *xsta
         if (img) { d.xh = att; d.xh_n = (int64_t)B * Tq; }
         MI_TRY(conv(d, st));
     }
-    const bool in_img = heads && ximg != nullptr;        // the layer inputs and x1 exist as operand images too
     MI_TRY(launch_token_stats(x1, B, 512, Tq, w_tr_stat1[br], st, in_img ? w_tr_x1img[br] : nullptr, (int64_t)B * Tq, cfg.dtype));
     {
         mi_conv_desc d = base_desc(l.lin1, tr_ktab512[br], x1, (int64_t)512 * Tq, gq);
@@ -901,7 +849,7 @@ int Model::run_tr_layer(int br, int k, int B, const float *x, const float2 *xsta
         d.pro_stats = (const float *)w_tr_stat1[br];
         d.y = ffh; d.y_bstride = (int64_t)2048 * Tq; d.y_cstride = Tq;
         if (img) { d.flags |= MI_FLAG_IMG; d.yh = ffh; d.yh_n = (int64_t)B * Tq; }
-        if (img && in_img) { d.xh = w_tr_x1img[br]; d.xh_n = (int64_t)B * Tq; }
+        if (in_img) { d.xh = w_tr_x1img[br]; d.xh_n = (int64_t)B * Tq; }
         MI_TRY(conv(d, st));
         mi_conv_desc e = base_desc(l.lin2, tr_ktab2048[br], ffh, (int64_t)2048 * Tq, gq);
         if (img) { e.xh = ffh; e.xh_n = (int64_t)B * Tq; }
@@ -971,8 +919,7 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
     // meet in the cross-transformer (once per layer: cross-attention reads the other branch's layer input) and in the final sum,
     // and their kernels -- a third of the spectral branch's size, many of them one or two waves of workgroups -- fill the tails
     // of each other's launches.  Every buffer the branches write is per branch (statistics slots, Gram accumulators, scratch).
-    static const bool one_stream = getenv("MI_ONE_STREAM") != nullptr;
-    const bool two = !one_stream && g_two_streams && !debug_sync() && side_streams() == MI_OK;
+    const bool two = !switches().one_stream && g_two_streams && !switches().debug_sync && side_streams() == MI_OK;
     hipStream_t stt = two ? side_st : st;
     auto fork = [&]() -> int {              // the side stream waits for everything enqueued on the caller's stream so far
         if (!two) return MI_OK;
@@ -1015,7 +962,7 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
             d.O1 = kFr[i + 1]; d.S1 = 4; d.epi = MI_EPI_LINEAR; d.flags = MI_FLAG_GELU;
             d.y = w_a; d.y_bstride = C * P; d.y_cstride = P;
             d.dma_rows = 1;                  // taps along the frequency axis only (float32: LDS-DMA main loop, gemm_conv.hip)
-            if (i && enc[i].conv.wtap && w_eimg[0][i - 1]) {
+            if (plan.enc_img[0][i]) {
                 // the previous level's output as a phase-split image: a stride-1 two-tap conv over its slots (rows o1, o1 + 1)
                 const int Q = kFr[i] / 4 + 1;
                 d.xh = w_eimg[0][i - 1]; d.xh_n = (int64_t)cfg.max_batch * Q * T; d.wtap = enc[i].conv.wtap; d.ntaps = 2; d.tap_k2 = 1;
@@ -1028,7 +975,7 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
             mi_conv_desc r = base_desc(enc[i].rewrite, enc[i].ktab_rw, w_a, C * P, go);
             r.plain = 1; r.epi = MI_EPI_GLU; r.y = w_skip[i]; r.y_bstride = C * P; r.y_cstride = P;
             if (i == 0) { r.flags = MI_FLAG_EMB; r.emb = freq_emb; }
-            if (i < 3 && enc[i + 1].conv.wtap && w_eimg[0][i]) {
+            if (i < 3 && plan.enc_img[0][i + 1]) {
                 const int64_t pq = (int64_t)(kFr[i + 1] / 4 + 1) * T;
                 r.flags |= MI_FLAG_IMG4 | MI_FLAG_TR_FREQ; r.yh = w_eimg[0][i]; r.yh_pq = pq; r.yh_n = (int64_t)cfg.max_batch * pq;
             }
@@ -1042,7 +989,7 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
             mi_conv_desc d = base_desc(tenc[i].conv, tenc[i].ktab_conv, xt, (int64_t)Cint * Lp[i], gin);
             d.O2 = Lp[i + 1]; d.o2_valid = Lt[i + 1]; d.S2 = 4; d.epi = MI_EPI_LINEAR; d.flags = MI_FLAG_GELU;
             d.y = w_ta; d.y_bstride = C * P; d.y_cstride = P;
-            if (i && tenc[i].conv.wtap && w_eimg[1][i - 1]) {
+            if (plan.enc_img[1][i]) {
                 const int Qp = round_up(ceil_div(Lt[i], 4) + 1, 4);
                 d.xh = w_eimg[1][i - 1]; d.xh_n = (int64_t)cfg.max_batch * Qp; d.wtap = tenc[i].conv.wtap; d.ntaps = 2; d.tap_k2 = 2;
                 d.D2 = Qp; d.x_ld = Qp; d.S2 = 1;
@@ -1051,7 +998,7 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
             MI_TRY(run_dconv(tenc[i].dconv, C, go, w_ta, w_tb, w_th, w_stats_t, w_st1_t, w_st2_t, stt, w_gram2_t, gram2t_bytes));
             mi_conv_desc r = base_desc(tenc[i].rewrite, tenc[i].ktab_rw, w_ta, C * P, go);
             r.plain = 1; r.epi = MI_EPI_GLU; r.y = w_skip_t[i]; r.y_bstride = C * P; r.y_cstride = P;
-            if (i < 3 && tenc[i + 1].conv.wtap && w_eimg[1][i]) {
+            if (i < 3 && plan.enc_img[1][i + 1]) {
                 const int64_t pq = round_up(ceil_div(Lt[i + 1], 4) + 1, 4);
                 r.flags |= MI_FLAG_IMG4; r.yh = w_eimg[1][i]; r.yh_pq = pq; r.yh_n = (int64_t)cfg.max_batch * pq;
             }
@@ -1063,8 +1010,7 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
     // ---- bottleneck: channel upsamplers, cross transformer, channel downsamplers -------------------
     int cur[2] = {0, 0};
     // half modes: the transformer's projections read 16-bit operand images of their inputs (written by the token kernels)
-    static const bool no_in_img = getenv("MI_NO_INPUT_IMAGE") != nullptr || getenv("MI_NO_QKV_HEADS") != nullptr || getenv("MI_NO_FFN_IMAGE") != nullptr;
-    const bool in_img = cfg.dtype != MI_DTYPE_F32 && !no_in_img;
+    const bool in_img = plan.in_img;
     for (int br = 0; br < 2; ++br) {
         const int P = br ? Tt : Tf;
         const Geo g{B, 1, P, 0};
@@ -1095,7 +1041,7 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
     // half modes: a decoder layer's input feeds nothing but its k x k rewrite conv, so its producer (the channel down-sampler,
     // then each transposed conv + GELU + skip) writes it ONLY as that conv's 16-bit operand image, into the same buffers, and
     // the conv gathers its taps by LDS-DMA (gemm_tap.hip)
-    const bool tapimg = cfg.dtype != MI_DTYPE_F32 && dec[0].rewrite.wtap && tdec[0].rewrite.wtap;
+    const bool tapimg = plan.tap_img;
     for (int br = 0; br < 2; ++br) {
         const int P = br ? Tt : Tf;
         const Geo g{B, 1, P, 0};

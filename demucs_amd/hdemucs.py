@@ -10,6 +10,7 @@ implementation of the network exists in this package and there is no CPU path.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from collections import OrderedDict
 from typing import Dict, List, Optional
 
@@ -22,6 +23,12 @@ from .hdemucs_weights import HDemucsConfig, hdemucs_schema
 __all__ = ["HDemucs"]
 
 MIN_LENGTH = 1               # demucs_amd/csrc/hmodel.hip: kMinLength (the reference forwards any length >= 1 too)
+
+
+def tail_overlap_enabled() -> bool:
+    """The schedulers run a track's shorter tail chunk on the side engine under the batched forward unless MI_NO_TAIL_OVERLAP is
+    set (the one switch Python reads; looked up at every call)."""
+    return os.environ.get("MI_NO_TAIL_OVERLAP") is None
 
 
 class HDemucs:

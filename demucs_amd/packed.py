@@ -23,7 +23,6 @@ under the main engine's batched forwards, as the single-track route runs each tr
 from __future__ import annotations
 
 import ctypes as C
-import os
 import random
 from dataclasses import dataclass, field
 from typing import Any, List, Optional, Sequence
@@ -31,7 +30,7 @@ from typing import Any, List, Optional, Sequence
 import torch
 
 from . import _lib
-from .hdemucs import HDemucs, MIN_LENGTH as _HDEMUCS_MIN_LENGTH
+from .hdemucs import HDemucs, MIN_LENGTH as _HDEMUCS_MIN_LENGTH, tail_overlap_enabled
 from .htdemucs import HTDemucs
 
 # column layout of the device tables (include/demucs_amd.h, MI_PACK_*)
@@ -266,7 +265,7 @@ def run(model, mixes: Sequence[torch.Tensor], device: torch.device, shifts: int,
         # on the main stream in plan order, after every full chunk's
         main = torch.cuda.current_stream(device)
         side = {}                                     # forward index -> (table, out)
-        if os.environ.get("MI_NO_TAIL_OVERLAP") is None:
+        if tail_overlap_enabled():
             for e, sub in enumerate(p.members):
                 mine = [i for i, fw in enumerate(p.forwards) if fw.member == e and _side_tail(p, fw)]
                 if not mine or len(mine) == sum(fw.member == e for fw in p.forwards):

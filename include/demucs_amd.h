@@ -682,6 +682,13 @@ int mi_debug_last_conv_route(void);
  * nothing, follows no pointer of the descriptor, works in a process that never touches the GPU.  Returns -1 for desc == NULL. */
 int mi_debug_conv_route(const struct mi_conv_desc *desc, int *tile);
 
+/* Debug aid: the MI_* environment switches as this process parsed them, when the library was loaded (INTEGRATION.md has the
+ * table): one `NAME=value` line per switch, the value being the parsed meaning, not the string -- 0 / 1 for an on / off switch,
+ * `MI_X6` none | default | all, `MI_SIDE_PRIO` low | normal | high, `MI_DCONV_ROW` wave | lds, `MI_TRANSPOSE_TILES` the mask.
+ * Writes at most n - 1 characters and a terminating NUL into buf (nothing when buf is NULL or n <= 0); returns the length of
+ * the whole text, as snprintf does.  Host code only. */
+int mi_debug_switches(char *buf, int32_t n);
+
 const char *mi_last_error(void);
 /* "demucs_amd <version> gfx950" */
 const char *mi_version(void);

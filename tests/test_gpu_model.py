@@ -181,7 +181,7 @@ def test_model_rejects_cpu_and_bad_shapes():
 
 @pytest.mark.skipif(os.environ.get("MI_X6") is not None or os.environ.get("MI_DCONV_ROW") is not None, reason="already inside the re-run")
 def test_non_default_kernel_switches_keep_parity():
-    """Non-default kernel routes, re-run together in ONE fresh process (the switches are read once, at packing / first launch;
+    """Non-default kernel routes, re-run together in ONE fresh process (the switches are read once, when the library is loaded;
     they touch disjoint layers):
       * MI_X6=1 (gemm_x6.hip: fp32 operands as three exact bf16 terms, six bf16 MFMA products, fp32 accumulate) on the
         transformer / 1x1 layers -- single process, as DESIGN.md section 8 requires for this mode;
@@ -189,10 +189,24 @@ def test_non_default_kernel_switches_keep_parity():
         layers; slower than the per-wave kernel, kept selectable);
       * MI_NO_DMA_TAP=1 / MI_NO_DMA_ROWS=1: the float32 k x k, strided and transposed convs back on the table-driven gather of
         conv_gemm_kernel (round 3's route, which the LDS-DMA main loops replaced by default).
-    The reference-golden and float64-oracle parity tests above must hold unchanged."""
+    The reference-golden and float64-oracle parity tests above must hold unchanged.  Then the half-mode switch groups, against
+    the reduced-precision floors (below)."""
     env = dict(os.environ, MI_X6="1", MI_X6_MODE="1", MI_DCONV_ROW="lds", MI_NO_DMA_TAP="1", MI_NO_DMA_ROWS="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-k",
                         "reference_golden or float64_oracle", "-p", "no:cacheprovider"], env=env, capture_output=True, text=True,
                        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "passed" in r.stdout
+    # The half-mode routes behind the image / statistics / schedule switches, one fresh process per group (the groups overlap in
+    # the layers they touch): group A -- float32 projection inputs, float32 encoder conv inputs, norm_out's statistics by a
+    # separate pass, one stream; group B -- float32 Q / K / V, table-driven decoder convs, time-branch DConv on the implicit-GEMM
+    # route; group C -- float32 attention output and FFN hidden tensor.  Each must meet the floors the default routes meet.
+    groups = {"A": dict(MI_NO_INPUT_IMAGE="1", MI_NO_ENC_IMAGE="1", MI_NO_LIN2_STATS="1", MI_ONE_STREAM="1"),
+              "B": dict(MI_NO_QKV_HEADS="1", MI_NO_TAP_IMAGE="1", MI_NO_DCONV_TIME="1"),
+              "C": dict(MI_NO_FFN_IMAGE="1")}
+    for tag, extra in groups.items():
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-k",
+                            "autocast_floor and autocast_seg_tones_w1", "-p", "no:cacheprovider"], env=dict(os.environ, **extra),
+                           capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        assert r.returncode == 0, f"group {tag}: " + r.stdout[-3000:] + r.stderr[-2000:]
+        assert "2 passed" in r.stdout, f"group {tag}: " + r.stdout[-1000:]

@@ -162,16 +162,28 @@ import sys
 import numpy as np
 import torch
 from demucs_amd import _lib
-from demucs_amd.htdemucs import HTDemucs
 from demucs_amd.synth import synth_mix
-from demucs_amd.weights import HTDemucsConfig, synthetic_state_dict
+# argv: output prefix, "default" | "switch", compute mode (f32 | bf16 | f16), engine (htdemucs | hdemucs)
+dtype = sys.argv[3] if len(sys.argv) > 3 else "f32"
+engine = sys.argv[4] if len(sys.argv) > 4 else "htdemucs"
 if sys.argv[2] == "switch":
     _lib.load().mi_set_split_bf16(0)
-cfg = HTDemucsConfig()
-m = HTDemucs(cfg.sources, max_batch=1)
-m.load_state_dict(synthetic_state_dict(cfg, 0))
+if engine == "hdemucs":
+    from demucs_amd.hdemucs import HDemucs
+    from demucs_amd.hdemucs_weights import HDemucsConfig, synthetic_hdemucs_state_dict
+    cfg = HDemucsConfig(channels=48, segment=3)
+    m = HDemucs(cfg.sources, max_batch=1, compute_dtype=dtype, channels=48, segment=3)
+    m.load_state_dict(synthetic_hdemucs_state_dict(cfg, 0))
+    length = 3 * cfg.samplerate
+else:
+    from demucs_amd.htdemucs import HTDemucs
+    from demucs_amd.weights import HTDemucsConfig, synthetic_state_dict
+    cfg = HTDemucsConfig()
+    m = HTDemucs(cfg.sources, max_batch=1, compute_dtype=dtype)
+    m.load_state_dict(synthetic_state_dict(cfg, 0))
+    length = cfg.segment_length
 m.to("cuda").eval()
-mix = torch.from_numpy(synth_mix(3, cfg.segment_length, "tones"))[None].cuda()
+mix = torch.from_numpy(synth_mix(3, length, "tones"))[None].cuda()
 m(mix)
 m.profile_begin()
 out = m(mix)
@@ -183,11 +195,11 @@ with open(sys.argv[1] + ".txt", "w") as f:
 """
 
 
-def _engine_run(tmp_path, tag, env_extra, mode="default"):
+def _engine_run(tmp_path, tag, env_extra, mode="default", dtype="f32", engine="htdemucs"):
     env = {k: v for k, v in os.environ.items() if k != "MI_X6"}
     env.update(env_extra, PYTHONPATH=ROOT)
     out = str(tmp_path / tag)
-    r = subprocess.run([sys.executable, "-c", _ENGINE, out, mode], env=env, capture_output=True, text=True, cwd=ROOT, timeout=600)
+    r = subprocess.run([sys.executable, "-c", _ENGINE, out, mode, dtype, engine], env=env, capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     rows = {}
     for line in open(out + ".txt"):
