@@ -46,6 +46,40 @@ static int get_tables(FftTables *out) {
     return MI_OK;
 }
 
+// One DConv layer of a handle-free test entry on the device: the nine natural-layout tensors as the checkpoint stores them
+// (layers.{d}.0.weight (h, C, 3), .0.bias (h), .1.weight / .1.bias (h), .3.weight (2C, h), .3.bias, .4.weight, .4.bias (2C),
+// .6.scale (C); h = C / 8), packed by dconv_pack_host like Model::load_dconv and uploaded with hipMalloc
+static size_t dconv_layer_floats(int C) { const size_t h = C / 8; return h * C * 3 + 3 * h + 2 * C * h + 6 * (size_t)C + C; }
+struct DConvTestLayer {
+    std::vector<void *> bufs;
+    DConvTimeLayer l{};
+    ~DConvTestLayer() { for (void *p : bufs) (void)hipFree(p); }
+    template <typename T> int up(const T *h, size_t n, const T **out) {
+        void *p = nullptr;
+        MI_HIP(hipMalloc(&p, n * sizeof(T)));
+        bufs.push_back(p);
+        MI_HIP(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice));
+        *out = (const T *)p;
+        return MI_OK;
+    }
+    int init(int C, const float *w) {
+        const int h = C / 8;
+        const float *w0 = w, *b0 = w0 + (size_t)h * C * 3, *g1w = b0 + h, *g1b = g1w + h, *w3 = g1b + h, *b3 = w3 + (size_t)2 * C * h,
+                    *g2w = b3 + 2 * C, *g2b = g2w + 2 * C, *ls = g2b + 2 * C;
+        const DConvHostPack p = dconv_pack_host(C, h, w0, b0, g1w, g1b, w3, b3);
+        MI_TRY(up(p.w0.data(), p.w0.size(), &l.w.w0)); MI_TRY(up(p.b0.data(), p.b0.size(), &l.w.b0));
+        MI_TRY(up(p.g1w.data(), p.g1w.size(), &l.w.g1w)); MI_TRY(up(p.g1b.data(), p.g1b.size(), &l.w.g1b));
+        MI_TRY(up(p.w3.data(), p.w3.size(), &l.w.w3));
+        MI_TRY(up(b3, (size_t)2 * C, &l.w.b3)); MI_TRY(up(g2w, (size_t)2 * C, &l.w.g2w)); MI_TRY(up(g2b, (size_t)2 * C, &l.w.g2b));
+        MI_TRY(up(ls, (size_t)C, &l.w.ls));
+        MI_TRY(up(p.gram_a.data(), p.gram_a.size(), &l.gram_a)); MI_TRY(up(p.gram_v.data(), p.gram_v.size(), &l.gram_v));
+        MI_TRY(up(p.gram_c.data(), p.gram_c.size(), &l.gram_c)); MI_TRY(up(p.gram_e1.data(), p.gram_e1.size(), &l.gram_e1));
+        MI_TRY(up(p.gram_e2.data(), p.gram_e2.size(), &l.gram_e2));
+        l.sum_b3 = p.sum_b3; l.sum_b3sq = p.sum_b3sq;
+        return MI_OK;
+    }
+};
+
 }  // namespace mi
 
 using namespace mi;
@@ -635,6 +669,48 @@ int mi_row_affine_pitch(const float *x_dev, int32_t B, int32_t C, int32_t L, int
     MI_REQUIRE(x_dev && norm_dev && y_dev && B > 0 && C > 0 && (int64_t)B * C <= 65535 && L > 0 && out_pitch >= L,
                "mi_row_affine_pitch: bad argument");
     return launch_row_affine_pitch(x_dev, B, C, L, out_pitch, (const float2 *)norm_dev, y_dev, (hipStream_t)stream);
+}
+
+// ---- test entries of the fused DConv kernels (dconv_row.hip, dconv_time.hip): argument checks, the engine's packing, the launcher
+int mi_dconv_row(const float *x_dev, float *y_dev, int32_t B, int32_t C, int32_t Fr, int32_t T, const float *weights_host, int32_t variant,
+                 void *stream) {
+    MI_REQUIRE(x_dev && y_dev && weights_host && B > 0 && Fr > 0 && (int64_t)B * Fr <= (1 << 24), "mi_dconv_row: bad argument");
+    MI_REQUIRE(((uintptr_t)x_dev & 7) == 0 && ((uintptr_t)y_dev & 7) == 0, "mi_dconv_row: tensors must be 8-byte aligned");
+    MI_REQUIRE(dconv_row_supported(C, T), "mi_dconv_row: C = %d must be 48 or 96, T = %d a multiple of 6 up to 384", C, T);
+    MI_REQUIRE(variant == 0 || variant == 1, "mi_dconv_row: variant 0 (one wave per row) or 1 (LDS-resident row)");
+    MI_REQUIRE(variant == 0 || dconv_row_lds_supported(C, T), "mi_dconv_row: the LDS-resident kernel does not take C = %d, T = %d", C, T);
+    const int64_t n = (int64_t)B * C * Fr * T;
+    MI_REQUIRE(x_dev == y_dev || x_dev + n <= y_dev || y_dev + n <= x_dev, "mi_dconv_row: y must be x itself or not overlap it");
+    DConvTestLayer l0, l1;
+    MI_TRY(l0.init(C, weights_host));
+    MI_TRY(l1.init(C, weights_host + dconv_layer_floats(C)));
+    hipStream_t st = (hipStream_t)stream;
+    const DConvRowArgs a{{l0.l, l1.l}, x_dev, y_dev, Fr, T};
+    int r = launch_dconv_row(a, C, B * Fr, variant == 1, st);
+    const hipError_t e = hipStreamSynchronize(st);           // the weights are freed on return
+    if (e != hipSuccess && r == MI_OK) r = set_error(MI_EHIP, "mi_dconv_row: hipStreamSynchronize: %s", hipGetErrorString(e));
+    return r;
+}
+
+int mi_dconv_time_layer(const float *x_dev, float *y_dev, int32_t B, int32_t C, int32_t Lv, int32_t Lp, int32_t dil,
+                        const float *weights_host, float *hbuf_dev, double *stats_dev, double *gram_dev, float *st_dev, void *stream) {
+    MI_REQUIRE(x_dev && y_dev && weights_host && hbuf_dev && stats_dev && gram_dev && st_dev, "mi_dconv_time_layer: null argument");
+    MI_REQUIRE(B >= 1 && B <= 65535, "mi_dconv_time_layer: B = %d outside [1, 65535] (the grid's y range)", B);
+    MI_REQUIRE(dconv_time_supported(C, Lp) && Lv >= 1 && Lp >= Lv, "mi_dconv_time_layer: C = %d must be 48 or 96, Lp = %d even and >= Lv = %d >= 1",
+               C, Lp, Lv);
+    MI_REQUIRE(dil == 1 || dil == 2, "mi_dconv_time_layer: dilation %d (1 or 2)", dil);
+    MI_REQUIRE((((uintptr_t)x_dev | (uintptr_t)y_dev | (uintptr_t)hbuf_dev | (uintptr_t)stats_dev | (uintptr_t)gram_dev | (uintptr_t)st_dev) & 7) == 0,
+               "mi_dconv_time_layer: buffers must be 8-byte aligned");
+    const int64_t n = (int64_t)B * C * Lp;
+    MI_REQUIRE(x_dev + n <= y_dev || y_dev + n <= x_dev, "mi_dconv_time_layer: y must not overlap x");
+    DConvTestLayer l;
+    MI_TRY(l.init(C, weights_host));
+    hipStream_t st = (hipStream_t)stream;
+    float2 *st1 = (float2 *)st_dev;
+    int r = launch_dconv_time_layer(l.l, C, dil, B, Lv, Lp, x_dev, y_dev, hbuf_dev, stats_dev, gram_dev, st1, st1 + B, st);
+    const hipError_t e = hipStreamSynchronize(st);           // the weights are freed on return
+    if (e != hipSuccess && r == MI_OK) r = set_error(MI_EHIP, "mi_dconv_time_layer: hipStreamSynchronize: %s", hipGetErrorString(e));
+    return r;
 }
 
 }  // extern "C"

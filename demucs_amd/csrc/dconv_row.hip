@@ -114,14 +114,14 @@ __device__ __forceinline__ void dconv_row_layer(const DConvTimeLayer &LT, const 
         }
     }
     // ---- GroupNorm(1, H) over (H, T) + GELU ------------------------------------------------------------------
+    // the lane's own sums in float64 too (the squares are exact there): a float32 sum of 6 H squares in front of s2 - s1 mean loses
+    // mean^2 / var times its rounding -- rstd 1e-5 off at mean^2 / var = 20 (tests/test_gpu_dconv_fused.py, family "offset")
     double s1 = 0.0, s2 = 0.0;
     if (on) {
-        float p1 = 0.f, p2 = 0.f;
 #pragma unroll
         for (int j = 0; j < kNC; ++j)
 #pragma unroll
-            for (int m = 0; m < H; ++m) { const float hv = hid[j][m >> 1][m & 1]; p1 += hv; p2 += hv * hv; }
-        s1 = p1; s2 = p2;
+            for (int m = 0; m < H; ++m) { const double hv = (double)hid[j][m >> 1][m & 1]; s1 += hv; s2 += hv * hv; }
     }
     wave_sum2(s1, s2);
     float g[kNC][HA];
@@ -312,13 +312,11 @@ __device__ __forceinline__ void dconv_rowlds_layer(const DConvTimeLayer &LT, flo
         }
     // ---- GroupNorm(1, H) over (H, T) + GELU: every wave holds the whole hidden row ------------------------------------------------
     double s1 = 0.0, s2 = 0.0;
-    if (on) {
-        float p1 = 0.f, p2 = 0.f;
+    if (on) {                               // float64 lane sums as in dconv_row_layer
 #pragma unroll
         for (int j = 0; j < kNC; ++j)
 #pragma unroll
-            for (int m = 0; m < H; ++m) { p1 += hv[j][m]; p2 += hv[j][m] * hv[j][m]; }
-        s1 = p1; s2 = p2;
+            for (int m = 0; m < H; ++m) { const double hd = (double)hv[j][m]; s1 += hd; s2 += hd * hd; }
     }
     wave_sum2(s1, s2);
     float g[kNC][HA];
@@ -469,18 +467,55 @@ __global__ __launch_bounds__(256) void dconv_rowlds_kernel(const DConvRowArgs a,
     }
 }
 
-bool dconv_row_supported(int C, int T) { return (C == 48 || C == 96) && T % kNC == 0 && T % 2 == 0 && T / kNC <= 64; }
+bool dconv_row_supported(int C, int T) { return (C == 48 || C == 96) && T > 0 && T % kNC == 0 && T % 2 == 0 && T / kNC <= 64; }
+bool dconv_row_lds_supported(int C, int T) { return C == 48 && dconv_row_supported(C, T) && T <= kRowLdsT; }
 
-int launch_dconv_row(const DConvRowArgs &a, int C, int rows, hipStream_t st) {
-    MI_REQUIRE(dconv_row_supported(C, a.T), "dconv_row: unsupported C=%d T=%d", C, a.T);
+DConvHostPack dconv_pack_host(int C, int h, const float *w0, const float *b0, const float *g1w, const float *g1b, const float *w3,
+                              const float *b3) {
+    const int HA = (h + 3) / 4 * 4;              // hidden index fastest, padded to a multiple of 4
+    DConvHostPack p;
+    p.w0.assign((size_t)C * 3 * HA, 0.f); p.b0.assign(HA, 0.f); p.g1w.assign(HA, 0.f); p.g1b.assign(HA, 0.f);
+    p.w3.assign((size_t)2 * C * HA, 0.f);
+    for (int m = 0; m < h; ++m) {
+        p.b0[m] = b0[m]; p.g1w[m] = g1w[m]; p.g1b[m] = g1b[m];
+        for (int c = 0; c < C; ++c)
+            for (int tap = 0; tap < 3; ++tap) p.w0[((size_t)c * 3 + tap) * HA + m] = w0[((size_t)m * C + c) * 3 + tap];
+    }
+    for (int m = 0; m < 2 * C; ++m)
+        for (int k = 0; k < h; ++k) p.w3[(size_t)m * HA + k] = w3[(size_t)m * h + k];
+    // second GroupNorm's statistics from the Gram matrix of the hidden activations (dconv_time.hip, dconv_row.hip)
+    p.gram_v.assign(h, 0.0); p.gram_c.assign(h, 0.0);
+    double sb = 0.0, sbq = 0.0;
+    for (int m = 0; m < 2 * C; ++m) { sb += (double)b3[m]; sbq += (double)b3[m] * (double)b3[m]; }
+    p.sum_b3 = sb; p.sum_b3sq = sbq;
+    for (int i = 0; i < h; ++i) {
+        for (int k = i; k < h; ++k) {
+            double a = 0.0;
+            for (int m = 0; m < 2 * C; ++m) a += (double)w3[(size_t)m * h + i] * (double)w3[(size_t)m * h + k];
+            p.gram_a.push_back(k == i ? a : 2.0 * a);
+        }
+        for (int m = 0; m < 2 * C; ++m) {
+            p.gram_v[i] += 2.0 * (double)w3[(size_t)m * h + i] * (double)b3[m];
+            p.gram_c[i] += (double)w3[(size_t)m * h + i];
+        }
+    }
+    // entry order (i, k = i .. h): k < h -> (W3^T W3 term, 0), k == h -> (2 W3^T b3, colsum)
+    for (int i = 0, q = 0; i < h; ++i) {
+        for (int k = i; k < h; ++k) { p.gram_e1.push_back(p.gram_a[q++]); p.gram_e2.push_back(0.0); }
+        p.gram_e1.push_back(p.gram_v[i]); p.gram_e2.push_back(p.gram_c[i]);
+    }
+    return p;
+}
+
+int launch_dconv_row(const DConvRowArgs &a, int C, int rows, bool lds_row, hipStream_t st) {
+    MI_REQUIRE(dconv_row_supported(C, a.T) && rows > 0, "dconv_row: unsupported C=%d T=%d rows=%d", C, a.T, rows);
     MI_REQUIRE(((uintptr_t)a.x & 7) == 0 && ((uintptr_t)a.y & 7) == 0, "dconv_row: tensors must be 8-byte aligned");
     static const int cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
     // C = 48: 4-wave workgroups (40 KiB of LDS: three per CU by LDS, registers allow three waves per SIMD);
     // C = 96: 8-wave workgroups (102 KiB: one per CU, two waves per SIMD as the 200 registers allow)
     // MI_DCONV_ROW=lds selects the LDS-resident kernel (1.0x the algorithmic HBM bytes, but 1.87 ms per level-0 launch against
     // 1.19 ms: one wave per SIMD exposes every LDS / barrier latency, and statistics + GELU are repeated in all four waves)
-    const bool lds_row = switches().dconv_row_lds;
-    if (C == 48 && lds_row && a.T <= kRowLdsT) {
+    if (lds_row && dconv_row_lds_supported(C, a.T)) {
         hipLaunchKernelGGL((dconv_rowlds_kernel<48, 6>), dim3(std::min(rows, cus)), dim3(256), 0, st, a, rows);
     } else if (C == 48) {
         const int nblk = std::min(ceil_div(rows, 4), 3 * cus);

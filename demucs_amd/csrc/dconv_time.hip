@@ -80,20 +80,22 @@ __global__ __launch_bounds__(256) void dconv_t_conv3_kernel(const DConvRowLayer 
             }
         }
     }
-    float p1 = 0.f, p2 = 0.f;
+    // the lane's own sums in float64 too (the squares are exact there): a float32 sum of 6 H squares in front of s2 - s1 mean loses
+    // mean^2 / var times its rounding -- rstd 1e-5 off at mean^2 / var = 20 (tests/test_gpu_dconv_fused.py, family "offset")
+    double p1 = 0.0, p2 = 0.0;
     if (on) {
         float *hb = hbuf + (size_t)b * HA * Lp + t0;
 #pragma unroll
         for (int m = 0; m < H; ++m) {
 #pragma unroll
             for (int j = 0; j < kTC; ++j)
-                if (t0 + j < Lv) { const float v = hid[j][m >> 1][m & 1]; p1 += v; p2 += v * v; }
+                if (t0 + j < Lv) { const double v = (double)hid[j][m >> 1][m & 1]; p1 += v; p2 += v * v; }
 #pragma unroll
             for (int j = 0; j < kTC; j += 2)
                 if (t0 + j < Lp) *reinterpret_cast<float2 *>(hb + (size_t)m * Lp + j) = make_float2(hid[j][m >> 1][m & 1], hid[j + 1][m >> 1][m & 1]);
         }
     }
-    double s1 = wsum((double)p1), s2 = wsum((double)p2);
+    double s1 = wsum(p1), s2 = wsum(p2);
     __shared__ double red[8];
     if ((tid & 63) == 0) { red[(tid >> 6) * 2] = s1; red[(tid >> 6) * 2 + 1] = s2; }
     __syncthreads();

@@ -92,8 +92,20 @@ struct DConvRowArgs {
     float *y;           // same shape (may alias x)
     int Fr, T;
 };
+// The host-side packing of one DConv layer (C channels, h = C / 8 hidden) from the checkpoint's natural-layout tensors -- the one
+// builder for Model::load_dconv and the handle-free test entries (each uploads with its own allocator): w0 (h, C, 3) -> [C][3][HA],
+// b0 / g1w / g1b -> [HA], w3 (2C, h) -> [2C][HA] (HA = h rounded up to 4, padding zero) and the float64 Gram constants of DConvTimeLayer
+struct DConvHostPack {
+    std::vector<float> w0, b0, g1w, g1b, w3;
+    std::vector<double> gram_a, gram_v, gram_c, gram_e1, gram_e2;
+    double sum_b3, sum_b3sq;
+};
+DConvHostPack dconv_pack_host(int C, int h, const float *w0, const float *b0, const float *g1w, const float *g1b, const float *w3,
+                              const float *b3);
 bool dconv_row_supported(int C, int T);
-int launch_dconv_row(const DConvRowArgs &a, int C, int rows, hipStream_t st);
+bool dconv_row_lds_supported(int C, int T);     // what the LDS-resident kernel takes (C = 48)
+// lds_row: the LDS-resident kernel where dconv_row_lds_supported(C, T) (Model passes switches().dconv_row_lds), else the per-wave one
+int launch_dconv_row(const DConvRowArgs &a, int C, int rows, bool lds_row, hipStream_t st);
 
 // dconv_time.hip: fused DConv layer of the time branch (C = 48 / 96), three streaming passes
 bool dconv_time_supported(int C, int Lp);

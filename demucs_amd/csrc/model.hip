@@ -367,46 +367,18 @@ int Model::load_dconv(const WeightTable &wt, const std::string &prefix, int C, i
             MI_TRY(upload(gw, &l.gram_wt)); MI_TRY(upload(gc, &l.gram_ct));
             l.sum_b = sb; l.sum_bsq = sbq;
         }
-        if (dw->has_row || dw->has_time) {          // packing of dconv_row.hip / dconv_time.hip: hidden index fastest, padded to a multiple of 4
-            const int HA = (h + 3) / 4 * 4;
-            std::vector<float> w0r((size_t)C * 3 * HA, 0.f), b0r(HA, 0.f), g1wr(HA, 0.f), g1br(HA, 0.f), w3r((size_t)2 * C * HA, 0.f);
-            for (int m = 0; m < h; ++m) {
-                b0r[m] = b0[m]; g1wr[m] = g1w[m]; g1br[m] = g1b[m];
-                for (int c = 0; c < C; ++c)
-                    for (int tap = 0; tap < 3; ++tap) w0r[((size_t)c * 3 + tap) * HA + m] = w0[((size_t)m * C + c) * 3 + tap];
-            }
-            for (int m = 0; m < 2 * C; ++m)
-                for (int k = 0; k < h; ++k) w3r[(size_t)m * HA + k] = w3[(size_t)m * h + k];
+        if (dw->has_row || dw->has_time) {          // packing of dconv_row.hip / dconv_time.hip (dconv_pack_host: the test entries pack with it too)
+            const DConvHostPack pk = dconv_pack_host(C, h, w0, b0, g1w, g1b, w3, b3);
             float *p0, *p1, *p2, *p3, *p4, *p5, *p6, *p7;
-            MI_TRY(upload(w0r, &p0)); MI_TRY(upload(b0r, &p1)); MI_TRY(upload(g1wr, &p2)); MI_TRY(upload(g1br, &p3));
-            MI_TRY(upload(w3r, &p4));
+            MI_TRY(upload(pk.w0, &p0)); MI_TRY(upload(pk.b0, &p1)); MI_TRY(upload(pk.g1w, &p2)); MI_TRY(upload(pk.g1b, &p3));
+            MI_TRY(upload(pk.w3, &p4));
             MI_TRY(pack_vec(b3, 2 * C, 2 * C, false, &p5)); MI_TRY(pack_vec(g2w, 2 * C, 2 * C, false, &p6));
             MI_TRY(pack_vec(g2b, 2 * C, 2 * C, false, &p7));
             dw->row[d] = DConvRowLayer{p0, p1, p2, p3, p4, p5, p6, p7, l.ls};
-            {     // second GroupNorm's statistics from the Gram matrix of the hidden activations (dconv_time.hip, dconv_row.hip)
-                std::vector<double> ga, gv(h, 0.0), gc(h, 0.0);
-                double sb = 0.0, sbq = 0.0;
-                for (int m = 0; m < 2 * C; ++m) { sb += (double)b3[m]; sbq += (double)b3[m] * (double)b3[m]; }
-                for (int i = 0; i < h; ++i) {
-                    for (int k = i; k < h; ++k) {
-                        double a = 0.0;
-                        for (int m = 0; m < 2 * C; ++m) a += (double)w3[(size_t)m * h + i] * (double)w3[(size_t)m * h + k];
-                        ga.push_back(k == i ? a : 2.0 * a);
-                    }
-                    for (int m = 0; m < 2 * C; ++m) {
-                        gv[i] += 2.0 * (double)w3[(size_t)m * h + i] * (double)b3[m];
-                        gc[i] += (double)w3[(size_t)m * h + i];
-                    }
-                }
-                std::vector<double> e1, e2;          // entry order (i, k = i .. h): k < h -> (W3^T W3 term, 0), k == h -> (2 W3^T b3, colsum)
-                for (int i = 0, q = 0; i < h; ++i) {
-                    for (int k = i; k < h; ++k) { e1.push_back(ga[q++]); e2.push_back(0.0); }
-                    e1.push_back(gv[i]); e2.push_back(gc[i]);
-                }
-                double *da, *dv, *dc, *de1, *de2;
-                MI_TRY(upload(ga, &da)); MI_TRY(upload(gv, &dv)); MI_TRY(upload(gc, &dc)); MI_TRY(upload(e1, &de1)); MI_TRY(upload(e2, &de2));
-                dw->tl[d] = DConvTimeLayer{dw->row[d], da, dv, dc, de1, de2, sb, sbq};
-            }
+            double *da, *dv, *dc, *de1, *de2;
+            MI_TRY(upload(pk.gram_a, &da)); MI_TRY(upload(pk.gram_v, &dv)); MI_TRY(upload(pk.gram_c, &dc));
+            MI_TRY(upload(pk.gram_e1, &de1)); MI_TRY(upload(pk.gram_e2, &de2));
+            dw->tl[d] = DConvTimeLayer{dw->row[d], da, dv, dc, de1, de2, pk.sum_b3, pk.sum_b3sq};
         }
     }
     return MI_OK;
@@ -744,7 +716,7 @@ int Model::run_dconv(const DConvW &w, int C, const Geo &g, float *x, float *tmp,
     if (w.has_row && g.row_mode == 1) {      // both layers in one LDS-resident pass, in place
         DConvRowArgs a{{w.tl[0], w.tl[1]}, x, x, g.D1, g.D2};
         return prof.timed(101, "dconv_row_kernel", 2.0 * 2.0 * (3.0 * C * h + 2.0 * 2 * C * h) * (double)rows * g.D2,
-                          2.0 * 4.0 * C * (double)rows * g.D2, st, [&] { return launch_dconv_row(a, C, rows, st); });
+                          2.0 * 4.0 * C * (double)rows * g.D2, st, [&] { return launch_dconv_row(a, C, rows, switches().dconv_row_lds, st); });
     }
     if (w.has_time && g.row_mode == 0 && g.D1 == 1) {     // time branch, C = 48 / 96: three streaming VALU passes per layer
         return prof.timed(102, "dconv_time_kernels", 2.0 * 2.0 * (3.0 * C * h + 2.0 * C * h) * (double)g.B * g.D2, 2.0 * 4.0 * C * (double)g.B * g.D2, st, [&] {

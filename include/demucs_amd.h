@@ -652,6 +652,29 @@ int mi_blstm_restitch(const float *frames_dev, int32_t B, int32_t C, int32_t T, 
 int mi_row_affine_pitch(const float *x_dev, int32_t B, int32_t C, int32_t L, int32_t out_pitch, const float *norm_dev, float *y_dev,
                         void *stream);
 
+/* ---- Kernel-level test entries of the fused DConv kernels (dconv_row.hip, dconv_time.hip).  A DConv residual layer
+ * (demucs/demucs.py:133-154) is conv1d(C -> C / 8, k = 3, dilation d, padding d) -> GroupNorm(1) -> GELU -> conv1d(C / 8 -> 2C, k = 1) ->
+ * GroupNorm(1) -> GLU -> LayerScale -> + x.  `weights_host` is a HOST array holding, per layer, its nine tensors in the checkpoint's
+ * natural layout, concatenated in this order (h = C / 8): 0.weight (h, C, 3), 0.bias (h), 1.weight (h), 1.bias (h), 3.weight (2C, h),
+ * 3.bias (2C), 4.weight (2C), 4.bias (2C), 6.scale (C).  The entries pack them with the function Model uses, upload, call the launcher
+ * the engine calls and wait for the stream (synchronous).  C = 48 or 96. ---- */
+
+/* Both layers (d = 1, then d = 2) of the frequency branch on every (b, fr) row of x (B, C, Fr, T): weights_host = layer 0 then layer 1.
+ *   T a multiple of 6, at most 384; x and y 8-byte aligned; y_dev may be x_dev itself (as the engine runs it) or must not overlap it.
+ *   variant 0: one wave per row (the default kernel); variant 1: the LDS-resident kernel (MI_DCONV_ROW=lds), C = 48 only -- what
+ *   it does not take is refused, not rerouted. */
+int mi_dconv_row(const float *x_dev, float *y_dev, int32_t B, int32_t C, int32_t Fr, int32_t T, const float *weights_host, int32_t variant,
+                 void *stream);
+
+/* One layer of dilation dil (1 or 2) of the time branch on x (B, C, Lp): Lv valid columns per row of pitch Lp (Lp even, Lp >= Lv >= 1),
+ *   1 <= B <= 65535; y (B, C, Lp) must not overlap x.  Columns Lv .. Lp - 1 of x are never used; those of y are unspecified.
+ *   The caller owns the workspace, all of it 8-byte aligned:
+ *     hbuf_dev   B * HA * Lp floats (HA = C / 8 rounded up to 4): the hidden tensor, any contents on entry;
+ *     stats_dev  B * 32 * 2 doubles and gram_dev B * 32 * 96 doubles: ZERO on entry and zero again on return;
+ *     st_dev     2 * B (mean, rstd) float pairs, written: [0, B) the first GroupNorm's statistics, [B, 2B) the second's. */
+int mi_dconv_time_layer(const float *x_dev, float *y_dev, int32_t B, int32_t C, int32_t Lv, int32_t Lp, int32_t dil,
+                        const float *weights_host, float *hbuf_dev, double *stats_dev, double *gram_dev, float *st_dev, void *stream);
+
 /* Debug aid: `hook(stream)` is called after every kernel launch the library makes (NULL switches it off).  Used by
  * tools/micro/poison_all.py to interleave a register / LDS poisoning kernel between the engine's kernels. */
 void mi_debug_set_post_launch_hook(void (*hook)(void *stream));
