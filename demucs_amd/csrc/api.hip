@@ -80,6 +80,43 @@ struct DConvTestLayer {
     }
 };
 
+// Scratch of the handle-free transform / normalisation entries: freed on return, after the stream has been waited for
+struct TestScratch {
+    std::vector<void *> bufs;
+    ~TestScratch() { for (void *p : bufs) (void)hipFree(p); }
+    template <typename T> int get(size_t n, T **out) {
+        void *p = nullptr;
+        MI_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        bufs.push_back(p);
+        *out = (T *)p;
+        return MI_OK;
+    }
+};
+// the stream is waited for before the scratch goes: a failure of the wait is the call's failure
+static int finish_entry(int r, hipStream_t st, const char *who) {
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess && r == MI_OK) r = set_error(MI_EHIP, "%s: hipStreamSynchronize: %s", who, hipGetErrorString(e));
+    return r;
+}
+
+// STFT frames (+ float64 statistics) -> [finalize mode 1 -> (norm, denorm)] -> transpose to the conv layout, normalised when norm_dev
+// is given: the sequence of Model::forward / HModel::forward
+static int stft_entry(const char *who, const float *mix_dev, int B, int L, float *x_dev, int x_pitch, float *norm_dev, float *denorm_dev,
+                      hipStream_t st) {
+    FftTables tb;
+    MI_TRY(get_tables(&tb));
+    const int T = (L + 1023) / 1024;
+    TestScratch ws;
+    float *zt = nullptr; double *stats = nullptr;
+    MI_TRY(ws.get((size_t)B * T * 4 * 2048, &zt));
+    MI_TRY(ws.get((size_t)2 * kStatSlots * B, &stats));
+    MI_HIP(hipMemsetAsync(stats, 0, sizeof(double) * 2 * kStatSlots * B, st));
+    int r = launch_stft_frames(mix_dev, B, L, tb, zt, stats, st);
+    if (r == MI_OK && norm_dev) r = launch_finalize_stats(stats, B, 4.0 * 2048 * T, 1e-5f, 1, (float2 *)norm_dev, (float2 *)denorm_dev, st);
+    if (r == MI_OK) r = launch_cac_transpose(zt, B, T, (const float2 *)norm_dev, x_dev, st, x_pitch);
+    return finish_entry(r, st, who);
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -421,36 +458,66 @@ int mi_deliver_resample_pcm(const int64_t *table_dev, int32_t n_rows, int64_t ma
 // Kernel-level entry points.  They allocate their scratch with hipMalloc and free it after a
 // stream synchronise: convenient for parity tests, not meant for the hot loop.
 int mi_stft_cac(const float *mix_dev, int32_t B, int32_t L, float *cac_dev, void *stream) {
-    MI_REQUIRE(mix_dev && cac_dev && B > 0 && L > 4096, "mi_stft_cac: bad argument");
+    MI_REQUIRE(mix_dev && cac_dev && B > 0 && B <= 16383 && L >= 1, "mi_stft_cac: bad argument");
+    return stft_entry("mi_stft_cac", mix_dev, B, L, cac_dev, 0, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int mi_stft_norm(const float *mix_dev, int32_t B, int32_t L, float *x_dev, int32_t x_pitch, float *norm_dev, float *denorm_dev, void *stream) {
+    MI_REQUIRE(mix_dev && x_dev && norm_dev && denorm_dev, "mi_stft_norm: null argument");
+    MI_REQUIRE(B >= 1 && B <= 16383, "mi_stft_norm: B = %d outside [1, 16383] (the transpose's grid holds 4 B planes)", B);
+    MI_REQUIRE(L >= 1, "mi_stft_norm: L = %d, at least one sample", L);
+    const int T = (L + 1023) / 1024;
+    MI_REQUIRE(x_pitch == 0 || x_pitch >= T, "mi_stft_norm: row pitch %d below T = %d", x_pitch, T);
+    return stft_entry("mi_stft_norm", mix_dev, B, L, x_dev, x_pitch, norm_dev, denorm_dev, (hipStream_t)stream);
+}
+
+int mi_istft_full(const float *y_dev, int32_t B, int32_t S, int32_t L, int32_t y_pitch, const float *denorm_f_dev, const float *xt_dev,
+                  int32_t xt_pitch, const float *denorm_t_dev, float *wav_dev, void *stream) {
+    MI_REQUIRE(y_dev && wav_dev, "mi_istft_full: null argument");
+    MI_REQUIRE(B >= 1 && S >= 1 && (int64_t)B * S <= 16383, "mi_istft_full: B = %d, S = %d: 1 <= B S <= 16383 (the transpose's grid holds 4 B S planes)",
+               B, S);
+    MI_REQUIRE(L >= 1, "mi_istft_full: L = %d, at least one sample", L);
+    const int T = (L + 1023) / 1024;
+    MI_REQUIRE(y_pitch == 0 || y_pitch >= T, "mi_istft_full: spectrogram row pitch %d below T = %d", y_pitch, T);
+    MI_REQUIRE((xt_dev != nullptr) == (denorm_t_dev != nullptr), "mi_istft_full: xt_dev and denorm_t_dev go together");
+    MI_REQUIRE(xt_pitch == 0 || xt_pitch >= L, "mi_istft_full: time-branch row pitch %d below L = %d", xt_pitch, L);
     FftTables tb;
     MI_TRY(get_tables(&tb));
-    const int T = (L + 1023) / 1024;
-    float *zt = nullptr; double *stats = nullptr;
-    MI_HIP(hipMalloc((void **)&zt, (size_t)B * T * 4 * 2048 * 4));
-    MI_HIP(hipMalloc((void **)&stats, sizeof(double) * 2 * kStatSlots * B));
+    TestScratch ws;
+    float *yt = nullptr, *fr = nullptr;
+    MI_TRY(ws.get((size_t)B * S * T * 4 * 2048, &yt));
+    MI_TRY(ws.get((size_t)B * S * T * 2 * 4096, &fr));
     hipStream_t st = (hipStream_t)stream;
-    int r = MI_OK;
-    if (hipMemsetAsync(stats, 0, sizeof(double) * 2 * kStatSlots * B, st) != hipSuccess) r = set_error(MI_EHIP, "memset failed");
-    if (r == MI_OK) r = launch_stft_frames(mix_dev, B, L, tb, zt, stats, st);
-    if (r == MI_OK) r = launch_cac_transpose(zt, B, T, nullptr, cac_dev, st);
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(zt); (void)hipFree(stats);
-    return r;
+    const int r = launch_istft(y_dev, B, S, L, (const float2 *)denorm_f_dev, xt_dev, (const float2 *)denorm_t_dev, tb, yt, fr, wav_dev, st,
+                               xt_pitch, y_pitch);
+    return finish_entry(r, st, "mi_istft_full");
 }
 
 int mi_istft_cac(const float *x_dev, int32_t B, int32_t S, int32_t L, float *wav_dev, void *stream) {
-    MI_REQUIRE(x_dev && wav_dev && B > 0 && S > 0 && L > 4096, "mi_istft_cac: bad argument");
-    FftTables tb;
-    MI_TRY(get_tables(&tb));
-    const int T = (L + 1023) / 1024;
-    float *yt = nullptr, *fr = nullptr;
-    MI_HIP(hipMalloc((void **)&yt, (size_t)B * S * T * 4 * 2048 * 4));
-    MI_HIP(hipMalloc((void **)&fr, (size_t)B * S * T * 2 * 4096 * 4));
+    MI_REQUIRE(x_dev && wav_dev && B > 0 && S > 0 && (int64_t)B * S <= 16383 && L >= 1, "mi_istft_cac: bad argument");
+    return mi_istft_full(x_dev, B, S, L, 0, nullptr, nullptr, 0, nullptr, wav_dev, stream);
+}
+
+// the per-item normalisation of the waveform (Model::forward): row_stats -> finalize mode 1 -> row_affine
+int mi_item_norm(const float *x_dev, int32_t rows, int64_t count, float *y_dev, float *norm_dev, float *denorm_dev, void *stream) {
+    MI_REQUIRE(x_dev && y_dev && norm_dev && denorm_dev, "mi_item_norm: null argument");
+    MI_REQUIRE(rows >= 1 && rows <= 65535, "mi_item_norm: rows = %d outside [1, 65535] (the grid's y range)", rows);
+    MI_REQUIRE(count >= 2, "mi_item_norm: count = %lld: the unbiased std divides by count - 1", (long long)count);
+    TestScratch ws;
+    double *stats = nullptr;
+    MI_TRY(ws.get((size_t)2 * kStatSlots * rows, &stats));
     hipStream_t st = (hipStream_t)stream;
-    const int r = launch_istft(x_dev, B, S, L, nullptr, nullptr, nullptr, tb, yt, fr, wav_dev, st);
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(yt); (void)hipFree(fr);
-    return r;
+    MI_HIP(hipMemsetAsync(stats, 0, sizeof(double) * 2 * kStatSlots * rows, st));
+    int r = launch_row_stats(x_dev, rows, count, count, stats, st);
+    if (r == MI_OK) r = launch_finalize_stats(stats, rows, (double)count, 1e-5f, 1, (float2 *)norm_dev, (float2 *)denorm_dev, st);
+    if (r == MI_OK) r = launch_row_affine(x_dev, rows, count, (const float2 *)norm_dev, y_dev, st);
+    return finish_entry(r, st, "mi_item_norm");
+}
+
+int mi_item_denorm(const float *x_dev, int32_t rows, int64_t count, const float *denorm_dev, float *y_dev, void *stream) {
+    MI_REQUIRE(x_dev && denorm_dev && y_dev, "mi_item_denorm: null argument");
+    MI_REQUIRE(rows >= 1 && rows <= 65535 && count >= 1, "mi_item_denorm: rows = %d outside [1, 65535] or count = %lld < 1", rows, (long long)count);
+    return launch_row_denorm(x_dev, rows, count, (const float2 *)denorm_dev, y_dev, (hipStream_t)stream);
 }
 
 int mi_conv_forward(const struct mi_conv_desc *desc, void *stream) {

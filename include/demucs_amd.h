@@ -503,6 +503,29 @@ int mi_stft_cac(const float *mix_dev, int32_t B, int32_t L, float *cac_dev, void
  *   x_dev (B,S,4,2048,T) -> wav_dev (B,S,2,L) with T = ceil(L/1024). */
 int mi_istft_cac(const float *x_dev, int32_t B, int32_t S, int32_t L, float *wav_dev, void *stream);
 
+/* The same transforms with everything the forwards pass to them, and the per-item normalisation around them (norms.hip), for
+ * kernel-level parity tests: the entries allocate their scratch, call the launchers the engine calls and wait for the stream
+ * (synchronous).  Any L >= 1 (mi_stft_cac / mi_istft_cac too): below 2 560 samples pad1d's short-input rule (demucs/hdemucs.py:29-36)
+ * zero-pads before it reflects.  T = ceil(L / 1024); 1 <= B (B S) <= 16383.
+ *
+ * mi_stft_norm: `_magnitude(_spec(mix))`, then `(x - mean) / (1e-5 + std)` over each item (demucs/htdemucs.py:545-548), as the
+ *   forwards run it: frames + float64 statistics, finalisation (unbiased std), normalising transpose.
+ *   mix_dev (B,2,L) -> x_dev (B,4,2048,x_pitch), columns T .. x_pitch - 1 untouched; x_pitch = 0 means T, otherwise >= T.
+ *   norm_dev receives B pairs (mean, 1 / (1e-5 + std)), denorm_dev B pairs (mean, std). */
+int mi_stft_norm(const float *mix_dev, int32_t B, int32_t L, float *x_dev, int32_t x_pitch, float *norm_dev, float *denorm_dev, void *stream);
+/* mi_istft_full: `_ispec(_mask(z, y * std + mean), length)` + `xt * std_t + mean_t` (demucs/htdemucs.py:625-656):
+ *   y_dev (B,S,4,2048,y_pitch) (0 = T, otherwise >= T), denorm_f_dev B pairs (mean, std) or NULL (no de-normalisation),
+ *   xt_dev (B,S,2,xt_pitch) (0 = L, otherwise >= L) with denorm_t_dev B pairs (mean_t, std_t): both or neither;
+ *   -> wav_dev (B,S,2,L). */
+int mi_istft_full(const float *y_dev, int32_t B, int32_t S, int32_t L, int32_t y_pitch, const float *denorm_f_dev, const float *xt_dev,
+                  int32_t xt_pitch, const float *denorm_t_dev, float *wav_dev, void *stream);
+/* mi_item_norm: `(x - mean) / (1e-5 + std)` over each of `rows` contiguous rows of `count` >= 2 floats (the time branch's input,
+ *   demucs/htdemucs.py:551-554; std unbiased): statistics, finalisation, apply.  x_dev -> y_dev (rows, count); norm_dev receives
+ *   `rows` pairs (mean, 1 / (1e-5 + std)), denorm_dev (mean, std).  1 <= rows <= 65535.
+ * mi_item_denorm: `x * std + mean` per row with denorm_dev = `rows` pairs (mean, std) (htdemucs.py:626,656); not synchronous. */
+int mi_item_norm(const float *x_dev, int32_t rows, int64_t count, float *y_dev, float *norm_dev, float *denorm_dev, void *stream);
+int mi_item_denorm(const float *x_dev, int32_t rows, int64_t count, const float *denorm_dev, float *y_dev, void *stream);
+
 /* Generic convolution / linear layer evaluated by the implicit-GEMM MFMA kernel (stands in for
  *   F.conv1d / F.conv2d / F.conv_transpose / F.linear as invoked at demucs/hdemucs.py:110,116,
  *   136,153,287,294,313,326, demucs/demucs.py:138,140, demucs/htdemucs.py:589-599).
