@@ -49,6 +49,10 @@ enum mi_epilogue {
 /* MI_FLAG_IMG on a CONVTR epilogue (half modes): the scattered result goes to `yh` as the operand image
  * [Cout / 8][yh_n positions][8] of the NEXT layer's k x k conv (position = b * y_cstride + scattered index); y is not written */
 
+/* mi_conv_desc.sink: the dump words of masked stores, then the zero page the loaders read (16-byte aligned) */
+#define MI_SINK_FLOATS 256
+#define MI_ZERO_PAGE_FLOATS 64
+
 typedef struct mi_ktab_entry {
     int32_t off; /* element offset added to the column base: ci*chan_stride + d1*D2 + d2 */
     int32_t d1;  /* i1 = o1*S1 + d1 must lie in [0, D1)                                   */
@@ -90,7 +94,10 @@ typedef struct mi_conv_desc {
                                o2 >= o2_valid are computed but never stored nor counted): lets rows whose length is
                                not a multiple of 4 keep 16-byte aligned starts and use the float4 loader            */
     int32_t ktab_len;       /* entries in ktab (0 = Kpad): the half-precision main loop steps K by 32 and needs Kpad rounded up to 32 */
-    float *sink;            /* >= 256 floats that out-of-range epilogue stores are diverted to; NULL = library-owned */
+    float *sink;            /* NULL = library-owned; else MI_SINK_FLOATS floats that out-of-range epilogue stores are diverted to (any
+                               contents), followed by MI_ZERO_PAGE_FLOATS floats that HOLD ZERO AND STAY ZERO: the kernels read
+                               sink + MI_SINK_FLOATS as the source of every out-of-tensor load (columns past N, k past K, conv padding)
+                               and never store there */
     const void *wx;         /* NULL, or the weights as the split-bf16 tile image of mi_conv_pack_split for THIS tile_m:
                                selects the 6-product bf16 MFMA main loop (gemm_x6.hip) for tile_m 64 / 96 / 128     */
     int32_t tr_stride;      /* CONVTR: 0 (= 4, crop 2: ConvTranspose k = 8, s = 4 with the reference's crop folded in), 4 or 2 */

@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_dma_kernel(const mi_conv_des
     const float *asrc = d.wt + (size_t)r0 * d.Mpad + m0 + c4;
     const size_t a_row2 = (size_t)2 * d.Mpad, a_step = (size_t)BK * d.Mpad;
     const ColInfo lc = decompose(n0 + c4, N, P, d.O2, d.O2);
-    const float *bsrc = lc.valid ? d.x + (size_t)lc.b * d.x_bstride + lc.p + (size_t)r0 * P : d.sink + 256;
+    const float *bsrc = lc.valid ? d.x + (size_t)lc.b * d.x_bstride + lc.p + (size_t)r0 * P : d.sink + MI_SINK_FLOATS;
     const size_t b_row2 = lc.valid ? (size_t)2 * P : 0, b_step = lc.valid ? (size_t)BK * P : 0;
 
 #define MI_DMA_TILE(kt, stage)                                                                                  \
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_dmatap_kernel(const mi_conv_
     constexpr int K2 = 3;                                    // NT = 9 (3 x 3) or 3 (k = 3): divisions by constants
     const int x_ld = d.x_ld ? d.x_ld : d.D2;
     const int64_t chan = (int64_t)d.D1 * x_ld;               // input channel stride
-    const float *zero = d.sink + 256;
+    const float *zero = d.sink + MI_SINK_FLOATS;
 
     // ---- A: this wave's transfers of every K step ------------------------------------------------------------------------------
     // BM = 128: two transfers of two 128-float rows each (rows 4 wave + 2 j + (lane >> 5)); BM = 96: transfer q moves floats
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_dmarow_kernel(const mi_conv_
     const int P = d.O1 * d.O2;
     const int o2v = d.o2_valid ? d.o2_valid : d.O2;
     const int x_ld = d.x_ld ? d.x_ld : d.D2;
-    const float *zero = d.sink + 256;
+    const float *zero = d.sink + MI_SINK_FLOATS;
 
     // ---- A: the [16][BM] image of a K step is BM / 16 transfers of 1 KiB: BM = 128: two per wave (two 128-float rows each);
     //      BM = 96: six (waves 0, 1 two, waves 2, 3 one); BM = 64: one per wave.  Transfer q moves floats [256 q, 256 q + 256)
@@ -591,13 +591,13 @@ int conv_pick_tile(int M) {
     return 128;
 }
 
-// 256-float dump for the epilogue's out-of-range stores (one word per thread), shared by all launches
-// ... followed by 64 floats that stay zero (source of the LDS-DMA loader for out-of-range columns)
+// MI_SINK_FLOATS-float dump for the epilogue's out-of-range stores (thread tid writes word tid % MI_SINK_FLOATS), shared by all
+// launches, followed by MI_ZERO_PAGE_FLOATS floats that stay zero (source of the LDS-DMA loader for out-of-range columns)
 static float *conv_sink() {
     static float *p = nullptr;
     if (!p) {
-        if (hipMalloc((void **)&p, 320 * sizeof(float)) != hipSuccess) { p = nullptr; return nullptr; }
-        (void)hipMemset(p, 0, 320 * sizeof(float));
+        if (hipMalloc((void **)&p, (MI_SINK_FLOATS + MI_ZERO_PAGE_FLOATS) * sizeof(float)) != hipSuccess) { p = nullptr; return nullptr; }
+        (void)hipMemset(p, 0, (MI_SINK_FLOATS + MI_ZERO_PAGE_FLOATS) * sizeof(float));
     }
     return p;
 }
@@ -606,7 +606,7 @@ static float *conv_sink() {
 // 256 bytes of zeros in device memory (the tail of the sink): source of LDS-DMA loads that fall outside a tensor
 const void *conv_zero_page() {
     float *p = conv_sink();
-    return p ? p + 256 : nullptr;
+    return p ? p + MI_SINK_FLOATS : nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -663,7 +663,8 @@ ConvRoute conv_route(const mi_conv_desc &d) {
     const int tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M);
     // plain fast path: a 1x1 / linear layer whose gather is the identity
     const int64_t P = (int64_t)d.O1 * d.O2;
-    const bool plain = d.plain && d.K == d.Kpad && P % 4 == 0 && d.x_bstride % 4 == 0 && ((uintptr_t)d.x & 15) == 0 &&
+    // (an operand-image input is never read through x: the float4 loader's conditions on K, P and x do not apply to it)
+    const bool plain = d.plain && (d.xh || (d.K == d.Kpad && P % 4 == 0 && d.x_bstride % 4 == 0 && ((uintptr_t)d.x & 15) == 0)) &&
                        d.S1 == 1 && d.S2 == 1 && d.D1 == d.O1 && (d.x_ld ? d.x_ld : d.D2) == d.O2;
     if (d.wtap) return {MI_ROUTE_TAP_HALF, tile, plain};
     if (d.half) return {MI_ROUTE_HALF, tile, plain};
@@ -689,7 +690,7 @@ ConvRoute conv_route(const mi_conv_desc &d) {
 int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     mi_conv_desc d = din;
     if (!d.sink) d.sink = conv_sink();
-    MI_REQUIRE(d.sink, "conv: could not allocate the store sink");
+    MI_REQUIRE(d.sink && ((uintptr_t)d.sink & 15) == 0, "conv: the store sink could not be allocated or is not 16-byte aligned");
     MI_REQUIRE((int64_t)d.Mpad * d.y_cstride < (1ll << 31), "conv: output channel stride too large for 32-bit row offsets");
     MI_REQUIRE(d.Kpad % BK == 0 && d.Kpad >= BK, "conv: Kpad %d must be a positive multiple of %d", d.Kpad, BK);
     MI_REQUIRE(d.Mpad % 4 == 0, "conv: Mpad %d must be a multiple of 4", d.Mpad);

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256, (WM * TM * TN <= 3 ? 3 : 2)) void conv_gemm_ha
             _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                           \
                 const int c = (kt) * HK + 16 * (i >> 1) + 2 * pg + (i & 1);                           \
                 const bool ok = pc.valid && c < d.K;                                                  \
-                const float4 t4 = *reinterpret_cast<const float4 *>(ok ? pcol + (size_t)c * P : d.sink + 256);          \
+                const float4 t4 = *reinterpret_cast<const float4 *>(ok ? pcol + (size_t)c * P : d.sink + MI_SINK_FLOATS);          \
                 pq4[S][i][0] = t4.x; pq4[S][i][1] = t4.y; pq4[S][i][2] = t4.z; pq4[S][i][3] = t4.w;                      \
             }                                                                                         \
         } else {                                                                                      \
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_half_img_kernel(const mi_con
     // B: this wave moves octet `wave` of the K step, columns [0, 64) and [64, 128) of the tile; columns outside the tensor
     // and octets past K come from the zero page
     const uint4 *xh = reinterpret_cast<const uint4 *>(d.xh);
-    const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + 256);
+    const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + MI_SINK_FLOATS);
     const bool c0 = n0 + lane < N, c1 = n0 + 64 + lane < N;
     const uint4 *b0 = xh + (size_t)wave * d.xh_n + n0 + lane;
     const size_t b_step = (size_t)4 * d.xh_n;
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_half_img256_kernel(const mi_
     // rows 128 (w & 1) + 64 j); B: the same over 256 columns.  Bases are wave-uniform, the lane offset is 16 lane.
     const uint4 *wh = reinterpret_cast<const uint4 *>(d.wh);
     const uint4 *xh = reinterpret_cast<const uint4 *>(d.xh);
-    const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + 256);
+    const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + MI_SINK_FLOATS);
     const int oct = wave >> 1, half = wave & 1;
     const uint4 *abase = wh + (size_t)oct * d.Mpad + m0 + 128 * half;
     const uint4 *bbase = xh + (size_t)oct * d.xh_n + n0 + 128 * half;
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_half_img256_kernel(const mi_
         stage = (stage + 1) & 3;
     }
 #undef MI_IMG2_TILE
-    conv_epilogue<TM, TN, MI_EPI_LINEAR, LFLAGS>(d, acc, m0, n0, wm, wn, N, P, o2v);
+    conv_epilogue<TM, TN, MI_EPI_LINEAR, LFLAGS, 512>(d, acc, m0, n0, wm, wn, N, P, o2v);
 }
 
 template <int HT, int LFLAGS>

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_half_tap_kernel(const mi_con
 
     const uint4 *wimg = reinterpret_cast<const uint4 *>(d.wtap);
     const uint4 *ximg = reinterpret_cast<const uint4 *>(d.xh);
-    const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + 256);
+    const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + MI_SINK_FLOATS);
     // this wave moves octet `wave` of every K step: A rows m0 + 64 j + lane, B columns n0 + 64 j + lane (j = 0, 1)
     const bool arow0 = m0 + lane < d.Mpad && lane < BM, arow1 = m0 + 64 + lane < d.Mpad && 64 + lane < BM;
     // output position of the two columns: (b, o1, o2); the input position of tap (d1, d2) is (o1 + d1, o2 + d2), stride 1

@@ -128,15 +128,20 @@ __device__ __forceinline__ void convtr_tile(const mi_conv_desc &d, const f32x16 
     }
 }
 
-// PLAIN = 1x1 / linear layer with K % 16 == 0 and (O1*O2) % 4 == 0: no gather table, float4 activation loads.
+// PLAIN = 1x1 / linear layer with K % 16 == 0 and (O1*O2) % 4 == 0: no gather table, float4 activation loads -- or one whose input is a
+// 16-bit operand image (mi_conv_desc.xh, K % 8 == 0, any O1*O2): x is never read, so the float4 loader's conditions do not apply.
 // Epilogue shared by the register-staged and the LDS-DMA main loops.
 // acc[a][b][r] is C[m][n] with n = n0 + (wn*TN + b)*32 + li, m = m0 + (wm*TM + a)*32 + (r & 3) + 8 * (r >> 2) + 4 * lh
-template <int TM, int TN, int EPI, int LFLAGS>
+// THREADS: the workgroup size, a multiple of MI_SINK_FLOATS
+template <int TM, int TN, int EPI, int LFLAGS, int THREADS = 256>
 __device__ __forceinline__ void conv_epilogue(const mi_conv_desc &d, f32x16 (&acc)[TM][TN], int m0, int n0, int wm, int wn, int N,
                                               int P, int o2v) {
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
     const int slot = blockIdx.x % kStatSlots;
-    float *const sink = d.sink + tid;
+    // one dump word per thread of a 256-thread workgroup; the 512-thread kernel (gemm_half.hip conv_gemm_half_img256_kernel) shares
+    // each word between two threads: the zero page starts at d.sink + MI_SINK_FLOATS and no store may reach it
+    static_assert(THREADS % MI_SINK_FLOATS == 0, "workgroup size is a multiple of the sink");
+    float *const sink = d.sink + (THREADS > MI_SINK_FLOATS ? tid & (MI_SINK_FLOATS - 1) : tid);
 #pragma unroll
     for (int b = 0; b < TN; ++b) {
         const int n = n0 + (wn * TN + b) * 32 + li;

@@ -133,7 +133,7 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
     const ColInfo lc = decompose(n0 + bn, N, P, d.O2, PLAIN ? d.O2 : o2v);
     const int i1b = lc.o1 * d.S1, i2b = lc.o2 * d.S2;
     const float *xcol = d.x + (size_t)lc.b * d.x_bstride + (PLAIN ? (size_t)lc.p : (size_t)i1b * (d.x_ld ? d.x_ld : d.D2) + i2b);
-    const float *bp = lc.valid ? xcol + (size_t)(8 * bh) * P : d.sink + 256;     // plain: channel stride = P
+    const float *bp = lc.valid ? xcol + (size_t)(8 * bh) * P : d.sink + MI_SINK_FLOATS;     // plain: channel stride = P
     const size_t b_row = lc.valid ? (size_t)P : 0, b_step = lc.valid ? (size_t)BK * P : 0;
     float breg[8];
     // plain DMA loader: this lane's 16 bytes of rows 4*wave + 2*i + (lane >> 5), i = 0, 1
@@ -142,7 +142,7 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
     const ColInfo rcol = decompose(n0 + rc4, N, P, d.O2, NT ? o2v : d.O2);
     const int x_ld = d.x_ld ? d.x_ld : d.D2;
     const int ri1 = rcol.o1 * d.S1;                            // row taps: the input row of tap d1 = 0
-    const float *rsrc = !rcol.valid ? d.sink + 256
+    const float *rsrc = !rcol.valid ? d.sink + MI_SINK_FLOATS
                         : d.x + (size_t)rcol.b * d.x_bstride +
                               (ROWS ? (size_t)ri1 * x_ld + rcol.o2 : (size_t)rcol.p + (NT ? 0 : (size_t)rrow * P));
     const size_t r_row2 = rcol.valid ? (size_t)2 * P : 0, r_step = rcol.valid ? (size_t)BK * P : 0;
@@ -169,7 +169,7 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
                 const int off = i ? (lh ? e3.x : e2.x) : (lh ? e1.x : e0.x);                                        \
                 const int dd1 = i ? (lh ? e3.y : e2.y) : (lh ? e1.y : e0.y);                                        \
                 const bool ok = rcol.valid && (unsigned)(ri1 + dd1) < (unsigned)d.D1;                               \
-                __builtin_amdgcn_global_load_lds((gvoid_t *)(ok ? rsrc + off : d.sink + 256), (lvoid_t *)(dst + 2 * i * BN), 16, 0, 0); \
+                __builtin_amdgcn_global_load_lds((gvoid_t *)(ok ? rsrc + off : d.sink + MI_SINK_FLOATS), (lvoid_t *)(dst + 2 * i * BN), 16, 0, 0); \
             }                                                                                                       \
         } else if constexpr (NT > 0) {                                                                              \
             _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
@@ -177,7 +177,7 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
                 const int i1 = rcol.o1 + t1 - d.tap_pad1;                                                           \
                 const bool ok = rcol.valid && k < d.K && (unsigned)i1 < (unsigned)d.D1;                             \
                 const float *g = rsrc + (int64_t)ci * P + (int64_t)(t1 - d.tap_pad1) * x_ld + (t2 - d.tap_pad2);    \
-                __builtin_amdgcn_global_load_lds((gvoid_t *)(ok ? g : d.sink + 256), (lvoid_t *)(dst + 2 * i * BN), 16, 0, 0); \
+                __builtin_amdgcn_global_load_lds((gvoid_t *)(ok ? g : d.sink + MI_SINK_FLOATS), (lvoid_t *)(dst + 2 * i * BN), 16, 0, 0); \
             }                                                                                                       \
         } else {                                                                                                    \
             const float *g = rsrc + (size_t)(kt) * r_step;                                                          \

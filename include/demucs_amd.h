@@ -19,8 +19,9 @@
  *     segment_length, max_batch, float32 / half) shares -- a bag of four fine-tuned models holds its ~0.57 GB per batched
  *     segment once: such handles must run one after the other on one stream (what apply_model's bag loop does), never
  *     concurrently; hdemucs handles own their workspace; (2) the schedule switches mi_set_two_streams / mi_set_istft_fused / mi_set_transpose_tiles
- *     and the MI_* environment variables (read once); (3) two small device blocks every launch may use: a 256-float sink for
- *     masked stores and 256 bytes of zeros (the source of out-of-frame LDS-DMA transfers).  A forward also uses a side stream
+ *     and the MI_* environment variables (read once); (3) one small device block every launch may use: a 256-float sink for
+ *     masked stores followed by 64 floats (256 bytes) that hold zero and stay zero, the source of out-of-frame LDS-DMA transfers
+ *     (MI_SINK_FLOATS, MI_ZERO_PAGE_FLOATS in demucs_amd/csrc/gemm_conv.h; a caller-provided mi_conv_desc.sink has the same layout).  A forward also uses a side stream
  *     owned by its handle; it is joined on the caller's stream before the call returns.
  */
 #ifndef DEMUCS_AMD_H
