@@ -154,6 +154,7 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_debug_set_post_launch_hook": (None, [C.c_void_p]),
     "mi_debug_last_conv_route": (C.c_int, []),
+    "mi_debug_last_conv_tile": (C.c_int, []),
     "mi_debug_conv_route": (C.c_int, [C.POINTER(MiConvDesc), C.POINTER(C.c_int)]),
     "mi_debug_switches": (C.c_int, [C.c_char_p, C.c_int32]),
     "mi_last_error": (C.c_char_p, []),

@@ -11,6 +11,7 @@ namespace mi {
 
 post_launch_hook_t g_post_launch_hook = nullptr;
 int g_last_conv_route = -1;
+int g_last_conv_tile = -1;
 
 char *last_error_buf() {
     static thread_local char buf[1024] = "";
@@ -126,8 +127,10 @@ extern "C" {
 const char *mi_last_error(void) { return last_error_buf(); }
 void mi_debug_set_post_launch_hook(void (*hook)(void *stream)) { g_post_launch_hook = hook; }
 int mi_debug_last_conv_route(void) { return g_last_conv_route; }
+int mi_debug_last_conv_tile(void) { return g_last_conv_tile; }
 int mi_debug_conv_route(const struct mi_conv_desc *desc, int *tile) {
     if (!desc) return -1;
+    if (conv_check_tile_m(*desc) != MI_OK) return -1;
     const ConvRoute r = conv_route(*desc);
     if (tile) *tile = r.tile;
     return r.route;
@@ -532,8 +535,10 @@ int mi_resample_frac(const float *x_dev, int32_t rows, int64_t length, const flo
 }
 
 int mi_conv_pack_split(const float *wt_dev, int32_t Kpad, int32_t Mpad, int32_t tile_m, void *wx_dev, void *stream) {
-    MI_REQUIRE(wt_dev && wx_dev && Kpad > 0 && Mpad > 0 && conv_x6_supported(tile_m), "mi_conv_pack_split: bad argument");
-    return launch_pack_split(wt_dev, Kpad, Mpad, tile_m, wx_dev, (hipStream_t)stream);
+    MI_REQUIRE(wt_dev && wx_dev && Kpad > 0 && Mpad > 0 && (conv_x6_supported(tile_m) || tile_m == 192), "mi_conv_pack_split: bad argument");
+    MI_REQUIRE(tile_m != 192 || Mpad % 192 == 0, "mi_conv_pack_split: tile_m 192 needs Mpad %% 192 == 0 (Mpad %d)", Mpad);
+    // a 192-row layer's image is the 96-row layout: the 192-row tile reads the images of M tiles 2 mt and 2 mt + 1
+    return launch_pack_split(wt_dev, Kpad, Mpad, tile_m == 192 ? 96 : tile_m, wx_dev, (hipStream_t)stream);
 }
 
 int mi_conv_pack_tap(const float *wt_dev, int32_t Mpad, int32_t Cin, int32_t ntaps, int32_t dtype, void *wtap_dev, void *stream) {

@@ -29,6 +29,7 @@ int set_error(int code, const char *fmt, ...);
 typedef void (*post_launch_hook_t)(void *stream);
 extern post_launch_hook_t g_post_launch_hook;
 extern int g_last_conv_route;          // mi_debug_last_conv_route (include/demucs_amd.h)
+extern int g_last_conv_tile;           // mi_debug_last_conv_tile
 
 #define MI_CHECK_LAUNCH()                                                   \
     do {                                                                    \

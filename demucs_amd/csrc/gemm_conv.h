@@ -86,7 +86,10 @@ typedef struct mi_conv_desc {
     const float *gn_stats;  /* float2 [rows] (mean, rstd) for MI_EPI_GN_GLU             */
     const float *gn_w, *gn_b; /* [Mpad] packed row order                                 */
     int32_t out_len;        /* CONVTR: valid output length along the scattered axis      */
-    int32_t tile_m;         /* 0 = choose automatically; else 32 / 64 / 96 / 128         */
+    int32_t tile_m;         /* 0 = choose automatically; else 32 / 64 / 96 / 128, the tile wt / bias / wx are packed for; or
+                               192 (M % 192 == 0, Mpad == M, float32): wx is the 96-row split image and the split-bf16 routes run
+                               the 192-row tile on pairs of its images (under-filled: the 96-row tile); without wx, and for
+                               every native kernel, 192 means 0 */
     int32_t plain;          /* 1: the gather is the identity over input channels (1x1 conv / linear with channel
                                stride O1*O2): enables the table-free float4 loader when shapes allow             */
     int32_t half;           /* 0, or MI_DTYPE_BF16 / MI_DTYPE_F16 (include/demucs_amd.h): run the main loop of gemm_half.hip on `wh` */
@@ -99,7 +102,7 @@ typedef struct mi_conv_desc {
                                sink + MI_SINK_FLOATS as the source of every out-of-tensor load (columns past N, k past K, conv padding)
                                and never store there */
     const void *wx;         /* NULL, or the weights as the split-bf16 tile image of mi_conv_pack_split for THIS tile_m:
-                               selects the 6-product bf16 MFMA main loop (gemm_x6.hip) for tile_m 64 / 96 / 128     */
+                               selects the 6-product bf16 MFMA main loop (gemm_x6.hip) for tile_m 64 / 96 / 128 / 192 */
     int32_t tr_stride;      /* CONVTR: 0 (= 4, crop 2: ConvTranspose k = 8, s = 4 with the reference's crop folded in), 4 or 2 */
     int32_t tr_pad;         /* CONVTR with tr_stride != 0: samples cropped from the front (0 = the un-cropped transposed conv)   */
     int32_t x_ld;           /* 0, or the row pitch of X along D2 in floats when it differs from D2 (padded frequency-branch rows of

@@ -619,8 +619,8 @@ int g_split_bf16 = 1;
 // Small batches: a layer whose 128-row tiles give fewer workgroups than the chip has CUs (B = 1: M = 512 and 2 688 tokens -> 84;
 // a k x k GLU conv: 6 x 21) runs on a smaller tile instead -- more workgroups at a lower per-workgroup rate.  Which tile that is
 // depends on the route (conv_route).  MI_SMALL_TILE=0: off
-static bool under_filled(const mi_conv_desc &d) {
-    return (int64_t)(d.Mpad / 128) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200;
+static bool under_filled(const mi_conv_desc &d, int tile = 128) {
+    return (int64_t)(d.Mpad / tile) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200;
 }
 
 // float32, stride-1 k x k conv with K2 = 3 whose geometry the descriptor states (ntaps, tap_k2, tap_pad*): the DMA loop above,
@@ -656,11 +656,18 @@ static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain, bool ha
            (d.epi == MI_EPI_CONVTR || tile != 64 || d.epi == MI_EPI_LINEAR);
 }
 
+int conv_check_tile_m(const mi_conv_desc &d) {
+    MI_REQUIRE(d.tile_m != 192 || (d.M > 0 && d.M % 192 == 0 && d.Mpad == d.M), "conv: tile_m 192 needs M %% 192 == 0 and no M padding (M %d, Mpad %d)", d.M, d.Mpad);
+    return MI_OK;
+}
+
 // The decision, top to bottom; the first test that holds wins (kernels.h ConvRoute)
 ConvRoute conv_route(const mi_conv_desc &d) {
     const bool image = d.wx && g_split_bf16;                // mi_set_split_bf16(0): native fp32 MFMA kernels only
     const Switches &sw = switches();
-    const int tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M);
+    // tile_m = 192 (a layer with M % 192 == 0 whose split image is a run of 96-row images): the float32 weights, and so every
+    // native and half-mode kernel, keep the tile conv_pick_tile gives
+    const int tile = d.tile_m && d.tile_m != 192 ? d.tile_m : conv_pick_tile(d.M);
     // plain fast path: a 1x1 / linear layer whose gather is the identity
     const int64_t P = (int64_t)d.O1 * d.O2;
     // (an operand-image input is never read through x: the float4 loader's conditions on K, P and x do not apply to it)
@@ -668,18 +675,27 @@ ConvRoute conv_route(const mi_conv_desc &d) {
                        d.S1 == 1 && d.S2 == 1 && d.D1 == d.O1 && (d.x_ld ? d.x_ld : d.D2) == d.O2;
     if (d.wtap) return {MI_ROUTE_TAP_HALF, tile, plain};
     if (d.half) return {MI_ROUTE_HALF, tile, plain};
-    const bool small = sw.small_tile && tile == 128 && under_filled(d), small_linear = small && plain && d.epi == MI_EPI_LINEAR;
+    const bool t192 = d.tile_m == 192 && image;
+    const bool small = sw.small_tile && tile == 128 && !t192 && under_filled(d), small_linear = small && plain && d.epi == MI_EPI_LINEAR;
+    // The 192-row layers: the 192-row tile where the loader family has it for the layer's epilogue and its workgroups fill the
+    // chip, else the 96-row tile on the same image (bit-identical to it); never the 64-row tile, which needs a 128-row image
+    const int lf = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS);
+    auto split_tile = [&](int ntaps) {
+        if (!t192) return small ? 64 : tile;
+        const bool filled = !(sw.small_tile && under_filled(d, 192));
+        return filled && conv_x6_tile192_supported(d.epi, d.epi == MI_EPI_LINEAR ? lf : 0, plain, ntaps) ? 192 : 96;
+    };
     // Split weight image.  An under-filled layer takes the 64-row tile that reads the 128-row image: bit-identical to the 128-row
     // tile, no second image.  The decoders' 3 x 3 / k = 3 rewrite convs: shifted-run DMA taps in front of the split-bf16 main loop
-    if (!plain && !sw.x6_plain_only && dmatap_eligible(d, tile, image, true)) return {MI_ROUTE_TAP_X6, small ? 64 : tile, plain};
+    if (!plain && !sw.x6_plain_only && dmatap_eligible(d, tile, image, true)) return {MI_ROUTE_TAP_X6, split_tile(d.ntaps), plain};
     // the frequency branch's encoder / transposed convs and the 1 x 1 + GLU rewrites: the DMA row loader in front of it
-    if (!sw.x6_plain_only && dmarow_eligible(d, tile, plain, image, true)) return {MI_ROUTE_ROWS_X6, small ? 64 : tile, plain};
+    if (!sw.x6_plain_only && dmarow_eligible(d, tile, plain, image, true)) return {MI_ROUTE_ROWS_X6, split_tile(-1), plain};
     // native DMA taps: an under-filled k x k GLU conv takes 96-row tiles
     const int ktile = small && !plain && d.epi == MI_EPI_GLU && d.Mpad % 96 == 0 ? 96 : tile;
     if (!plain && dmatap_eligible(d, ktile, image)) return {MI_ROUTE_DMATAP, ktile, plain};
     if (dmarow_eligible(d, tile, plain, image)) return {MI_ROUTE_DMAROW, tile, plain};
     // the split-bf16 main loop behind the plain loader or the gather table (MI_X6_MODE=1: plain layers only)
-    if (image && conv_x6_supported(tile) && (!sw.x6_plain_only || plain)) return {MI_ROUTE_X6, small_linear ? 64 : tile, plain};
+    if (image && conv_x6_supported(tile) && (!sw.x6_plain_only || plain)) return {MI_ROUTE_X6, t192 ? split_tile(0) : small_linear ? 64 : tile, plain};
     // native fp32 kernels: an under-filled plain linear layer takes 64-row tiles
     const int ntile = small_linear && d.Mpad % 64 == 0 ? 64 : tile;
     const bool dma = plain && ntile == 128 && d.epi == MI_EPI_LINEAR && !sw.no_dma;
@@ -689,6 +705,7 @@ ConvRoute conv_route(const mi_conv_desc &d) {
 // validate, decide (conv_route), launch
 int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     mi_conv_desc d = din;
+    MI_TRY(conv_check_tile_m(d));
     if (!d.sink) d.sink = conv_sink();
     MI_REQUIRE(d.sink && ((uintptr_t)d.sink & 15) == 0, "conv: the store sink could not be allocated or is not 16-byte aligned");
     MI_REQUIRE((int64_t)d.Mpad * d.y_cstride < (1ll << 31), "conv: output channel stride too large for 32-bit row offsets");
@@ -729,8 +746,10 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     MI_REQUIRE(!d.xh || d.half, "conv: an operand-image input needs a half-precision layer");
 
     const ConvRoute r = conv_route(d);
-    const int image_tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M);       // the tile the layer's weight images were packed for
+    // the tile the layer's split image was packed for: a 192-row layer's is a run of 96-row images
+    const int image_tile = d.tile_m == 192 ? 96 : d.tile_m ? d.tile_m : conv_pick_tile(d.M);
     g_last_conv_route = r.route;
+    g_last_conv_tile = r.tile;
     switch (r.route) {
         case MI_ROUTE_TAP_HALF: return launch_conv_tap(d, r.tile, st);
         case MI_ROUTE_HALF: return launch_conv_half(d, r.tile, r.plain, st);

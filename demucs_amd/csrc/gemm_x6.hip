@@ -11,7 +11,10 @@
 // Tile image in LDS, per operand and K step of 16: [part 3][k-half 2][row or column][8 bf16] -- a 32x32x16
 // fragment (lane l: row l&31, k = 8*(l>>5) .. +7) is ONE conflict-free ds_read_b128 per part.
 //   A (weights): split once at load time into exactly this image per (M tile, K step) (pack_split_kernel),
-//                so the loader is pure LDS-DMA (global_load_lds_dwordx4, no registers, no ds_write).
+//                so the loader is pure LDS-DMA (global_load_lds_dwordx4, no registers, no ds_write).  Tiles: 128, 96 and 64 rows
+//                on an image of their own, 64 rows on the halves of a 128-row image (HALF_IMG: under-filled 128-row layers) and
+//                192 rows (WM 2, TM 3: 36 MFMAs per wave and K step behind the same split, waits and barrier) on PAIRS of
+//                96-row images, for layers with M % 192 == 0 (mi_conv_desc.tile_m = 192; under-filled: the 96-row tile).
 //   B (activations): thread (column n = tid & 127, k-half = tid >> 7) takes its 8 k values, splits them in registers
 //                (v_cvt_pk_bf16_f32, round-to-nearest residuals) and writes three 16-byte words.  The values come from
 //                the raw fp32 tile that LDS-DMA lands two K steps ahead (plain layers: channel runs; the decoders' 3 x 3 /
@@ -91,9 +94,15 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
     constexpr int A_BYTES = BM * 96, B_BYTES = BN * 96, STAGE = A_BYTES + B_BYTES;
     constexpr int A_CHUNKS = A_BYTES / 1024;                 // 1 KiB per wave-wide DMA instruction
     static_assert(!HALF_IMG || BM == 64, "HALF_IMG: 64-row tile of a 128-row image");
+    // PAIR: the 192-row tile (WM 2, TM 3).  Wave row wm owns rows [96 wm, 96 wm + 96), so the tile reads the two consecutive
+    // 96-row images 2 mt and 2 mt + 1 of pack_split_kernel's layout (nine 1 KiB chunks each per K step) and keeps them one after the
+    // other in LDS: the same fragments, products and k order as the 96-row tile on that image, so both give bit-identical results
+    constexpr bool PAIR = BM == 192;
+    static_assert(!PAIR || (WM == 2 && TM == 3), "192-row tile: two wave rows of 96 rows");
+    constexpr int IMG_ROWS = PAIR ? 96 : BM, IMG_BYTES = IMG_ROWS * 96, IMG_CHUNKS = IMG_BYTES / 1024;
     // one K step of the image: [part 3][k-half 2][image rows][16 bytes]; the 64-row half of a 128-row image is the first or the
     // second KiB of each 2 KiB (part, k-half) block
-    constexpr int A_KSTEP = HALF_IMG ? 2 * A_BYTES : A_BYTES, A_CHUNK_STRIDE = HALF_IMG ? 2048 : 1024;
+    constexpr int A_KSTEP = HALF_IMG ? 2 * A_BYTES : IMG_BYTES, A_CHUNK_STRIDE = HALF_IMG ? 2048 : 1024;
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
     // plain layers: the fp32 activation tile [16][128] lands here by LDS-DMA two K steps ahead and is split from LDS
     // (a VMEM wave-instruction costs ~12-16 cycles whatever its width: 2 x 1 KiB DMA per wave replace 8 dword loads)
@@ -115,14 +124,14 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
     const int nk = d.Kpad / BK;
 
     // ---- A: LDS-DMA of the pre-split image; wave w moves chunks w, w + 4, ... -------------------------
-    const unsigned char *aimg = reinterpret_cast<const unsigned char *>(d.wx) + (size_t)(HALF_IMG ? mt >> 1 : mt) * nk * A_KSTEP +
+    const unsigned char *aimg = reinterpret_cast<const unsigned char *>(d.wx) + (size_t)(HALF_IMG ? mt >> 1 : PAIR ? 2 * mt : mt) * nk * A_KSTEP +
                                 (HALF_IMG ? (mt & 1) * 1024 : 0) + lane * 16;
 #define MI_A_DMA(kt, stage)                                                                                         \
     do {                                                                                                            \
         _Pragma("unroll") for (int c = 0; c < (A_CHUNKS + 3) / 4; ++c) {                                             \
-            const int chunk = c * 4 + wave;                                                                         \
+            const int chunk = c * 4 + wave, img = PAIR ? chunk / IMG_CHUNKS : 0, ic = chunk - img * IMG_CHUNKS;      \
             if (chunk < A_CHUNKS)                                                                                   \
-                __builtin_amdgcn_global_load_lds((gvoid_t *)(aimg + (size_t)(kt) * A_KSTEP + chunk * A_CHUNK_STRIDE), \
+                __builtin_amdgcn_global_load_lds((gvoid_t *)(aimg + ((size_t)img * nk + (kt)) * A_KSTEP + ic * A_CHUNK_STRIDE), \
                                                  (lvoid_t *)(smem + (stage) * STAGE + chunk * 1024), 16, 0, 0);     \
         }                                                                                                           \
     } while (0)
@@ -269,7 +278,8 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
         for (int p = 0; p < 3; ++p) {
 #pragma unroll
             for (int a = 0; a < TM; ++a)
-                af[a][p] = *reinterpret_cast<const bf16x8 *>(As + (((p * 2 + lh) * BM) + (wm * TM + a) * 32 + li) * 16);
+                af[a][p] = *reinterpret_cast<const bf16x8 *>(As + (PAIR ? wm * IMG_BYTES : 0) +
+                                                             (((p * 2 + lh) * IMG_ROWS) + ((PAIR ? 0 : wm * TM) + a) * 32 + li) * 16);
 #pragma unroll
             for (int b = 0; b < TN; ++b)
                 bf[b][p] = *reinterpret_cast<const bf16x8 *>(Bs + (((p * 2 + lh) * BN) + (wn * TN + b) * 32 + li) * 16);
@@ -345,6 +355,15 @@ __global__ __launch_bounds__(256, 2) void conv_rows_x6_kernel(const mi_conv_desc
     conv_x6_body<WM, WN, TM, TN, EPI, LFLAGS, false, HALF_IMG, kRowTaps>(d, N, MT, Gm);
 }
 
+// Which (epilogue, LINEAR flag set, loader) combinations the 192-row tile is compiled for: the layers of the float32 engine with
+// M % 192 == 0 -- the tap convs (GLU), the row-tap layers (LINEAR + GELU, CONVTR, 1 x 1 + GLU) and the self-attention in_proj
+// (plain LINEAR with MI_FLAG_LN).  Anything else with such an M runs the 96-row tile on the same image
+static constexpr bool conv_x6_tile192(int epi, int lflags, bool plain, int ntaps) {
+    if (ntaps > 0) return epi == MI_EPI_GLU;
+    if (ntaps == kRowTaps) return (epi == MI_EPI_LINEAR && lflags == MI_FLAG_GELU) || epi == MI_EPI_CONVTR || epi == MI_EPI_GLU;
+    return plain && epi == MI_EPI_LINEAR && lflags == MI_FLAG_LN;
+}
+
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false, int NTAPS = 0>
 static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
@@ -364,12 +383,17 @@ static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
 
 // `tile` is the tile gemm_conv.hip conv_route decided, `image_tile` the one the split image was packed for: they differ for the
 // under-filled 128-row layers, which run 64-row tiles that read the 128-row image (bit-identical to the 128-row tile, no second
-// image).  NTAPS: the loader (0: plain / gather table, 9 or 3: shifted-run taps, kRowTaps: row taps)
+// image), and for the 192-row layers (image_tile 96), which run the 192-row tile on pairs of their 96-row images or, under-filled,
+// the 96-row tile.  NTAPS: the loader (0: plain / gather table, 9 or 3: shifted-run taps, kRowTaps: row taps)
 template <int EPI, int LFLAGS, bool PLAIN, int NTAPS>
 static int launch_tile_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st) {
     if (tile != image_tile) {
         if constexpr (NTAPS != 0 || (PLAIN && EPI == MI_EPI_LINEAR)) {
             if (tile == 64 && image_tile == 128) return launch_cfg_x6<1, 4, 2, 1, EPI, LFLAGS, PLAIN, true, NTAPS>(d, st);
+        }
+        // the 192-row tile on a pair of 96-row images: the loaders' own epilogues, and the plain LINEAR layer on LayerNorm-ed tokens
+        if constexpr (conv_x6_tile192(EPI, LFLAGS, PLAIN, NTAPS)) {
+            if (tile == 192 && image_tile == 96) return launch_cfg_x6<2, 2, 3, 2, EPI, LFLAGS, PLAIN, false, NTAPS>(d, st);
         }
         return set_error(MI_EINVAL, "conv x6: no %d-row tile on a %d-row image for epilogue %d", tile, image_tile, EPI);
     }
@@ -383,6 +407,9 @@ static int launch_tile_x6(const mi_conv_desc &d, int tile, int image_tile, hipSt
 }
 
 bool conv_x6_supported(int tile) { return tile == 128 || tile == 96 || tile == 64; }
+
+// gemm_conv.hip conv_route asks with the descriptor's epilogue and flags; launch_tile_x6 with its template arguments
+bool conv_x6_tile192_supported(int epi, int lflags, bool plain, int ntaps) { return conv_x6_tile192(epi, lflags, plain, ntaps); }
 
 // d has been validated by launch_conv (gemm_conv.hip): a stride-1 GLU conv with K2 = 3, dilation 1, NT = 9 or 3 taps, its row
 // pitch a multiple of 4 and equal to O2, image tile 96 or 128 (dmatap_eligible)
@@ -403,7 +430,7 @@ int launch_conv_rows_x6(const mi_conv_desc &d, int tile, int image_tile, hipStre
     MI_REQUIRE(image_tile == 96 || image_tile == 128, "conv rows x6: 96- or 128-row tile (tile %d)", image_tile);
     if (d.epi == MI_EPI_CONVTR) return launch_tile_x6<MI_EPI_CONVTR, 0, false, kRowTaps>(d, tile, image_tile, st);
     if (d.epi == MI_EPI_GLU) {
-        MI_REQUIRE(image_tile == 128, "conv rows x6: GLU on a 128-row tile (tile %d)", image_tile);
+        MI_REQUIRE(image_tile == 128 || d.tile_m == 192, "conv rows x6: GLU on a 128-row tile or a 192-row layer (tile %d)", image_tile);
         return launch_tile_x6<MI_EPI_GLU, 0, false, kRowTaps>(d, tile, image_tile, st);
     }
     MI_REQUIRE(d.epi == MI_EPI_LINEAR && (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) == MI_FLAG_GELU,

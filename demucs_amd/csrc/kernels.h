@@ -115,10 +115,12 @@ int launch_dconv_time_layer(const DConvTimeLayer &l, int C, int dil, int B, int 
 // gemm_conv.hip
 int launch_conv(const mi_conv_desc &d, hipStream_t st);
 int conv_pick_tile(int M);
+int conv_check_tile_m(const mi_conv_desc &d);     // MI_OK, or MI_EINVAL with the error set: tile_m = 192 on a layer that cannot take it
 extern int g_split_bf16;     // 0 (mi_set_split_bf16): native fp32 MFMA kernels even where a split weight image exists
 // Which kernel launch_conv runs for a descriptor, decided from the descriptor alone (no HIP call, no pointer followed):
 // route: mi_conv_route (include/demucs_amd.h); tile: the rows of the tile that kernel runs, after every small-batch substitution
-// (routes 4, 7, 8: 64 under a 128-row layer = the 64-row tile that reads the 128-row image); plain: the 1x1 / linear fast path
+// (routes 4, 7, 8: 64 under a 128-row layer = the 64-row tile that reads the 128-row image; 192 or 96 under a tile_m = 192
+// layer = the 192-row tile on pairs of its 96-row images, or the 96-row tile on them); plain: the 1x1 / linear fast path
 struct ConvRoute { int route; int tile; bool plain; };
 ConvRoute conv_route(const mi_conv_desc &d);
 // Every environment switch of the engine (INTEGRATION.md has the table), parsed once, when the library is loaded (switches.hip:
@@ -160,6 +162,9 @@ struct Switches {
 const Switches &switches();
 // gemm_x6.hip: `tile` as decided by conv_route, `image_tile` the tile the split image was packed for
 bool conv_x6_supported(int tile);
+// the 192-row tile exists for this epilogue, LINEAR flag set (GELU / SCALE / RES / LN / STATS bits; 0 for other epilogues) and
+// loader (ntaps: 9 or 3 shifted-run taps, -1 row taps, 0 plain or gather table)
+bool conv_x6_tile192_supported(int epi, int lflags, bool plain, int ntaps);
 int launch_conv_x6(const mi_conv_desc &d, int tile, int image_tile, bool plain, hipStream_t st);
 int launch_conv_tap_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);      // stride-1 3 x 3 / k = 3 GLU convs (route 7)
 int launch_conv_rows_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);     // row-tap encoder / transposed convs (route 8)

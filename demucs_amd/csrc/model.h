@@ -17,7 +17,7 @@ struct Geo;
 
 struct PackedConv {
     float *wt = nullptr, *bias = nullptr;
-    void *wx = nullptr;            // split-bf16 tile image of wt (gemm_x6.hip) when the tile has that main loop
+    void *wx = nullptr;            // split-bf16 tile image of wt (gemm_x6.hip) when the tile has that main loop; tile == 192: 96-row images
     void *wh = nullptr;            // bf16 / fp16 operand image of wt (gemm_half.hip) in the reduced-precision modes
     void *wtap = nullptr;          // ... and, for k x k convs fed by an operand image, the tap-ordered image (gemm_tap.hip)
     int ntaps = 0;

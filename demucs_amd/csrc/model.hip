@@ -113,9 +113,10 @@ static const char *kEpiNames[6] = {"linear", "glu", "bias_stats", "stats_only", 
 int Model::conv(const mi_conv_desc &d, hipStream_t st) {
     if (!prof.on) return launch_conv(d, st);
     // The row of this launch: which main loop runs is conv_route's answer, asked before the launch.  Rows stay keyed by the layer's
-    // own tile (the one its weights are packed for) and the descriptor's `plain`, not by the small-batch tile the kernel runs
+    // own tile (the one its float32 weights are packed for: conv_pick_tile(M) for a 192-row layer) and the descriptor's `plain`,
+    // not by the small-batch or the 192-row tile the kernel runs
     const int route = conv_route(d).route;
-    const int tile = d.tile_m ? d.tile_m : conv_pick_tile(d.M), ti = tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3;
+    const int tile = d.tile_m && d.tile_m != 192 ? d.tile_m : conv_pick_tile(d.M), ti = tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3;
     // bf16 / fp16 operand or split-bf16 main loops: classes of their own.  The split-bf16 tap convs (conv_tap_x6_kernel) and row-tap
     // convs (conv_rows_x6_kernel: the frequency branch's encoder / transposed convs, the encoders' 1 x 1 + GLU rewrites): rows of
     // their own, named after the kernel -- the conv_gemm_x6 rows stay the linears' ones
@@ -192,9 +193,14 @@ int Model::pack_split(PackedConv *pc, SplitScope scope) {
     const bool in_default = scope == SPLIT_DEFAULT || (scope == SPLIT_ROWS && !sw.no_dma_rows);
     const bool want = sw.x6_scope == 2 || (sw.x6_scope == 1 && in_default && cfg.dtype == MI_DTYPE_F32);
     if (!want || !conv_x6_supported(pc->tile)) return MI_OK;
+    // M % 192 == 0 (decoders 0 .. 2 and their time twins, the self-attention in_proj, the deeper frequency-branch layers): 96-row
+    // images, which the 192-row tile reads in pairs and the 96-row tile singly (gemm_conv.h tile_m = 192).  The float32 weights
+    // and the bias keep conv_pick_tile's Mpad, which is M for these layers; the image costs the same 6 Kpad Mpad bytes as before
+    const bool t192 = pc->M % 192 == 0 && pc->Mpad == pc->M;
     MI_TRY(dev_alloc(&pc->wx, (size_t)6 * pc->Kpad * pc->Mpad));
-    MI_TRY(launch_pack_split(pc->wt, pc->Kpad, pc->Mpad, pc->tile, pc->wx, nullptr));
+    MI_TRY(launch_pack_split(pc->wt, pc->Kpad, pc->Mpad, t192 ? 96 : pc->tile, pc->wx, nullptr));
     MI_HIP(hipStreamSynchronize(nullptr));
+    if (t192) pc->tile = 192;
     return MI_OK;
 }
 

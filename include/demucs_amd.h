@@ -538,7 +538,8 @@ int mi_conv_forward(const struct mi_conv_desc *desc, void *stream);
  *   [Mpad/tile_m][Kpad/16][3 terms][2 k-halves][tile_m][8] bf16 (6 * Kpad * Mpad bytes) that mi_conv_desc.wx takes:
  *   each weight w = hi + mid + lo exactly, so the 6-product bf16 MFMA loop reproduces the fp32 product sum
  *   (no reference counterpart: it is the load-time half of how F.conv / F.linear run on the matrix cores).
- *   tile_m must be the tile the layer will run with (64, 96 or 128). */
+ *   tile_m must be the tile the layer will run with (64, 96 or 128), or 192 for a layer with Mpad % 192 == 0 that sets
+ *   mi_conv_desc.tile_m = 192: that writes the 96-row layout, which the 192-row tile reads two images at a time. */
 int mi_conv_pack_split(const float *wt_dev, int32_t Kpad, int32_t Mpad, int32_t tile_m, void *wx_dev, void *stream);
 
 /* mi_conv_pack_tap: weights of a k x k stride-1 conv for the operand-image route of the half modes (gemm_tap.hip): from the
@@ -723,10 +724,16 @@ enum mi_conv_route {
  * not thread-safe. */
 int mi_debug_last_conv_route(void);
 
+/* Debug aid, as mi_debug_last_conv_route: the rows of the tile the LAST mi_conv_forward of this process ran (what
+ * mi_debug_conv_route answers in *tile); -1 before any call. */
+int mi_debug_last_conv_tile(void);
+
 /* Debug aid: the route mi_conv_forward WOULD take for `desc` (under the environment switches and mi_set_split_bf16 as they
  * stand) and, in *tile (may be NULL), the rows of the tile that kernel runs, after every small-batch substitution: for the
- * split-bf16 routes 64 under a 128-row layer means the 64-row tile that reads the 128-row image.  Host code only: launches
- * nothing, follows no pointer of the descriptor, works in a process that never touches the GPU.  Returns -1 for desc == NULL. */
+ * split-bf16 routes 64 under a 128-row layer means the 64-row tile that reads the 128-row image, and a tile_m = 192 layer
+ * answers 192 (the 192-row tile on pairs of its 96-row images) or, under-filled, 96.  Host code only: launches nothing, follows
+ * no pointer of the descriptor, works in a process that never touches the GPU.  Returns -1 for desc == NULL and for a
+ * descriptor whose tile_m is 192 while its M is no multiple of 192 or is padded (mi_last_error names it). */
 int mi_debug_conv_route(const struct mi_conv_desc *desc, int *tile);
 
 /* Debug aid: the MI_* environment switches as this process parsed them, when the library was loaded (INTEGRATION.md has the
