@@ -316,9 +316,10 @@ __global__ __launch_bounds__(256, 1) void attention_heads_kernel(const uint4 *__
     }
 }
 
-// q / k / v: per-head token-major 16-bit tensors [B][heads][T pitch][64]; the pitches are multiples of 64 rows so that every
-// tile read stays inside the allocation (rows past Tk are never used: their probabilities are exactly zero and the DMA reads
-// the zero page instead).  Output: `oh` (operand image with oh_n columns) or float32 o (B, heads * 64, Tq).
+// q / k / v: per-head token-major 16-bit tensors [B][heads][T pitch][64].  Any pitch >= T is safe (the engine passes Tq, Tk): a
+// tile is read whole only if (t + 1) * 64 <= Tk, the ragged last tile takes its rows >= Tk from the zero page and never from the
+// tensor (their scores enter as -inf, their probabilities are exactly zero), and a query row >= Tq is replaced by row 0 and
+// never stored.  Output: `oh` (operand image with oh_n columns) or float32 o (B, heads * 64, Tq).
 int launch_attention_heads(const void *q, const void *k, const void *v, const void *zero_page, int B, int heads, int Tq, int Tk, int Tq_pitch,
                            int Tk_pitch, int dtype, void *oh, int64_t oh_n, float *o, int64_t o_bs, hipStream_t st) {
     MI_REQUIRE(dtype == MI_DTYPE_BF16 || dtype == MI_DTYPE_F16, "attention: per-head operands exist in the half modes only (dtype %d)", dtype);

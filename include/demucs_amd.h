@@ -61,7 +61,10 @@ typedef struct mi_config {
 /* Compute modes.  F32 is the parity mode (fp32 MFMA, exact fp32 arithmetic, <= 1e-4 of the CPU reference).
  * BF16 / F16 round the OPERANDS of every conv / linear GEMM and of the attention products to bf16 / fp16 and
  * feed them to v_mfma_f32_32x32x16_{bf16,f16}; accumulation, biases, GroupNorm / LayerNorm statistics, softmax,
- * GELU / GLU, the STFT / iSTFT and all activations in HBM stay float32 (BASELINE.json configs[2], configs[4]). */
+ * GELU / GLU, the STFT / iSTFT and all activations in HBM stay float32 (BASELINE.json configs[2], configs[4]).
+ * One rounding to nearest even moves a value x by at most half an ulp: relative to |x| that is 2^-8 (bf16) / 2^-11 (fp16)
+ * at the bottom of x's binade and 2^-9 / 2^-12 at its top; bounds on the half modes (tests/test_gpu_attention.py,
+ * tests/test_gpu_half_linear.py) use the half ulp itself or the bottom-of-binade figure, never the smaller one. */
 #define MI_DTYPE_F32 0
 #define MI_DTYPE_BF16 1
 #define MI_DTYPE_F16 2
@@ -580,6 +583,13 @@ int mi_attention_split(const float *q_dev, const float *k_dev, const float *v_de
  *   = softmax(q k^T / 8) v per head (demucs/transformer.py:339-377,466-512). */
 int mi_attention_heads(const void *q_dev, const void *k_dev, const void *v_dev, float *o_dev, int32_t B, int32_t heads, int32_t Tq, int32_t Tk,
                        int32_t Tq_pitch, int32_t Tk_pitch, int32_t dtype, void *stream);
+
+/* mi_attention_heads with the result written as the 16-bit operand image of the projection that consumes it (out_proj): the only
+ *   output form the half-mode engine uses.  img_dev[heads * 64 / 8][n_img][8] bf16 / fp16 (by `dtype`), column b * Tq + query,
+ *   n_img >= B * Tq, 16-byte aligned; element [c / 8][b * Tq + query][c % 8] is channel c = head * 64 + d of mi_attention_heads'
+ *   float32 result rounded to nearest even; columns past B * Tq are left untouched.  Feeds mi_conv_desc.xh. */
+int mi_attention_heads_image(const void *q_dev, const void *k_dev, const void *v_dev, void *img_dev, int64_t n_img, int32_t B, int32_t heads,
+                             int32_t Tq, int32_t Tk, int32_t Tq_pitch, int32_t Tk_pitch, int32_t dtype, void *stream);
 
 /* mi_attention in a half mode with the result written as the 16-bit operand image of the projection that consumes it
  *   (out_proj, demucs/transformer.py:418-419 inside nn.MultiheadAttention): img_dev[(heads * 64) / 8][n_img][8] bf16 / fp16,

@@ -884,7 +884,7 @@ def test_attention_matches_softmax(lib, dtype):
     _lib.check(lib.mi_attention(qd.data_ptr(), kv.data_ptr(), kv.data_ptr() + 512 * Tk * 4, o.data_ptr(), B, H, Tq, Tk, 512 * Tq,
                                 1024 * Tk, 512 * Tq, dtype, stream()), "mi_attention")
     torch.cuda.synchronize()
-    # half modes: Q, K, V and the probabilities are rounded to the operand type (2^-9 / 2^-12 relative), softmax in float32
+    # half modes: Q, K, V and the probabilities are rounded to the operand type (half an ulp: 2^-9 / 2^-12 relative at the top of a binade, 2^-8 / 2^-11 at its bottom), softmax in float32
     assert maxerr(o, want) < [2e-5, 6e-2, 8e-3][dtype]        # scores reach |s| ~ 30 at the spiked key: 2^-9 (2^-12) relative on them moves a probability by several percent
     if dtype:
         # the same result as out_proj's 16-bit operand image: exactly the rounding of the float32 output, [channel / 8][b Tq + q][8]
@@ -902,7 +902,7 @@ def test_attention_matches_softmax(lib, dtype):
 def test_attention_heads_matches_softmax(lib, dtype, Tq, Tk, pitch, spike):
     """`mi_attention_heads` (attention_heads.hip): the half modes' attention on the 16-bit per-head token-major operands the
     in-projections write (K / V tiles by LDS-DMA, swizzled LDS image, transposed V reads).  The float64 softmax of the SAME
-    rounded operands is the reference, so only the probabilities' rounding (2^-9 / 2^-12 relative) and float32 accumulation
+    rounded operands is the reference, so only the probabilities' rounding (half an ulp: at most 2^-8 / 2^-11 relative) and float32 accumulation
     remain: tight bounds on un-spiked data; the spiked case (|score| ~ 30) gets the bound of test_attention_matches_softmax.
     Ragged Tq / Tk (last tile masked, rows past Tk read from the zero page), row pitches above the token counts, a long key axis."""
     B, H = 2, 8
