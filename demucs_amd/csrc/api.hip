@@ -1,9 +1,6 @@
 // extern "C" surface of libdemucs_amd.so (declared in include/demucs_amd.h).
 #include <new>
 
-#include "common.h"
-#include "gemm_conv.h"
-#include "kernels.h"
 #include "hmodel.h"
 #include "model.h"
 
@@ -49,7 +46,7 @@ static int get_tables(FftTables *out) {
 
 // One DConv layer of a handle-free test entry on the device: the nine natural-layout tensors as the checkpoint stores them
 // (layers.{d}.0.weight (h, C, 3), .0.bias (h), .1.weight / .1.bias (h), .3.weight (2C, h), .3.bias, .4.weight, .4.bias (2C),
-// .6.scale (C); h = C / 8), packed by dconv_pack_host like Model::load_dconv and uploaded with hipMalloc
+// .6.scale (C); h = C / 8), packed by dconv_pack_host like EngineCore::load_dconv and uploaded with hipMalloc
 static size_t dconv_layer_floats(int C) { const size_t h = C / 8; return h * C * 3 + 3 * h + 2 * C * h + 6 * (size_t)C + C; }
 struct DConvTestLayer {
     std::vector<void *> bufs;
@@ -118,6 +115,21 @@ static int stft_entry(const char *who, const float *mix_dev, int B, int L, float
     return finish_entry(r, st, who);
 }
 
+// A handle of the C interface is the EngineCore part of an engine.  An entry that needs one engine gets it here: a handle of
+// the other kind is refused (MI_EINVAL, nullptr) before anything else reads it.
+static const char *const kKindNames[2] = {"htdemucs", "hdemucs"};
+template <typename Engine>
+static Engine *engine_of(void *handle, EngineKind want, const char *entry) {
+    EngineCore *core = static_cast<EngineCore *>(handle);
+    if (core->kind != want) {
+        set_error(MI_EINVAL, "%s: the handle belongs to the %s engine, this entry takes one of the %s engine", entry, kKindNames[core->kind], kKindNames[want]);
+        return nullptr;
+    }
+    return static_cast<Engine *>(core);
+}
+static Model *as_model(void *handle, const char *entry) { return engine_of<Model>(handle, ENGINE_HTDEMUCS, entry); }
+static HModel *as_hmodel(void *handle, const char *entry) { return engine_of<HModel>(handle, ENGINE_HDEMUCS, entry); }
+
 }  // namespace mi
 
 using namespace mi;
@@ -144,26 +156,30 @@ int mi_model_create(const mi_config *cfg, const mi_tensor_desc *weights, size_t 
     if (!m) return set_error(MI_ENOMEM, "mi_model_create: host allocation failed");
     const int r = m->init(*cfg, weights, n_weights);
     if (r != MI_OK) { delete m; return r; }
-    *handle = m;
+    *handle = static_cast<EngineCore *>(m);
     return MI_OK;
 }
 
 void mi_model_destroy(void *handle) {
     if (!handle) return;
+    Model *m = as_model(handle, "mi_model_destroy");
+    if (!m) return;
     (void)hipDeviceSynchronize();
-    delete (Model *)handle;
+    delete m;
 }
 
 int mi_model_forward(void *handle, const float *mix_dev, float *out_dev, int32_t B, void *stream) {
     if (!handle) return set_error(MI_EINVAL, "mi_model_forward: null handle");
-    return ((Model *)handle)->forward(mix_dev, out_dev, B, (hipStream_t)stream);
+    Model *m = as_model(handle, "mi_model_forward");
+    return m ? m->forward(mix_dev, out_dev, B, (hipStream_t)stream) : MI_EINVAL;
 }
 
 int mi_model_tap(void *handle, const char *name, float *dst_dev, int32_t B, int64_t *numel_per_item, void *stream) {
     if (!handle || !name || !numel_per_item) return set_error(MI_EINVAL, "mi_model_tap: null argument");
+    Model *m = as_model(handle, "mi_model_tap");
+    if (!m) return MI_EINVAL;
     const float *src = nullptr;
     const float **ptr_dev = &src;
-    Model *m = (Model *)handle;
     const std::string n(name);
     const int64_t T = m->T, Tf = 8 * T, Tt = m->Lt[4];
     static const int ch[4] = {48, 96, 192, 384}, fr[4] = {512, 128, 32, 8};
@@ -190,7 +206,8 @@ int mi_model_tap(void *handle, const char *name, float *dst_dev, int32_t B, int6
 int mi_model_forward_core(void *handle, const float *mix_dev, const float *mag_dev, float *spec_out_dev, float *time_out_dev,
                           int32_t B, void *stream) {
     if (!handle) return set_error(MI_EINVAL, "mi_model_forward_core: null handle");
-    return ((Model *)handle)->forward_core(mix_dev, mag_dev, spec_out_dev, time_out_dev, B, (hipStream_t)stream);
+    Model *m = as_model(handle, "mi_model_forward_core");
+    return m ? m->forward_core(mix_dev, mag_dev, spec_out_dev, time_out_dev, B, (hipStream_t)stream) : MI_EINVAL;
 }
 
 // ---- Hybrid Demucs v3 (hdemucs_mmi) handles ------------------------------------------------------------------------
@@ -201,24 +218,28 @@ int mi_hmodel_create(const mi_config *cfg, const mi_tensor_desc *weights, size_t
     if (!m) return set_error(MI_ENOMEM, "mi_hmodel_create: host allocation failed");
     const int r = m->hinit(*cfg, weights, n_weights);
     if (r != MI_OK) { delete m; return r; }
-    *handle = m;
+    *handle = static_cast<EngineCore *>(m);
     return MI_OK;
 }
 
 void mi_hmodel_destroy(void *handle) {
     if (!handle) return;
+    HModel *m = as_hmodel(handle, "mi_hmodel_destroy");
+    if (!m) return;
     (void)hipDeviceSynchronize();
-    delete (HModel *)handle;
+    delete m;
 }
 
 int mi_hmodel_forward(void *handle, const float *mix_dev, float *out_dev, int32_t B, int32_t length, void *stream) {
     if (!handle) return set_error(MI_EINVAL, "mi_hmodel_forward: null handle");
-    return ((HModel *)handle)->hforward(mix_dev, out_dev, B, length, (hipStream_t)stream);
+    HModel *m = as_hmodel(handle, "mi_hmodel_forward");
+    return m ? m->hforward(mix_dev, out_dev, B, length, (hipStream_t)stream) : MI_EINVAL;
 }
 
 int mi_hmodel_tap(void *handle, const char *name, float *dst_dev, int32_t B, int64_t *numel_per_item, void *stream) {
     if (!handle || !name || !numel_per_item) return set_error(MI_EINVAL, "mi_hmodel_tap: null argument");
-    HModel *m = (HModel *)handle;
+    HModel *m = as_hmodel(handle, "mi_hmodel_tap");
+    if (!m) return MI_EINVAL;
     auto it = m->taps.find(name);
     if (it == m->taps.end()) return set_error(MI_EINVAL, "mi_hmodel_tap: unknown tap '%s'", name);
     *numel_per_item = it->second.second;
@@ -231,15 +252,19 @@ int mi_hmodel_tap(void *handle, const char *name, float *dst_dev, int32_t B, int
 
 int mi_hmodel_status(void *handle, void *stream) {
     if (!handle) return set_error(MI_EINVAL, "mi_hmodel_status: null handle");
+    HModel *m = as_hmodel(handle, "mi_hmodel_status");
+    if (!m) return MI_EINVAL;
     MI_HIP(hipStreamSynchronize((hipStream_t)stream));
-    HModel *m = (HModel *)handle;
     MI_REQUIRE(!m->lstm_timeout || *(volatile unsigned *)m->lstm_timeout == 0,
                "a forward's persistent LSTM kernel timed out waiting for its hidden-state exchange (GPU shared with another process's "
                "persistent kernels?): its output and every later one are invalid; MI_LSTM_STEPS=1 selects the one-launch-per-step recurrence");
     return MI_OK;
 }
 
-int64_t mi_hmodel_device_bytes(void *handle) { return handle ? ((HModel *)handle)->device_bytes + ((HModel *)handle)->hws_bytes : 0; }
+int64_t mi_hmodel_device_bytes(void *handle) {
+    HModel *m = handle ? as_hmodel(handle, "mi_hmodel_device_bytes") : nullptr;
+    return m ? m->weights.bytes + m->work.bytes : 0;
+}
 
 int mi_set_two_streams(int32_t enabled) {
     const int old = g_two_streams;
@@ -267,13 +292,13 @@ int mi_set_transpose_tiles(int32_t enabled) {
 
 int mi_profile_begin(void *handle) {
     if (!handle) return set_error(MI_EINVAL, "mi_profile_begin: null handle");
-    ((Model *)handle)->prof.begin();
+    static_cast<EngineCore *>(handle)->prof.begin();
     return MI_OK;
 }
 
 int mi_profile_end(void *handle, mi_profile_row *rows, int32_t max_rows, int32_t *n_rows, void *stream) {
     if (!handle || !rows || !n_rows) return set_error(MI_EINVAL, "mi_profile_end: null argument");
-    Model *m = (Model *)handle;
+    EngineCore *m = static_cast<EngineCore *>(handle);
     MI_TRY(m->prof.end((hipStream_t)stream));
     int n = 0;
     for (const ProfRow &r : m->prof.rows) {
@@ -288,9 +313,8 @@ int mi_profile_end(void *handle, mi_profile_row *rows, int32_t max_rows, int32_t
 }
 
 int64_t mi_model_device_bytes(void *handle) {
-    if (!handle) return 0;
-    Model *m = (Model *)handle;
-    return m->device_bytes + (m->ws ? m->ws->bytes : 0);       // weights + the (possibly shared) workspace
+    Model *m = handle ? as_model(handle, "mi_model_device_bytes") : nullptr;
+    return m ? m->weights.bytes + (m->ws ? m->ws->mem.bytes : 0) : 0;       // weights + the (possibly shared) workspace
 }
 
 int mi_segments_gather(const float *track_dev, int64_t track_len, int32_t channels, const int64_t *starts_dev, int32_t B,

@@ -1,11 +1,10 @@
 // Hybrid Demucs v3 engine state (`hdemucs_mmi` architecture: the reference's HDemucs with its default hyper-parameters,
-// demucs/hdemucs.py:366-580).  Reuses the packing helpers and the conv launcher of the htdemucs engine (Model).
+// demucs/hdemucs.py:366-580).  The packing helpers, the conv launcher and the DConv block are the shared ones (EngineCore).
 #pragma once
 #include <map>
 #include <string>
 
-#include "model.h"
-#include "model_internal.h"
+#include "engine_core.h"
 
 namespace mi {
 
@@ -30,10 +29,10 @@ struct HGeo {                   // everything that depends on the input length
     std::map<std::string, const mi_ktab_entry *> ktabs;
     DConvW enc_dconv[4], tenc_dconv[4];      // copies of the weights with this geometry's gather tables
     uint64_t last_use = 0;                   // forward counter at the last use: the least recently used geometry is evicted
-    int64_t bytes = 0;                       // device bytes of `ktabs`
 };
 
-struct HModel : Model {
+struct HModel : EngineCore {
+    HModel() : EngineCore(ENGINE_HDEMUCS) {}
     // As Model::plan: decided once, at the end of hinit, from cfg.dtype, switches() and what was packed and allocated
     struct HPlan {
         bool deep_tap = false;      // half modes: the k = 3 convs of layers 4 / 5 and decoders 0 / 1 read tap images (where they have the weights)
@@ -42,14 +41,14 @@ struct HModel : Model {
         bool last_tap = false;      // ... the outermost transposed conv's input included
         bool two_streams = false;   // the waveform branch may run on the side stream (with mi_set_two_streams)
     } hplan;
-    int Lmax = 0, Tmax = 0;
+    int S = 0, Lmax = 0, Tmax = 0;
     int hCh[7] = {};             // layer widths: channels << level (48 ... 3 072 for hdemucs_mmi; 4 ... 256 for demucs_unittest)
     HEncW henc[6], htenc[5];
     HDecW hdec[6], htdec[5];
+    float *freq_emb = nullptr;
     std::map<int, HGeo> geos;              // at most kMaxGeos cached input lengths (LRU): every track's tail chunk and every
     uint64_t use_clock = 0;                // random shift brings a new length, and a long-lived handle sees many tracks
-    std::vector<void *> hws;     // workspace allocations (freed with the handle)
-    int64_t hws_bytes = 0;
+    DeviceArena work;            // workspace allocations (freed with the handle)
     // workspace
     float *x_t0 = nullptr, *x_zt = nullptr, *x_0 = nullptr, *x_skip[6] = {}, *x_skip_t[4] = {}, *x_inject = nullptr;
     float *x_a = nullptr, *x_b = nullptr, *x_h = nullptr, *x_ta = nullptr, *x_tb = nullptr, *x_th = nullptr;
@@ -62,6 +61,8 @@ struct HModel : Model {
     int eimg_L = -1, eimg_B = -1;     // geometry the images' zero slots are valid for
     float *x_gimg = nullptr, *x_tgimg = nullptr;      // half modes: 16-bit operand images of the decoders' GLU outputs (hmodel.hip)
     double *x_stats = nullptr, *x_stats_t = nullptr;
+    double *x_gram2 = nullptr, *x_gram2_t = nullptr;      // run_dconv's Gram accumulators: the spectral branch's (EngineCore::dconv_gram2) and,
+    size_t x_gram2_bytes = 0, x_gram2t_bytes = 0;         // for the side stream, the waveform branch's own
     float2 *x_st1 = nullptr, *x_st2 = nullptr, *x_st1t = nullptr, *x_st2t = nullptr, *x_nf = nullptr, *x_df = nullptr, *x_nt = nullptr,
            *x_dt = nullptr;
     size_t x_stats_bytes = 0;
@@ -75,7 +76,6 @@ struct HModel : Model {
     int hforward(const float *mix, float *out, int B, int L, hipStream_t st);
 
    private:
-    int halloc(void **p, size_t bytes);
     int geometry(int L, HGeo **out);
     void evict_lru();
     int ktab(HGeo &g, const Gather &ga, int Kpad, const mi_ktab_entry **out);

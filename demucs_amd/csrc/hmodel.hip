@@ -21,16 +21,7 @@ constexpr int kMinLength = 1;          // the reference forwards chunks down to 
 constexpr size_t kMaxGeos = 24;        // cached input lengths per handle (least recently used one evicted)
 static const int hFr[5] = {2048, 512, 128, 32, 8};
 
-int HModel::halloc(void **p, size_t bytes) {
-    bytes = (bytes + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) return set_error(MI_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    hws.push_back(*p);
-    hws_bytes += (int64_t)bytes;
-    return MI_OK;
-}
 HModel::~HModel() {
-    for (void *p : hws) (void)hipFree(p);
     if (lstm_timeout) (void)hipHostFree(lstm_timeout);
 }
 
@@ -198,7 +189,7 @@ int HModel::hinit(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
     lt[0] = Lmax;
     for (int i = 0; i < 5; ++i) lt[i + 1] = (lt[i] + 3) / 4;
     for (int i = 0; i < 6; ++i) lp[i] = round_up(lt[i], 4);
-    auto A = [&](float **p, size_t per_item) { return halloc((void **)p, (per_item + 64) * B * sizeof(float)); };
+    auto A = [&](float **p, size_t per_item) { return work.alloc((void **)p, (per_item + 64) * B * sizeof(float)); };
     MI_TRY(A(&x_t0, (size_t)2 * lp[0])); MI_TRY(A(&x_zt, 4 * 2048 * T)); MI_TRY(A(&x_0, 4 * 2048 * T));
     size_t big = 0, hid = 0;          // largest layer tensor; largest DConv hidden tensor (round_up(C / 4, 16) channels: more than C when C < 16)
     for (int i = 0; i < 4; ++i) {
@@ -229,12 +220,12 @@ int HModel::hinit(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
     MI_TRY(A(&x_xf, C3 * fw)); MI_TRY(A(&x_gx, C6 * fw)); MI_TRY(A(&x_o0, C4 * fw)); MI_TRY(A(&x_o1, C4 * fw)); MI_TRY(A(&x_xl, C3 * fw));
     MI_TRY(A(&x_qkc, (3 * C3 + 16) * T)); MI_TRY(A(&x_att, C3 * T));
     MI_TRY(A(&x_lstm, 6 * C3 * (fw / 200 + 2)));          // LSTM state: h ping / pong and c for every (direction, sequence)
-    MI_TRY(halloc(&x_lstm_scratch, lstm_persist_scratch_bytes()));
+    MI_TRY(work.alloc(&x_lstm_scratch, lstm_persist_scratch_bytes()));
     MI_HIP(hipHostMalloc((void **)&lstm_timeout, 64, hipHostMallocMapped));
     *lstm_timeout = 0;
     // (the decoder inputs carry 128 bytes of slack in front as well: the float32 k x k convs read them by LDS-DMA in runs shifted
     // by one sample, gemm_conv.hip conv_gemm_dmatap_kernel; A() already leaves 64 floats per item behind)
-    auto AS = [&](float **p, size_t per_item) { const int r = halloc((void **)p, ((per_item + 64) * B + 64) * sizeof(float)); if (r == MI_OK) *p += 32; return r; };
+    auto AS = [&](float **p, size_t per_item) { const int r = work.alloc((void **)p, ((per_item + 64) * B + 64) * sizeof(float)); if (r == MI_OK) *p += 32; return r; };
     MI_TRY(A(&x_dec[0], C4 * T)); MI_TRY(AS(&x_dec[1], C3 * 8 * T)); MI_TRY(AS(&x_dec[2], hCh[2] * 32 * T)); MI_TRY(AS(&x_dec[3], hCh[1] * 128 * T));
     MI_TRY(AS(&x_dec[4], hCh[0] * 512 * T)); MI_TRY(A(&x_dec[5], (size_t)4 * S * 2048 * T));
     MI_TRY(AS(&x_tdec[0], (size_t)C3 * lp[4])); MI_TRY(AS(&x_tdec[1], (size_t)hCh[2] * lp[3])); MI_TRY(AS(&x_tdec[2], (size_t)hCh[1] * lp[2]));
@@ -242,18 +233,19 @@ int HModel::hinit(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
     MI_TRY(A(&x_yt, (size_t)4 * S * 2048 * T)); MI_TRY(A(&x_fr, (size_t)S * T * 2 * 4096));
     const size_t max_rows = B * 512;
     x_stats_bytes = max_rows * kStatSlots * 2 * sizeof(double);
-    MI_TRY(halloc((void **)&x_stats, x_stats_bytes)); MI_TRY(halloc((void **)&x_stats_t, x_stats_bytes));
+    MI_TRY(work.alloc((void **)&x_stats, x_stats_bytes)); MI_TRY(work.alloc((void **)&x_stats_t, x_stats_bytes));
     MI_HIP(hipMemset(x_stats, 0, x_stats_bytes)); MI_HIP(hipMemset(x_stats_t, 0, x_stats_bytes));
-    gram2_bytes = B * ((size_t)4 << 20);                  // Model::run_dconv's Gram accumulators: B x 512 rows x 32 x 32 float64 at layer 0
-    MI_TRY(halloc((void **)&w_gram2, gram2_bytes));
-    MI_HIP(hipMemset(w_gram2, 0, gram2_bytes));
-    gram2t_bytes = B * ((size_t)2 << 20);                 // the waveform branch's own accumulators: it runs on the side stream
-    MI_TRY(halloc((void **)&w_gram2_t, gram2t_bytes));
-    MI_HIP(hipMemset(w_gram2_t, 0, gram2t_bytes));
-    MI_TRY(halloc((void **)&x_st1, max_rows * sizeof(float2))); MI_TRY(halloc((void **)&x_st2, max_rows * sizeof(float2)));
-    MI_TRY(halloc((void **)&x_st1t, max_rows * sizeof(float2))); MI_TRY(halloc((void **)&x_st2t, max_rows * sizeof(float2)));
-    MI_TRY(halloc((void **)&x_nf, B * sizeof(float2))); MI_TRY(halloc((void **)&x_df, B * sizeof(float2)));
-    MI_TRY(halloc((void **)&x_nt, B * sizeof(float2))); MI_TRY(halloc((void **)&x_dt, B * sizeof(float2)));
+    x_gram2_bytes = B * ((size_t)4 << 20);                // run_dconv's Gram accumulators: B x 512 rows x 32 x 32 float64 at layer 0
+    MI_TRY(work.alloc((void **)&x_gram2, x_gram2_bytes));
+    MI_HIP(hipMemset(x_gram2, 0, x_gram2_bytes));
+    dconv_gram2 = x_gram2; dconv_gram2_bytes = x_gram2_bytes;     // no time-kernel buffer: load_dconv(comp = 4) never sets has_time
+    x_gram2t_bytes = B * ((size_t)2 << 20);               // the waveform branch's own accumulators: it runs on the side stream
+    MI_TRY(work.alloc((void **)&x_gram2_t, x_gram2t_bytes));
+    MI_HIP(hipMemset(x_gram2_t, 0, x_gram2t_bytes));
+    MI_TRY(work.alloc((void **)&x_st1, max_rows * sizeof(float2))); MI_TRY(work.alloc((void **)&x_st2, max_rows * sizeof(float2)));
+    MI_TRY(work.alloc((void **)&x_st1t, max_rows * sizeof(float2))); MI_TRY(work.alloc((void **)&x_st2t, max_rows * sizeof(float2)));
+    MI_TRY(work.alloc((void **)&x_nf, B * sizeof(float2))); MI_TRY(work.alloc((void **)&x_df, B * sizeof(float2)));
+    MI_TRY(work.alloc((void **)&x_nt, B * sizeof(float2))); MI_TRY(work.alloc((void **)&x_dt, B * sizeof(float2)));
     {   // the forward's plan
         const Switches &sw = switches();
         const bool half = cfg.dtype != MI_DTYPE_F32;
@@ -277,30 +269,22 @@ int HModel::ktab(HGeo &g, const Gather &ga, int Kpad, const mi_ktab_entry **out)
     auto it = g.ktabs.find(key);
     if (it == g.ktabs.end()) {
         mi_ktab_entry *t = nullptr;
-        const int64_t before = device_bytes;
         MI_TRY(make_ktab(ga, Kpad, &t));
-        g.bytes += device_bytes - before;
         it = g.ktabs.emplace(key, t).first;
     }
     *out = it->second;
     return MI_OK;
 }
 
-// Drops the least recently used geometry: its gather tables are freed (hipFree waits for the device, so no launch that
-// still reads them is in flight) and taken off the handle's allocation list.
+// Drops the least recently used geometry: its gather tables are released (hipFree waits for the device, so no launch that
+// still reads them is in flight).
 void HModel::evict_lru() {
     auto victim = geos.end();
     for (auto it = geos.begin(); it != geos.end(); ++it)
         if (victim == geos.end() || it->second.last_use < victim->second.last_use) victim = it;
     if (victim == geos.end()) return;
     (void)hipDeviceSynchronize();
-    for (auto &kv : victim->second.ktabs) {
-        void *p = const_cast<mi_ktab_entry *>(kv.second);
-        auto a = std::find(allocs.begin(), allocs.end(), p);
-        if (a != allocs.end()) allocs.erase(a);
-        (void)hipFree(p);
-    }
-    device_bytes -= victim->second.bytes;
+    for (auto &kv : victim->second.ktabs) weights.release(const_cast<mi_ktab_entry *>(kv.second));
     geos.erase(victim);
 }
 
@@ -393,7 +377,7 @@ int HModel::run_deep(HGeo &g, HEncW &e, int C, int Tn, int B, float *x, float *t
             gi.plain = 1; gi.epi = MI_EPI_LINEAR; gi.y = x_gx; gi.y_bstride = (int64_t)8 * H * W; gi.y_cstride = W;
             MI_TRY(conv(gi, st));
             // the LSTM recurrence: W dependent launches timed as one span (bench.py's latency roofline of the mode); row 103 is its own
-            // (101 is Model::run_dconv's dconv_row_kernel)
+            // (101 is EngineCore::run_dconv's dconv_row_kernel)
             MI_TRY(prof.timed(103, switches().lstm_steps ? "lstm_step_kernel" : "lstm_persist_kernel", (double)W * 2.0 * 8.0 * H * H * N,
                               (double)W * (8.0 * H * H + 8.0 * H * N) * 4.0, st,
                               [&] { return run_lstm(x_gx, l.whhT[layer], N, H, W, layer ? x_o1 : x_o0, st); }, W));
@@ -437,8 +421,8 @@ int HModel::hforward(const float *mix, float *out, int B, int L, hipStream_t st)
     if (x_dirty) {
         MI_HIP(hipMemsetAsync(x_stats, 0, x_stats_bytes, st));
         MI_HIP(hipMemsetAsync(x_stats_t, 0, x_stats_bytes, st));
-        MI_HIP(hipMemsetAsync(w_gram2, 0, gram2_bytes, st));
-        MI_HIP(hipMemsetAsync(w_gram2_t, 0, gram2t_bytes, st));
+        MI_HIP(hipMemsetAsync(x_gram2, 0, x_gram2_bytes, st));
+        MI_HIP(hipMemsetAsync(x_gram2_t, 0, x_gram2t_bytes, st));
         x_dirty = false;
     }
     const int r = hforward_impl(mix, out, B, L, st);
@@ -517,7 +501,7 @@ int HModel::hforward_impl(const float *mix, float *out, int B, int L, hipStream_
                 d.D2 = Qp; d.x_ld = Qp; d.S2 = 1;
             }
             MI_TRY(conv(d, stt));
-            MI_TRY(run_dconv(g.tenc_dconv[i], C, go, x_ta, x_tb, x_th, x_stats_t, x_st1t, x_st2t, stt, w_gram2_t, gram2t_bytes));
+            MI_TRY(run_dconv(g.tenc_dconv[i], C, go, x_ta, x_tb, x_th, x_stats_t, x_st1t, x_st2t, stt, x_gram2_t, x_gram2t_bytes));
             MI_TRY(ktab(g, Gather{C, 1, 1, 1, 1, 0, 0, P, (int)P}, htenc[i].rewrite.Kpad, &k));
             mi_conv_desc r = base_desc(htenc[i].rewrite, k, x_ta, C * P, go);
             r.plain = 1; r.epi = MI_EPI_GLU; r.y = x_skip_t[i]; r.y_bstride = C * P; r.y_cstride = P;

@@ -11,13 +11,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from collections import OrderedDict
 from typing import Dict, List, Optional
 
-import numpy as np
 import torch
 
 from . import _lib
+from ._engine_model import EngineModel
 from .hdemucs_weights import HDemucsConfig, hdemucs_schema
 
 __all__ = ["HDemucs"]
@@ -31,9 +30,7 @@ def tail_overlap_enabled() -> bool:
     return os.environ.get("MI_NO_TAIL_OVERLAP") is None
 
 
-class HDemucs:
-    COMPUTE_DTYPES = {"f32": 0, "bf16": 1, "f16": 2}
-
+class HDemucs(EngineModel):
     #: reference keywords that cannot change an eval-mode forward of this architecture
     _INERT = frozenset(("rescale", "dconv_init", "emb_smooth", "wiener_iters", "end_iters", "wiener_residual", "multi_freqs_depth"))
     #: reference keywords whose value the engine hard-codes
@@ -52,8 +49,7 @@ class HDemucs:
             else:
                 raise ValueError(f"unsupported HDemucs argument {k!r}")
         cfg.validate()
-        if compute_dtype not in self.COMPUTE_DTYPES:
-            raise ValueError(f"compute_dtype must be one of {sorted(self.COMPUTE_DTYPES)}, got {compute_dtype!r}")
+        self._check_compute_dtype(compute_dtype)
         self.cfg = cfg
         self.sources = list(sources)
         self.samplerate = cfg.samplerate
@@ -62,54 +58,11 @@ class HDemucs:
         self.max_batch = int(max_batch)
         self.compute_dtype = compute_dtype
         self._schema = hdemucs_schema(cfg)
-        self._state: Optional["OrderedDict[str, np.ndarray]"] = None
+        self._state = None                              # key -> float32 array, set by load_state_dict
         self._handles: Dict[tuple, tuple] = {}          # (device, aux) -> (handle, max_length); aux: the single-item side engine
         self._side_streams: Dict[torch.device, "torch.cuda.Stream"] = {}
         self._device: Optional[torch.device] = None
         self.training = False
-
-    # ---- nn.Module-like surface ---------------------------------------------------------------------------------
-    def load_state_dict(self, state, strict: bool = True):
-        missing = [k for k in self._schema if k not in state]
-        unexpected = [k for k in state if k not in self._schema]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict: missing {missing[:4]}, unexpected {unexpected[:4]}")
-        new: "OrderedDict[str, np.ndarray]" = OrderedDict()
-        for k, shape in self._schema.items():
-            v = state[k]
-            if isinstance(v, torch.Tensor):
-                v = v.detach().to("cpu", torch.float32).numpy()
-            v = np.ascontiguousarray(v, dtype=np.float32)
-            if tuple(v.shape) != tuple(shape):
-                raise RuntimeError(f"size mismatch for {k}: checkpoint {tuple(v.shape)} vs model {tuple(shape)}")
-            new[k] = v
-        self._state = new
-        self._release()
-        return self
-
-    def state_dict(self):
-        if self._state is None:
-            raise RuntimeError("HDemucs has no weights: call load_state_dict first")
-        return OrderedDict((k, torch.from_numpy(v.copy())) for k, v in self._state.items())
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError("demucs_amd.HDemucs is inference-only")
-        return self
-
-    def parameters(self):
-        yield torch.empty(0, device=self._device or torch.device("cpu"))
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self._device = device          # handles are cached per device (see HTDemucs.to)
-        return self
 
     # ---- engine handle ------------------------------------------------------------------------------------------
     def _release(self):
@@ -120,18 +73,8 @@ class HDemucs:
 
     release = _release
 
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
     def _ensure_handle(self, length: int, aux: bool = False) -> int:
-        if self._state is None:
-            raise RuntimeError("HDemucs has no weights: call load_state_dict first")
-        if self._device is None or self._device.type != "cuda":
-            raise _lib.EngineError("demucs_amd.HDemucs only runs on a GPU device (MI355X); call .to('cuda'). "
-                                   "There is no CPU implementation in this package.")
+        self._require_runnable()
         key = (self._device, bool(aux))
         have = self._handles.get(key)
         if have is not None and have[1] >= length:
@@ -142,17 +85,11 @@ class HDemucs:
                 lib.mi_hmodel_destroy(C.c_void_p(have[0]))
             del self._handles[key]
         max_length = max(int(length), int(float(self.segment) * self.samplerate), MIN_LENGTH)
-        names = list(self._state)
-        descs = (_lib.MiTensorDesc * len(names))()
-        for i, k in enumerate(names):
-            v = self._state[k]
-            descs[i].name = k.encode()
-            descs[i].data = v.ctypes.data
-            descs[i].numel = v.size
+        descs = self._tensor_descs()
         cfg = _lib.MiConfig(len(self.sources), max_length, 1 if aux else self.max_batch, self.COMPUTE_DTYPES[self.compute_dtype])
         h = C.c_void_p()
         with torch.cuda.device(self._device):
-            _lib.check(lib.mi_hmodel_create(C.byref(cfg), descs, len(names), C.byref(h)), "mi_hmodel_create")
+            _lib.check(lib.mi_hmodel_create(C.byref(cfg), descs, len(descs), C.byref(h)), "mi_hmodel_create")
         self._handles[key] = (h.value, max_length)
         return h.value
 
@@ -182,25 +119,11 @@ class HDemucs:
         _lib.check(_lib.load().mi_profile_begin(C.c_void_p(h)), "mi_profile_begin")
 
     def profile_end(self):
-        rows = (_lib.MiProfileRow * 128)()
-        n = C.c_int32()
-        h = self._handles[(self._device, False)][0]
-        with torch.cuda.device(self._device):
-            _lib.check(_lib.load().mi_profile_end(C.c_void_p(h), rows, 128, C.byref(n), C.c_void_p(_lib.current_stream_ptr())),
-                       "mi_profile_end")
-        return [dict(name=rows[i].name.decode(), launches=rows[i].launches, ms=rows[i].ms, flops=rows[i].flops, bytes=rows[i].bytes)
-                for i in range(n.value)]
+        return self._profile_end(self._handles[(self._device, False)][0])
 
     def tap(self, name: str, batch: int) -> torch.Tensor:
         """Copy of an internal activation of the last forward (parity tests), shape (batch, numel)."""
-        lib, n = _lib.load(), C.c_int64()
-        h = C.c_void_p(self._handles[(self._device, False)][0])
-        _lib.check(lib.mi_hmodel_tap(h, name.encode(), None, batch, C.byref(n), None), "mi_hmodel_tap")
-        out = torch.empty(batch, n.value, device=self._device, dtype=torch.float32)
-        with torch.cuda.device(self._device):
-            _lib.check(lib.mi_hmodel_tap(h, name.encode(), out.data_ptr(), batch, C.byref(n), C.c_void_p(_lib.current_stream_ptr())),
-                       "mi_hmodel_tap")
-        return out
+        return self._tap("mi_hmodel_tap", self._handles[(self._device, False)][0], name, batch)
 
     # ---- forward --------------------------------------------------------------------------------------------------
     def __call__(self, mix: torch.Tensor, aux: bool = False) -> torch.Tensor:

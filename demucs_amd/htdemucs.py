@@ -13,24 +13,19 @@ from __future__ import annotations
 
 import ctypes as C
 import random
-from collections import OrderedDict
 from fractions import Fraction
 from typing import Dict, List, Optional
 
-import numpy as np
 import torch
 
 from . import _lib
+from ._engine_model import EngineModel
 from .weights import HTDemucsConfig, check_reference_keyword, htdemucs_schema
 
 __all__ = ["HTDemucs"]
 
 
-class HTDemucs:
-    #: compute modes of the engine (mi_config.dtype): operand type of the matrix-core GEMMs and of attention;
-    #: accumulation, statistics, norms, softmax and the STFT / iSTFT are float32 in every mode
-    COMPUTE_DTYPES = {"f32": 0, "bf16": 1, "f16": 2}
-
+class HTDemucs(EngineModel):
     def __init__(self, sources: List[str], segment=Fraction(39, 5), max_batch: int = 8, compute_dtype: str = "f32", **kwargs):
         cfg = HTDemucsConfig(sources=list(sources), segment=Fraction(segment) if not isinstance(segment, Fraction) else segment)
         for k, v in kwargs.items():            # accept the reference's keyword names, reject other architectures
@@ -46,65 +41,12 @@ class HTDemucs:
         self.segment = cfg.segment
         self.use_train_segment = True
         self.max_batch = int(max_batch)
-        if compute_dtype not in self.COMPUTE_DTYPES:
-            raise ValueError(f"compute_dtype must be one of {sorted(self.COMPUTE_DTYPES)}, got {compute_dtype!r}")
-        self.compute_dtype = compute_dtype
+        self.compute_dtype = self._check_compute_dtype(compute_dtype)
         self._schema = htdemucs_schema(cfg)
-        self._state: Optional["OrderedDict[str, np.ndarray]"] = None
+        self._state = None                               # key -> float32 array, set by load_state_dict
         self._handles: Dict[torch.device, int] = {}      # engine handle per GPU the model has been used on
         self._device: Optional[torch.device] = None
         self.training = False
-
-    # ---- nn.Module-like surface ---------------------------------------------------------------
-    def load_state_dict(self, state: Dict[str, "np.ndarray | torch.Tensor"], strict: bool = True):
-        """Accepts the reference checkpoint's `state` (float32 or float16, states.py:83-107)."""
-        missing = [k for k in self._schema if k not in state]
-        unexpected = [k for k in state if k not in self._schema]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict: missing {missing[:4]}..., unexpected {unexpected[:4]}..."
-                               if len(missing) + len(unexpected) > 8 else
-                               f"Error(s) in loading state_dict: missing {missing}, unexpected {unexpected}")
-        new: "OrderedDict[str, np.ndarray]" = OrderedDict()
-        for k, shape in self._schema.items():
-            v = state[k]
-            if isinstance(v, torch.Tensor):
-                v = v.detach().to("cpu", torch.float32).numpy()
-            v = np.ascontiguousarray(v, dtype=np.float32)
-            if tuple(v.shape) != tuple(shape):
-                raise RuntimeError(f"size mismatch for {k}: checkpoint {tuple(v.shape)} vs model {tuple(shape)}")
-            new[k] = v
-        self._state = new
-        self._release()
-        return self
-
-    def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
-        if self._state is None:
-            raise RuntimeError("HTDemucs has no weights: call load_state_dict first")
-        return OrderedDict((k, torch.from_numpy(v.copy())) for k, v in self._state.items())
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError("demucs_amd.HTDemucs is inference-only")
-        return self
-
-    def parameters(self):
-        """A single placeholder tensor on the model's device (apply.py:213 asks for the device)."""
-        dev = self._device or torch.device("cpu")
-        yield torch.empty(0, device=dev)
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        # Engine handles are cached per device: `apply_model` moves every sub-model of a bag to the compute device and
-        # back to its "home" on each call (apply.py:213-218); re-packing 42 M weights each time would dominate.
-        # `release()` frees them explicitly.
-        self._device = device
-        return self
 
     def valid_length(self, length: int) -> int:
         """reference: demucs/htdemucs.py:511-525"""
@@ -128,39 +70,20 @@ class HTDemucs:
         """Free the packed weights (and, with the last handle of its kind, the shared workspace) on every GPU."""
         self._release()
 
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
     def _ensure_handle(self) -> int:
         if self._device in self._handles:
             return self._handles[self._device]
-        if self._state is None:
-            raise RuntimeError("HTDemucs has no weights: call load_state_dict first")
-        if self._device is None or self._device.type != "cuda":
-            raise _lib.EngineError("demucs_amd.HTDemucs only runs on a GPU device (MI355X); call .to('cuda'). "
-                                   "There is no CPU implementation in this package.")
-        lib = _lib.load()
-        names = list(self._state)
-        descs = (_lib.MiTensorDesc * len(names))()
-        for i, k in enumerate(names):
-            v = self._state[k]
-            descs[i].name = k.encode()
-            descs[i].data = v.ctypes.data
-            descs[i].numel = v.size
+        self._require_runnable()
+        descs = self._tensor_descs()
         cfg = _lib.MiConfig(len(self.sources), self.segment_length, self.max_batch, self.COMPUTE_DTYPES[self.compute_dtype])
         h = C.c_void_p()
         with torch.cuda.device(self._device):
-            _lib.check(lib.mi_model_create(C.byref(cfg), descs, len(names), C.byref(h)), "mi_model_create")
+            _lib.check(_lib.load().mi_model_create(C.byref(cfg), descs, len(descs), C.byref(h)), "mi_model_create")
         self._handles[self._device] = h.value
         return h.value
 
     def set_compute_dtype(self, compute_dtype: str):
-        if compute_dtype not in self.COMPUTE_DTYPES:
-            raise ValueError(f"compute_dtype must be one of {sorted(self.COMPUTE_DTYPES)}, got {compute_dtype!r}")
-        if compute_dtype != self.compute_dtype:
+        if self._check_compute_dtype(compute_dtype) != self.compute_dtype:
             self.compute_dtype = compute_dtype
             self._release()
 
@@ -177,23 +100,11 @@ class HTDemucs:
 
     def profile_end(self):
         """[{name, launches, ms, flops, bytes}] per kernel class since profile_begin (synchronises)."""
-        rows = (_lib.MiProfileRow * 128)()
-        n = C.c_int32()
-        with torch.cuda.device(self._device):
-            _lib.check(_lib.load().mi_profile_end(C.c_void_p(self._ensure_handle()), rows, 128, C.byref(n),
-                                                  C.c_void_p(_lib.current_stream_ptr())), "mi_profile_end")
-        return [dict(name=rows[i].name.decode(), launches=rows[i].launches, ms=rows[i].ms, flops=rows[i].flops,
-                     bytes=rows[i].bytes) for i in range(n.value)]
+        return self._profile_end(self._ensure_handle())
 
     def tap(self, name: str, batch: int) -> torch.Tensor:
         """Copy of an internal activation of the last forward (parity tests), shape (batch, numel)."""
-        lib, h, n = _lib.load(), C.c_void_p(self._ensure_handle()), C.c_int64()
-        _lib.check(lib.mi_model_tap(h, name.encode(), None, batch, C.byref(n), None), "mi_model_tap")
-        out = torch.empty(batch, n.value, device=self._device, dtype=torch.float32)
-        with torch.cuda.device(self._device):
-            _lib.check(lib.mi_model_tap(h, name.encode(), out.data_ptr(), batch, C.byref(n),
-                                        C.c_void_p(_lib.current_stream_ptr())), "mi_model_tap")
-        return out
+        return self._tap("mi_model_tap", self._ensure_handle(), name, batch)
 
     # ---- forward --------------------------------------------------------------------------------
     def forward_segments(self, mix: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -14,6 +14,8 @@
  *     default stream).  All work is enqueued asynchronously on `stream`; no call synchronises
  *     the device except mi_model_create / mi_model_destroy.
  *   - a handle is single-stream: do not use one handle from two streams/threads at once.
+ *   - a handle knows its engine: an mi_model_* entry given an hdemucs handle, or an mi_hmodel_* entry given an htdemucs one,
+ *     returns MI_EINVAL (the byte counts: 0) before it touches the handle's state or the GPU; mi_profile_begin / _end take both.
  *   - PROCESS-WIDE STATE (one process per GPU is the deployment).  Handles are independent EXCEPT for: (1) the activation
  *     workspace of the htdemucs engine, which every handle created on the same device with the same (n_sources,
  *     segment_length, max_batch, float32 / half) shares -- a bag of four fine-tuned models holds its ~0.57 GB per batched

@@ -1,7 +1,7 @@
 """The fused DConv kernels alone, through the C ABI, against float64: dconv_row.hip (`mi_dconv_row`: both residual layers of the
 frequency branch on one (batch, bin) row per wave, and the LDS-resident variant) and dconv_time.hip (`mi_dconv_time_layer`: one
 residual layer of the time branch in three streaming passes, the second GroupNorm's statistics from a Gram matrix in self-cleaning
-float64 slot buffers).  The entries pack the checkpoint's natural-layout tensors with the function Model::load_dconv uses.
+float64 slot buffers).  The entries pack the checkpoint's natural-layout tensors with the function EngineCore::load_dconv uses.
 
 Reference: torch on the CPU in float64 of demucs/demucs.py:133-154,
     conv1d(dilation d, padding d) -> GroupNorm(1) -> GELU -> 1x1 -> GroupNorm(1) -> GLU -> LayerScale -> + x,
