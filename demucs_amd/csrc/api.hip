@@ -319,7 +319,8 @@ int64_t mi_model_device_bytes(void *handle) {
 
 int mi_segments_gather(const float *track_dev, int64_t track_len, int32_t channels, const int64_t *starts_dev, int32_t B,
                        int32_t valid, float *seg_dev, int64_t seg_capacity, void *stream) {
-    MI_REQUIRE(track_dev && starts_dev && seg_dev && B > 0 && valid > 0 && channels > 0, "mi_segments_gather: bad argument");
+    MI_REQUIRE(track_dev && starts_dev && seg_dev && B > 0 && B <= 65535 && valid > 0 && channels > 0 && channels <= 65535,
+               "mi_segments_gather: bad argument");
     MI_REQUIRE((int64_t)B * channels * valid <= seg_capacity, "mi_segments_gather: %d x %d x %d floats do not fit seg_dev (%lld)", B,
                channels, valid, (long long)seg_capacity);
     return launch_segments_gather(track_dev, track_len, channels, starts_dev, B, valid, seg_dev, (hipStream_t)stream);
@@ -328,8 +329,8 @@ int mi_segments_gather(const float *track_dev, int64_t track_len, int32_t channe
 int mi_ola_accumulate(float *acc_dev, int64_t acc_len, int32_t rows, const float *model_out_dev, int32_t valid,
                       int64_t out_capacity, const int64_t *offs_dev, const int32_t *lens_dev, const int32_t *trim_dev, int32_t B,
                       int64_t span_lo, int64_t span_hi, const float *weight_dev, int32_t weight_len, void *stream) {
-    MI_REQUIRE(acc_dev && model_out_dev && offs_dev && lens_dev && trim_dev && weight_dev && B > 0 && rows > 0 && valid > 0 &&
-               weight_len > 0, "mi_ola_accumulate: bad argument");
+    MI_REQUIRE(acc_dev && model_out_dev && offs_dev && lens_dev && trim_dev && weight_dev && B > 0 && rows > 0 && rows <= 65535 &&
+               valid > 0 && weight_len > 0, "mi_ola_accumulate: bad argument");
     MI_REQUIRE((int64_t)B * rows * valid <= out_capacity, "mi_ola_accumulate: %d x %d x %d floats exceed model_out_dev (%lld)", B, rows,
                valid, (long long)out_capacity);
     MI_REQUIRE(span_hi <= acc_len, "mi_ola_accumulate: span end %lld past the accumulator (%lld)", (long long)span_hi, (long long)acc_len);
@@ -339,7 +340,8 @@ int mi_ola_accumulate(float *acc_dev, int64_t acc_len, int32_t rows, const float
 
 int mi_ola_finish(float *acc_dev, int64_t acc_len, int32_t rows, int64_t acc_off0, const int64_t *offs_dev,
                   const int32_t *lens_dev, int32_t n_segments, int32_t max_len, const float *weight_dev, void *stream) {
-    MI_REQUIRE(acc_dev && offs_dev && lens_dev && weight_dev && n_segments > 0, "mi_ola_finish: bad argument");
+    MI_REQUIRE(acc_dev && offs_dev && lens_dev && weight_dev && n_segments > 0 && rows > 0 && rows <= 65535,
+               "mi_ola_finish: bad argument");
     return launch_ola_finish(acc_dev, acc_len, rows, acc_off0, offs_dev, lens_dev, n_segments, max_len, weight_dev,
                              (hipStream_t)stream);
 }

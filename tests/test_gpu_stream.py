@@ -147,11 +147,17 @@ def assert_same_bits(got, want, what=""):
         raise AssertionError(f"{what}: {len(bad)} of {got.numel()} differ, e.g. {list(zip(idx, pairs))}")
 
 
-@pytest.mark.parametrize("members,shifts", [(1, 0), (1, 1), (1, 3), (2, 2), (3, 1), (4, 3), (2, 0)])
-def test_emit_kernel_equals_the_torch_operations(members, shifts):
+EMIT_SL = 3000
+# stride 0.75 SL is the two-fold overlap of overlap=0.25; SL // 4 is four-fold, where the float32 sum of weights depends on its order
+EMIT_CASES = [pytest.param(m, s, 2250, id=f"{m}-{s}") for m, s in [(1, 0), (1, 1), (1, 3), (2, 2), (3, 1), (4, 3), (2, 0)]]
+EMIT_CASES += [pytest.param(m, s, EMIT_SL // 4, id=f"{m}-{s}-fourfold") for m, s in [(1, 0), (2, 2)]]
+
+
+@pytest.mark.parametrize("members,shifts,stride", EMIT_CASES)
+def test_emit_kernel_equals_the_torch_operations(members, shifts, stride):
     lib = _lib.load()
     g = torch.Generator().manual_seed(members * 10 + shifts)
-    S, Ch, SL, stride, L = 4, 2, 3000, 2250, 10000
+    S, Ch, SL, L = 4, 2, EMIT_SL, 10000
     rows = S * Ch
     weights = (torch.cat([torch.arange(1, SL // 2 + 1), torch.arange(SL - SL // 2, 0, -1)]) / (SL // 2)).float().cuda()
     bag = [[float(x) for x in torch.rand(S, generator=g) * 2] for _ in range(members)] if members > 1 else None
