@@ -545,18 +545,17 @@ static int launch_dmarow(const mi_conv_desc &d, int tile, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// `dma` (route MI_ROUTE_DMA): the LDS-DMA linear tile instead of the register-staged loader -- a plain LINEAR layer on the 128-row tile
+// The native kernels, `r` as conv_route decided.  Route MI_ROUTE_DMA: the LDS-DMA linear tile instead of the register-staged
+// loader -- a plain LINEAR layer on the 128-row tile
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN>
-static int launch_cfg(const mi_conv_desc &d, bool dma, hipStream_t st) {
+static int launch_cfg(const mi_conv_desc &d, const ConvRoute &r, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
+    const bool dma = r.route == MI_ROUTE_DMA;
     const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
     MI_REQUIRE(N64 < (1ll << 31) - 256, "conv: too many output positions (%lld)", (long long)N64);
     MI_REQUIRE(d.Mpad % BM == 0, "conv: Mpad %d not a multiple of the %d-row tile", d.Mpad, BM);
     const int N = (int)N64, MT = d.Mpad / BM, NT = ceil_div(N, BN);
-    // M groups (gemm_tile.h) halve this kernel's L2 misses on the 4 MiB weight matrices (TCC hit rate 48 % -> 74 %) but
-    // the misses were Infinity-Cache hits: no time is gained and every activation tile is then fetched from HBM by
-    // several XCDs (+10 % HBM bytes), so the fp32 path keeps one group unless MI_MGROUPS=1.
-    const int Gm = switches().mgroups ? pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 4) : 1;
+    const int Gm = r.mgroups ? pick_m_groups(MT, (size_t)d.Kpad * d.Mpad * 4) : 1;
     const unsigned grid = grouped_grid(MT, NT, Gm);
     if constexpr (PLAIN && BM == 128 && EPI == MI_EPI_LINEAR) {
         if (dma) {
@@ -572,23 +571,14 @@ static int launch_cfg(const mi_conv_desc &d, bool dma, hipStream_t st) {
 }
 
 template <int EPI, int LFLAGS, bool PLAIN>
-static int launch_tile(const mi_conv_desc &d, int tile, bool dma, hipStream_t st) {
-    switch (tile) {
-        case 128: return launch_cfg<2, 2, 2, 2, EPI, LFLAGS, PLAIN>(d, dma, st);
-        case 96: return launch_cfg<1, 4, 3, 1, EPI, LFLAGS, PLAIN>(d, dma, st);
-        case 64: return launch_cfg<1, 4, 2, 1, EPI, LFLAGS, PLAIN>(d, dma, st);
-        case 32: return launch_cfg<1, 4, 1, 1, EPI, LFLAGS, PLAIN>(d, dma, st);
+static int launch_tile(const mi_conv_desc &d, const ConvRoute &r, hipStream_t st) {
+    switch (r.tile) {
+        case 128: return launch_cfg<2, 2, 2, 2, EPI, LFLAGS, PLAIN>(d, r, st);
+        case 96: return launch_cfg<1, 4, 3, 1, EPI, LFLAGS, PLAIN>(d, r, st);
+        case 64: return launch_cfg<1, 4, 2, 1, EPI, LFLAGS, PLAIN>(d, r, st);
+        case 32: return launch_cfg<1, 4, 1, 1, EPI, LFLAGS, PLAIN>(d, r, st);
     }
-    return set_error(MI_EINVAL, "conv: unsupported tile_m %d", tile);
-}
-
-int conv_pick_tile(int M) {
-    if (M <= 32) return 32;
-    if (M <= 64) return 64;
-    if (M % 128 == 0) return 128;
-    if (M % 96 == 0) return 96;
-    if (M <= 96) return 96;
-    return 128;
+    return set_error(MI_EINVAL, "conv: unsupported tile_m %d", r.tile);
 }
 
 // MI_SINK_FLOATS-float dump for the epilogue's out-of-range stores (thread tid writes word tid % MI_SINK_FLOATS), shared by all
@@ -602,149 +592,18 @@ static float *conv_sink() {
     return p;
 }
 
-
 // 256 bytes of zeros in device memory (the tail of the sink): source of LDS-DMA loads that fall outside a tensor
 const void *conv_zero_page() {
     float *p = conv_sink();
     return p ? p + MI_SINK_FLOATS : nullptr;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Which kernel a float32 layer runs: the environment switches, the eligibility of the loaders and conv_route, which turns them
-// into one value.  Nothing below this line and above launch_conv touches the GPU.
-
-// process-wide switch of the split-bf16 main loops (mi_set_split_bf16): 0 ignores every split weight image
-int g_split_bf16 = 1;
-
-// Small batches: a layer whose 128-row tiles give fewer workgroups than the chip has CUs (B = 1: M = 512 and 2 688 tokens -> 84;
-// a k x k GLU conv: 6 x 21) runs on a smaller tile instead -- more workgroups at a lower per-workgroup rate.  Which tile that is
-// depends on the route (conv_route).  MI_SMALL_TILE=0: off
-static bool under_filled(const mi_conv_desc &d, int tile = 128) {
-    return (int64_t)(d.Mpad / tile) * ceil_div((int64_t)d.B * d.O1 * d.O2, BN) < 200;
-}
-
-// float32, stride-1 k x k conv with K2 = 3 whose geometry the descriptor states (ntaps, tap_k2, tap_pad*): the DMA loop above,
-// or, for a layer with a usable split weight image (`has_image`) when asked for it (`split`), the same shifted-run loader in front of the split-bf16 main loop (gemm_x6.hip
-// conv_tap_x6_kernel; GLU only)
-static bool dmatap_eligible(const mi_conv_desc &d, int tile, bool has_image, bool split = false) {
-    const bool off = switches().no_dma_tap;
-    const int ld = d.x_ld ? d.x_ld : d.D2;
-    if (switches().no_dma_dconv && d.epi == MI_EPI_BIAS_STATS) return false;      // A/B switch for the BIAS_STATS kind alone
-    const int dil = d.tap_dil2 ? d.tap_dil2 : 1;
-    // GLU: the decoders' 3 x 3 / k = 3 rewrite convs (96- / 128-row tiles); BIAS_STATS: the DConv blocks' dilated k = 3 convs (32- / 64-row)
-    const bool kind = (d.epi == MI_EPI_GLU && (tile == 96 || tile == 128) && (d.ntaps == 9 || d.ntaps == 3) && dil == 1) ||
-                      (d.epi == MI_EPI_BIAS_STATS && (tile == 32 || tile == 64) && d.ntaps == 3 && (dil == 1 || dil == 2) && d.flags == 0);
-    return !off && !d.half && (split ? has_image && d.epi == MI_EPI_GLU : !has_image) && kind && d.tap_k2 == 3 && d.Mpad % tile == 0 &&
-           d.K % d.ntaps == 0 && d.S1 == 1 && d.S2 == 1 && d.O1 == d.D1 && d.O2 == ld && ld % 4 == 0 && d.tap_pad2 == dil &&
-           d.tap_pad1 == (d.ntaps / 3 - 1) / 2 && !(d.flags & (MI_FLAG_IMG | MI_FLAG_IMG4)) && d.x_bstride == (int64_t)(d.K / d.ntaps) * d.D1 * ld;
-}
-// float32 layer with row taps only (the caller vouches for the table: `dma_rows`; a plain layer's table is the identity): see above.
-// `split`: such a layer with a split weight image -- a strided encoder conv (LINEAR + GELU) or transposed conv on a 96- / 128-row
-// tile, a 1 x 1 + GLU layer on a 128-row tile -- takes the same row loader in front of the split-bf16 main loop (gemm_x6.hip
-// conv_rows_x6_kernel); MI_NO_DMA_ROWS=1 turns both off
-static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain, bool has_image, bool split = false) {
-    const bool off = switches().no_dma_rows;
-    const int ld = d.x_ld ? d.x_ld : d.D2;
-    const int lf = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS | MI_FLAG_IMG | MI_FLAG_IMG4 | MI_FLAG_HEADS);
-    // 1x1 + GLU / GroupNorm-GLU: 128-row tiles only -- the 96-row ones are the level-0 / 1 rewrites (K = 48 / 96: three or six K steps,
-    // bound by their output), where the register-staged kernel's four workgroups per CU measured 3 % faster (476 vs 490 us)
-    const bool epi_ok = (d.epi == MI_EPI_LINEAR && lf == MI_FLAG_GELU && !plain) || d.epi == MI_EPI_CONVTR ||
-                        ((d.epi == MI_EPI_GLU || d.epi == MI_EPI_GN_GLU) && plain && tile == 128 && !(d.flags & (MI_FLAG_IMG | MI_FLAG_IMG4)));
-    if (split && (d.epi == MI_EPI_GN_GLU || tile == 64)) return false;
-    return !off && !d.half && (split ? has_image : !has_image) && d.ktab && epi_ok && (plain || d.dma_rows) && (tile == 64 || tile == 96 || tile == 128) &&
-           d.Mpad % tile == 0 && d.S2 == 1 && d.O2 == ld && ld % 4 == 0 && ((uintptr_t)d.x & 3) == 0 && ((uintptr_t)d.ktab & 63) == 0 &&
-           (d.epi == MI_EPI_CONVTR || tile != 64 || d.epi == MI_EPI_LINEAR);
-}
-
-int conv_check_tile_m(const mi_conv_desc &d) {
-    MI_REQUIRE(d.tile_m != 192 || (d.M > 0 && d.M % 192 == 0 && d.Mpad == d.M), "conv: tile_m 192 needs M %% 192 == 0 and no M padding (M %d, Mpad %d)", d.M, d.Mpad);
-    return MI_OK;
-}
-
-// The decision, top to bottom; the first test that holds wins (kernels.h ConvRoute)
-ConvRoute conv_route(const mi_conv_desc &d) {
-    const bool image = d.wx && g_split_bf16;                // mi_set_split_bf16(0): native fp32 MFMA kernels only
-    const Switches &sw = switches();
-    // tile_m = 192 (a layer with M % 192 == 0 whose split image is a run of 96-row images): the float32 weights, and so every
-    // native and half-mode kernel, keep the tile conv_pick_tile gives
-    const int tile = d.tile_m && d.tile_m != 192 ? d.tile_m : conv_pick_tile(d.M);
-    // plain fast path: a 1x1 / linear layer whose gather is the identity
-    const int64_t P = (int64_t)d.O1 * d.O2;
-    // (an operand-image input is never read through x: the float4 loader's conditions on K, P and x do not apply to it)
-    const bool plain = d.plain && (d.xh || (d.K == d.Kpad && P % 4 == 0 && d.x_bstride % 4 == 0 && ((uintptr_t)d.x & 15) == 0)) &&
-                       d.S1 == 1 && d.S2 == 1 && d.D1 == d.O1 && (d.x_ld ? d.x_ld : d.D2) == d.O2;
-    if (d.wtap) return {MI_ROUTE_TAP_HALF, tile, plain};
-    if (d.half) return {MI_ROUTE_HALF, tile, plain};
-    const bool t192 = d.tile_m == 192 && image;
-    const bool small = sw.small_tile && tile == 128 && !t192 && under_filled(d), small_linear = small && plain && d.epi == MI_EPI_LINEAR;
-    // The 192-row layers: the 192-row tile where the loader family has it for the layer's epilogue and its workgroups fill the
-    // chip, else the 96-row tile on the same image (bit-identical to it); never the 64-row tile, which needs a 128-row image
-    const int lf = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS);
-    auto split_tile = [&](int ntaps) {
-        if (!t192) return small ? 64 : tile;
-        const bool filled = !(sw.small_tile && under_filled(d, 192));
-        return filled && conv_x6_tile192_supported(d.epi, d.epi == MI_EPI_LINEAR ? lf : 0, plain, ntaps) ? 192 : 96;
-    };
-    // Split weight image.  An under-filled layer takes the 64-row tile that reads the 128-row image: bit-identical to the 128-row
-    // tile, no second image.  The decoders' 3 x 3 / k = 3 rewrite convs: shifted-run DMA taps in front of the split-bf16 main loop
-    if (!plain && !sw.x6_plain_only && dmatap_eligible(d, tile, image, true)) return {MI_ROUTE_TAP_X6, split_tile(d.ntaps), plain};
-    // the frequency branch's encoder / transposed convs and the 1 x 1 + GLU rewrites: the DMA row loader in front of it
-    if (!sw.x6_plain_only && dmarow_eligible(d, tile, plain, image, true)) return {MI_ROUTE_ROWS_X6, split_tile(-1), plain};
-    // native DMA taps: an under-filled k x k GLU conv takes 96-row tiles
-    const int ktile = small && !plain && d.epi == MI_EPI_GLU && d.Mpad % 96 == 0 ? 96 : tile;
-    if (!plain && dmatap_eligible(d, ktile, image)) return {MI_ROUTE_DMATAP, ktile, plain};
-    if (dmarow_eligible(d, tile, plain, image)) return {MI_ROUTE_DMAROW, tile, plain};
-    // the split-bf16 main loop behind the plain loader or the gather table (MI_X6_MODE=1: plain layers only)
-    if (image && conv_x6_supported(tile) && (!sw.x6_plain_only || plain)) return {MI_ROUTE_X6, t192 ? split_tile(0) : small_linear ? 64 : tile, plain};
-    // native fp32 kernels: an under-filled plain linear layer takes 64-row tiles
-    const int ntile = small_linear && d.Mpad % 64 == 0 ? 64 : tile;
-    const bool dma = plain && ntile == 128 && d.epi == MI_EPI_LINEAR && !sw.no_dma;
-    return {dma ? MI_ROUTE_DMA : MI_ROUTE_TABLE, ntile, plain};
-}
-
-// validate, decide (conv_route), launch
+// fill the sink, validate and decide (conv_route.hip), launch
 int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     mi_conv_desc d = din;
-    MI_TRY(conv_check_tile_m(d));
     if (!d.sink) d.sink = conv_sink();
     MI_REQUIRE(d.sink && ((uintptr_t)d.sink & 15) == 0, "conv: the store sink could not be allocated or is not 16-byte aligned");
-    MI_REQUIRE((int64_t)d.Mpad * d.y_cstride < (1ll << 31), "conv: output channel stride too large for 32-bit row offsets");
-    MI_REQUIRE(d.Kpad % BK == 0 && d.Kpad >= BK, "conv: Kpad %d must be a positive multiple of %d", d.Kpad, BK);
-    MI_REQUIRE(d.Mpad % 4 == 0, "conv: Mpad %d must be a multiple of 4", d.Mpad);
-    MI_REQUIRE(d.O2 >= 32 || d.row_mode == 0 || (d.epi != MI_EPI_BIAS_STATS && d.epi != MI_EPI_STATS_ONLY),
-               "conv: statistics epilogue needs O2 >= 32");
-    MI_REQUIRE(d.pro == 0, "conv: the fused GroupNorm+GELU prologue was replaced by launch_gn_gelu");
-    MI_REQUIRE(!(d.flags & MI_FLAG_IMG4) || (d.epi == MI_EPI_GLU && d.half && d.yh && d.yh_pq > 0 && d.yh_n >= (int64_t)d.B * d.yh_pq && d.M % 32 == 0 &&
-                                             ((uintptr_t)d.yh & 15) == 0),
-               "conv: MI_FLAG_IMG4 needs a half-mode GLU layer with M %% 32 == 0 and an aligned phase image of >= B * yh_pq positions per plane");
-    MI_REQUIRE(!(d.flags & MI_FLAG_STATS) || (d.epi == MI_EPI_LINEAR && d.stats && d.O2 >= 32 && d.row_mode == 0),
-               "conv: MI_FLAG_STATS needs a LINEAR layer, a statistics buffer and O2 >= 32");
-    MI_REQUIRE(!(d.flags & MI_FLAG_LN) || (d.pro_stats && d.scale && d.epi == MI_EPI_LINEAR), "conv: MI_FLAG_LN needs pro_stats and scale");
-    const int64_t P = (int64_t)d.O1 * d.O2;
-    MI_REQUIRE(!(d.flags & MI_FLAG_IMG) || d.epi == MI_EPI_CONVTR ||
-               (d.half && d.yh && d.epi == MI_EPI_LINEAR && d.M % 8 == 0 && d.yh_n >= (int64_t)d.B * P && ((uintptr_t)d.yh & 15) == 0) ||
-               (d.half && d.yh && d.epi == MI_EPI_GLU && d.M % 32 == 0 && !(d.flags & (MI_FLAG_IMG4 | MI_FLAG_EMB)) && d.yh_n >= (int64_t)d.B * P &&
-                ((uintptr_t)d.yh & 15) == 0),
-               "conv: MI_FLAG_IMG needs a half-precision LINEAR layer with M %% 8 == 0 (or GLU layer with M %% 32 == 0) and an aligned "
-               "output image of >= B * P columns");
-    MI_REQUIRE(d.epi != MI_EPI_CONVTR || ((int64_t)d.Mpad * d.y_cstride < (1ll << 30) && (d.tr_stride == 0 || d.tr_stride == 2 || d.tr_stride == 4) &&
-                                          d.M % (d.tr_stride == 2 ? 2 : 4) == 0),
-               "conv: transposed conv needs stride 2 or 4, M a multiple of it and 30-bit output offsets per item");
-    {   // the scatter epilogue is compiled for these flag sets (gemm_tile.h convtr_tile)
-        const int f = d.flags & (MI_FLAG_GELU | MI_FLAG_RES | MI_FLAG_IMG);
-        MI_REQUIRE(d.epi != MI_EPI_CONVTR || f == 0 || (d.tr_stride != 2 && (f == (MI_FLAG_GELU | MI_FLAG_RES) || f == (MI_FLAG_GELU | MI_FLAG_RES | MI_FLAG_IMG))),
-                   "conv: transposed conv epilogue supports no flags, GELU|RES or GELU|RES|IMG (stride 2: no flags), got %d", d.flags);
-    }
-    MI_REQUIRE(!(d.flags & MI_FLAG_IMG) || d.epi != MI_EPI_CONVTR ||
-               (d.half && d.yh && d.yh_n >= (int64_t)d.B * d.y_cstride && ((uintptr_t)d.yh & 15) == 0),
-               "conv: MI_FLAG_IMG on a transposed conv needs a half mode and an output image of >= B * y_cstride positions");
-    MI_REQUIRE(!d.wtap || (d.half && d.xh), "conv: tap-ordered weights need a half mode and an operand-image input");
-    // (a layer with tap-ordered weights answers to the check above alone)
-    MI_REQUIRE(d.wtap || !(d.flags & MI_FLAG_HEADS) || (d.half && d.yh && d.epi == MI_EPI_LINEAR && d.M % 512 == 0 && d.O1 == 1 && d.yh_n >= d.O2 &&
-                                                        ((uintptr_t)d.yh & 15) == 0 && !(d.flags & MI_FLAG_IMG)),
-               "conv: MI_FLAG_HEADS needs a half-precision LINEAR layer on tokens (O1 = 1) with M %% 512 == 0 and an aligned output");
-    MI_REQUIRE(!d.xh || d.half, "conv: an operand-image input needs a half-precision layer");
-
+    MI_TRY(conv_validate(d));
     const ConvRoute r = conv_route(d);
     // the tile the layer's split image was packed for: a 192-row layer's is a run of 96-row images
     const int image_tile = d.tile_m == 192 ? 96 : d.tile_m ? d.tile_m : conv_pick_tile(d.M);
@@ -752,7 +611,9 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     g_last_conv_tile = r.tile;
     switch (r.route) {
         case MI_ROUTE_TAP_HALF: return launch_conv_tap(d, r.tile, st);
-        case MI_ROUTE_HALF: return launch_conv_half(d, r.tile, r.plain, st);
+        case MI_ROUTE_HALF:
+        case MI_ROUTE_HALF_IMG:
+        case MI_ROUTE_HALF_IMG256: return launch_conv_half(d, r, st);
         case MI_ROUTE_TAP_X6: return launch_conv_tap_x6(d, r.tile, image_tile, st);
         case MI_ROUTE_ROWS_X6: return launch_conv_rows_x6(d, r.tile, image_tile, st);
         case MI_ROUTE_X6: return launch_conv_x6(d, r.tile, image_tile, r.plain, st);
@@ -768,10 +629,9 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
             return set_error(MI_EINVAL, "conv: DMA row route has no epilogue %d", d.epi);
     }
     // MI_ROUTE_TABLE, MI_ROUTE_DMA: the native fp32 kernels
-    const bool dma = r.route == MI_ROUTE_DMA;
     return dispatch_epilogue(d, [&](auto epi, auto lflags) {
         constexpr int E = decltype(epi)::value, F = decltype(lflags)::value;
-        return r.plain ? launch_tile<E, F, true>(d, r.tile, dma, st) : launch_tile<E, F, false>(d, r.tile, dma, st);
+        return r.plain ? launch_tile<E, F, true>(d, r, st) : launch_tile<E, F, false>(d, r, st);
     });
 }
 

@@ -480,8 +480,7 @@ static int launch_cfg_half(const mi_conv_desc &d, hipStream_t st) {
 template <int HT, int EPI, int LFLAGS, bool PLAIN>
 static int launch_tile_half(const mi_conv_desc &d, int tile, hipStream_t st) {
     if constexpr (PLAIN && EPI == MI_EPI_LINEAR) {
-        // 256 x 128 for the transformer's linear layers: the 128 x 128 tile is bound by cache bandwidth (43 FLOP per byte of
-        // float32 activations + 16-bit weights); twice the rows per activation tile brings that to 64
+        // 256 x 128 for the transformer's linear layers (conv_route)
         if (tile == 256) return launch_cfg_half<HT, 2, 2, 4, 2, EPI, LFLAGS, PLAIN>(d, st);
     }
     switch (tile) {
@@ -493,66 +492,31 @@ static int launch_tile_half(const mi_conv_desc &d, int tile, hipStream_t st) {
     return set_error(MI_EINVAL, "conv half: unsupported tile_m %d", tile);
 }
 
+// `r` as conv_route decided: the kernel family (route) and its tile; the launchers below add the checks of their own operands
 template <int HT>
-static int launch_conv_half_t(const mi_conv_desc &d, int tile, bool plain, hipStream_t st) {
-#define MI_DISPATCH(E)                                              \
-    case E: return plain ? launch_tile_half<HT, E, 0, true>(d, tile, st) : launch_tile_half<HT, E, 0, false>(d, tile, st)
-#define MI_LINEAR(F)                                                \
-    case F: return plain ? launch_tile_half<HT, MI_EPI_LINEAR, F, true>(d, tile, st) : launch_tile_half<HT, MI_EPI_LINEAR, F, false>(d, tile, st)
-    if (d.xh) {         // input given as a 16-bit operand image: lin2 / out_proj, and (256-row tile) the in-projections and lin1
-        const int f = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_IMG | MI_FLAG_HEADS | MI_FLAG_STATS);
-        MI_REQUIRE(d.epi == MI_EPI_LINEAR && plain, "conv: an operand-image input needs a plain LINEAR layer");
-        // residual epilogues (out_proj, lin2: 340 MB of float32 residual read + output write per launch) keep the 256 x 128 tile
-        // at two workgroups per CU, whose epilogues overlap each other's main loops: measured 9.63 ms against 9.79 for the
-        // linear class with the 256 x 256 tile here (MI_IMG256=1: A/B switch)
-        const bool img256 = switches().img256;
-        if (f == (MI_FLAG_SCALE | MI_FLAG_RES)) {
-            if (img256 && d.Mpad % 256 == 0) return launch_half_img256<HT, MI_FLAG_SCALE | MI_FLAG_RES>(d, st);
-            return d.Mpad % 256 == 0 ? launch_half_img<HT, 4, MI_FLAG_SCALE | MI_FLAG_RES>(d, st) : launch_half_img<HT, 2, MI_FLAG_SCALE | MI_FLAG_RES>(d, st);
+static int launch_conv_half_t(const mi_conv_desc &d, const ConvRoute &r, hipStream_t st) {
+    return dispatch_epilogue_half(d, [&](auto epi, auto lflags) {
+        constexpr int E = decltype(epi)::value, F = decltype(lflags)::value;
+        constexpr int SR = MI_FLAG_SCALE | MI_FLAG_RES;
+        if (r.route == MI_ROUTE_HALF) return r.plain ? launch_tile_half<HT, E, F, true>(d, r.tile, st) : launch_tile_half<HT, E, F, false>(d, r.tile, st);
+        // input given as a 16-bit operand image: the four flag sets these two families are compiled for (conv_validate)
+        if constexpr (E == MI_EPI_LINEAR && (F == SR || F == (MI_FLAG_LN | MI_FLAG_HEADS) || F == (MI_FLAG_LN | MI_FLAG_GELU | MI_FLAG_IMG))) {
+            if (r.route == MI_ROUTE_HALF_IMG256) return launch_half_img256<HT, F>(d, st);
         }
-        if (f == (MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS))
-            return d.Mpad % 256 == 0 ? launch_half_img<HT, 4, MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS>(d, st)
-                                     : launch_half_img<HT, 2, MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS>(d, st);
-        if (f == (MI_FLAG_LN | MI_FLAG_HEADS)) return launch_half_img256<HT, MI_FLAG_LN | MI_FLAG_HEADS>(d, st);
-        if (f == (MI_FLAG_LN | MI_FLAG_GELU | MI_FLAG_IMG)) return launch_half_img256<HT, MI_FLAG_LN | MI_FLAG_GELU | MI_FLAG_IMG>(d, st);
+        if constexpr (E == MI_EPI_LINEAR && (F == SR || F == (SR | MI_FLAG_STATS))) {
+            if (r.route == MI_ROUTE_HALF_IMG) return r.tile == 256 ? launch_half_img<HT, 4, F>(d, st) : launch_half_img<HT, 2, F>(d, st);
+        }
         return set_error(MI_EINVAL, "conv: an operand-image input is not instantiated for LINEAR flags %d", d.flags);
-    }
-    if (d.epi == MI_EPI_LINEAR) {
-        switch (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_IMG | MI_FLAG_HEADS | MI_FLAG_STATS)) {
-            MI_LINEAR(MI_FLAG_LN | MI_FLAG_GELU | MI_FLAG_IMG);
-            MI_LINEAR(MI_FLAG_LN | MI_FLAG_HEADS);
-            MI_LINEAR(0);
-            MI_LINEAR(MI_FLAG_GELU);
-            MI_LINEAR(MI_FLAG_RES);
-            MI_LINEAR(MI_FLAG_RES | MI_FLAG_IMG);
-            MI_LINEAR(MI_FLAG_SCALE | MI_FLAG_RES);
-            MI_LINEAR(MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS);
-            MI_LINEAR(MI_FLAG_LN);
-            MI_LINEAR(MI_FLAG_LN | MI_FLAG_GELU);
-        }
-        return set_error(MI_EINVAL, "conv: unsupported LINEAR flag combination %d", d.flags);
-    }
-#undef MI_LINEAR
-    switch (d.epi) {
-        MI_DISPATCH(MI_EPI_GLU);
-        MI_DISPATCH(MI_EPI_BIAS_STATS);
-        MI_DISPATCH(MI_EPI_STATS_ONLY);
-        MI_DISPATCH(MI_EPI_GN_GLU);
-        MI_DISPATCH(MI_EPI_CONVTR);
-    }
-#undef MI_DISPATCH
-    return set_error(MI_EINVAL, "conv: unsupported epilogue %d", d.epi);
+    });
 }
 
-// d has been validated by launch_conv (gemm_conv.hip), which also decided `plain`
-int launch_conv_half(const mi_conv_desc &d, int tile, bool plain, hipStream_t st) {
+// d has been validated by launch_conv (gemm_conv.hip)
+int launch_conv_half(const mi_conv_desc &d, const ConvRoute &r, hipStream_t st) {
     MI_REQUIRE(d.wh && ((uintptr_t)d.wh & 15) == 0, "conv half: weight image missing or misaligned");
-    MI_REQUIRE(plain || d.ktab_len >= (d.Kpad + HK - 1) / HK * HK, "conv half: gather table has %d entries, the K step of %d needs %d",
+    MI_REQUIRE(r.plain || d.ktab_len >= (d.Kpad + HK - 1) / HK * HK, "conv half: gather table has %d entries, the K step of %d needs %d",
                d.ktab_len, HK, (d.Kpad + HK - 1) / HK * HK);
-    const bool wide = switches().half_tile256;
-    if (wide && plain && tile == 128 && d.epi == MI_EPI_LINEAR && d.Mpad % 256 == 0) tile = 256;
-    if (d.half == MI_DTYPE_BF16) return launch_conv_half_t<MI_DTYPE_BF16>(d, tile, plain, st);
-    if (d.half == MI_DTYPE_F16) return launch_conv_half_t<MI_DTYPE_F16>(d, tile, plain, st);
+    if (d.half == MI_DTYPE_BF16) return launch_conv_half_t<MI_DTYPE_BF16>(d, r, st);
+    if (d.half == MI_DTYPE_F16) return launch_conv_half_t<MI_DTYPE_F16>(d, r, st);
     return set_error(MI_EINVAL, "conv half: operand type %d", d.half);
 }
 

@@ -11,8 +11,7 @@ namespace mi {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BK = 16;
-constexpr int BN = 128;
+// tile constants BK, BN: kernels.h (the host-side route decision counts workgroups with them)
 
 struct ColInfo {   // decomposition of one output column n = (b, o1, o2)
     int b, o1, o2, p;
@@ -349,8 +348,24 @@ static inline int pick_m_groups(int MT, size_t weight_bytes) {
 }
 static inline unsigned grouped_grid(int MT, int NT, int Gm) { return 8u * (MT / Gm) * ((NT + 8 / Gm - 1) / (8 / Gm)); }
 
-// Host side: the (epilogue, LINEAR flag set) combinations the float32 kernels are compiled for, as compile-time constants:
-// calls f(std::integral_constant<int, EPI>, std::integral_constant<int, LFLAGS>) for the descriptor's pair
+// Host side: the (epilogue, LINEAR flag set) combinations the kernels are compiled for, as compile-time constants: each list
+// calls f(std::integral_constant<int, EPI>, std::integral_constant<int, LFLAGS>) for the descriptor's pair.
+// The epilogues other than LINEAR (LFLAGS 0), common to the float32 and the half kernels
+template <class F>
+static inline int dispatch_other_epilogue(const mi_conv_desc &d, F &&f) {
+    using std::integral_constant;
+    constexpr integral_constant<int, 0> none{};
+    switch (d.epi) {
+        case MI_EPI_GLU: return f(integral_constant<int, MI_EPI_GLU>(), none);
+        case MI_EPI_BIAS_STATS: return f(integral_constant<int, MI_EPI_BIAS_STATS>(), none);
+        case MI_EPI_STATS_ONLY: return f(integral_constant<int, MI_EPI_STATS_ONLY>(), none);
+        case MI_EPI_GN_GLU: return f(integral_constant<int, MI_EPI_GN_GLU>(), none);
+        case MI_EPI_CONVTR: return f(integral_constant<int, MI_EPI_CONVTR>(), none);
+    }
+    return set_error(MI_EINVAL, "conv: unsupported epilogue %d", d.epi);
+}
+
+// the float32 kernels (gemm_conv.hip, gemm_x6.hip)
 template <class F>
 static inline int dispatch_epilogue(const mi_conv_desc &d, F &&f) {
     using std::integral_constant;
@@ -368,14 +383,33 @@ static inline int dispatch_epilogue(const mi_conv_desc &d, F &&f) {
         }
         return set_error(MI_EINVAL, "conv: unsupported LINEAR flag combination %d", d.flags);
     }
-    switch (d.epi) {
-        case MI_EPI_GLU: return f(integral_constant<int, MI_EPI_GLU>(), none);
-        case MI_EPI_BIAS_STATS: return f(integral_constant<int, MI_EPI_BIAS_STATS>(), none);
-        case MI_EPI_STATS_ONLY: return f(integral_constant<int, MI_EPI_STATS_ONLY>(), none);
-        case MI_EPI_GN_GLU: return f(integral_constant<int, MI_EPI_GN_GLU>(), none);
-        case MI_EPI_CONVTR: return f(integral_constant<int, MI_EPI_CONVTR>(), none);
+    return dispatch_other_epilogue(d, f);
+}
+
+// The same for the half modes (gemm_half.hip, gemm_tap.hip): the LINEAR flag sets the register-staged conv_gemm_half_kernel is
+// compiled for -- here the IMG and HEADS bits count too -- and its five other epilogues.  The operand-image and the tap kernels
+// take four of these pairs each and refuse the rest
+constexpr int kHalfLinearFlags = MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_IMG | MI_FLAG_HEADS | MI_FLAG_STATS;
+template <class F>
+static inline int dispatch_epilogue_half(const mi_conv_desc &d, F &&f) {
+    using std::integral_constant;
+    if (d.epi == MI_EPI_LINEAR) {
+        constexpr integral_constant<int, MI_EPI_LINEAR> lin{};
+        switch (d.flags & kHalfLinearFlags) {
+            case MI_FLAG_LN | MI_FLAG_GELU | MI_FLAG_IMG: return f(lin, integral_constant<int, MI_FLAG_LN | MI_FLAG_GELU | MI_FLAG_IMG>());
+            case MI_FLAG_LN | MI_FLAG_HEADS: return f(lin, integral_constant<int, MI_FLAG_LN | MI_FLAG_HEADS>());
+            case 0: return f(lin, integral_constant<int, 0>());
+            case MI_FLAG_GELU: return f(lin, integral_constant<int, MI_FLAG_GELU>());
+            case MI_FLAG_RES: return f(lin, integral_constant<int, MI_FLAG_RES>());
+            case MI_FLAG_RES | MI_FLAG_IMG: return f(lin, integral_constant<int, MI_FLAG_RES | MI_FLAG_IMG>());
+            case MI_FLAG_SCALE | MI_FLAG_RES: return f(lin, integral_constant<int, MI_FLAG_SCALE | MI_FLAG_RES>());
+            case MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS: return f(lin, integral_constant<int, MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_STATS>());
+            case MI_FLAG_LN: return f(lin, integral_constant<int, MI_FLAG_LN>());
+            case MI_FLAG_LN | MI_FLAG_GELU: return f(lin, integral_constant<int, MI_FLAG_LN | MI_FLAG_GELU>());
+        }
+        return set_error(MI_EINVAL, "conv: unsupported LINEAR flag combination %d", d.flags);
     }
-    return set_error(MI_EINVAL, "conv: unsupported epilogue %d", d.epi);
+    return dispatch_other_epilogue(d, f);
 }
 
 }  // namespace mi

@@ -60,7 +60,7 @@ int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx,
 // vendor GEMMs use -- are clean).  hipcc picks the VGPR form whenever the registers fit; one inline-asm AGPR operand in
 // the kernel makes it allocate AGPRs and place every MFMA accumulator there.
 // HALF_IMG: a 64-row tile that reads its rows out of the 128-row weight image (the small-batch tile of the plain linear
-// layers, of the tap and of the row-tap convs: gemm_conv.hip conv_route): the same fragments, products and k order as the 128-row tile, so both give
+// layers, of the tap and of the row-tap convs: conv_route): the same fragments, products and k order as the 128-row tile, so both give
 // bit-identical results.
 // NT (taps, 9 or 3; 0 = none): the B loader of the float32 decoders' stride-1 3 x 3 / k = 3 rewrite convs (conv_tap_x6_kernel).
 // Row k = ci * NT + tap of the raw [16][128] activation tile is, for 128 consecutive output positions, a run of input row ci
@@ -79,7 +79,6 @@ int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx,
 // rows) are SCALAR loads in inline asm, issued in the same asm statement as the end-of-step vmcnt(0) wait and counted with
 // lgkmcnt(0) there: their latency passes under the wait for the ring, and hipcc never sees them (as VMEM loads inside the loop it
 // would wait vmcnt(0) for them; as compiler-visible scalar loads its lgkmcnt bookkeeping would not know of them).
-constexpr int kRowTaps = -1;
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG, int NT>
 __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N, const int MT, const int Gm) {
     constexpr int BM = WM * TM * 32;
@@ -355,15 +354,6 @@ __global__ __launch_bounds__(256, 2) void conv_rows_x6_kernel(const mi_conv_desc
     conv_x6_body<WM, WN, TM, TN, EPI, LFLAGS, false, HALF_IMG, kRowTaps>(d, N, MT, Gm);
 }
 
-// Which (epilogue, LINEAR flag set, loader) combinations the 192-row tile is compiled for: the layers of the float32 engine with
-// M % 192 == 0 -- the tap convs (GLU), the row-tap layers (LINEAR + GELU, CONVTR, 1 x 1 + GLU) and the self-attention in_proj
-// (plain LINEAR with MI_FLAG_LN).  Anything else with such an M runs the 96-row tile on the same image
-static constexpr bool conv_x6_tile192(int epi, int lflags, bool plain, int ntaps) {
-    if (ntaps > 0) return epi == MI_EPI_GLU;
-    if (ntaps == kRowTaps) return (epi == MI_EPI_LINEAR && lflags == MI_FLAG_GELU) || epi == MI_EPI_CONVTR || epi == MI_EPI_GLU;
-    return plain && epi == MI_EPI_LINEAR && lflags == MI_FLAG_LN;
-}
-
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false, int NTAPS = 0>
 static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
@@ -381,7 +371,7 @@ static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     return MI_OK;
 }
 
-// `tile` is the tile gemm_conv.hip conv_route decided, `image_tile` the one the split image was packed for: they differ for the
+// `tile` is the tile conv_route decided, `image_tile` the one the split image was packed for: they differ for the
 // under-filled 128-row layers, which run 64-row tiles that read the 128-row image (bit-identical to the 128-row tile, no second
 // image), and for the 192-row layers (image_tile 96), which run the 192-row tile on pairs of their 96-row images or, under-filled,
 // the 96-row tile.  NTAPS: the loader (0: plain / gather table, 9 or 3: shifted-run taps, kRowTaps: row taps)
@@ -405,11 +395,6 @@ static int launch_tile_x6(const mi_conv_desc &d, int tile, int image_tile, hipSt
     }
     return set_error(MI_EINVAL, "conv x6: unsupported tile_m %d", tile);
 }
-
-bool conv_x6_supported(int tile) { return tile == 128 || tile == 96 || tile == 64; }
-
-// gemm_conv.hip conv_route asks with the descriptor's epilogue and flags; launch_tile_x6 with its template arguments
-bool conv_x6_tile192_supported(int epi, int lflags, bool plain, int ntaps) { return conv_x6_tile192(epi, lflags, plain, ntaps); }
 
 // d has been validated by launch_conv (gemm_conv.hip): a stride-1 GLU conv with K2 = 3, dilation 1, NT = 9 or 3 taps, its row
 // pitch a multiple of 4 and equal to O2, image tile 96 or 128 (dmatap_eligible)

@@ -112,21 +112,27 @@ bool dconv_time_supported(int C, int Lp);
 int launch_dconv_time_layer(const DConvTimeLayer &l, int C, int dil, int B, int Lv, int Lp, const float *x, float *y, float *hbuf,
                             double *stats, double *gram, float2 *st1, float2 *st2, hipStream_t st);
 
-// gemm_conv.hip
+// gemm_conv.hip: fill the sink, validate (conv_validate), decide (conv_route), launch
 int launch_conv(const mi_conv_desc &d, hipStream_t st);
+
+// conv_route.hip: which kernel a conv / linear layer runs -- host code only, no kernel and no HIP call
+constexpr int BK = 16;       // K step of the float32 main loops
+constexpr int BN = 128;      // columns of a block tile
 int conv_pick_tile(int M);
 int conv_check_tile_m(const mi_conv_desc &d);     // MI_OK, or MI_EINVAL with the error set: tile_m = 192 on a layer that cannot take it
+int conv_validate(const mi_conv_desc &d);         // MI_OK, or MI_EINVAL with the error set: a descriptor no kernel takes (d.sink is not looked at)
 extern int g_split_bf16;     // 0 (mi_set_split_bf16): native fp32 MFMA kernels even where a split weight image exists
 // Which kernel launch_conv runs for a descriptor, decided from the descriptor alone (no HIP call, no pointer followed):
-// route: mi_conv_route (include/demucs_amd.h); tile: the rows of the tile that kernel runs, after every small-batch substitution
+// route: mi_conv_route (include/demucs_amd.h); tile: the rows of the tile that kernel runs, after every substitution
 // (routes 4, 7, 8: 64 under a 128-row layer = the 64-row tile that reads the 128-row image; 192 or 96 under a tile_m = 192
-// layer = the 192-row tile on pairs of its 96-row images, or the 96-row tile on them); plain: the 1x1 / linear fast path
-struct ConvRoute { int route; int tile; bool plain; };
+// layer = the 192-row tile on pairs of its 96-row images, or the 96-row tile on them; routes 5, 9, 10: 256 = the half modes'
+// 256-row tiles); plain: the 1x1 / linear fast path; mgroups: MI_MGROUPS, the M-grouped tile order of routes 0 and 1
+struct ConvRoute { int route; int tile; bool plain; bool mgroups; };
 ConvRoute conv_route(const mi_conv_desc &d);
 // Every environment switch of the engine (INTEGRATION.md has the table), parsed once, when the library is loaded (switches.hip:
 // the only file that looks at the environment).  The values are the parsed meanings, not the strings.
 struct Switches {
-    // ---- the float32 conv kernels (conv_route) ----
+    // ---- the conv kernels (conv_route) ----
     bool no_dma;            // MI_NO_DMA: plain linear layers on the register-staged loader
     bool no_dma_tap;        // MI_NO_DMA_TAP: no shifted-run DMA taps (routes 2 and 7)
     bool no_dma_rows;       // MI_NO_DMA_ROWS: no DMA row taps (routes 3 and 8)
@@ -134,6 +140,8 @@ struct Switches {
     bool small_tile;        // MI_SMALL_TILE (default 1): smaller tiles for under-filled 128-row layers
     bool mgroups;           // MI_MGROUPS: M-grouped tile order in the native fp32 kernels
     bool x6_plain_only;     // MI_X6_MODE=1: the split-bf16 loop for plain layers only
+    bool img256;            // MI_IMG256 (a non-zero number): the 256 x 256 tile (route 10) for the half modes' residual epilogues on image inputs
+    bool half_tile256;      // MI_HALF_TILE256 (default 1): the half modes' 256-row tile for plain linear layers (route 5)
     // ---- packing and schedule of both engines ----
     int x6_scope;           // MI_X6: which layers get a split-bf16 weight image: unset 1 = the default scope (Model::pack_split), 0 = none, anything else 2 = every layer
     bool no_tap_image;      // MI_NO_TAP_IMAGE: half modes, no tap-ordered weight images: the k x k convs walk gather tables over float32 tensors
@@ -156,22 +164,28 @@ struct Switches {
     int transpose_tiles;    // MI_TRANSPOSE_TILES: initial g_transpose_tiles mask (bit 0 STFT frames, 1 cac_transpose, 2 spec_transpose): unset 0, a number above 1 its low three bits, anything else 7
     bool istft_split;       // MI_ISTFT_SPLIT: g_istft_fused starts at 0 (inverse transform and overlap-add as two kernels)
     bool dconv_row_lds;     // MI_DCONV_ROW (first letter l): the LDS-resident DConv row kernel for C = 48
-    bool img256;            // MI_IMG256 (a non-zero number): the 256 x 256 tile for the half modes' residual epilogues on image inputs
-    bool half_tile256;      // MI_HALF_TILE256 (default 1): the half modes' 256-row tile for plain linear layers
 };
 const Switches &switches();
 // gemm_x6.hip: `tile` as decided by conv_route, `image_tile` the tile the split image was packed for
-bool conv_x6_supported(int tile);
-// the 192-row tile exists for this epilogue, LINEAR flag set (GELU / SCALE / RES / LN / STATS bits; 0 for other epilogues) and
-// loader (ntaps: 9 or 3 shifted-run taps, -1 row taps, 0 plain or gather table)
-bool conv_x6_tile192_supported(int epi, int lflags, bool plain, int ntaps);
+constexpr bool conv_x6_supported(int tile) { return tile == 128 || tile == 96 || tile == 64; }
+// Which (epilogue, LINEAR flag set, loader) combinations the 192-row tile is compiled for: the layers of the float32 engine with
+// M % 192 == 0 -- the tap convs (GLU), the row-tap layers (LINEAR + GELU, CONVTR, 1 x 1 + GLU) and the self-attention in_proj
+// (plain LINEAR with MI_FLAG_LN).  Anything else with such an M runs the 96-row tile on the same image.  lflags: the GELU / SCALE /
+// RES / LN / STATS bits (0 for other epilogues); ntaps: the loader -- 9 or 3 shifted-run taps, kRowTaps row taps, 0 plain or
+// gather table.  conv_route asks with the descriptor's epilogue and flags, launch_tile_x6 with its template arguments
+constexpr int kRowTaps = -1;
+constexpr bool conv_x6_tile192(int epi, int lflags, bool plain, int ntaps) {
+    if (ntaps > 0) return epi == MI_EPI_GLU;
+    if (ntaps == kRowTaps) return (epi == MI_EPI_LINEAR && lflags == MI_FLAG_GELU) || epi == MI_EPI_CONVTR || epi == MI_EPI_GLU;
+    return plain && epi == MI_EPI_LINEAR && lflags == MI_FLAG_LN;
+}
 int launch_conv_x6(const mi_conv_desc &d, int tile, int image_tile, bool plain, hipStream_t st);
 int launch_conv_tap_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);      // stride-1 3 x 3 / k = 3 GLU convs (route 7)
 int launch_conv_rows_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);     // row-tap encoder / transposed convs (route 8)
 int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx, hipStream_t st);
 
-// gemm_half.hip: bf16 / fp16 operand main loop (mi_config.dtype)
-int launch_conv_half(const mi_conv_desc &d, int tile, bool plain, hipStream_t st);
+// gemm_half.hip: bf16 / fp16 operand main loops (mi_config.dtype); `r` as decided by conv_route (routes 5, 9, 10)
+int launch_conv_half(const mi_conv_desc &d, const ConvRoute &r, hipStream_t st);
 int launch_pack_half(const float *wt, int Kpad, int Mpad, int dtype, void *wh, hipStream_t st);
 // gemm_tap.hip: k x k stride-1 convs on operand-image inputs (tap-minor K order), half modes
 int conv_tap_pairs_pad(int Cin, int ntaps);

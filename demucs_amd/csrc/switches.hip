@@ -25,6 +25,8 @@ static Switches read_switches() {
     s.mgroups = present("MI_MGROUPS");
     const char *mode = getenv("MI_X6_MODE");
     s.x6_plain_only = mode && atoi(mode) == 1;
+    s.img256 = nonzero("MI_IMG256", false);
+    s.half_tile256 = nonzero("MI_HALF_TILE256", true);
     s.x6_scope = present("MI_X6") ? (nonzero("MI_X6", false) ? 2 : 0) : 1;
     s.no_tap_image = present("MI_NO_TAP_IMAGE");
     s.no_enc_image = present("MI_NO_ENC_IMAGE");
@@ -48,8 +50,6 @@ static Switches read_switches() {
     s.istft_split = present("MI_ISTFT_SPLIT");
     const char *row = getenv("MI_DCONV_ROW");
     s.dconv_row_lds = row && row[0] == 'l';
-    s.img256 = nonzero("MI_IMG256", false);
-    s.half_tile256 = nonzero("MI_HALF_TILE256", true);
     return s;
 }
 

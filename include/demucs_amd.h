@@ -725,12 +725,17 @@ enum mi_conv_route {
     MI_ROUTE_DMATAP = 2,   /* LDS-DMA shifted-run taps (conv_gemm_dmatap_kernel) */
     MI_ROUTE_DMAROW = 3,   /* LDS-DMA row taps (conv_gemm_dmarow_kernel) */
     MI_ROUTE_X6 = 4,       /* split-bf16 (gemm_x6.hip conv_gemm_x6_kernel) */
-    MI_ROUTE_HALF = 5,     /* half-mode loops (gemm_half.hip) */
+    MI_ROUTE_HALF = 5,     /* half modes, register-staged loader (gemm_half.hip conv_gemm_half_kernel); tile 32 / 64 / 96 / 128, or 256 for
+                              a plain LINEAR layer of 128-row tiles with Mpad % 256 == 0 (MI_HALF_TILE256=0: 128) */
     MI_ROUTE_TAP_HALF = 6, /* half-mode tap images (gemm_tap.hip) */
     MI_ROUTE_TAP_X6 = 7,   /* split-bf16 with LDS-DMA shifted-run taps (gemm_x6.hip conv_tap_x6_kernel: stride-1 3 x 3 / k = 3 GLU
                               convs with a split image and the geometry of route 2) */
-    MI_ROUTE_ROWS_X6 = 8   /* split-bf16 with LDS-DMA row taps (gemm_x6.hip conv_rows_x6_kernel: the row-tap layers of route 3 --
+    MI_ROUTE_ROWS_X6 = 8,  /* split-bf16 with LDS-DMA row taps (gemm_x6.hip conv_rows_x6_kernel: the row-tap layers of route 3 --
                               LINEAR + GELU or CONVTR on 96- / 128-row tiles, 1 x 1 + GLU on 128-row tiles -- with a split image) */
+    MI_ROUTE_HALF_IMG = 9, /* half modes, operand-image input, 3-stage LDS-DMA ring (gemm_half.hip conv_gemm_half_img_kernel: plain
+                              LINEAR with SCALE|RES or SCALE|RES|STATS); tile 256 where Mpad % 256 == 0, else 128 */
+    MI_ROUTE_HALF_IMG256 = 10 /* half modes, operand-image input, 512-thread 256 x 256 tile (gemm_half.hip conv_gemm_half_img256_kernel:
+                              plain LINEAR with LN|HEADS or LN|GELU|IMG; with SCALE|RES under MI_IMG256=1 where Mpad % 256 == 0); tile 256 */
 };
 
 /* Debug aid for the kernel tests: the route the LAST mi_conv_forward of this process took; -1 before any call.  Process-wide,
@@ -742,7 +747,7 @@ int mi_debug_last_conv_route(void);
 int mi_debug_last_conv_tile(void);
 
 /* Debug aid: the route mi_conv_forward WOULD take for `desc` (under the environment switches and mi_set_split_bf16 as they
- * stand) and, in *tile (may be NULL), the rows of the tile that kernel runs, after every small-batch substitution: for the
+ * stand) and, in *tile (may be NULL), the rows of the tile that kernel runs, after every substitution: for the
  * split-bf16 routes 64 under a 128-row layer means the 64-row tile that reads the 128-row image, and a tile_m = 192 layer
  * answers 192 (the 192-row tile on pairs of its 96-row images) or, under-filled, 96.  Host code only: launches nothing, follows
  * no pointer of the descriptor, works in a process that never touches the GPU.  Returns -1 for desc == NULL and for a

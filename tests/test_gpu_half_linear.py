@@ -21,6 +21,9 @@ the float32 y of the same launch without IMG / HEADS bit for bit.  STATS: the 32
 sums of the stored y itself (each lane adds at most 64 values in float32 before its float64 reduction: 64 * 2^-24 * sum|y|, 65 *
 2^-24 * sum y^2) and against the reference (count * bound more).  Every case prints restated, kernel, bound and their ratio.
 
+After every launch `mi_debug_last_conv_route` / `mi_debug_last_conv_tile` must name the family and the tile that the rules of
+conv_route (csrc/conv_route.hip) give for the descriptor under the switches the process was started with.
+
 Every launch passes a caller-owned sink -- guard, 256 dump floats, 64 zeros, guard -- and the zeros and guards must survive: the
 512-thread kernel's SCALE|RES form used to store its masked values over the zero page (and past a 320-float sink)."""
 import ctypes as C
@@ -49,6 +52,7 @@ SINK, ZERO, GUARD, GUARD_VALUE = 256, 64, 64, -12345.0          # csrc/gemm_conv
 SENT16 = 0x5A5A                                                  # 16-bit outputs start as this pattern
 KS = [8, 32, 40, 64, 96, 128, 160, 512]     # one live octet; nk = 1; nk = 2 with a masked tail; 64; 3- and 4-stage ring full; first reuse; the model's
 NS = [1, 31, 64, 127, 128, 129, 255, 256, 257, 2049]             # around the 128- / 256-column tiles; 2049: NT = 9, a second XCD group
+HALF, HALF_IMG, HALF_IMG256 = 5, 9, 10                          # enum mi_conv_route (include/demucs_amd.h)
 FAMILY = {LN: "ln", LN | FLAG_GELU: "ln_gelu", FLAG_SCALE | FLAG_RES: "scale_res", FLAG_RES: "res"}
 
 # largest max-abs distance of the float32 restatement from float64 over the family's cases, {(family, type, K): distance}
@@ -261,11 +265,34 @@ def describe(o, flags, xh=True, xpad=0, ypad=0, nan_col=None, **over):
     return kw, out
 
 
+@functools.lru_cache(maxsize=1)
+def switches(lib):
+    """The MI_* switches as the library parsed them when it was loaded."""
+    n = lib.mi_debug_switches(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    lib.mi_debug_switches(buf, n + 1)
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+
+
+def expected_route(lib, o, flags, xh):
+    """(route, tile): the 512-thread kernel for LN|HEADS and LN|GELU|IMG (and, under MI_IMG256=1, for SCALE|RES where Mpad % 256 == 0);
+    the 3-stage kernel for SCALE|RES[|STATS], 256 rows where Mpad % 256 == 0, else 128; without an input image the register-staged
+    kernel, 256 rows where Mpad % 256 == 0 unless MI_HALF_TILE256=0."""
+    wide = device_side(o).Mpad % 256 == 0
+    if not xh:
+        return HALF, 256 if wide and switches(lib)["MI_HALF_TILE256"] == "1" else 128
+    if flags & LN or (switches(lib)["MI_IMG256"] == "1" and wide and not flags & STATS):
+        return HALF_IMG256, 256
+    return HALF_IMG, 256 if wide else 128
+
+
 def run(lib, o, flags, **opt):
     kw, out = describe(o, flags, **opt)
     desc, keep = conv_desc(**kw)
     _lib.check(lib.mi_conv_forward(C.byref(desc), stream()), "mi_conv_forward")
     torch.cuda.synchronize()
+    took, want = (lib.mi_debug_last_conv_route(), lib.mi_debug_last_conv_tile()), expected_route(lib, o, flags, opt.get("xh", True))
+    assert took == want, f"flags {flags} {o.mode} K {o.K} B {o.B} T {o.T} M {o.M}: (route, tile) {took}, expected {want}"
     check_sink(out.sink, f"flags {flags} {o.mode} K {o.K} B {o.B} T {o.T} M {o.M}")
     del keep
     return out
@@ -519,10 +546,16 @@ def kernel_names(fn):
 
 def child_main(which):
     lib = _lib.load()
-    n = lib.mi_debug_switches(None, 0)
-    buf = C.create_string_buffer(n + 1)
-    lib.mi_debug_switches(buf, n + 1)
-    got = dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+    got = switches(lib)
+    # what run() holds every launch below to, spelled out for this child's switches: (M, flags, input image) -> (route, tile)
+    SR = FLAG_SCALE | FLAG_RES
+    pinned = {"default": {(512, LN | HEADS, True): (HALF_IMG256, 256), (256, SR, True): (HALF_IMG, 256), (384, SR | STATS, True): (HALF_IMG, 128),
+                          (256, LN, False): (HALF, 256), (128, LN, False): (HALF, 128)},
+              "img256": {(256, SR, True): (HALF_IMG256, 256), (512, SR, True): (HALF_IMG256, 256), (120, SR, True): (HALF_IMG, 128),
+                         (256, SR | STATS, True): (HALF_IMG, 256)},
+              "tile128": {(256, LN, False): (HALF, 128), (512, LN | HEADS, False): (HALF, 128)}}[which]
+    for (M, flags, xh), want in pinned.items():
+        assert expected_route(lib, operands("bf16", 64, 2, 40, M), flags, xh) == want, (which, M, flags, xh)
 
     def body():
         for mode in MODES:

@@ -33,6 +33,16 @@ def test_no_static_initialised_from_the_environment():
     assert len(re.findall(r"\bstatic\s+const\s+Switches\b", _sources()[READER])) == 1
 
 
+def test_conv_launchers_do_not_ask_the_switches():
+    """Which conv kernel runs is conv_route's answer (conv_route.hip: host code only); the files that hold the kernels and their
+    launchers take it and never look at a switch."""
+    src = _sources()
+    asking = [name for name in ("gemm_conv.hip", "gemm_x6.hip", "gemm_half.hip", "gemm_tap.hip") if "switches()" in src[name]]
+    assert asking == [], asking
+    assert "switches()" in src["conv_route.hip"]
+    assert "__global__" not in src["conv_route.hip"] and "hipLaunchKernelGGL" not in src["conv_route.hip"]
+
+
 def test_split_scope_is_not_mutable_state():
     hits = [name for name, text in _sources().items() if re.search(r"split_linears|split_taps|split_rows", text)]
     assert hits == [], hits
