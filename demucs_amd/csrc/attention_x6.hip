@@ -16,7 +16,19 @@
 // Both images are [part 3][8][64][16 bytes]: one conflict-free ds_read_b128 per fragment term.  K and V are split once per
 // tile by the threads that stage them (global -> registers during the previous tile -> three bf16 planes in LDS).
 //
+// ONLINE SOFTMAX WITH A THRESHOLDED RESCALE.  Each query keeps a reference max mref and p = exp(s - mref); mref follows the
+// query's sub-tile max only when that passes it by more than TAU, so p <= e^TAU and the rescale of the 32 O^T accumulator
+// registers (an AGPR read, a multiply and an AGPR write each) leaves the hot path: a wave enters the block when any of its
+// queries moves, and there each query multiplies by its own factor, exactly 1 if it does not move, so a query's bits do not
+// depend on the other 31.
+//
 // ACCUMULATORS IN AGPRs (see gemm_x6.hip): built with -amdgpu-mfma-vgpr-form=0 and the inline-asm anchor below.
+// REGISTERS.  hipcc splits the file 128 / 128 at two waves per SIMD.  The empty asm anchors in the key loop pin O^T to AGPRs
+// outside the rescale block and the split Q fragments to VGPRs at the head of every sub-tile; without them hipcc carries O^T
+// through the loop in VGPRs and copies Q out of AGPRs before every score product.  The staged K tile then lands in AGPRs
+// straight from the loads.  Built with -fno-slp-vectorize (Makefile): packed fp32 adds beside MFMAs cost more than the two
+// scalar ones they replace, and the scalar form frees the register pairs that kept part of Q parked.  DESIGN.md section 8
+// has the instruction counts.
 #include "common.h"
 #include "kernels.h"
 #include "split_bf16.h"
@@ -27,8 +39,12 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) char gchar;      // global-memory pointers that stay global through an asm anchor
+typedef __attribute__((address_space(1))) float gfloat;
 constexpr int HD = 64;       // head dim
 constexpr int KT = 64;       // keys per LDS tile
+constexpr float LOG2E = 1.44269504088896340736f;
+constexpr float TAU = 8.0f;   // the reference max of the online softmax follows a query's max only past this distance
 
 __device__ __forceinline__ f32x16 mfma6(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 acc) {
     // the six products, smallest terms first (gemm_x6.hip's PA / PB order)
@@ -52,7 +68,7 @@ __device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&out)[3]) {
 
 }  // namespace
 
-// Two workgroups per CU (128 VGPRs + 95 AGPRs, no scratch); at three (168 registers) hipcc spills 127 VGPRs to scratch.
+// Two workgroups per CU (128 VGPRs + 70 AGPRs, no scratch); at three (168 registers) hipcc spills to scratch.
 __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                               const float *__restrict__ v, float *__restrict__ o, int Tq, int Tk,
                                                               int64_t q_bs, int64_t kv_bs, int64_t o_bs, int planes, int heads) {
@@ -95,7 +111,8 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float *__res
     f32x16 oacc[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { oacc[0][r] = 0.f; oacc[1][r] = 0.f; }
-    float mrun = -INFINITY, lrun = 0.f;     // running max (both halves agree) and this half's partial sum
+    // reference max (both halves agree), -mref log2(e) as the exponent's addend, and this half's partial sum
+    float mref = -INFINITY, nml2 = INFINITY, lrun = 0.f;
 
     // global -> register staging of the next K / V tile.  K: key k0 + lane, rows 8 g .. 8 g + 7 for g = wave, wave + 4 (coalesced
     // dwords; the image writes are consecutive 16-byte words).  V: rows d = (lane & 7) + 8 wave + 32 i, keys 16 ms + 4 h + {0..3, 8..11}
@@ -104,19 +121,30 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float *__res
     float kst[2][8];
     float4 vst[2][2];
     // Keys past Tk (ragged last tile) load from a clamped in-bounds address and are replaced by 0: no branch per load.
+    // Every load is a wave-uniform row base plus one 32-bit byte offset per lane (launch_attention_x6 keeps 4 HD Tk under 2^32).
+    // The K row bases are opaque scalars: hipcc otherwise folds them into sixteen 64-bit vector addresses per tile.
+    const gchar *krow[2][8];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            krow[i][j] = (const gchar *)(kp + (size_t)(8 * (wave + 4 * i) + j) * Tk);
+            asm("" : "+s"(krow[i][j]));
+        }
     auto stage_load = [&](int k0) {
         const bool kok = k0 + lane < Tk;
-        const int kc = kok ? k0 + lane : Tk - 1;
+        const unsigned kc = 4u * (unsigned)(kok ? k0 + lane : Tk - 1);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) kst[i][j] = kp[(size_t)(8 * (wave + 4 * i) + j) * Tk + kc];
+            for (int j = 0; j < 8; ++j) kst[i][j] = *(const gfloat *)(krow[i][j] + kc);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const int key = k0 + vc + 8 * c;          // Tk % 4 == 0: the 4 keys are all in range or all out
-                vst[i][c] = *reinterpret_cast<const float4 *>(vp + (size_t)(vd + 32 * i) * Tk + (key < Tk ? key : Tk - 4));
+                const unsigned vo = 4u * ((unsigned)((lane & 7) * Tk) + (unsigned)(key < Tk ? key : Tk - 4));
+                vst[i][c] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(vp + (size_t)(8 * wave + 32 * i) * Tk) + vo);
             }
     };
     // the zeroing of out-of-range keys happens here, after the loads have landed
@@ -154,6 +182,7 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float *__res
 
     stage_load(0);
     for (int k0 = 0; k0 < Tk; k0 += KT) {
+        asm volatile("" : "+a"(oacc[0]), "+a"(oacc[1]));
         __syncthreads();                     // previous tile fully consumed
         stage_mask(k0);
         stage_store();
@@ -163,6 +192,9 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float *__res
         for (int sub = 0; sub < 2; ++sub) {
             const int kb = sub * 32;
             if (k0 + kb >= Tk) break;            // (wave-uniform) a ragged last tile with no key in this sub-tile
+            asm volatile("" : "+a"(oacc[0]), "+a"(oacc[1]));     // register anchors: see the header
+#pragma unroll
+            for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(qx[t][0]), "+v"(qx[t][1]), "+v"(qx[t][2]));
             // S^T[key][query]: 4 k steps of 16 d
             f32x16 sacc;
 #pragma unroll
@@ -187,21 +219,31 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float *__res
 #pragma unroll
             for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, s[r]);
             mloc = fmaxf(mloc, __shfl_xor(mloc, 32));
-            const float mnew = fmaxf(mrun, mloc);
-            // exp through v_exp_f32, as attention_kernel; masked keys give exp(-inf) = 0
-            float psum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __expf(s[r] - mnew);
-                s[r] = p;
-                psum += p;
+            // Thresholded rescale: p = exp(s - mref) against a reference max that moves only when a query's sub-tile max passes it
+            // by more than TAU (p <= e^TAU, lrun <= Tk e^TAU).  Each query decides for itself; the others multiply by exactly 1.
+            if (k0 + kb == 0) {                  // first sub-tile: the accumulators are still zero, nothing to rescale
+                mref = mloc;
+                nml2 = -(mloc * LOG2E);
             }
-            if (__any(mnew != mrun)) {          // the running max moved for some query of this wave: rescale
-                const float alpha = __expf(mrun - mnew);       // exp(-inf) = 0 on the first tile
+            if (__any(mloc > mref + TAU)) {
+                const bool up = mloc > mref + TAU;
+                const float nnew = -(mloc * LOG2E);
+                const float alpha = up ? __builtin_amdgcn_exp2f(nnew - nml2) : 1.0f;       // exp(mref - mloc), in the addends' rounding
+                mref = up ? mloc : mref;
+                nml2 = up ? nnew : nml2;
                 lrun *= alpha;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { oacc[0][r] *= alpha; oacc[1][r] *= alpha; }
-                mrun = mnew;
+            }
+            asm volatile("" : "+a"(oacc[0]), "+a"(oacc[1]));     // O^T stays in AGPRs outside the rescale block
+            // exp(s - mref) as v_exp_f32 of one fused multiply-add (the rounding of nml2 is common to a query's keys and cancels in
+            // the normalisation); masked keys give exp(-inf) = 0
+            float psum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], LOG2E, nml2));
+                s[r] = p;
+                psum += p;
             }
             lrun += psum;
             // O^T[d][query] += V[d][key] P^T[key][query]: 2 k steps of 16 keys (registers 8 m .. 8 m + 7) x 2 d tiles
@@ -239,6 +281,7 @@ __global__ __launch_bounds__(256, 2) void attention_x6_kernel(const float *__res
 int launch_attention_x6(const float *q, const float *k, const float *v, float *o, int B, int heads, int Tq, int Tk, int64_t q_bs,
                         int64_t kv_bs, int64_t o_bs, hipStream_t st) {
     MI_REQUIRE(Tk % 4 == 0, "attention x6: Tk %% 4 != 0 (%d)", Tk);
+    MI_REQUIRE(Tk < (1 << 24), "attention x6: Tk %d too long for 32-bit staging offsets", Tk);
     MI_REQUIRE(((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && kv_bs % 4 == 0, "attention x6: k/v must be 16-byte aligned");
     const int planes = B * heads;
     hipLaunchKernelGGL(attention_x6_kernel, dim3((unsigned)(ceil_div(Tq, 128) * ((planes + 7) / 8) * 8)), dim3(256), 0, st, q, k, v, o,
