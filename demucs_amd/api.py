@@ -133,7 +133,7 @@ class Separator:
 
     def separate_stream(self, mean: Optional[float] = None, std: Optional[float] = None, sr: Optional[int] = None,
                         length: Optional[int] = None, convert: bool = False, channels: Optional[int] = None,
-                        deliver: Optional[Delivery] = None) -> "SeparatorStream":
+                        deliver: Optional[Delivery] = None, pcm: Optional[str] = None) -> "SeparatorStream":
         """`separate_tensor` for a track that arrives block by block (demucs_amd/stream.py): `push(block)` takes (channels, n)
         float32 and returns `{source: (channels, m)}` of the newly final samples, `finish()` the rest.
 
@@ -159,7 +159,18 @@ class Separator:
         tap the stream has emitted (`delivered` counts them, at most `output_hold` behind floor(new * emitted / old)), `finish()`
         the rest, floor(new * L / old) in all for L samples at M.  With `convert=True` and `samplerate=sr` a feed gets its stems back
         at its own rate; the length then is floor(new' * floor(new * N / old) / old') for N input samples (sr -> M reduces to
-        old:new, M -> sr to old':new'), which can be a sample or two short of N: nothing is padded."""
+        old:new, M -> sr to old':new'), which can be a sample or two short of N: nothing is padded.
+
+        With `pcm=` ("i16", "i24" or "f32") a block is what a socket, a capture device or a WAV file read in pieces delivers:
+        little-endian frames with the channels interleaved, as a bytes-like object or a 1-D uint8 tensor that may end anywhere
+        (the incomplete last frame waits for the next push; `finish()` drops it, `trailing_bytes` counts it; a device block must
+        be whole frames), or an (n, channels) int16 / float32 tensor.  The bytes cross to the device as they are and are
+        de-interleaved, converted (`v / 32768`, `v / 8388608`: both exact) and normalised there, so the stems are those of the float
+        stream fed the same values, bit for bit.  `length`, `pushed_input`, `latency` and `input_latency` count frames.  With
+        `Delivery(fmt="i16")` a stream is then a transcoding loop without host arithmetic: wire frames in, wire frames out."""
+        if pcm is not None:                 # refused before any RNG call
+            from .audio import check_pcm
+            check_pcm(pcm, _is_engine(self._model) and torch.device(self._device).type == "cuda")
         if not convert:
             if channels is not None and channels != self._audio_channels:
                 raise ValueError(f"separate_stream: {channels} input channels are not the model's {self._audio_channels}; pass "
@@ -176,11 +187,11 @@ class Separator:
             in_length, length = int(length), plan.final_count(int(length))
         st = ModelStream(self._model, shifts=self._shifts, overlap=self._overlap, segment=self._segment, split=self._split,
                          device=self._device, length=length, progress=self._progress, callback=self._callback,
-                         affine=None if mean is None else (mean, std), deliver=deliver)
+                         affine=None if mean is None else (mean, std), deliver=deliver, pcm=pcm if plan is None else None)
         if plan is None:
             return SeparatorStream(st, self._model.sources)
         return ConvertingSeparatorStream(st, self._model.sources, plan, channels or self._audio_channels,
-                                         in_length if length is not None else None, self._device_index)
+                                         in_length if length is not None else None, self._device_index, pcm=pcm)
 
     def _convert_plan(self, sr: Optional[int], channels: Optional[int]):
         """The refusals of a converting stream (before any device work or RNG call) and its `audio.ConvertPlan`; None when the
@@ -304,6 +315,11 @@ class SeparatorStream:
         return self.stream.latency
 
     @property
+    def trailing_bytes(self) -> int:
+        """Bytes of an incomplete last frame of a `pcm=` stream: carried to the next push, dropped by `finish()`."""
+        return self.stream.trailing_bytes
+
+    @property
     def delivered(self) -> int:
         """Frames returned so far by a stream that delivers at another sample rate (`Delivery(samplerate=R)`), at R."""
         return self.stream.delivered
@@ -321,9 +337,13 @@ class ConvertingSeparatorStream(SeparatorStream):
     (old / new the rates divided by their gcd): the converter holds back at most `width + old - 1` input samples and the model's
     stream `latency` of its own; a push that meets both bounds at once reaches it."""
 
-    def __init__(self, stream, sources, plan, src_channels, in_length, device_index):
+    def __init__(self, stream, sources, plan, src_channels, in_length, device_index, pcm=None):
         super().__init__(stream, sources)
         self.plan, self.src_channels, self.in_length = plan, int(src_channels), in_length
+        self.pcm, self.feed = pcm, None
+        if pcm is not None:
+            from .audio import PcmFeed
+            self.feed = PcmFeed(pcm, self.src_channels)
         self.input_latency = plan.width + plan.old - 1 + stream.latency * plan.old // plan.new
         self.pushed_input = 0
         self._device_index = device_index
@@ -332,14 +352,19 @@ class ConvertingSeparatorStream(SeparatorStream):
     def push(self, block: torch.Tensor) -> Dict[str, torch.Tensor]:
         if self.stream.finished:
             raise RuntimeError("push after finish()")
-        if not isinstance(block, torch.Tensor) or block.dim() != 2 or block.shape[0] != self.src_channels:
+        if self.feed is not None:
+            block = self.feed.accept(block)                # whole frames of wire PCM; the converter reads them as they are
+        elif not isinstance(block, torch.Tensor) or block.dim() != 2 or block.shape[0] != self.src_channels:
             shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
             raise ValueError(f"expected a ({self.src_channels}, n) block, got {shape}")
         if self.in_length is not None and self.pushed_input + block.shape[1] > self.in_length:
             raise ValueError(f"pushed {self.pushed_input + block.shape[1]} samples, more than the declared length {self.in_length}")
+        if self.feed is not None:
+            self.feed.commit(block)
         if self._cv is None:
             from .audio import ConvertStream
-            self._cv = ConvertStream(None, None, self.stream.audio_channels, device=self._device_index(), plan=self.plan)
+            self._cv = ConvertStream(None, None, self.stream.audio_channels, device=self._device_index(), plan=self.plan,
+                                     pcm=self.pcm, src_channels=self.src_channels if self.pcm is not None else None)
         y = self._cv.push(block, on_device=True)
         self.pushed_input = self._cv.pushed
         return self._stems(self.stream.push(y), block.device)
@@ -358,6 +383,10 @@ class ConvertingSeparatorStream(SeparatorStream):
         if isinstance(parts[0], dict):                      # delivered frames: (m, channels) per name
             return self._stems({k: torch.cat([p[k] for p in parts], 0) for k in parts[0]}, to)
         return self._stems(parts[0] if len(parts) == 1 else torch.cat(parts, -1), to)
+
+    @property
+    def trailing_bytes(self) -> int:
+        return 0 if self.feed is None else self.feed.trailing_bytes
 
     def _stems(self, out, to) -> Dict[str, torch.Tensor]:
         host = to is not None and torch.device(to).type == "cpu"
@@ -378,9 +407,14 @@ class SeparatorStreamGroup:
         self.group, self.sources, self.separator = group, list(sources), separator
 
     def open(self, mean: Optional[float] = None, std: Optional[float] = None, length: Optional[int] = None,
-             sr: Optional[int] = None, channels: Optional[int] = None, deliver: Optional[Delivery] = None):
-        """`length`, `sr` and `channels` describe the stream's INPUT, as for `separate_stream(convert=True)`; `deliver` is
-        `separate_stream`'s, each stream with its own."""
+             sr: Optional[int] = None, channels: Optional[int] = None, deliver: Optional[Delivery] = None,
+             pcm: Optional[str] = None):
+        """`length`, `sr` and `channels` describe the stream's INPUT, as for `separate_stream(convert=True)`; `deliver` and `pcm`
+        are `separate_stream`'s, each stream with its own: a group may mix float, int16, int24 and float32 PCM feeds, and a call
+        stays one append launch, one convert-append launch and one H2D."""
+        if pcm is not None:
+            from .audio import check_pcm
+            check_pcm(pcm, _is_engine(self.separator.model) and torch.device(self.separator._device).type == "cuda")
         if (mean is None) != (std is None):
             raise ValueError("separate_stream_group: give both mean and std, or neither")
         convert = None
@@ -388,7 +422,11 @@ class SeparatorStreamGroup:
             plan = self.separator._convert_plan(sr, channels)
             if plan is not None:
                 convert = (plan, int(channels or self.separator.audio_channels))
-        return self.group.open(length=length, affine=None if mean is None else (mean, std), convert=convert, deliver=deliver)
+        return self.group.open(length=length, affine=None if mean is None else (mean, std), convert=convert, deliver=deliver,
+                               pcm=pcm, channels=None if convert is not None else channels)
+
+    def trailing_bytes(self, key) -> int:
+        return self.group.trailing_bytes(key)
 
     def push(self, blocks) -> Dict[object, Dict[str, torch.Tensor]]:
         return {k: _named(self.sources, v) for k, v in self.group.push(blocks).items()}

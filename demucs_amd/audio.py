@@ -100,6 +100,185 @@ def check_stream_channels(src_channels: int, channels: int) -> None:
         raise ValueError('The audio file has less channels than requested but is not mono.')
 
 
+# ---- wire PCM in: what a socket, a capture device or a WAV file read in pieces delivers (demucs_amd/csrc/ingest.hip) ------------
+PCM_PLANAR = 0                                  # include/demucs_amd.h: MI_PCM_PLANAR, a planar float32 row of a PCM table
+# name -> (MI_PCM_* code, bytes per sample, dtype of an (n, channels) tensor block or None); little-endian, channels interleaved
+PCM_FORMATS = {"i16": (1, 2, torch.int16), "i24": (2, 3, None), "f32": (3, 4, torch.float32)}
+APPEND_PCM_COLS, CVT_PCM_COLS = 8, 21           # MI_APPEND_PCM_COLS, MI_CVT_PCM_COLS
+
+
+def check_pcm(pcm, engine: bool = True) -> None:
+    """The refusals of a PCM stream that need no block (no device work, no RNG call)."""
+    if pcm not in PCM_FORMATS:
+        raise ValueError(f"Invalid PCM format {pcm!r}: 'i16', 'i24' or 'f32'")
+    if not engine:
+        raise ValueError("a PCM stream runs on the GPU engines (HTDemucs / HDemucs on a cuda device); there is no CPU "
+                         "implementation of the ingest kernels in this package")
+
+
+class PcmBlock:
+    """The whole frames of one push of a PCM stream: `n` frames of `src_channels` channels, as host byte pieces (the carried
+    bytes, then the block's) or as one uint8 device tensor.  `shape` is the planar block's, so a scheduler counts it as one."""
+
+    def __init__(self, fmt: str, src_channels: int, n: int, pieces=None, dev=None, carry: bytes = b""):
+        self.fmt, self.src_channels, self.n, self.pieces, self.dev, self.carry = fmt, src_channels, n, pieces, dev, carry
+        self.code, self.width, _ = PCM_FORMATS[fmt]
+        self.shape = (src_channels, n)
+        self.nbytes = n * src_channels * self.width
+        self.device = torch.device("cpu") if dev is None else dev.device
+
+    def stage(self, host) -> None:
+        """The host pieces into `host`, a numpy uint8 view of `nbytes` bytes of a pinned buffer."""
+        at = 0
+        for p in self.pieces:
+            host[at:at + len(p)] = p
+            at += len(p)
+
+    def on_device(self, dev, keep: list) -> torch.Tensor:
+        """The frames as a uint8 tensor on `dev`: a device block where it is, a host block by one H2D from a pinned copy."""
+        if self.dev is not None:
+            return self.dev if self.dev.device == torch.device(dev) else self.dev.to(dev)
+        host = torch.empty(max(1, self.nbytes), dtype=torch.uint8, pin_memory=True)
+        self.stage(host.numpy()[:self.nbytes])
+        raw = torch.empty(max(1, self.nbytes), dtype=torch.uint8, device=dev)
+        raw.copy_(host, non_blocking=True)
+        keep += [host, raw]
+        return raw
+
+
+class PcmFeed:
+    """The host side of a PCM stream (no device work): it cuts a byte stream that stops wherever the transport stopped into whole
+    frames.  The incomplete trailing frame of a host chunk, at most `frame_bytes - 1` bytes, is carried and goes in front of the
+    next; `trailing_bytes` counts the carried bytes, which a finished stream drops as a decoder does.  `accept` validates a block
+    and changes nothing; `commit` makes its carry the feed's."""
+
+    def __init__(self, fmt: str, src_channels: int):
+        check_pcm(fmt)
+        if int(src_channels) != src_channels or src_channels < 1:
+            raise ValueError(f"a block needs at least one channel, got {src_channels}")
+        self.fmt, self.src_channels = fmt, int(src_channels)
+        self.frame_bytes = self.src_channels * PCM_FORMATS[fmt][1]
+        self.carry = b""
+
+    @property
+    def trailing_bytes(self) -> int:
+        return len(self.carry)
+
+    def _refuse(self, block):
+        dtype = PCM_FORMATS[self.fmt][2]
+        typed = "" if dtype is None else f", or an (n, {self.src_channels}) {dtype} tensor"
+        got = f"{tuple(block.shape)} {block.dtype}" if isinstance(block, torch.Tensor) else type(block).__name__
+        return ValueError(f"expected a block of {self.fmt!r} PCM: bytes, bytearray, memoryview or a 1-D torch.uint8 tensor{typed}; "
+                          f"got {got}")
+
+    def accept(self, block) -> PcmBlock:
+        import numpy as np
+        frame, width = self.frame_bytes, PCM_FORMATS[self.fmt][1]
+        if isinstance(block, torch.Tensor):
+            if block.dim() == 2 and block.dtype == PCM_FORMATS[self.fmt][2] and block.shape[1] == self.src_channels:
+                raw = block.contiguous().view(torch.uint8).reshape(-1)
+            elif block.dim() == 1 and block.dtype == torch.uint8:
+                raw = block.contiguous()
+            else:
+                raise self._refuse(block)
+            if raw.device.type != "cpu":
+                if self.carry:
+                    raise ValueError(f"a device block cannot follow an incomplete host frame ({len(self.carry)} bytes are carried)")
+                if raw.numel() % frame:
+                    raise ValueError(f"a device block must be whole frames of {frame} bytes, got {raw.numel()} bytes")
+                if width != 3 and raw.numel() and raw.data_ptr() % width:
+                    raise ValueError(f"a device block of {self.fmt!r} PCM must be aligned to its {width}-byte samples")
+                return PcmBlock(self.fmt, self.src_channels, raw.numel() // frame, dev=raw)
+            data = raw.numpy()
+        else:
+            try:
+                data = np.frombuffer(block, dtype=np.uint8)
+            except (TypeError, ValueError, BufferError):
+                raise self._refuse(block) from None
+        have = len(self.carry)
+        whole = (have + len(data)) // frame * frame
+        if whole == 0:
+            return PcmBlock(self.fmt, self.src_channels, 0, pieces=[], carry=self.carry + data.tobytes())
+        pieces = ([np.frombuffer(self.carry, dtype=np.uint8)] if have else []) + [data[:whole - have]]
+        return PcmBlock(self.fmt, self.src_channels, whole // frame, pieces=pieces, carry=data[whole - have:].tobytes())
+
+    def commit(self, blk: PcmBlock) -> None:
+        self.carry = blk.carry
+
+
+def _pcm_planar(raw: torch.Tensor, fmt: str, src_channels: int, n: int, channels: int, stats=None) -> torch.Tensor:
+    """mi_pcm_planar on the uint8 device tensor `raw`: (channels, n) float32 on its device."""
+    out = torch.empty(channels, n, device=raw.device, dtype=torch.float32)
+    if n:
+        with torch.cuda.device(raw.device):
+            _lib.check(_lib.load().mi_pcm_planar(raw.data_ptr(), PCM_FORMATS[fmt][0], src_channels, n, channels,
+                                                 stats.data_ptr() if stats is not None else None, out.data_ptr(),
+                                                 C.c_void_p(_lib.current_stream_ptr())), "mi_pcm_planar")
+    return out
+
+
+def pcm_to_tensor(data, fmt: str, channels: int, device="cuda") -> torch.Tensor:
+    """A whole buffer of interleaved PCM (`PCM_FORMATS`; bytes-like, a 1-D uint8 tensor or an (n, channels) int16 / float32 tensor,
+    on the host or a device) as the (channels, n) float32 tensor `Separator.separate_tensor` takes, on `device`: one H2D of the
+    bytes as they are and one `mi_pcm_planar`, no host pass over the samples.  int16 v becomes v / 32768, int24 v / 8388608, both
+    exact; float32 keeps its bits.  An incomplete last frame is dropped."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.EngineError("demucs_amd.audio.pcm_to_tensor only runs on a GPU device (MI355X)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    blk = PcmFeed(fmt, channels).accept(data)
+    if blk.n == 0:
+        return torch.empty(blk.src_channels, 0, device=dev)
+    keep = []
+    with torch.cuda.device(dev):
+        return _pcm_planar(blk.on_device(dev, keep), fmt, blk.src_channels, blk.n, blk.src_channels)
+
+
+_WAVE_SUBFORMAT_TAIL = bytes.fromhex("000000001000800000aa00389b71")
+
+
+def wav_info(head):
+    """`wav_header`'s inverse: from the first bytes of a RIFF / WAVE file, `(fmt, channels, samplerate, frames or None,
+    data_offset)` -- the `PCM_FORMATS` name of its samples, and where they start -- or None while `head` does not yet reach the
+    samples.  Takes format tags 1 (PCM: 16 or 24 bits) and 3 (IEEE float: 32 bits), WAVE_FORMAT_EXTENSIBLE with either as its
+    sub-format, any chunks before `data`, and the 0xFFFFFFFF sizes of a stream of unknown length (frames None); anything else
+    (RIFX, 8-bit, int32, ADPCM, ...) is a ValueError."""
+    import struct
+    b = bytes(head)
+    if b[:4] != b"RIFF"[:len(b[:4])]:
+        raise ValueError(f"wav_info: not a little-endian RIFF file (it starts with {b[:4]!r})")
+    if b[8:12] != b"WAVE"[:len(b[8:12])]:
+        raise ValueError(f"wav_info: not a WAVE file (form type {b[8:12]!r})")
+    pos, found = 12, None
+    while pos + 8 <= len(b):
+        tag, size = b[pos:pos + 4], struct.unpack_from("<I", b, pos + 4)[0]
+        if tag == b"data":
+            if found is None:
+                raise ValueError("wav_info: the data chunk comes before the fmt chunk")
+            fmt, channels, rate, align = found
+            return fmt, channels, rate, None if size == 0xFFFFFFFF else size // align, pos + 8
+        if tag == b"fmt ":
+            if size < 16:
+                raise ValueError(f"wav_info: a fmt chunk of {size} bytes")
+            if pos + 8 + size > len(b):
+                return None
+            code, channels, rate, _, align, bits = struct.unpack_from("<HHIIHH", b, pos + 8)
+            if code == 0xFFFE:
+                if size < 40 or b[pos + 34:pos + 48] != _WAVE_SUBFORMAT_TAIL:
+                    raise ValueError("wav_info: WAVE_FORMAT_EXTENSIBLE with a sub-format that is neither PCM nor IEEE float")
+                code = struct.unpack_from("<H", b, pos + 32)[0]
+            fmt = {(1, 16): "i16", (1, 24): "i24", (3, 32): "f32"}.get((code, bits))
+            if fmt is None:
+                raise ValueError(f"wav_info: format tag {code} with {bits} bits per sample is not supported (16 / 24-bit PCM and "
+                                 "32-bit float are)")
+            if channels < 1 or rate < 1 or align != channels * bits // 8:
+                raise ValueError(f"wav_info: {channels} channels at {rate} Hz with a block align of {align} bytes")
+            found = (fmt, channels, rate, align)
+        pos += 8 + size + (size & 1)
+    return None
+
+
 class ConvertPlan:
     """The arithmetic of a streaming `resample_frac` (no device work).  For old / new = the rates divided by their gcd, `width`
     and klen = 2 * width + old as `sinc_bank` builds them, output n * new + i reads inputs clamp(n * old - width + k), k < klen.
@@ -186,10 +365,12 @@ class _BankArena:
         return self.offs[key]
 
 
-def convert_audio_stream(from_samplerate: int, to_samplerate: int, channels: int, device="cuda", affine=None) -> "ConvertStream":
+def convert_audio_stream(from_samplerate: int, to_samplerate: int, channels: int, device="cuda", affine=None, pcm=None,
+                         src_channels=None) -> "ConvertStream":
     """`convert_audio` for a track that arrives block by block: `torch.cat([*pushes, finish], -1)` equals
-    `convert_audio(full, from_samplerate, to_samplerate, channels)` bit for bit for every partition of the input."""
-    return ConvertStream(from_samplerate, to_samplerate, channels, device=device, affine=affine)
+    `convert_audio(full, from_samplerate, to_samplerate, channels)` bit for bit for every partition of the input.
+    `pcm=` ("i16", "i24", "f32") with `src_channels=` takes the blocks as interleaved wire PCM instead (see `ConvertStream`)."""
+    return ConvertStream(from_samplerate, to_samplerate, channels, device=device, affine=affine, pcm=pcm, src_channels=src_channels)
 
 
 class ConvertStream:
@@ -197,9 +378,16 @@ class ConvertStream:
     final, on the block's device; `finish()` returns the rest.  `pushed` counts input samples, `emitted` output samples;
     `floor(new * pushed / old) - emitted <= hold`, and some push reaches it.  The source channel count is the first block's.
     `affine=(mean, s)` writes `(y - mean) / s` instead (mi_track_affine inverse = 0 on the converted samples).
-    Device state: two sides of (channels, klen - 1) carried input samples, whatever the stream's duration."""
+    Device state: two sides of (channels, klen - 1) carried input samples, whatever the stream's duration.
 
-    def __init__(self, from_samplerate, to_samplerate, channels: int, device="cuda", affine=None, plan=None):
+    With `pcm=` and `src_channels=` a block is interleaved little-endian PCM of that format (`PCM_FORMATS`): a bytes-like object
+    or a 1-D uint8 tensor that may end anywhere (a `PcmFeed` carries the incomplete frame to the next push; a device block must be
+    whole frames), or an (n, src_channels) int16 / float32 tensor.  `mi_streams_convert_append_pcm` reads the frames where the
+    float entry reads planar floats, so the outputs are those of the float stream on `v / 32768`, bit for bit; `pushed` counts
+    frames and `trailing_bytes` the bytes of an incomplete last frame, which `finish()` drops."""
+
+    def __init__(self, from_samplerate, to_samplerate, channels: int, device="cuda", affine=None, plan=None, pcm=None,
+                 src_channels=None):
         self.plan = plan if plan is not None else ConvertPlan(from_samplerate, to_samplerate)
         self.channels = int(channels)
         if self.channels < 1:
@@ -211,6 +399,13 @@ class ConvertStream:
         self.hold = self.plan.hold
         self.pushed = self.emitted = 0
         self.src_channels = None
+        self.feed = None
+        if pcm is not None:
+            if src_channels is None:
+                raise ValueError("a PCM stream needs src_channels=: the frames do not say how many channels they hold")
+            self.feed = PcmFeed(pcm, src_channels)
+            check_stream_channels(self.feed.src_channels, self.channels)
+            self.src_channels = self.feed.src_channels
         self.finished = False
         self.affine = None if affine is None else tuple(float(v) for v in affine)
         self._hist = self._stats = None
@@ -234,7 +429,12 @@ class ConvertStream:
                     self._hist = torch.zeros(2, ch, plan.carry, device=dev)
                 if self._stats is None and self.affine is not None:
                     self._stats = torch.tensor(self.affine, dtype=torch.float32).to(dev)
-                src = block.to(device=dev, dtype=torch.float32).contiguous() if n_in else None
+                keep = []
+                wire = isinstance(block, PcmBlock)
+                if wire:
+                    src = block.on_device(dev, keep) if n_in else None
+                else:
+                    src = block.to(device=dev, dtype=torch.float32).contiguous() if n_in else None
                 arena = _BankArena.get(dev)
                 bank_off = arena.offset(plan)
                 bank, hist, stats = arena.buf, self._hist, self._stats
@@ -243,13 +443,18 @@ class ConvertStream:
                 row = [src.data_ptr() if n_in else 0, self.src_channels or 1, n_in, self.pushed, h_len, self._side * side,
                        (1 - self._side) * side, self._h0, nxt, out0, n_out, self.pushed + n_in if final else -1, plan.old, plan.new,
                        plan.width, bank_off, 0, n_out, 0, 0 if stats is not None else -1]
+                lib = _lib.load()
+                entry, name = lib.mi_streams_convert_append, "mi_streams_convert_append"
+                if self.feed is not None:                  # the final call of a PCM stream has no block: any format
+                    row.append(PCM_FORMATS[self.feed.fmt][0])
+                    entry, name = lib.mi_streams_convert_append_pcm, "mi_streams_convert_append_pcm"
                 table = torch.tensor(row, dtype=torch.int64).to(dev)
                 win = out if n_out else table              # nothing is written when n_out == 0: any live pointer
-                _lib.check(_lib.load().mi_streams_convert_append(
+                _lib.check(entry(
                     win.data_ptr(), max(1, out.numel()), ch, table.data_ptr(), 1, plan.groups(n_out),
                     bank.data_ptr() if bank.numel() else None, bank.numel(), hist.data_ptr() if hist is not None else None,
                     0 if hist is None else hist.numel(), stats.data_ptr() if stats is not None else None, int(stats is not None),
-                    plan.lds_floats(), C.c_void_p(_lib.current_stream_ptr())), "mi_streams_convert_append")
+                    plan.lds_floats(), C.c_void_p(_lib.current_stream_ptr())), name)
                 if not final and not plan.copy:
                     self._side, self._h0 = 1 - self._side, nxt
         self.pushed += n_in
@@ -261,6 +466,13 @@ class ConvertStream:
         """`on_device=True` leaves the output on the stream's device whatever the block's."""
         if self.finished:
             raise RuntimeError("push after finish()")
+        if self.feed is not None:
+            blk = block
+            if not isinstance(block, PcmBlock):            # a caller with a feed of its own hands over whole frames
+                blk = self.feed.accept(block)
+                self.feed.commit(blk)
+            self._out_device = blk.device
+            return self._call(blk, final=False, on_device=on_device)
         if not isinstance(block, torch.Tensor) or block.dim() != 2:
             raise ValueError(f"expected a (channels, n) block, got {tuple(getattr(block, 'shape', ()))}")
         if self.src_channels is None:
@@ -276,6 +488,11 @@ class ConvertStream:
             raise RuntimeError("finish() called twice")
         self.finished = True
         return self._call(None, final=True, on_device=on_device)
+
+    @property
+    def trailing_bytes(self) -> int:
+        """Bytes of an incomplete last frame of a PCM stream: carried to the next push, dropped by `finish()`."""
+        return 0 if self.feed is None else self.feed.trailing_bytes
 
 
 # ---- after the separation: what demucs.separate does with the stems before any encoder sees them ----------------------

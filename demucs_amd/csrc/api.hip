@@ -420,6 +420,38 @@ int mi_streams_convert_append(float *win_dev, int64_t win_capacity, int32_t chan
                                          hist_dev, hist_capacity, stats_dev, n_stats, lds_floats, (hipStream_t)stream);
 }
 
+int mi_pcm_planar(const void *src_dev, int32_t fmt, int32_t src_ch, int64_t n, int32_t channels, const float *stats_dev, float *dst_dev,
+                  void *stream) {
+    MI_REQUIRE(fmt == MI_PCM_I16 || fmt == MI_PCM_I24 || fmt == MI_PCM_F32, "mi_pcm_planar: unknown format %d", fmt);
+    MI_REQUIRE(src_ch >= 1 && channels >= 1 && (src_ch == 1 || src_ch >= channels) && n >= 0 && n <= INT64_MAX / 4 / src_ch,
+               "mi_pcm_planar: bad argument");
+    if (n == 0) return MI_OK;
+    const int width = fmt == MI_PCM_I16 ? 2 : fmt == MI_PCM_I24 ? 3 : 4;
+    MI_REQUIRE(src_dev && dst_dev && n * src_ch * width / 16 + 24 <= (int64_t)INT32_MAX * 256, "mi_pcm_planar: bad argument");
+    MI_REQUIRE(width == 3 || (uintptr_t)src_dev % width == 0, "mi_pcm_planar: the source is not aligned to its %d-byte samples", width);
+    return launch_pcm_planar((const unsigned char *)src_dev, fmt, src_ch, n, channels, stats_dev, dst_dev, (hipStream_t)stream);
+}
+
+int mi_streams_append_pcm(float *win_dev, int64_t win_capacity, int32_t channels, const int64_t *table_dev, int32_t n_streams,
+                          int64_t max_bytes, const float *stats_dev, int32_t n_stats, void *stream) {
+    MI_REQUIRE(win_dev && table_dev && channels > 0 && n_streams > 0 && n_streams <= 65535 && max_bytes >= 1 &&
+               max_bytes <= (int64_t)INT32_MAX * 1024 && win_capacity > 0 && n_stats >= 0 && (n_stats == 0 || stats_dev),
+               "mi_streams_append_pcm: bad argument");
+    return launch_streams_append_pcm(win_dev, win_capacity, channels, table_dev, n_streams, max_bytes, stats_dev, n_stats,
+                                     (hipStream_t)stream);
+}
+
+int mi_streams_convert_append_pcm(float *win_dev, int64_t win_capacity, int32_t channels, const int64_t *table_dev, int32_t n_streams,
+                                  int64_t max_groups, const float *bank_dev, int64_t bank_capacity, float *hist_dev,
+                                  int64_t hist_capacity, const float *stats_dev, int32_t n_stats, int32_t lds_floats, void *stream) {
+    MI_REQUIRE(win_dev && table_dev && channels > 0 && n_streams > 0 && (int64_t)n_streams * channels <= 65535 && max_groups >= 1 &&
+               max_groups <= INT32_MAX && win_capacity > 0 && bank_capacity >= 0 && (bank_capacity == 0 || bank_dev) &&
+               hist_capacity >= 0 && (hist_capacity == 0 || hist_dev) && n_stats >= 0 && (n_stats == 0 || stats_dev) &&
+               lds_floats >= 1 && lds_floats <= MI_CVT_LDS_FLOATS, "mi_streams_convert_append_pcm: bad argument");
+    return launch_streams_convert_append_pcm(win_dev, win_capacity, channels, table_dev, n_streams, max_groups, bank_dev, bank_capacity,
+                                             hist_dev, hist_capacity, stats_dev, n_stats, lds_floats, (hipStream_t)stream);
+}
+
 int mi_streams_compact(float *dst_dev, int64_t dst_capacity, const float *src_dev, int64_t src_capacity, const int64_t *table_dev,
                        int32_t n_rows, int64_t max_len, void *stream) {
     MI_REQUIRE(dst_dev && src_dev && table_dev && dst_dev != src_dev && n_rows > 0 && n_rows <= 65535 && max_len >= 1 && dst_capacity > 0 &&

@@ -15,6 +15,7 @@
 // Memory bound on paper (4 B in / 4 B out per sample, the bank stays in L2); the tap loop is LDS-issue bound.
 #include "common.h"
 #include "kernels.h"
+#include "pcm_ingest.h"
 
 namespace mi {
 
@@ -28,6 +29,10 @@ __host__ __device__ inline int cvt_subruns(int64_t old_sr, int64_t width, int ld
     return (int)(g > CVT_G ? CVT_G : g);
 }
 
+// One body for both entries: PCM = false is mi_streams_convert_append (rows of MI_CVT_COLS, every block planar float32), PCM = true
+// mi_streams_convert_append_pcm (rows of MI_CVT_PCM_COLS, whose FMT column names the block's format).  Only `block(i)`, the read of
+// input sample P0 + i of this row, depends on the format; the history (float32), the tap loop, `ready` and the staging are the same code.
+template <bool PCM>
 __global__ __launch_bounds__(256) void streams_convert_append_kernel(float *__restrict__ win, int64_t win_cap, int channels,
                                                                      const int64_t *__restrict__ table,
                                                                      const float *__restrict__ bank, int64_t bank_cap,
@@ -35,7 +40,7 @@ __global__ __launch_bounds__(256) void streams_convert_append_kernel(float *__re
                                                                      const float *__restrict__ stats, int n_stats, int lds_floats) {
     extern __shared__ float xs[];
     const int s = blockIdx.y / channels, c = blockIdx.y % channels;
-    const int64_t *t = table + (size_t)s * MI_CVT_COLS;
+    const int64_t *t = table + (size_t)s * (PCM ? MI_CVT_PCM_COLS : MI_CVT_COLS);
     const int64_t n_in = t[MI_CVT_N_IN], src_ch = t[MI_CVT_SRC_CH], P0 = t[MI_CVT_BEFORE];
     const int64_t h_len = t[MI_CVT_HIST_LEN], h_rd = t[MI_CVT_HIST_RD], h_wr = t[MI_CVT_HIST_WR];
     const int64_t h0 = t[MI_CVT_HIST_START], h1 = t[MI_CVT_HIST_NEXT];
@@ -50,11 +55,18 @@ __global__ __launch_bounds__(256) void streams_convert_append_kernel(float *__re
     const bool rd_ok = h_ok && h_rd >= 0 && h_rd <= hist_cap - (int64_t)channels * h_len;
     const bool wr_ok = h_ok && h_wr >= 0 && h_wr <= hist_cap - (int64_t)channels * h_len;
     const int64_t srow = src_ch == 1 ? 0 : (c < src_ch ? c : src_ch - 1);      // mono feeds every row; else the first `channels` rows
-    const float *src = reinterpret_cast<const float *>(static_cast<uintptr_t>(t[MI_CVT_SRC])) + srow * n_in;
+    const uintptr_t addr = static_cast<uintptr_t>(t[MI_CVT_SRC]);
+    const float *src = reinterpret_cast<const float *>(addr) + srow * n_in;
+    const int fmt = PCM ? (int)t[MI_CVT_PCM_FMT] : MI_PCM_PLANAR;
+    const bool wire = PCM && fmt != MI_PCM_PLANAR;          // interleaved wire frames: pcm_ingest.h reads them
+    if (wire && (t[MI_CVT_PCM_FMT] != fmt || !pcm_source_ok(fmt, src_ch, addr))) return;
+    auto block = [&](int64_t i) -> float {
+        return wire ? pcm_sample(reinterpret_cast<const unsigned char *>(addr), fmt, src_ch, i, srow) : src[i];
+    };
     const float *hr = hist + (rd_ok ? h_rd + (int64_t)c * h_len : 0);
     // input sample j of this row: from the block when it starts at or after P0, else from the read side of the history
     auto sample = [&](int64_t j) -> float {
-        if (j >= P0) return j - P0 < n_in ? src[j - P0] : 0.f;
+        if (j >= P0) return j - P0 < n_in ? block(j - P0) : 0.f;
         const int64_t r = j - h0;
         return rd_ok && r >= 0 && r < h_len ? hr[r] : 0.f;
     };
@@ -129,7 +141,17 @@ __global__ __launch_bounds__(256) void streams_convert_append_kernel(float *__re
 int launch_streams_convert_append(float *win, int64_t win_cap, int channels, const int64_t *table, int n_streams, int64_t max_groups,
                                   const float *bank, int64_t bank_cap, float *hist, int64_t hist_cap, const float *stats, int n_stats,
                                   int lds_floats, hipStream_t st) {
-    hipLaunchKernelGGL(streams_convert_append_kernel, dim3((unsigned)max_groups, n_streams * channels), dim3(256),
+    hipLaunchKernelGGL(streams_convert_append_kernel<false>, dim3((unsigned)max_groups, n_streams * channels), dim3(256),
+                       (size_t)lds_floats * sizeof(float), st, win, win_cap, channels, table, bank, bank_cap, hist, hist_cap, stats,
+                       n_stats, lds_floats);
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}
+
+int launch_streams_convert_append_pcm(float *win, int64_t win_cap, int channels, const int64_t *table, int n_streams,
+                                      int64_t max_groups, const float *bank, int64_t bank_cap, float *hist, int64_t hist_cap,
+                                      const float *stats, int n_stats, int lds_floats, hipStream_t st) {
+    hipLaunchKernelGGL(streams_convert_append_kernel<true>, dim3((unsigned)max_groups, n_streams * channels), dim3(256),
                        (size_t)lds_floats * sizeof(float), st, win, win_cap, channels, table, bank, bank_cap, hist, hist_cap, stats,
                        n_stats, lds_floats);
     MI_CHECK_LAUNCH();

@@ -244,6 +244,15 @@ int launch_resample_frac(const float *x, int rows, int64_t L, const float *table
 int launch_streams_convert_append(float *win, int64_t win_cap, int channels, const int64_t *table, int n_streams, int64_t max_groups,
                                   const float *bank, int64_t bank_cap, float *hist, int64_t hist_cap, const float *stats, int n_stats,
                                   int lds_floats, hipStream_t st);
+int launch_streams_convert_append_pcm(float *win, int64_t win_cap, int channels, const int64_t *table, int n_streams,
+                                      int64_t max_groups, const float *bank, int64_t bank_cap, float *hist, int64_t hist_cap,
+                                      const float *stats, int n_stats, int lds_floats, hipStream_t st);
+
+// ingest.hip: wire PCM (interleaved int16 / int24 / float32 frames) to planar float32, alone and as the streams' append
+int launch_pcm_planar(const unsigned char *src, int fmt, int src_ch, int64_t n, int channels, const float *stats, float *dst,
+                      hipStream_t st);
+int launch_streams_append_pcm(float *win, int64_t win_cap, int channels, const int64_t *table, int n_streams, int64_t max_bytes,
+                              const float *stats, int n_stats, hipStream_t st);
 
 const void *conv_zero_page();      // gemm_conv.hip: 256 bytes of device zeros
 // attention_heads.hip: half modes, per-head token-major 16-bit operands (MI_FLAG_HEADS), LDS-DMA ring

@@ -147,14 +147,23 @@ class _Rate:
 
 def apply_model_stream(model, shifts: int = 1, overlap: float = 0.25, transition_power: float = 1.0, segment=None,
                        device=None, length: Optional[int] = None, split: bool = True, progress: bool = False,
-                       callback=None, deliver: Optional[Delivery] = None) -> "ModelStream":
+                       callback=None, deliver: Optional[Delivery] = None, pcm: Optional[str] = None,
+                       channels: Optional[int] = None) -> "ModelStream":
     """Start a stream; see the module docstring.  `st.push(block)` takes (channels, n) float32 on the host or a device and
     returns the newly final stems (S, channels, m); `st.finish()` returns the rest.  `device` defaults to the first block's.
     With `deliver=Delivery(...)` both return `{name: (m, channels) frames}` instead (one more launch per push, `mi_deliver_pcm`
     on the emitted span; host blocks get the frames by one D2H of their bytes and no float stems leave the device).  With
-    `Delivery(samplerate=R)` the frames are at R Hz (`mi_deliver_resample_pcm` in that launch's place)."""
+    `Delivery(samplerate=R)` the frames are at R Hz (`mi_deliver_resample_pcm` in that launch's place).
+
+    With `pcm=` ("i16", "i24" or "f32"; `channels=` source channels, the model's by default, or 1 to feed every row) a block is
+    wire PCM instead: little-endian frames with the channels interleaved, as a bytes-like object or a 1-D uint8 tensor that may
+    end anywhere, or as an (n, channels) int16 / float32 tensor.  The bytes go to the device as they are and `mi_pcm_planar`
+    de-interleaves, converts (`v / 32768`, `v / 8388608`: exact) and normalises them there, so the stems are those of the float
+    stream fed the same values, bit for bit.  The incomplete last frame of a host chunk waits on the host for the next push
+    (`audio.PcmFeed`); `finish()` drops it and `trailing_bytes` counts it.  `length`, `pushed` and `latency` count frames."""
     return ModelStream(model, shifts=shifts, overlap=overlap, transition_power=transition_power, segment=segment, device=device,
-                       length=length, split=split, progress=progress, callback=callback, deliver=deliver)
+                       length=length, split=split, progress=progress, callback=callback, deliver=deliver, pcm=pcm,
+                       channels=channels)
 
 
 class _Member:
@@ -203,7 +212,7 @@ class ModelStream:
     floor(new * emitted / old) - delivered <= output_hold, and some push reaches it."""
 
     def __init__(self, model, shifts=1, overlap=0.25, transition_power=1.0, segment=None, device=None, length=None,
-                 split=True, progress=False, callback=None, affine=None, deliver=None):
+                 split=True, progress=False, callback=None, affine=None, deliver=None, pcm=None, channels=None):
         from .apply import BagOfModels
         from . import distributed
         if not split:
@@ -241,6 +250,16 @@ class ModelStream:
             if plan is not None:
                 self.rate = _Rate(plan, len(self.outputs), self.audio_channels)
                 self.output_hold = plan.hold
+        # wire PCM blocks (`audio.PcmFeed`): refused here, before any RNG call
+        self.feed = None
+        if pcm is not None:
+            from .audio import PcmFeed, check_pcm, check_stream_channels
+            check_pcm(pcm, all(m.kind != "generic" for m in self.members) and (self.device is None or self.device.type == "cuda"))
+            self.feed = PcmFeed(pcm, self.audio_channels if channels is None else channels)
+            check_stream_channels(self.feed.src_channels, self.audio_channels)
+        elif channels is not None and channels != self.audio_channels:
+            raise ValueError(f"expected {self.audio_channels} channels, got {channels}: a stream of float blocks converts no "
+                             "channel layout")
         # Separator.separate_stream: blocks are normalised `(x - mean) / s` and stems restored `x * s + mean`, s = std + 1e-8
         self.affine = None
         if affine is not None:
@@ -320,9 +339,22 @@ class ModelStream:
                 random.randrange(1)
 
     # ---- public --------------------------------------------------------------------------------------------------------
+    @property
+    def trailing_bytes(self) -> int:
+        """Bytes of an incomplete last frame of a PCM stream: carried to the next push, dropped by `finish()`."""
+        return 0 if self.feed is None else self.feed.trailing_bytes
+
     def push(self, block: torch.Tensor) -> torch.Tensor:
         if self.finished:
             raise RuntimeError("push after finish()")
+        if self.feed is not None:
+            blk = self.feed.accept(block)
+            if self.length is not None and self.pushed + blk.n > self.length:
+                raise ValueError(f"pushed {self.pushed + blk.n} samples, more than the declared length {self.length}")
+            self._start(blk.device)
+            self.feed.commit(blk)
+            self._out_device = blk.device
+            return self._exec.push(blk)
         if block.dim() != 2 or block.shape[0] != self.audio_channels:
             raise ValueError(f"expected a ({self.audio_channels}, n) block, got {tuple(block.shape)}: a stream converts no "
                              "channel layout")
@@ -550,13 +582,21 @@ class _EngineExec:
     def _stream(self):
         return C.c_void_p(_lib.current_stream_ptr())
 
-    def _append(self, block):
+    def _append(self, block, alive):
         st = self.st
         keep = st._keep_from()
-        blk = block.to(device=st.device, dtype=torch.float32, copy=self.stats is not None).contiguous()
-        if self.stats is not None and blk.numel():
-            _lib.check(self.lib.mi_track_affine(blk.data_ptr(), blk.numel(), self.stats.data_ptr(), 0, self._stream()),
-                       "mi_track_affine")
+        if st.feed is not None:             # wire PCM: the bytes as they came, then de-interleave / convert / normalise on the device
+            from .audio import _pcm_planar
+            if block.n:
+                blk = _pcm_planar(block.on_device(st.device, alive), block.fmt, block.src_channels, block.n, st.audio_channels,
+                                  self.stats)
+            else:
+                blk = torch.empty(st.audio_channels, 0, device=st.device)
+        else:
+            blk = block.to(device=st.device, dtype=torch.float32, copy=self.stats is not None).contiguous()
+            if self.stats is not None and blk.numel():
+                _lib.check(self.lib.mi_track_affine(blk.data_ptr(), blk.numel(), self.stats.data_ptr(), 0, self._stream()),
+                           "mi_track_affine")
         self.win = torch.cat([self.win[:, keep - self.win0:], blk], 1).contiguous()
         self.win0 = keep
         st.pushed += block.shape[1]
@@ -767,7 +807,7 @@ class _EngineExec:
         st = self.st
         keep = []
         with torch.cuda.device(st.device):
-            self._append(block)
+            self._append(block, keep)
             units = st._ready(final=False)
             self._relayout(units)
             self._run(units, keep)
@@ -844,7 +884,8 @@ class StreamGroup:
         self._exec = None
 
     # ---- public --------------------------------------------------------------------------------------------------------
-    def open(self, length: Optional[int] = None, affine=None, convert=None, deliver: Optional[Delivery] = None):
+    def open(self, length: Optional[int] = None, affine=None, convert=None, deliver: Optional[Delivery] = None,
+             pcm: Optional[str] = None, channels: Optional[int] = None):
         """A new stream; makes the RNG calls `ModelStream(..., length=length)` makes.  Returns its key.
 
         `deliver=Delivery(...)`: the stream's results are `{name: (m, channels) frames}` (see `Delivery`), each stream of a group
@@ -852,7 +893,23 @@ class StreamGroup:
 
         `convert=(audio.ConvertPlan, source channels)`: the stream's blocks are (source channels, n) at the plan's input rate and
         pass through the streaming `convert_audio` into its window (one `mi_streams_convert_append` for all such streams of a
-        call); `length` then counts input samples, and the RNG calls are those of the converted length."""
+        call); `length` then counts input samples, and the RNG calls are those of the converted length.
+
+        `pcm=` ("i16", "i24", "f32"): the stream's blocks are interleaved wire PCM (`apply_model_stream`'s rule; `channels=` source
+        channels unless `convert=` names them).  A call with such a stream uses `mi_streams_append_pcm` /
+        `mi_streams_convert_append_pcm` for all its streams, the float ones as planar rows: still one append launch, one
+        convert-append launch and one H2D, in which a host block travels as its raw bytes."""
+        feed = None
+        if pcm is not None:                 # refused here, before any RNG call
+            from .audio import PcmFeed, check_pcm, check_stream_channels
+            check_pcm(pcm, all(m.kind != "generic" for m in self.members) and (self.device is None or self.device.type == "cuda"))
+            if convert is not None and channels is not None and int(channels) != int(convert[1]):
+                raise ValueError(f"channels={channels} contradicts convert=, which names {convert[1]} source channels")
+            feed = PcmFeed(pcm, convert[1] if convert is not None else self.audio_channels if channels is None else channels)
+            check_stream_channels(feed.src_channels, self.audio_channels)
+        elif convert is None and channels is not None and channels != self.audio_channels:
+            raise ValueError(f"expected {self.audio_channels} channels, got {channels}: a stream of float blocks converts no "
+                             "channel layout")
         if deliver is not None:             # refused here, before any RNG call
             deliver.for_stream(self.sources, all(m.kind != "generic" for m in self.members) and
                                (self.device is None or self.device.type == "cuda"), self.samplerate, self.audio_channels)
@@ -870,6 +927,7 @@ class StreamGroup:
             length = None if length is None else plan.final_count(int(length))
         st = ModelStream(self.model, device=self.device, length=length, affine=affine, deliver=deliver, **self._kw)
         st.convert = conv
+        st.feed = feed
         key = self._next
         self._next += 1
         self._streams[key] = st
@@ -889,6 +947,10 @@ class StreamGroup:
     def pushed(self, key) -> int:
         return self._stream(key).pushed
 
+    def trailing_bytes(self, key) -> int:
+        """Bytes of an incomplete last frame of a PCM stream, carried to its next push."""
+        return self._stream(key).trailing_bytes
+
     def device_bytes(self) -> int:
         """Bytes of device memory the group itself holds (state buffer, stats, forward buffers)."""
         return 0 if self._exec is None else self._exec.device_bytes()
@@ -897,9 +959,16 @@ class StreamGroup:
         """`{key: (channels, n) block}` -> `{key: (S, channels, m) newly final stems}` (a delivering stream: `{name: (m, channels)
         frames}`), the streams taken in the mapping's order."""
         items = list(blocks.items())
+        accepted = {}
         for key, block in items:
             st = self._stream(key)
             cv = getattr(st, "convert", None)
+            if st.feed is not None:
+                blk = accepted[key] = st.feed.accept(block)
+                at, length = (cv.pushed, cv.length) if cv is not None else (st.pushed, st.length)
+                if length is not None and at + blk.n > length:
+                    raise ValueError(f"pushed {at + blk.n} samples, more than the declared length {length}")
+                continue
             if cv is not None:
                 if not isinstance(block, torch.Tensor) or block.dim() != 2 or block.shape[0] != cv.src_channels:
                     shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
@@ -914,8 +983,10 @@ class StreamGroup:
                 raise ValueError(f"pushed {st.pushed + block.shape[1]} samples, more than the declared length {st.length}")
         if not items:
             return {}
-        self._start(items[0][1].device)
-        return self._exec.push([(k, self._streams[k], b) for k, b in items])
+        self._start(accepted.get(items[0][0], items[0][1]).device)
+        for key, blk in accepted.items():
+            self._streams[key].feed.commit(blk)
+        return self._exec.push([(k, self._streams[k], accepted.get(k, b)) for k, b in items])
 
     def finish(self, keys) -> dict:
         """Ends the streams `keys` (in that order) and returns `{key: remaining stems}`."""
@@ -1020,6 +1091,23 @@ class _Slot:
         self.placed = False
 
 
+class _Staging:
+    """The host blocks of one call, behind its table in the pinned upload: [(table index of the row's source column, byte offset,
+    block)].  A wire PCM block travels as its raw bytes from a 16-byte boundary (the ingest kernels' widest load), a float block as
+    float32."""
+
+    def __init__(self):
+        self.items, self.end = [], 0
+
+    def add(self, pos: int, block) -> None:
+        from .audio import PcmBlock
+        wire = isinstance(block, PcmBlock)
+        align = 16 if wire else 4
+        self.end = -(-self.end // align) * align
+        self.items.append((pos, self.end, block))
+        self.end += block.nbytes if wire else 4 * block.numel()
+
+
 class _GroupEngineExec:
     def __init__(self, g: StreamGroup):
         from .apply import _transition_weight
@@ -1047,6 +1135,7 @@ class _GroupEngineExec:
         self.hist = None
         self.hist_used = 0
         self.hist_free = {}
+        self.last_upload = (0, 0)          # bytes of the last call's table and of its whole pinned upload
 
     def device_bytes(self) -> int:
         n = self.state.numel() + self.stats.numel() + sum(t.numel() for b in self.bufs.values() for t in set(b))
@@ -1267,7 +1356,8 @@ class _GroupEngineExec:
                 for pi, o, n in us:
                     ps = slot.st.passes[pi]
                     ps.hi = max(ps.hi, o + n)
-            append, staged = self._append_rows(blocks, table, keep)
+            staged = _Staging()
+            append = self._append_rows(blocks, table, keep, staged)
             convert = self._convert_rows(jobs, table, keep, staged)
             plan = [(e, valid, fw, *self._forward_tables(e, valid, fw, table)) for e, valid, fw in self._plan(units)]
             emit = self._emit_rows(work, table)
@@ -1283,20 +1373,28 @@ class _GroupEngineExec:
                                                            C.c_void_p(base + 8 * COMPACT_COLS * (first + r0)), nr, longest,
                                                            self._stream()), "mi_streams_compact")
                 self.state = state
-            if append is not None:
-                at, n_rows, longest = append
+            if append is not None and append[3]:        # a wire PCM block among them: the entry with a format per row
+                at, n_rows, _, max_bytes = append
+                _lib.check(self.lib.mi_streams_append_pcm(self.state.data_ptr(), self.state.numel(), C_, C.c_void_p(base + 8 * at),
+                                                          n_rows, max_bytes, self.stats.data_ptr(), self.n_stats, self._stream()),
+                           "mi_streams_append_pcm")
+            elif append is not None:
+                at, n_rows, longest, _ = append
                 _lib.check(self.lib.mi_streams_append(self.state.data_ptr(), self.state.numel(), C_, C.c_void_p(base + 8 * at), n_rows,
                                                       longest, self.stats.data_ptr(), self.n_stats, self._stream()),
                            "mi_streams_append")
             if convert is not None:
                 from .audio import _BankArena
-                at, n_rows, groups, lds_floats = convert
+                at, n_rows, groups, lds_floats, wire = convert
                 bank, hist = _BankArena.get(dev).buf, self.hist
-                _lib.check(self.lib.mi_streams_convert_append(self.state.data_ptr(), self.state.numel(), C_, C.c_void_p(base + 8 * at),
-                                                              n_rows, groups, bank.data_ptr() if bank.numel() else None, bank.numel(),
-                                                              hist.data_ptr() if hist is not None else None,
-                                                              0 if hist is None else hist.numel(), self.stats.data_ptr(), self.n_stats,
-                                                              lds_floats, self._stream()), "mi_streams_convert_append")
+                entry, name = self.lib.mi_streams_convert_append, "mi_streams_convert_append"
+                if wire:
+                    entry, name = self.lib.mi_streams_convert_append_pcm, "mi_streams_convert_append_pcm"
+                _lib.check(entry(self.state.data_ptr(), self.state.numel(), C_, C.c_void_p(base + 8 * at),
+                                 n_rows, groups, bank.data_ptr() if bank.numel() else None, bank.numel(),
+                                 hist.data_ptr() if hist is not None else None,
+                                 0 if hist is None else hist.numel(), self.stats.data_ptr(), self.n_stats,
+                                 lds_floats, self._stream()), name)
             for e, valid, fw, at, n_tiles in plan:
                 self._forward(e, valid, fw, base + 8 * at, n_tiles, keep)
             outs = self._emit(emit, base)
@@ -1318,52 +1416,61 @@ class _GroupEngineExec:
                     self.state = torch.zeros(0, device=dev)
             return outs
 
-    def _append_rows(self, blocks, table, keep):
-        """mi_streams_append's rows.  Device blocks are read where they are; a host block's source is named once the call's
-        upload buffer exists (`_upload`).  Returns ((first row, rows, longest block) or None, [(table index, float offset, block)])."""
+    def _append_rows(self, blocks, table, keep, staged):
+        """mi_streams_append's rows, or mi_streams_append_pcm's (MI_APPEND_PCM_*: a format and a source channel count more per
+        row, the float blocks as planar rows) when a block of the call is wire PCM.  Device blocks are read where they are; a host
+        block joins `staged`, and its source is named once the call's upload buffer exists (`_upload`).  Returns (first row, rows,
+        longest block, largest source in bytes if the rows are the PCM entry's else 0) or None."""
+        from .audio import PCM_PLANAR, PcmBlock
         g = self.g
+        C_ = g.audio_channels
         live = [(key, slot, b) for key, slot, b in blocks if b.shape[1] > 0]
         if not live:
-            return None, []
+            return None
+        wire = any(isinstance(b, PcmBlock) for _, _, b in live)
         at = len(table)
-        longest, staged, off = 1, [], 0
+        longest, max_bytes = 1, 0
         for key, slot, b in live:
             n = b.shape[1]
+            pcm = isinstance(b, PcmBlock)
             if b.device.type == "cpu":
-                staged.append((len(table), off, b))
-                off += b.numel()
+                staged.add(len(table), b)
                 src = 0
             else:
-                d = b.to(device=g.device, dtype=torch.float32).contiguous()
+                d = b.on_device(g.device, keep) if pcm else b.to(device=g.device, dtype=torch.float32).contiguous()
                 keep.append(d)
                 src = d.data_ptr()
             table += [src, n, slot.w_base, slot.w_cap, slot.st.pushed - n - slot.w0, slot.stats]
+            if wire:
+                table += [b.code, b.src_channels] if pcm else [PCM_PLANAR, C_]
+                max_bytes = max(max_bytes, b.nbytes if pcm else 4 * C_ * n)
             longest = max(longest, n)
-        return (at, len(live), longest), staged
+        return at, len(live), longest, max_bytes
 
     def _convert_rows(self, jobs, table, keep, staged):
         """mi_streams_convert_append's rows (MI_CVT_*) for the converting streams of the call with a block or final outputs; host
         blocks join `staged`.  Flips every such stream's history side.  Returns (first index, rows, workgroups per row, LDS
         floats) or None."""
-        from .audio import CVT_COLS, _BankArena
+        from .audio import CVT_COLS, CVT_PCM_COLS, PCM_PLANAR, PcmBlock, _BankArena
         g = self.g
         C_ = g.audio_channels
         live = [j for j in jobs if j[3] > 0 or j[5] > 0]
         if not live:
             return None
+        # a wire PCM block among them: mi_streams_convert_append_pcm's rows (one column more, the block's format) for all
+        wire = any(isinstance(j[2], PcmBlock) for j in live)
         arena = _BankArena.get(g.device)
         at = len(table)
         groups, lds_floats = 1, 1
-        off = sum(b.numel() for _, _, b in staged)
         for slot, cv, b, n_in, out0, n_out, nxt in live:
             plan, final = cv.plan, b is None
+            pcm = isinstance(b, PcmBlock)
             self._hist_region(cv)
             src = 0
             if n_in and b.device.type == "cpu":
-                staged.append((len(table), off, b))
-                off += b.numel()
+                staged.add(len(table), b)
             elif n_in:
-                d = b.to(device=g.device, dtype=torch.float32).contiguous()
+                d = b.on_device(g.device, keep) if pcm else b.to(device=g.device, dtype=torch.float32).contiguous()
                 keep.append(d)
                 src = d.data_ptr()
             side = C_ * plan.carry
@@ -1371,30 +1478,35 @@ class _GroupEngineExec:
             table += [src, cv.src_channels, n_in, cv.pushed - n_in, plan.carry, base + cv.side * side, base + (1 - cv.side) * side,
                       cv.h0, nxt, out0, n_out, cv.pushed if final else -1, plan.old, plan.new, plan.width, arena.offset(plan),
                       slot.w_base, slot.w_cap, slot.st.pushed - n_out - slot.w0, slot.stats]
+            if wire:
+                table.append(b.code if pcm else PCM_PLANAR)
             if not final and not plan.copy:
                 cv.side, cv.h0 = 1 - cv.side, nxt
             groups = max(groups, plan.groups(n_out))
             lds_floats = max(lds_floats, plan.lds_floats())
-        assert (len(table) - at) == CVT_COLS * len(live)
-        return at, len(live), groups, lds_floats
+        assert (len(table) - at) == (CVT_PCM_COLS if wire else CVT_COLS) * len(live)
+        return at, len(live), groups, lds_floats, wire
 
     def _upload(self, table, staged, keep) -> int:
-        """The call's int64 table and its host blocks (float32) in one pinned buffer, down in ONE H2D.  Returns the table's
-        device address."""
+        """The call's int64 table and its host blocks (`_Staging`: float32, or a wire PCM block's raw bytes) in one pinned
+        buffer, down in ONE H2D.  Returns the table's device address."""
+        from .audio import PcmBlock
         T = max(1, len(table))
         f_at = -(-8 * T // 16) * 16
-        n_floats = sum(b.numel() for _, _, b in staged)
-        nbytes = f_at + 4 * n_floats
+        nbytes = f_at + staged.end
         dev_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.g.device)
         base = dev_buf.data_ptr()
-        for pos, off, _ in staged:
-            table[pos] = base + f_at + 4 * off
+        for pos, off, _ in staged.items:
+            table[pos] = base + f_at + off
         host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-        np.frombuffer(host.numpy(), dtype=np.int64, count=T)[:] = table or [0]
-        if staged:
-            floats = host[f_at:].view(torch.float32)
-            for _, off, b in staged:
-                floats[off:off + b.numel()].view(b.shape).copy_(b)
+        raw = host.numpy()
+        np.frombuffer(raw, dtype=np.int64, count=T)[:] = table or [0]
+        for _, off, b in staged.items:
+            if isinstance(b, PcmBlock):
+                b.stage(raw[f_at + off:f_at + off + b.nbytes])
+            else:
+                host[f_at + off:f_at + off + 4 * b.numel()].view(torch.float32).view(b.shape).copy_(b)
+        self.last_upload = (8 * T, nbytes)
         dev_buf.copy_(host, non_blocking=True)
         keep += [host, dev_buf]
         return base

@@ -370,6 +370,50 @@ int mi_streams_convert_append(float *win_dev, int64_t win_capacity, int32_t chan
                               int64_t max_groups, const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity,
                               const float *stats_dev, int32_t n_stats, int32_t lds_floats, void *stream);
 
+/* ---- wire PCM in (demucs_amd/csrc/ingest.hip, pcm_ingest.h) ------------------------------------------------------------------
+ * A block of a live feed as it comes off the wire: n frames of src_ch channels, little-endian, the channels interleaved per frame.
+ *   MI_PCM_I16   2 bytes per sample, value float32(v) * 2^-15;
+ *   MI_PCM_I24   3 bytes per sample, packed, sign-extended from bit 23, value float32(v) * 2^-23;
+ *   MI_PCM_F32   4 bytes per sample, the bits unchanged (NaN, +-Inf, -0 and subnormals as they are).
+ * Both products are exact in float32, so a PCM block gives the bits the float entries give for `v / 32768` (`v / 8388608`).
+ * MI_PCM_PLANAR names a planar float32 (channels, n) block in a table of the entries below: the row then behaves exactly as a row
+ * of the float entry (mi_streams_append / mi_streams_convert_append), so one launch serves a mix of formats.
+ * The source address must be aligned to the sample width (any byte address for MI_PCM_I24); no byte outside
+ * [src, src + n * src_ch * width) is read.  The channel map is convert_audio_channels' per-sample one: a mono source feeds every
+ * destination row, otherwise row c reads source channel c (src_ch >= channels).
+ *
+ * mi_pcm_planar: one block at the DEVICE address src_dev -> planar float32 (channels, n) at dst_dev, as `(x - mean) / s`
+ *   (mi_track_affine inverse = 0) when stats_dev names a (mean, s) pair; n = 0 does nothing.
+ * mi_streams_append_pcm: mi_streams_append with a format per row.  Row s of the table (MI_APPEND_PCM_COLS) is MI_APPEND_*'s six
+ *   columns (N in frames), then FMT (MI_PCM_*) and SRC_CH (ignored for MI_PCM_PLANAR, whose source is (channels, n) floats).  The
+ *   writes are clamped to the row's window columns as in mi_streams_append; a row with an unknown format, a misaligned source or a
+ *   channel count the map does not take writes nothing.  max_bytes >= every row's source size in bytes (grid size).
+ * mi_streams_convert_append_pcm: mi_streams_convert_append with a format per row: MI_CVT_*'s twenty columns, then FMT
+ *   (MI_CVT_PCM_COLS).  The block is (n_in frames, src_ch) in that format; the carried history stays float32, and the filter chain
+ *   is the same code, so the outputs equal mi_streams_convert_append's on the converted planar floats bit for bit. */
+#define MI_PCM_PLANAR 0
+#define MI_PCM_I16 1
+#define MI_PCM_I24 2
+#define MI_PCM_F32 3
+#define MI_APPEND_PCM_SRC 0
+#define MI_APPEND_PCM_N 1
+#define MI_APPEND_PCM_DST_OFF 2
+#define MI_APPEND_PCM_DST_LEN 3
+#define MI_APPEND_PCM_COL 4
+#define MI_APPEND_PCM_STATS 5
+#define MI_APPEND_PCM_FMT 6
+#define MI_APPEND_PCM_SRC_CH 7
+#define MI_APPEND_PCM_COLS 8
+#define MI_CVT_PCM_FMT 20
+#define MI_CVT_PCM_COLS 21
+int mi_pcm_planar(const void *src_dev, int32_t fmt, int32_t src_ch, int64_t n, int32_t channels, const float *stats_dev, float *dst_dev,
+                  void *stream);
+int mi_streams_append_pcm(float *win_dev, int64_t win_capacity, int32_t channels, const int64_t *table_dev, int32_t n_streams,
+                          int64_t max_bytes, const float *stats_dev, int32_t n_stats, void *stream);
+int mi_streams_convert_append_pcm(float *win_dev, int64_t win_capacity, int32_t channels, const int64_t *table_dev, int32_t n_streams,
+                                  int64_t max_groups, const float *bank_dev, int64_t bank_capacity, float *hist_dev,
+                                  int64_t hist_capacity, const float *stats_dev, int32_t n_stats, int32_t lds_floats, void *stream);
+
 /* mi_resample_frac: `julius.resample_frac` as called by `demucs.audio.convert_audio` (demucs/audio.py:169-172), the step
  *   `Separator.separate_tensor` runs first when the input sample rate differs from the model's (demucs/api.py:265-266).
  *   old_sr / new_sr already divided by their gcd; table_dev (new_sr, 2*width + old_sr) is julius' windowed-sinc kernel bank
