@@ -124,6 +124,12 @@ __device__ __forceinline__ void lds_dma16_s(const void *sbase, unsigned voff, vo
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(l) : "memory", "m0");
 }
 #pragma clang diagnostic pop
+// The builtin form of the same instruction, which hipcc does track: the float32 main loops (gemm_conv.hip, the raw activation
+// ring of gemm_x6.hip) are scheduled around the waits it places and keep it.  lds_wave_base must be wave-uniform here too.
+__device__ __forceinline__ void lds_dma16_tracked(const void *g, void *lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void *)g, (__attribute__((address_space(3))) void *)lds_wave_base,
+                                     16, 0, 0);
+}
 
 // packed fp32 math: v_pk_fma_f32 issues two IEEE fmas per lane per instruction (same results as two fmaf)
 typedef float v2f __attribute__((ext_vector_type(2)));

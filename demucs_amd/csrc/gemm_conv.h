@@ -117,8 +117,12 @@ typedef struct mi_conv_desc {
     void *yh;               /* MI_FLAG_IMG: the OUTPUT image (M % 8 == 0); y is not written                                      */
     int64_t yh_n;
     /* k x k stride-1 conv on an operand-image input (gemm_tap.hip): the weights with k ordered (channel octet, tap, channel % 8)
-       (mi_conv_pack_tap) and the kernel geometry; xh must be set, x / ktab are ignored */
+       (mi_conv_pack_tap); with wtap, xh must be set and x / ktab are ignored */
     const void *wtap;
+    /* The kernel geometry.  With wtap: of that conv.  WITHOUT wtap and xh, on a float32 layer: stating it selects the shifted-run
+       LDS-DMA tap loader (routes 2 and 7; conv_route.hip dmatap_eligible has the conditions), which reads x itself -- up to 8 bytes
+       before and 20 bytes after the tensor at x, so the caller must own that much readable slack on both sides (gemm_loop.h
+       TapRows; the engine's buffers and the tests carry 128 bytes).  Leave ntaps 0 for an exact-size x at an allocation boundary. */
     int32_t ntaps, tap_k2, tap_pad1, tap_pad2; /* K1 * K2 taps, K2 columns per kernel row, padding along d1 / d2                  */
     int32_t tap_dil1, tap_dil2;                /* tap step along d1 / d2: 0 = 1; -1 for the two taps of a transposed conv (input q - j) */
     int64_t yh_pq;                             /* MI_FLAG_IMG4: positions per item and plane of the phase-split output image        */

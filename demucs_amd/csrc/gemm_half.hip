@@ -13,12 +13,10 @@
 //   * K step 32 = two MFMA k steps; LDS double buffer, global -> register prefetch of step k+1 under the MFMAs of k.
 // Bias, GroupNorm / LayerNorm statistics, GELU / GLU / sigmoid, LayerScale and residual adds run in float32 on the
 // float32 accumulators exactly as in the fp32 mode.
-#include "gemm_tile.h"
+#include "gemm_loop.h"
 
 namespace mi {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -33,14 +31,6 @@ __device__ __forceinline__ unsigned pack2(float a, float b) {
         const f16x2 h = {(_Float16)a, (_Float16)b};
         return __builtin_bit_cast(unsigned, h);
     }
-}
-
-template <int HT>
-__device__ __forceinline__ f32x16 mfma16(const uint4 a, const uint4 b, const f32x16 c) {
-    if (HT == MI_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
 // Wt[Kpad][Mpad] fp32 -> Wh[Kh/8][Mpad][8] (Kh = Kpad rounded up to 32; the tail is zero)
@@ -75,10 +65,9 @@ __global__ __launch_bounds__(256, (WM * TM * TN <= 3 ? 3 : 2)) void conv_gemm_ha
     static_assert(WM * WN == 4, "4 waves");
     __shared__ uint4 As[2][4][BM];
     __shared__ uint4 Bs[2][4][BN];
-    {   // accumulators in AGPRs (see gemm_x6.hip: VGPR-form bf16 MFMA streams disturbed co-resident processes on this pool)
-        float agpr_anchor = 0.f;
-        asm volatile("; accumulators in AGPRs %0" : "+a"(agpr_anchor));
-    }
+    agpr_anchor();
+    // its own prologue, not gemm_loop.h's: with wg_tile two instantiations per operand type change occupancy (6 -> 5 and 3 -> 4
+    // waves per SIMD) and two of the 256-row ones their spills
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
@@ -184,12 +173,7 @@ __global__ __launch_bounds__(256, (WM * TM * TN <= 3 ? 3 : 2)) void conv_gemm_ha
     } while (0)
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    zero_acc(acc);
 
     const int li = lane & 31, lh = lane >> 5;
     // one K step on LDS stage `cur`
@@ -248,26 +232,14 @@ __global__ __launch_bounds__(256, (WM * TM * TN <= 3 ? 3 : 2)) void conv_gemm_ha
 // global_load_lds_dwordx4 through a 3-stage ring -- TWO K steps in flight behind a counted s_waitcnt vmcnt, one raw
 // s_barrier per K step, no staging registers, no conversion (the scheme of conv_gemm_dma_kernel in gemm_conv.hip).
 // BM = 64 TM rows; a stage is 4 BM + 512 sixteen-byte words (24 KiB at TM = 4: two workgroups per CU).
-typedef __attribute__((address_space(1))) const void hgvoid_t;
-typedef __attribute__((address_space(3))) void hlvoid_t;
-
 template <int HT, int TM, int LFLAGS>
 __global__ __launch_bounds__(256, 2) void conv_gemm_half_img_kernel(const mi_conv_desc d, const int N, const int MT, const int Gm) {
     constexpr int TN = 2, WN = 2, BM = 2 * TM * 32, NA = BM / 64;
     constexpr int A_W = 4 * BM, SW = A_W + 4 * BN;                  // 16-byte words per stage: A image then B image
     __shared__ __attribute__((aligned(16))) uint4 smem[3 * SW];
-    {
-        float agpr_anchor = 0.f;
-        asm volatile("; accumulators in AGPRs %0" : "+a"(agpr_anchor));
-    }
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    int mt, nt;
-    if (!tile_of_block(MT, Gm, N, mt, nt)) return;
-    const int m0 = mt * BM, n0 = nt * BN;
-    const int P = d.O1 * d.O2;
-    const int o2v = d.o2_valid ? d.o2_valid : d.O2;
+    agpr_anchor();
+    Wg w;
+    if (!wg_tile<WN, BM>(d, MT, Gm, N, w)) return;
     const int nk = (d.Kpad + HK - 1) / HK;
 
     // A: flat [octet][row] image of the K step; wave instruction i = wave * NA + j covers words 64 i .. 64 i + 63
@@ -275,67 +247,33 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_half_img_kernel(const mi_con
     const uint4 *asrc[NA];
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
-        const int w = 64 * (wave * NA + j) + lane;
-        asrc[j] = wh + (size_t)(w / BM) * d.Mpad + m0 + w % BM;
+        const int word = 64 * (w.wave * NA + j) + w.lane;
+        asrc[j] = wh + (size_t)(word / BM) * d.Mpad + w.m0 + word % BM;
     }
     const size_t a_step = (size_t)4 * d.Mpad;
     // B: this wave moves octet `wave` of the K step, columns [0, 64) and [64, 128) of the tile; columns outside the tensor
     // and octets past K come from the zero page
     const uint4 *xh = reinterpret_cast<const uint4 *>(d.xh);
     const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + MI_SINK_FLOATS);
-    const bool c0 = n0 + lane < N, c1 = n0 + 64 + lane < N;
-    const uint4 *b0 = xh + (size_t)wave * d.xh_n + n0 + lane;
+    const bool c0 = w.n0 + w.lane < N, c1 = w.n0 + 64 + w.lane < N;
+    const uint4 *b0 = xh + (size_t)w.wave * d.xh_n + w.n0 + w.lane;
     const size_t b_step = (size_t)4 * d.xh_n;
 
-#define MI_IMG_TILE(kt, stage)                                                                                      \
-    do {                                                                                                            \
-        uint4 *sa = smem + (stage) * SW + 64 * (wave * NA), *sb = smem + (stage) * SW + A_W + wave * BN;             \
-        _Pragma("unroll") for (int j = 0; j < NA; ++j)                                                               \
-            lds_dma16(asrc[j] + (size_t)(kt) * a_step, sa + 64 * j);                                                 \
-        const bool kin = ((kt) * 4 + wave) * 8 < d.K;                                                               \
-        const uint4 *g = b0 + (size_t)(kt) * b_step;                                                                \
-        lds_dma16((kin && c0) ? g : zero, sb);                                                                      \
-        lds_dma16((kin && c1) ? g + 64 : zero, sb + 64);                                                            \
-    } while (0)
-
     f32x16 acc[TM][TN];
+    zero_acc(acc);
+    dma_ring3(
+        nk, NA + 2, RingNop(),
+        [&](int kt, int stage) {
+            uint4 *sa = smem + stage * SW + 64 * (w.wave * NA), *sb = smem + stage * SW + A_W + w.wave * BN;
 #pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int li = lane & 31, lh = lane >> 5;
-    MI_IMG_TILE(0, 0);
-    if (nk > 1) MI_IMG_TILE(1, 1);
-    int stage = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        // tile kt has landed once all but this wave's newest tile (NA + 2 instructions) are done -- for every wave
-        if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NA + 2) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        // stage (kt + 2) % 3 was last read in the previous iteration, which every wave has finished
-        if (kt + 2 < nk) MI_IMG_TILE(kt + 2, stage == 0 ? 2 : stage - 1);
-        const uint4 *As = smem + stage * SW, *Bs = As + A_W;
-        uint4 af[2][TM], bf[2][TN];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-            for (int a = 0; a < TM; ++a) af[s][a] = As[(2 * s + lh) * BM + (wm * TM + a) * 32 + li];
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bf[s][b] = Bs[(2 * s + lh) * BN + (wn * TN + b) * 32 + li];
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) acc[a][b] = mfma16<HT>(af[s][a], bf[s][b], acc[a][b]);
-        stage = stage == 2 ? 0 : stage + 1;
-    }
-#undef MI_IMG_TILE
-    conv_epilogue<TM, TN, MI_EPI_LINEAR, LFLAGS>(d, acc, m0, n0, wm, wn, N, P, o2v);
+            for (int j = 0; j < NA; ++j) lds_dma16(asrc[j] + (size_t)kt * a_step, sa + 64 * j);
+            const bool kin = (kt * 4 + w.wave) * 8 < d.K;
+            const uint4 *g = b0 + (size_t)kt * b_step;
+            lds_dma16((kin && c0) ? g : zero, sb);
+            lds_dma16((kin && c1) ? g + 64 : zero, sb + 64);
+        },
+        RingNop(), [&](int stage) { half_kstep<HT, TM, TN, BM, BN>(smem + stage * SW, smem + stage * SW + A_W, w, acc); });
+    conv_epilogue<TM, TN, MI_EPI_LINEAR, LFLAGS>(d, acc, w.m0, w.n0, w.wm, w.wn, N, w.P, w.o2v);
 }
 
 
@@ -351,21 +289,14 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_half_img256_kernel(const mi_
     constexpr int TM = 4, TN = 2, WN = 4, BM = 256, BN2 = 256, NST = 4;
     constexpr int A_W = 4 * BM, SW = A_W + 4 * BN2;               // 16-byte words per stage: A image then B image (32 KiB)
     __shared__ __attribute__((aligned(16))) uint4 smem[NST * SW];
-    {
-        float agpr_anchor = 0.f;
-        asm volatile("; accumulators in AGPRs %0" : "+a"(agpr_anchor));
-    }
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
+    agpr_anchor();
+    const Wg w = wg_lanes<WN>(d);
     // XCD-aware order: workgroups id, id + 8, ... share an L2; XCD x walks the N tiles nt = x (mod 8), the M tiles of one N
     // tile back to back (they share the activation tile; the weights stay L2 resident)
     const int xj = blockIdx.x >> 3;
     const int nt = (xj / MT) * 8 + (blockIdx.x & 7), mt = xj % MT;
     if (nt >= NT) return;                                          // grid padding (whole workgroup, before any barrier)
     const int m0 = mt * BM, n0 = nt * BN2;
-    const int P = d.O1 * d.O2;
-    const int o2v = d.o2_valid ? d.o2_valid : d.O2;
     const int nk = (d.Kpad + HK - 1) / HK;
 
     // A: K step image = 4 octets x 256 rows = 16 wave instructions of 64 words; wave w issues 2 w and 2 w + 1 (octet w / 2,
@@ -373,12 +304,12 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_half_img256_kernel(const mi_
     const uint4 *wh = reinterpret_cast<const uint4 *>(d.wh);
     const uint4 *xh = reinterpret_cast<const uint4 *>(d.xh);
     const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + MI_SINK_FLOATS);
-    const int oct = wave >> 1, half = wave & 1;
+    const int oct = w.wave >> 1, half = w.wave & 1;
     const uint4 *abase = wh + (size_t)oct * d.Mpad + m0 + 128 * half;
     const uint4 *bbase = xh + (size_t)oct * d.xh_n + n0 + 128 * half;
     const size_t a_step = (size_t)4 * d.Mpad, b_step = (size_t)4 * d.xh_n;
     const bool full_n = n0 + BN2 <= N;                              // wave-uniform: the ragged last column tile takes per-lane sources
-    const unsigned loff = 16u * lane;
+    const unsigned loff = 16u * w.lane;
 #define MI_IMG2_TILE(kt, stage)                                                                                      \
     do {                                                                                                             \
         uint4 *sa = smem + (stage) * SW + oct * BM + 128 * half, *sb = smem + (stage) * SW + A_W + oct * BN2 + 128 * half; \
@@ -390,21 +321,15 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_half_img256_kernel(const mi_
             lds_dma16_s(gb, loff, sb);                                                                               \
             lds_dma16_s(gb + 64, loff, sb + 64);                                                                     \
         } else {                                                                                                     \
-            const int c_ = n0 + 128 * half + lane;                                                                   \
-            lds_dma16((kin && c_ < N) ? gb + lane : zero, sb);                                                       \
-            lds_dma16((kin && c_ + 64 < N) ? gb + 64 + lane : zero, sb + 64);                                        \
+            const int c_ = n0 + 128 * half + w.lane;                                                                 \
+            lds_dma16((kin && c_ < N) ? gb + w.lane : zero, sb);                                                     \
+            lds_dma16((kin && c_ + 64 < N) ? gb + 64 + w.lane : zero, sb + 64);                                      \
         }                                                                                                            \
     } while (0)
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    zero_acc(acc);
 
-    const int li = lane & 31, lh = lane >> 5;
     MI_IMG2_TILE(0, 0);
     if (nk > 1) MI_IMG2_TILE(1, 1);
     if (nk > 2) MI_IMG2_TILE(2, 2);
@@ -417,14 +342,15 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_half_img256_kernel(const mi_
         __builtin_amdgcn_s_barrier();
         // stage (kt + 3) % 4 was last read in the previous iteration, which every wave has finished
         if (kt + 3 < nk) MI_IMG2_TILE(kt + 3, (stage + 3) & 3);
+        // its own K step, not half_kstep: through the shared function every instantiation spills 8 to 52 bytes more per lane
         const uint4 *As = smem + stage * SW, *Bs = As + A_W;
         uint4 af[2][TM], bf[2][TN];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
 #pragma unroll
-            for (int a = 0; a < TM; ++a) af[s][a] = As[(2 * s + lh) * BM + (wm * TM + a) * 32 + li];
+            for (int a = 0; a < TM; ++a) af[s][a] = As[(2 * s + w.lh) * BM + (w.wm * TM + a) * 32 + w.li];
 #pragma unroll
-            for (int b = 0; b < TN; ++b) bf[s][b] = Bs[(2 * s + lh) * BN2 + (wn * TN + b) * 32 + li];
+            for (int b = 0; b < TN; ++b) bf[s][b] = Bs[(2 * s + w.lh) * BN2 + (w.wn * TN + b) * 32 + w.li];
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s)
@@ -435,17 +361,16 @@ __global__ __launch_bounds__(512, 1) void conv_gemm_half_img256_kernel(const mi_
         stage = (stage + 1) & 3;
     }
 #undef MI_IMG2_TILE
-    conv_epilogue<TM, TN, MI_EPI_LINEAR, LFLAGS, 512>(d, acc, m0, n0, wm, wn, N, P, o2v);
+    conv_epilogue<TM, TN, MI_EPI_LINEAR, LFLAGS, 512>(d, acc, m0, n0, w.wm, w.wn, N, w.P, w.o2v);
 }
 
 template <int HT, int LFLAGS>
 static int launch_half_img256(const mi_conv_desc &d, hipStream_t st) {
-    const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
-    MI_REQUIRE(N64 < (1ll << 31) - 256 && N64 <= d.xh_n, "conv: %lld output positions, operand image has %lld columns", (long long)N64,
-               (long long)d.xh_n);
-    MI_REQUIRE(d.Mpad % 256 == 0 && d.K % 8 == 0 && ((uintptr_t)d.xh & 15) == 0, "conv: operand-image layer (256-row tile) needs Mpad %% 256 == 0, K %% 8 == 0");
-    const int N = (int)N64, MT = d.Mpad / 256, NT = ceil_div(N, 256);
-    hipLaunchKernelGGL((conv_gemm_half_img256_kernel<HT, LFLAGS>), dim3((unsigned)(8 * MT * ((NT + 7) / 8))), dim3(512), 0, st, d, N, MT, NT);
+    ConvGeom g;
+    MI_TRY(conv_geom(d, "conv", 256, 256, g, 256));
+    MI_REQUIRE(g.N <= d.xh_n, "conv: %d output positions, operand image has %lld columns", g.N, (long long)d.xh_n);
+    MI_REQUIRE(d.K % 8 == 0 && ((uintptr_t)d.xh & 15) == 0, "conv: operand-image layer (256-row tile) needs K %% 8 == 0 and an aligned image");
+    hipLaunchKernelGGL((conv_gemm_half_img256_kernel<HT, LFLAGS>), dim3((unsigned)(8 * g.MT * ((g.NT + 7) / 8))), dim3(512), 0, st, d, g.N, g.MT, g.NT);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }
@@ -453,27 +378,20 @@ static int launch_half_img256(const mi_conv_desc &d, hipStream_t st) {
 template <int HT, int TM, int LFLAGS>
 static int launch_half_img(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = 2 * TM * 32;
-    const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
-    MI_REQUIRE(N64 < (1ll << 31) - 256 && N64 <= d.xh_n, "conv: %lld output positions, operand image has %lld columns", (long long)N64,
-               (long long)d.xh_n);
-    MI_REQUIRE(d.Mpad % BM == 0 && d.K % 8 == 0 && ((uintptr_t)d.xh & 15) == 0, "conv: operand-image layer needs Mpad %% %d == 0, K %% 8 == 0", BM);
-    const int N = (int)N64, MT = d.Mpad / BM, NT = ceil_div(N, BN);
-    hipLaunchKernelGGL((conv_gemm_half_img_kernel<HT, TM, LFLAGS>), dim3(grouped_grid(MT, NT, 1)), dim3(256), 0, st, d, N, MT, 1);
-    MI_CHECK_LAUNCH();
+    ConvGeom g;
+    MI_TRY(conv_geom(d, "conv", BM, BM, g));
+    MI_REQUIRE(g.N <= d.xh_n, "conv: %d output positions, operand image has %lld columns", g.N, (long long)d.xh_n);
+    MI_REQUIRE(d.K % 8 == 0 && ((uintptr_t)d.xh & 15) == 0, "conv: operand-image layer needs K %% 8 == 0 and an aligned image");
+    MI_LAUNCH_TILES((conv_gemm_half_img_kernel<HT, TM, LFLAGS>), d, g, 1, st);
     return MI_OK;
 }
 
 template <int HT, int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN>
 static int launch_cfg_half(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
-    const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
-    MI_REQUIRE(N64 < (1ll << 31) - 256, "conv: too many output positions (%lld)", (long long)N64);
-    MI_REQUIRE(d.Mpad % BM == 0, "conv: Mpad %d not a multiple of the %d-row tile", d.Mpad, BM);
-    const int N = (int)N64, MT = d.Mpad / BM, NT = ceil_div(N, BN);
-    const int Gm = 1;
-    const unsigned grid = grouped_grid(MT, NT, Gm);
-    hipLaunchKernelGGL((conv_gemm_half_kernel<HT, WM, WN, TM, TN, EPI, LFLAGS, PLAIN>), dim3(grid), dim3(256), 0, st, d, N, MT, Gm);
-    MI_CHECK_LAUNCH();
+    ConvGeom g;
+    MI_TRY(conv_geom(d, "conv", BM, BM, g));
+    MI_LAUNCH_TILES((conv_gemm_half_kernel<HT, WM, WN, TM, TN, EPI, LFLAGS, PLAIN>), d, g, 1, st);
     return MI_OK;
 }
 

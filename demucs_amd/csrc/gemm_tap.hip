@@ -16,24 +16,9 @@
 // Weights: the same packed rows (GLU interleave included) with k permuted to that order (mi_conv_pack_tap).
 // Three-stage ring, counted vmcnt, one barrier per K step; A rows are padded to 128 per octet in LDS so that every wave
 // issues the same number of DMA instructions whatever the tile height.
-#include "gemm_tile.h"
+#include "gemm_loop.h"
 
 namespace mi {
-
-namespace {
-typedef __bf16 tbf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 tf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 tbf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 tf16x2 __attribute__((ext_vector_type(2)));
-
-template <int HT>
-__device__ __forceinline__ f32x16 tmfma(const uint4 a, const uint4 b, const f32x16 c) {
-    if (HT == MI_DTYPE_BF16)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tbf16x8, a), __builtin_bit_cast(tbf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tf16x8, a), __builtin_bit_cast(tf16x8, b), c, 0, 0, 0);
-}
-}  // namespace
 
 // Wt[Kpad][Mpad] fp32 (k = ci * ntaps + tap) -> Wtap[pairs rounded up to 4][Mpad][8], pair = (ci / 8) * ntaps + tap
 template <int HT>
@@ -44,10 +29,7 @@ __global__ void pack_tap_kernel(const float *__restrict__ wt, int Mpad, int Cin,
     const int j = (int)(idx & 7), m = (int)((idx >> 3) % Mpad), p = (int)((idx >> 3) / Mpad);
     const int co = p / ntaps, tap = p - co * ntaps, ci = 8 * co + j;
     const float x = ci < Cin ? wt[(size_t)(ci * ntaps + tap) * Mpad + m] : 0.f;
-    unsigned bits;
-    if (HT == MI_DTYPE_BF16) { const tbf16x2 h = {(__bf16)x, (__bf16)0.f}; bits = __builtin_bit_cast(unsigned, h); }
-    else { const tf16x2 h = {(_Float16)x, (_Float16)0.f}; bits = __builtin_bit_cast(unsigned, h); }
-    out[idx] = (unsigned short)(bits & 0xffffu);
+    out[idx] = (unsigned short)(pack_half2(HT, x, 0.f) & 0xffffu);
 }
 
 int conv_tap_pairs_pad(int Cin, int ntaps) { return (Cin / 8 * ntaps + 3) / 4 * 4; }
@@ -72,18 +54,9 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_half_tap_kernel(const mi_con
     static_assert(WN * TN * 32 == BN && WM * WN == 4 && BM <= AP, "4 waves, 128 columns, at most 128 rows");
     constexpr int SW = 4 * AP + 4 * BN;                          // 16-byte words per stage (16 KiB)
     __shared__ __attribute__((aligned(16))) uint4 smem[3 * SW];
-    {
-        float agpr_anchor = 0.f;
-        asm volatile("; accumulators in AGPRs %0" : "+a"(agpr_anchor));
-    }
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    int mt, nt;
-    if (!tile_of_block(MT, Gm, N, mt, nt)) return;
-    const int m0 = mt * BM, n0 = nt * BN;
-    const int P = d.O1 * d.O2;
-    const int o2v = d.o2_valid ? d.o2_valid : d.O2;
+    agpr_anchor();
+    Wg w;
+    if (!wg_tile<WN, BM>(d, MT, Gm, N, w)) return;
     const int ntaps = d.ntaps, npairs = d.K / 8;                 // K = Cin * ntaps, Cin % 8 == 0
     const int nk = (npairs + 3) / 4;
 
@@ -91,79 +64,47 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_half_tap_kernel(const mi_con
     const uint4 *ximg = reinterpret_cast<const uint4 *>(d.xh);
     const uint4 *zero = reinterpret_cast<const uint4 *>(d.sink + MI_SINK_FLOATS);
     // this wave moves octet `wave` of every K step: A rows m0 + 64 j + lane, B columns n0 + 64 j + lane (j = 0, 1)
-    const bool arow0 = m0 + lane < d.Mpad && lane < BM, arow1 = m0 + 64 + lane < d.Mpad && 64 + lane < BM;
+    const bool arow0 = w.m0 + w.lane < d.Mpad && w.lane < BM, arow1 = w.m0 + 64 + w.lane < d.Mpad && 64 + w.lane < BM;
     // output position of the two columns: (b, o1, o2); the input position of tap (d1, d2) is (o1 + d1, o2 + d2), stride 1
     int cb[2], co1[2], co2[2];
     bool cok[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const ColInfo c = decompose(n0 + 64 * j + lane, N, P, d.O2, o2v);
+        const ColInfo c = decompose(w.n0 + 64 * j + w.lane, N, w.P, d.O2, w.o2v);
         cb[j] = c.b; co1[j] = c.o1; co2[j] = c.o2; cok[j] = c.valid;
     }
     const int x_ld = d.x_ld ? d.x_ld : d.D2;                     // row pitch of the input positions (= O2 of this stride-1 conv)
     const int64_t npos = d.xh_n;                                 // positions per channel octet of the image
     // (channel octet, tap) of this wave's octet, advanced by four pairs per K step (scalar arithmetic)
     const int K2 = d.tap_k2, K1 = ntaps / K2, dil1 = d.tap_dil1 ? d.tap_dil1 : 1, dil2 = d.tap_dil2 ? d.tap_dil2 : 1;
-    int p_idx = wave, p_oct = wave / ntaps, p_t1 = (wave - p_oct * ntaps) / K2, p_t2 = (wave - p_oct * ntaps) - p_t1 * K2;
+    int p_idx = w.wave, p_oct = w.wave / ntaps, p_t1 = (w.wave - p_oct * ntaps) / K2, p_t2 = (w.wave - p_oct * ntaps) - p_t1 * K2;
 
-#define MI_TAP_TILE(stage)                                                                                            \
-    do {                                                                                                              \
-        uint4 *sa = smem + (stage) * SW + wave * AP, *sb = smem + (stage) * SW + 4 * AP + wave * BN;                  \
-        const bool pin = p_idx < npairs;                                                                              \
-        const uint4 *ga = wimg + (size_t)p_idx * d.Mpad + m0 + lane;                                                  \
-        lds_dma16((pin && arow0) ? ga : zero, sa);                                                                    \
-        lds_dma16((pin && arow1) ? ga + 64 : zero, sa + 64);                                                          \
-        const int d1 = p_t1 * dil1 - d.tap_pad1, d2 = p_t2 * dil2 - d.tap_pad2;                                       \
-        const uint4 *gx = ximg + (size_t)p_oct * npos;                                                                \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                               \
-            const int i1 = co1[j] + d1, i2 = co2[j] + d2;                                                             \
-            const bool ok = pin && cok[j] && (unsigned)i1 < (unsigned)d.D1 && (unsigned)i2 < (unsigned)d.D2;          \
-            const uint4 *src = gx + ((size_t)cb[j] * d.D1 + i1) * x_ld + i2;                                          \
-            lds_dma16(ok ? src : zero, sb + 64 * j);                                                                  \
-        }                                                                                                             \
-        p_idx += 4; p_t2 += 4;                                                                                        \
-        while (p_t2 >= K2) { p_t2 -= K2; ++p_t1; }                                                                    \
-        while (p_t1 >= K1) { p_t1 -= K1; ++p_oct; }                                                                   \
-    } while (0)
+    // this wave's four transfers of the next K step (the ring issues them in order: the state above advances with each call)
+    const auto issue = [&](int, int stage) {
+        uint4 *sa = smem + stage * SW + w.wave * AP, *sb = smem + stage * SW + 4 * AP + w.wave * BN;
+        const bool pin = p_idx < npairs;
+        const uint4 *ga = wimg + (size_t)p_idx * d.Mpad + w.m0 + w.lane;
+        lds_dma16((pin && arow0) ? ga : zero, sa);
+        lds_dma16((pin && arow1) ? ga + 64 : zero, sa + 64);
+        const int d1 = p_t1 * dil1 - d.tap_pad1, d2 = p_t2 * dil2 - d.tap_pad2;
+        const uint4 *gx = ximg + (size_t)p_oct * npos;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int i1 = co1[j] + d1, i2 = co2[j] + d2;
+            const bool ok = pin && cok[j] && (unsigned)i1 < (unsigned)d.D1 && (unsigned)i2 < (unsigned)d.D2;
+            const uint4 *src = gx + ((size_t)cb[j] * d.D1 + i1) * x_ld + i2;
+            lds_dma16(ok ? src : zero, sb + 64 * j);
+        }
+        p_idx += 4; p_t2 += 4;
+        while (p_t2 >= K2) { p_t2 -= K2; ++p_t1; }
+        while (p_t1 >= K1) { p_t1 -= K1; ++p_oct; }
+    };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int li = lane & 31, lh = lane >> 5;
-    MI_TAP_TILE(0);
-    if (nk > 1) MI_TAP_TILE(1);
-    int stage = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        // tile kt has landed once all but this wave's newest tile (4 instructions) are done -- for every wave after the barrier
-        if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        // stage (kt + 2) % 3 was last read in the previous iteration, which every wave has finished
-        if (kt + 2 < nk) MI_TAP_TILE(stage == 0 ? 2 : stage - 1);
-        const uint4 *As = smem + stage * SW, *Bs = As + 4 * AP;
-        uint4 af[2][TM], bf[2][TN];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-            for (int a = 0; a < TM; ++a) af[s][a] = As[(2 * s + lh) * AP + (wm * TM + a) * 32 + li];
-#pragma unroll
-            for (int b = 0; b < TN; ++b) bf[s][b] = Bs[(2 * s + lh) * BN + (wn * TN + b) * 32 + li];
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) acc[a][b] = tmfma<HT>(af[s][a], bf[s][b], acc[a][b]);
-        stage = stage == 2 ? 0 : stage + 1;
-    }
-#undef MI_TAP_TILE
-    conv_epilogue<TM, TN, EPI, LFLAGS>(d, acc, m0, n0, wm, wn, N, P, o2v);
+    zero_acc(acc);
+    dma_ring3(nk, 4, RingNop(), issue, RingNop(),
+              [&](int stage) { half_kstep<HT, TM, TN, AP, BN>(smem + stage * SW, smem + stage * SW + 4 * AP, w, acc); });
+    conv_epilogue<TM, TN, EPI, LFLAGS>(d, acc, w.m0, w.n0, w.wm, w.wn, N, w.P, w.o2v);
 }
 
 // x[b][C][P] float32 (channel stride P, batch stride C P) -> image [C / 8][B P][8] in one streaming pass (coalesced along positions)
@@ -193,12 +134,9 @@ int launch_f32_to_image(const float *x, int B, int C, int64_t P, int dtype, void
 template <int HT, int WM, int WN, int TM, int TN, int EPI, int LFLAGS>
 static int launch_tap_cfg(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
-    const int64_t N64 = (int64_t)d.B * d.O1 * d.O2;
-    MI_REQUIRE(N64 < (1ll << 31) - 256, "conv tap: too many output positions (%lld)", (long long)N64);
-    MI_REQUIRE(d.Mpad % BM == 0, "conv tap: Mpad %d not a multiple of the %d-row tile", d.Mpad, BM);
-    const int N = (int)N64, MT = d.Mpad / BM, NT = ceil_div(N, BN);
-    hipLaunchKernelGGL((conv_gemm_half_tap_kernel<HT, WM, WN, TM, TN, EPI, LFLAGS>), dim3(grouped_grid(MT, NT, 1)), dim3(256), 0, st, d, N, MT, 1);
-    MI_CHECK_LAUNCH();
+    ConvGeom g;
+    MI_TRY(conv_geom(d, "conv tap", BM, BM, g));
+    MI_LAUNCH_TILES((conv_gemm_half_tap_kernel<HT, WM, WN, TM, TN, EPI, LFLAGS>), d, g, 1, st);
     return MI_OK;
 }
 

@@ -580,7 +580,9 @@ int mi_item_denorm(const float *x_dev, int32_t rows, int64_t count, const float 
 /* Generic convolution / linear layer evaluated by the implicit-GEMM MFMA kernel (stands in for
  *   F.conv1d / F.conv2d / F.conv_transpose / F.linear as invoked at demucs/hdemucs.py:110,116,
  *   136,153,287,294,313,326, demucs/demucs.py:138,140, demucs/htdemucs.py:589-599).
- *   See demucs_amd/csrc/gemm_conv.h (mi_conv_desc) for the field meanings. */
+ *   See demucs_amd/csrc/gemm_conv.h (mi_conv_desc) for the field meanings.
+ *   A float32 descriptor that states its kernel geometry (ntaps / tap_*) may run the shifted-run tap loader (routes 2 and 7), which
+ *   reads up to 8 bytes before and 20 bytes after the tensor at `x`: the caller owns that slack (gemm_conv.h, beside `ntaps`). */
 struct mi_conv_desc;
 int mi_conv_forward(const struct mi_conv_desc *desc, void *stream);
 

@@ -2,6 +2,8 @@
 MFMA products, fp32 accumulate), which the float32 htdemucs engine takes by default.
 
   * every epilogue flag set the transformer uses (LN, LN|GELU, SCALE|RES, SCALE|RES|STATS) against float64;
+  * the native LDS-DMA tile (gemm_conv.hip conv_gemm_dma_kernel) on each of its seven flag sets against float64 and, bit for
+    bit, against the table-driven route;
   * the same products in the same k order on every tile the launch heuristics can pick: the 128-row tile, the 64-row
     small-batch tile reading the 128-row image, and a 64-row image, bit for bit; B = 1 against a batched call;
   * the engine default (split route), MI_X6=0 and the process-wide switch mi_set_split_bf16(0) (native fp32 kernels), which
@@ -23,6 +25,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAG_LN, FLAG_STATS = 32, 256
 ROUTE_X6, ROUTE_DMA = 4, 1          # mi_debug_last_conv_route: split-bf16 loop, native fp32 LDS-DMA linear tile
+ROUTE_TABLE = 0                     # the register-staged native kernel behind the gather table
 
 
 @pytest.fixture(scope="module")
@@ -36,14 +39,14 @@ def rnd(*shape, seed, scale=1.0):
     return torch.randn(*shape, generator=g, dtype=torch.float64) * scale
 
 
-def _linear(flags, B, Tn, K, seed, tile_m=128, x6=True):
+def _linear(flags, B, Tn, K, seed, tile_m=128, x6=True, plain=1):
     """One transformer linear (M = 512) on tokens (B, K, Tn) -> (y, stats or None, float64 expectation)."""
     M = 512
     x = rnd(B, K, Tn, seed=seed)
     W, b = rnd(M, K, seed=seed + 1, scale=K ** -0.5), rnd(M, seed=seed + 2, scale=0.2)
     wt, bias, _, Mpad, _, Kpad, _ = pack_w(W, b, tile=tile_m)
     kw = dict(x6=x6, wt=wt, M=M, Mpad=Mpad, K=K, Kpad=Kpad, ktab=ktab(K, 1, 1, 1, 1, 0, 0, Tn, Tn, Kpad), x=x.float().cuda(),
-              x_bstride=K * Tn, B=B, D1=1, D2=Tn, O1=1, O2=Tn, S1=1, S2=1, plain=1, epi=EPI_LINEAR, flags=flags, bias=bias,
+              x_bstride=K * Tn, B=B, D1=1, D2=Tn, O1=1, O2=Tn, S1=1, S2=1, plain=plain, epi=EPI_LINEAR, flags=flags, bias=bias,
               y_bstride=M * Tn, y_cstride=Tn, tile_m=tile_m)
     acc = torch.einsum("mk,bkt->bmt", W, x)
     if flags & FLAG_LN:
@@ -138,6 +141,22 @@ def test_x6_linear_single_item_equals_batched(lib, name):
         assert lib.mi_debug_last_conv_route() == ROUTE_X6
         outs.append(y)
     assert torch.equal(outs[0][:1], outs[1])
+
+
+@pytest.mark.parametrize("name", ["none", "gelu", "res"] + list(FLAG_SETS))
+def test_native_dma_linear_tile_equals_the_table_route(lib, name):
+    """Every LINEAR flag set conv_gemm_dma_kernel is compiled for (gemm_tile.h dispatch_epilogue), those the transformer does not
+    use (none, GELU, RES) included, on the native LDS-DMA tile: against float64 at the file's tolerance and, bit for bit, against
+    the same layer declared non-plain, which runs the register-staged kernel behind the gather table (same products, same k
+    order).  M = 512 on 6 600 columns: 4 x 52 tiles (the 128-row tile; the last column tile has 72 columns), K = 80: five K
+    steps, so the ring wraps."""
+    flags = {"none": 0, "gelu": FLAG_GELU, "res": FLAG_RES, **FLAG_SETS}[name]
+    y, _, want = _linear(flags, 2, 3300, 80, seed=500, x6=False)
+    assert (lib.mi_debug_last_conv_route(), lib.mi_debug_last_conv_tile()) == (ROUTE_DMA, 128)
+    assert maxerr(y, want) < 3e-5
+    y_tab, _, _ = _linear(flags, 2, 3300, 80, seed=500, x6=False, plain=0)
+    assert (lib.mi_debug_last_conv_route(), lib.mi_debug_last_conv_tile()) == (ROUTE_TABLE, 128)
+    assert torch.equal(y, y_tab)
 
 
 def test_split_switch_selects_native_route(lib):
