@@ -22,11 +22,11 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib
-from .audio import convert_audio
+from .audio import ConvertingStatsStream, MonoStatsStream, TrackStats, convert_audio
 from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
 from .stream import Delivery, ModelStream, StreamGroup
 
-__all__ = ["Separator", "SeparatorStream", "Delivery", "LoadModelError", "list_models"]
+__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "LoadModelError", "list_models"]
 
 
 class LoadModelError(Exception):
@@ -133,7 +133,8 @@ class Separator:
 
     def separate_stream(self, mean: Optional[float] = None, std: Optional[float] = None, sr: Optional[int] = None,
                         length: Optional[int] = None, convert: bool = False, channels: Optional[int] = None,
-                        deliver: Optional[Delivery] = None, pcm: Optional[str] = None) -> "SeparatorStream":
+                        deliver: Optional[Delivery] = None, pcm: Optional[str] = None,
+                        stats: Optional[TrackStats] = None) -> "SeparatorStream":
         """`separate_tensor` for a track that arrives block by block (demucs_amd/stream.py): `push(block)` takes (channels, n)
         float32 and returns `{source: (channels, m)}` of the newly final samples, `finish()` the rest.
 
@@ -167,7 +168,38 @@ class Separator:
         be whole frames), or an (n, channels) int16 / float32 tensor.  The bytes cross to the device as they are and are
         de-interleaved, converted (`v / 32768`, `v / 8388608`: both exact) and normalised there, so the stems are those of the float
         stream fed the same values, bit for bit.  `length`, `pushed_input`, `latency` and `input_latency` count frames.  With
-        `Delivery(fmt="i16")` a stream is then a transcoding loop without host arithmetic: wire frames in, wire frames out."""
+        `Delivery(fmt="i16")` a stream is then a transcoding loop without host arithmetic: wire frames in, wire frames out.
+
+        `stats=` takes the `audio.TrackStats` that `analyse_stream` returned for the same input in place of `mean` and `std`: the
+        affine is its `(mean, s)` as the statistics kernel wrote them, with no further `+ 1e-8`, and `length` defaults to its
+        `input_length`.  With the track's own statistics the stems equal `separate_tensor`'s bit for bit."""
+        self._check_stream_input(sr, channels, convert, pcm)
+        if (mean is None) != (std is None):
+            raise ValueError("separate_stream: give both mean and std, or neither")
+        if stats is not None:
+            if mean is not None:
+                raise ValueError("separate_stream: give stats, or mean and std, not both: stats already holds the normaliser "
+                                 "s = std + 1e-8")
+            if not isinstance(stats, TrackStats):
+                raise ValueError(f"separate_stream: stats must be an audio.TrackStats, got {type(stats).__name__}")
+            if length is None:
+                length = stats.input_length
+        plan = self._convert_plan(sr, channels) if convert else None
+        if plan is not None and length is not None:
+            if int(length) < 0:
+                raise ValueError(f"length must be >= 0, got {length}")
+            in_length, length = int(length), plan.final_count(int(length))
+        st = ModelStream(self._model, shifts=self._shifts, overlap=self._overlap, segment=self._segment, split=self._split,
+                         device=self._device, length=length, progress=self._progress, callback=self._callback,
+                         affine=None if mean is None else (mean, std), deliver=deliver, pcm=pcm if plan is None else None,
+                         stats=stats)
+        if plan is None:
+            return SeparatorStream(st, self._model.sources)
+        return ConvertingSeparatorStream(st, self._model.sources, plan, channels or self._audio_channels,
+                                         in_length if length is not None else None, self._device_index, pcm=pcm)
+
+    def _check_stream_input(self, sr: Optional[int], channels: Optional[int], convert: bool, pcm: Optional[str]) -> None:
+        """The refusals `separate_stream` and `analyse_stream` share ahead of `_convert_plan` (no device work, no RNG call)."""
         if pcm is not None:                 # refused before any RNG call
             from .audio import check_pcm
             check_pcm(pcm, _is_engine(self._model) and torch.device(self._device).type == "cuda")
@@ -178,20 +210,42 @@ class Separator:
             if sr is not None and sr != self._samplerate:
                 raise ValueError(f"separate_stream: input sample rate {sr} is not the model's {self._samplerate}; a stream does not "
                                  "resample unless convert=True")
-        if (mean is None) != (std is None):
-            raise ValueError("separate_stream: give both mean and std, or neither")
+
+    def analyse_stream(self, sr: Optional[int] = None, channels: Optional[int] = None, convert: bool = False,
+                       pcm: Optional[str] = None):
+        """The analysis pass in front of `separate_stream`: a stream whose `push(block)` takes the blocks `separate_stream` takes
+        for the same arguments (and refuses what it refuses) and whose `finish()` returns the `audio.TrackStats` of the track --
+        the `(mean, s)` that `separate_tensor(wav, sr)` computes internally, with the same bits, for every partition of the
+        input.  Device memory is bounded: 4 MiB of carried sums (`audio.MonoStatsStream`), plus the converter's carried samples
+        when `convert=True` puts an `audio.ConvertStream` in front.  Read the input twice: once into this stream, once into
+        `separate_stream(stats=...)` with the same `sr`, `channels`, `convert` and `pcm`."""
+        self._check_stream_input(sr, channels, convert, pcm)
         plan = self._convert_plan(sr, channels) if convert else None
-        if plan is not None and length is not None:
-            if int(length) < 0:
-                raise ValueError(f"length must be >= 0, got {length}")
-            in_length, length = int(length), plan.final_count(int(length))
-        st = ModelStream(self._model, shifts=self._shifts, overlap=self._overlap, segment=self._segment, split=self._split,
-                         device=self._device, length=length, progress=self._progress, callback=self._callback,
-                         affine=None if mean is None else (mean, std), deliver=deliver, pcm=pcm if plan is None else None)
         if plan is None:
-            return SeparatorStream(st, self._model.sources)
-        return ConvertingSeparatorStream(st, self._model.sources, plan, channels or self._audio_channels,
-                                         in_length if length is not None else None, self._device_index, pcm=pcm)
+            return MonoStatsStream(self._audio_channels, device=self._device, pcm=pcm,
+                                   src_channels=None if pcm is None else self._audio_channels)
+        return ConvertingStatsStream(plan, self._audio_channels, channels or self._audio_channels, self._device_index(), pcm=pcm)
+
+    def separate_blocks(self, source, sr: Optional[int] = None, channels: Optional[int] = None, pcm: Optional[str] = None,
+                        deliver: Optional[Delivery] = None):
+        """`separate_tensor(wav, sr)` for a track that never exists whole on the host or the device, read twice: `source()` returns
+        a fresh iterator over the track's blocks each time it is called (`separate_stream`'s blocks for `sr`, `channels` and
+        `pcm`, converted on the device when they are not the model's).  Pass 1 pushes them through `analyse_stream`, pass 2 through
+        `separate_stream(stats=..., length=...)`; this generator yields what every `push` and then `finish` of pass 2 return.
+        Concatenated, the stems equal `separate_tensor`'s bit for bit, with `random` left in the same state; with `deliver=` the
+        frames equal `audio.deliver`'s on those stems, under a delivering stream's refusals (raised before pass 1)."""
+        if deliver is not None:
+            deliver.for_stream(self._model.sources, _is_engine(self._model) and torch.device(self._device).type == "cuda",
+                               self._samplerate, self._audio_channels)
+        an = self.analyse_stream(sr=sr, channels=channels, convert=True, pcm=pcm)
+        for block in source():
+            an.push(block)
+        stats = an.finish()
+        st = self.separate_stream(stats=stats, sr=sr, channels=channels, convert=True, pcm=pcm, deliver=deliver,
+                                  length=stats.input_length)
+        for block in source():
+            yield st.push(block)
+        yield st.finish()
 
     def _convert_plan(self, sr: Optional[int], channels: Optional[int]):
         """The refusals of a converting stream (before any device work or RNG call) and its `audio.ConvertPlan`; None when the
@@ -408,22 +462,26 @@ class SeparatorStreamGroup:
 
     def open(self, mean: Optional[float] = None, std: Optional[float] = None, length: Optional[int] = None,
              sr: Optional[int] = None, channels: Optional[int] = None, deliver: Optional[Delivery] = None,
-             pcm: Optional[str] = None):
+             pcm: Optional[str] = None, stats: Optional[TrackStats] = None):
         """`length`, `sr` and `channels` describe the stream's INPUT, as for `separate_stream(convert=True)`; `deliver` and `pcm`
         are `separate_stream`'s, each stream with its own: a group may mix float, int16, int24 and float32 PCM feeds, and a call
-        stays one append launch, one convert-append launch and one H2D."""
+        stays one append launch, one convert-append launch and one H2D.  `stats=` (an `audio.TrackStats`, from `analyse_stream`)
+        replaces `mean` and `std` as in `separate_stream`; `length` then defaults to its `input_length`."""
         if pcm is not None:
             from .audio import check_pcm
             check_pcm(pcm, _is_engine(self.separator.model) and torch.device(self.separator._device).type == "cuda")
         if (mean is None) != (std is None):
             raise ValueError("separate_stream_group: give both mean and std, or neither")
+        if stats is not None and mean is not None:
+            raise ValueError("separate_stream_group: give stats, or mean and std, not both: stats already holds the normaliser "
+                             "s = std + 1e-8")
         convert = None
         if sr is not None or channels is not None:
             plan = self.separator._convert_plan(sr, channels)
             if plan is not None:
                 convert = (plan, int(channels or self.separator.audio_channels))
         return self.group.open(length=length, affine=None if mean is None else (mean, std), convert=convert, deliver=deliver,
-                               pcm=pcm, channels=None if convert is not None else channels)
+                               pcm=pcm, channels=None if convert is not None else channels, stats=stats)
 
     def trailing_bytes(self, key) -> int:
         return self.group.trailing_bytes(key)

@@ -495,6 +495,186 @@ class ConvertStream:
         return 0 if self.feed is None else self.feed.trailing_bytes
 
 
+# ---- track statistics for a stream: mi_mono_stats block by block (demucs_amd/csrc/stats_stream.hip) -----------------------
+class TrackStats:
+    """The normaliser of `Separator.separate_tensor` for one track, as `mi_mono_stats` computes it: `mean` and `s`, the float32
+    mono mean and `std + 1e-8` (the 1e-8 already added; NaN for a track of one sample, as torch's unbiased std), of `length`
+    samples at the model's rate.  `input_length` counts the frames pushed when a converter sat in front of the analysis, else it
+    equals `length`.  Immutable; `separate_stream(stats=...)` takes it as it is."""
+    __slots__ = ("mean", "s", "length", "input_length")
+
+    def __init__(self, mean, s, length, input_length=None):
+        import numpy as np
+        vals = []
+        for name, v in (("mean", mean), ("s", s)):
+            if isinstance(v, (bool, str, bytes)) or not isinstance(v, (int, float, np.floating, np.integer)):
+                raise ValueError(f"TrackStats: {name} must be a real number, got {v!r}")
+            v = float(v)
+            with np.errstate(over="ignore"):
+                r = float(np.float32(v))
+            if r != v and not (math.isnan(r) and math.isnan(v)):
+                raise ValueError(f"TrackStats: {name} must be a float32 value as mi_mono_stats writes it, got {v!r}")
+            vals.append(v)
+        lens = []
+        for name, v in (("length", length), ("input_length", length if input_length is None else input_length)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"TrackStats: {name} must be a positive integer, got {v!r}")
+            lens.append(int(v))
+        for name, v in zip(self.__slots__, vals + lens):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("TrackStats is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("TrackStats is immutable")
+
+    def _key(self):
+        return (*(("nan",) if math.isnan(v) else (v,) for v in (self.mean, self.s)), self.length, self.input_length)
+
+    def __eq__(self, other):
+        return isinstance(other, TrackStats) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"TrackStats(mean={self.mean!r}, s={self.s!r}, length={self.length}, input_length={self.input_length})"
+
+
+class MonoStatsStream:
+    """`mi_mono_stats` for a track that arrives block by block: `push(block)` adds a block, `finish()` returns the `TrackStats`
+    of everything pushed, with the bits `mi_mono_stats` gives for the whole (channels, length) track, for every partition.
+    A block is planar (channels, n) float32 on the host or a device; with `pcm=` and `src_channels=` interleaved wire PCM as
+    `ConvertStream` takes it (a bytes-like object or a 1-D uint8 tensor that may end anywhere, a `PcmFeed` carrying the incomplete
+    frame; an (n, src_channels) int16 / float32 tensor; or a `PcmBlock`), read by the kernel where it lies with `mi_pcm_planar`'s
+    channel map.  A push is one H2D for a host block and one `mi_mono_stats_update` launch.  `pushed` counts samples per channel
+    (frames), `trailing_bytes` the bytes of an incomplete last frame, which `finish()` drops.  Device state: 4 MiB of per-thread
+    sums (`mi_mono_stats_state_bytes`), whatever the track's duration."""
+
+    def __init__(self, channels: int, device="cuda", pcm=None, src_channels=None):
+        self.channels = int(channels)
+        if self.channels < 1:
+            raise ValueError(f"channels must be >= 1, got {channels}")
+        self.feed = None
+        if pcm is not None:
+            if src_channels is None:
+                raise ValueError("a PCM stream needs src_channels=: the frames do not say how many channels they hold")
+            self.feed = PcmFeed(pcm, src_channels)
+            check_stream_channels(self.feed.src_channels, self.channels)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.EngineError("demucs_amd.audio.MonoStatsStream only runs on a GPU device (MI355X)")
+        self.device = dev
+        self.pushed = 0
+        self.finished = False
+        self._state = self._scratch = self._stats = None
+
+    def device_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self._state, self._scratch, self._stats) if t is not None)
+
+    @property
+    def trailing_bytes(self) -> int:
+        return 0 if self.feed is None else self.feed.trailing_bytes
+
+    def _on(self):
+        """The device as a context, its index resolved at the first device work."""
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        return torch.cuda.device(self.device)
+
+    def _update(self, src: torch.Tensor, code: int, src_channels: int, n: int) -> None:
+        lib = _lib.load()
+        if self._state is None:
+            self._state = torch.zeros(lib.mi_mono_stats_state_bytes(), dtype=torch.uint8, device=self.device)
+        _lib.check(lib.mi_mono_stats_update(src.data_ptr(), code, src_channels, n, self.channels, self.pushed, self._state.data_ptr(),
+                                            C.c_void_p(_lib.current_stream_ptr())), "mi_mono_stats_update")
+        self.pushed += n
+
+    def push(self, block) -> None:
+        if self.finished:
+            raise RuntimeError("push after finish()")
+        if self.feed is not None or isinstance(block, PcmBlock):
+            blk = block
+            if not isinstance(block, PcmBlock):            # a caller with a feed of its own hands over whole frames
+                blk = self.feed.accept(block)
+                self.feed.commit(blk)
+            else:
+                check_stream_channels(blk.src_channels, self.channels)
+            if blk.n:
+                keep = []
+                with self._on():
+                    self._update(blk.on_device(self.device, keep), blk.code, blk.src_channels, blk.n)
+            return
+        if not isinstance(block, torch.Tensor) or block.dim() != 2 or block.shape[0] != self.channels:
+            shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
+            raise ValueError(f"expected a ({self.channels}, n) block, got {shape}")
+        if block.shape[1]:
+            with self._on():
+                src = block.to(device=self.device, dtype=torch.float32).contiguous()
+                self._update(src, PCM_PLANAR, self.channels, block.shape[1])
+
+    def finish(self) -> TrackStats:
+        if self.finished:
+            raise RuntimeError("finish() called twice")
+        if self.pushed == 0:
+            raise ValueError("the stream ended before any sample was pushed")
+        self.finished = True
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            self._scratch = torch.empty(lib.mi_mono_stats_scratch_bytes(), dtype=torch.uint8, device=self.device)
+            self._stats = torch.empty(2, dtype=torch.float32, device=self.device)
+            _lib.check(lib.mi_mono_stats_finish(self._state.data_ptr(), self.pushed, self._scratch.data_ptr(), self._stats.data_ptr(),
+                                                C.c_void_p(_lib.current_stream_ptr())), "mi_mono_stats_finish")
+            mean, s = self._stats.cpu().tolist()
+        return TrackStats(mean, s, self.pushed)
+
+
+class ConvertingStatsStream:
+    """`Separator.analyse_stream` for an input at another sample rate or channel count: a `ConvertStream` on the device whose
+    outputs feed a `MonoStatsStream`, so the statistics are those of `convert_audio(...)` of the whole track.  `pushed` counts
+    input frames; `finish()` fills `TrackStats.input_length` with it."""
+
+    def __init__(self, plan, channels: int, src_channels: int, device, pcm=None):
+        self.convert = ConvertStream(None, None, channels, device=device, plan=plan, pcm=pcm,
+                                     src_channels=src_channels if pcm is not None else None)
+        self.stats = MonoStatsStream(channels, device=device)
+        self.src_channels = int(src_channels)
+
+    @property
+    def pushed(self) -> int:
+        return self.convert.pushed
+
+    @property
+    def finished(self) -> bool:
+        return self.stats.finished
+
+    @property
+    def trailing_bytes(self) -> int:
+        return self.convert.trailing_bytes
+
+    def device_bytes(self) -> int:
+        return self.convert.device_bytes() + self.stats.device_bytes()
+
+    def push(self, block) -> None:
+        if self.stats.finished:
+            raise RuntimeError("push after finish()")
+        if self.convert.feed is None and (not isinstance(block, torch.Tensor) or block.dim() != 2 or
+                                          block.shape[0] != self.src_channels):
+            shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
+            raise ValueError(f"expected a ({self.src_channels}, n) block, got {shape}")
+        self.stats.push(self.convert.push(block, on_device=True))
+
+    def finish(self) -> TrackStats:
+        if self.stats.finished:
+            raise RuntimeError("finish() called twice")
+        if self.convert.pushed == 0:
+            raise ValueError("the stream ended before any sample was pushed")
+        self.stats.push(self.convert.finish(on_device=True))
+        st = self.stats.finish()
+        return TrackStats(st.mean, st.s, st.length, self.convert.pushed)
+
+
 # ---- after the separation: what demucs.separate does with the stems before any encoder sees them ----------------------
 _CLIP_MODES = {"rescale": 1, "clamp": 2, "tanh": 3}
 

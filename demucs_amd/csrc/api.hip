@@ -466,6 +466,32 @@ int mi_mono_stats(const float *wav_dev, int32_t channels, int64_t length, void *
     return launch_mono_stats(wav_dev, channels, length, (double *)scratch_dev, stats_dev, (hipStream_t)stream);
 }
 
+int32_t mi_mono_stats_state_bytes(void) { return mono_stats_state_bytes(); }
+
+int mi_mono_stats_update(const void *src_dev, int32_t fmt, int32_t src_ch, int64_t n, int32_t channels, int64_t before, void *state_dev,
+                         void *stream) {
+    MI_REQUIRE(fmt == MI_PCM_PLANAR || fmt == MI_PCM_I16 || fmt == MI_PCM_I24 || fmt == MI_PCM_F32,
+               "mi_mono_stats_update: unknown format %d", fmt);
+    const bool planar = fmt == MI_PCM_PLANAR;
+    const int64_t per = planar ? channels : src_ch;        // samples per position in the block
+    MI_REQUIRE(channels >= 1 && (planar || (src_ch >= 1 && (src_ch == 1 || src_ch >= channels))) && n >= 0 && n <= INT64_MAX / 4 / per &&
+                   before >= 0 && before <= INT64_MAX - n,
+               "mi_mono_stats_update: bad argument");
+    MI_REQUIRE(state_dev && (uintptr_t)state_dev % 8 == 0, "mi_mono_stats_update: the state is null or not aligned to its doubles");
+    if (n == 0) return MI_OK;
+    const int width = fmt == MI_PCM_I16 ? 2 : fmt == MI_PCM_I24 ? 3 : 4;
+    MI_REQUIRE(src_dev, "mi_mono_stats_update: bad argument");
+    MI_REQUIRE(width == 3 || (uintptr_t)src_dev % width == 0, "mi_mono_stats_update: the source is not aligned to its %d-byte samples",
+               width);
+    return launch_mono_stats_update((const unsigned char *)src_dev, fmt, src_ch, n, channels, before, (double *)state_dev,
+                                    (hipStream_t)stream);
+}
+
+int mi_mono_stats_finish(const void *state_dev, int64_t length, void *scratch_dev, float *stats_dev, void *stream) {
+    MI_REQUIRE(state_dev && (uintptr_t)state_dev % 8 == 0 && scratch_dev && stats_dev && length >= 1, "mi_mono_stats_finish: bad argument");
+    return launch_mono_stats_finish((const double *)state_dev, length, (double *)scratch_dev, stats_dev, (hipStream_t)stream);
+}
+
 int mi_track_affine(float *x_dev, int64_t numel, const float *stats_dev, int32_t inverse, void *stream) {
     MI_REQUIRE(x_dev && stats_dev && numel >= 1 && (inverse == 0 || inverse == 1), "mi_track_affine: bad argument");
     return launch_track_affine(x_dev, numel, stats_dev, inverse, (hipStream_t)stream);

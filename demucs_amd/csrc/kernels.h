@@ -254,6 +254,12 @@ int launch_pcm_planar(const unsigned char *src, int fmt, int src_ch, int64_t n, 
 int launch_streams_append_pcm(float *win, int64_t win_cap, int channels, const int64_t *table, int n_streams, int64_t max_bytes,
                               const float *stats, int n_stats, hipStream_t st);
 
+// stats_stream.hip: mi_mono_stats block by block, the per-thread sums carried in device memory
+int mono_stats_state_bytes();
+int launch_mono_stats_update(const unsigned char *src, int fmt, int src_ch, int64_t n, int channels, int64_t before, double *state,
+                             hipStream_t st);
+int launch_mono_stats_finish(const double *state, int64_t length, double *scratch, float *stats, hipStream_t st);
+
 const void *conv_zero_page();      // gemm_conv.hip: 256 bytes of device zeros
 // attention_heads.hip: half modes, per-head token-major 16-bit operands (MI_FLAG_HEADS), LDS-DMA ring
 int launch_attention_heads(const void *q, const void *k, const void *v, const void *zero_page, int B, int heads, int Tq, int Tk, int Tq_pitch,
@@ -262,6 +268,7 @@ int launch_attention_heads(const void *q, const void *k, const void *v, const vo
 // post.hip: Separator normalisation, clip prevention, two-stems sums
 int post_stats_scratch_bytes();
 int launch_mono_stats(const float *wav, int channels, int64_t length, double *scratch, float *stats, hipStream_t st);
+int launch_mono_stats_final(const double *scratch, int64_t length, float *stats, hipStream_t st);
 int launch_stream_emit(const float *acc, int64_t acc_cap, int n_sources, int channels, const int64_t *passes, int n_passes,
                        const int64_t *segs, int n_segs, const float *weights, int64_t weights_cap, const float *scales, int n_members,
                        int shifts, int bag, const float *stats, int64_t n, float *out, hipStream_t st);

@@ -6,31 +6,20 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "mono_stats.h"
 #include "post_ops.h"
 
 namespace mi {
 
-constexpr int kPostBlocks = 1024;      // partial-sum slots of the statistics pass (fixed: the result does not depend on the grid)
-
-// ref = wav.mean(0) (float32, channel sum then / channels, api.py:267); partial sums of ref and ref^2 in float64.
+// ref = wav.mean(0) (float32, channel sum then / channels, api.py:267); partial sums of ref and ref^2 in float64 (mono_stats.h).
 // grid kPostBlocks x 256; block b reduces the positions p = b*256 + t, + kPostBlocks*256, ...: a fixed assignment.
 __global__ __launch_bounds__(256) void mono_stats_partial_kernel(const float *__restrict__ wav, int channels, int64_t length,
                                                                  double *__restrict__ part) {
     double s = 0.0, q = 0.0;
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < length; p += (int64_t)kPostBlocks * 256) {
-        float a = wav[p];
-        for (int c = 1; c < channels; ++c) a = __fadd_rn(a, wav[(size_t)c * length + p]);
-        const float m = __fdiv_rn(a, (float)channels);
-        s += (double)m;
-        q += (double)m * (double)m;
-    }
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < length; p += (int64_t)kPostBlocks * 256)
+        mono_stats_step([&](int c) { return wav[(size_t)c * length + p]; }, channels, s, q);
     __shared__ double sh[2][256];
-    sh[0][threadIdx.x] = s; sh[1][threadIdx.x] = q;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) { sh[0][threadIdx.x] += sh[0][threadIdx.x + w]; sh[1][threadIdx.x] += sh[1][threadIdx.x + w]; }
-        __syncthreads();
-    }
+    mono_stats_tree(s, q, sh);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = sh[0][0]; part[2 * blockIdx.x + 1] = sh[1][0]; }
 }
 
@@ -110,6 +99,10 @@ int post_stats_scratch_bytes() { return kPostBlocks * 2 * (int)sizeof(double); }
 int launch_mono_stats(const float *wav, int channels, int64_t length, double *scratch, float *stats, hipStream_t st) {
     hipLaunchKernelGGL(mono_stats_partial_kernel, dim3(kPostBlocks), dim3(256), 0, st, wav, channels, length, scratch);
     MI_CHECK_LAUNCH();
+    return launch_mono_stats_final(scratch, length, stats, st);
+}
+
+int launch_mono_stats_final(const double *scratch, int64_t length, float *stats, hipStream_t st) {
     hipLaunchKernelGGL(mono_stats_final_kernel, dim3(1), dim3(256), 0, st, scratch, length, stats);
     MI_CHECK_LAUNCH();
     return MI_OK;

@@ -212,7 +212,7 @@ class ModelStream:
     floor(new * emitted / old) - delivered <= output_hold, and some push reaches it."""
 
     def __init__(self, model, shifts=1, overlap=0.25, transition_power=1.0, segment=None, device=None, length=None,
-                 split=True, progress=False, callback=None, affine=None, deliver=None, pcm=None, channels=None):
+                 split=True, progress=False, callback=None, affine=None, deliver=None, pcm=None, channels=None, stats=None):
         from .apply import BagOfModels
         from . import distributed
         if not split:
@@ -260,9 +260,14 @@ class ModelStream:
         elif channels is not None and channels != self.audio_channels:
             raise ValueError(f"expected {self.audio_channels} channels, got {channels}: a stream of float blocks converts no "
                              "channel layout")
-        # Separator.separate_stream: blocks are normalised `(x - mean) / s` and stems restored `x * s + mean`, s = std + 1e-8
+        # Separator.separate_stream: blocks are normalised `(x - mean) / s` and stems restored `x * s + mean`, s = std + 1e-8;
+        # `stats` (an `audio.TrackStats`: what the statistics kernels computed) names mean and s as they are
         self.affine = None
-        if affine is not None:
+        if stats is not None:
+            if affine is not None:
+                raise ValueError("give stats, or mean and std, not both: stats already holds the normaliser s = std + 1e-8")
+            self.affine = (float(stats.mean), float(stats.s))
+        elif affine is not None:
             mean, std = (float(v) for v in affine)
             self.affine = (float(np.float32(mean)), float(np.float32(std) + np.float32(1e-8)))
 
@@ -885,7 +890,7 @@ class StreamGroup:
 
     # ---- public --------------------------------------------------------------------------------------------------------
     def open(self, length: Optional[int] = None, affine=None, convert=None, deliver: Optional[Delivery] = None,
-             pcm: Optional[str] = None, channels: Optional[int] = None):
+             pcm: Optional[str] = None, channels: Optional[int] = None, stats=None):
         """A new stream; makes the RNG calls `ModelStream(..., length=length)` makes.  Returns its key.
 
         `deliver=Delivery(...)`: the stream's results are `{name: (m, channels) frames}` (see `Delivery`), each stream of a group
@@ -898,7 +903,15 @@ class StreamGroup:
         `pcm=` ("i16", "i24", "f32"): the stream's blocks are interleaved wire PCM (`apply_model_stream`'s rule; `channels=` source
         channels unless `convert=` names them).  A call with such a stream uses `mi_streams_append_pcm` /
         `mi_streams_convert_append_pcm` for all its streams, the float ones as planar rows: still one append launch, one
-        convert-append launch and one H2D, in which a host block travels as its raw bytes."""
+        convert-append launch and one H2D, in which a host block travels as its raw bytes.
+
+        `stats=` (an `audio.TrackStats`) in place of `affine=`: the stream's affine is its `(mean, s)` as they are, and `length`
+        defaults to its `input_length`."""
+        if stats is not None:
+            if affine is not None:
+                raise ValueError("give stats, or mean and std, not both: stats already holds the normaliser s = std + 1e-8")
+            if length is None:
+                length = stats.input_length
         feed = None
         if pcm is not None:                 # refused here, before any RNG call
             from .audio import PcmFeed, check_pcm, check_stream_channels
@@ -925,7 +938,7 @@ class StreamGroup:
                 raise ValueError(f"length must be >= 0, got {length}")
             conv = _Conv(plan, int(src_channels), None if length is None else int(length))
             length = None if length is None else plan.final_count(int(length))
-        st = ModelStream(self.model, device=self.device, length=length, affine=affine, deliver=deliver, **self._kw)
+        st = ModelStream(self.model, device=self.device, length=length, affine=affine, deliver=deliver, stats=stats, **self._kw)
         st.convert = conv
         st.feed = feed
         key = self._next

@@ -431,6 +431,22 @@ int32_t mi_mono_stats_scratch_bytes(void);
 int mi_mono_stats(const float *wav_dev, int32_t channels, int64_t length, void *scratch_dev, float *stats_dev, void *stream);
 int mi_track_affine(float *x_dev, int64_t numel, const float *stats_dev, int32_t inverse, void *stream);
 
+/* mi_mono_stats for a track that arrives block by block (demucs_amd/csrc/stats_stream.hip): the same (mean, s), bit for bit, for
+ * every partition of the track.  mi_mono_stats runs on a fixed grid of 262 144 threads, position p belongs to thread p % 262144
+ * and a thread adds its positions in ascending order, so the carried state is one (sum, sum of squares) pair of doubles per
+ * thread: state_dev, mi_mono_stats_state_bytes() = 2 x 262 144 x 8 bytes (4 MiB), 8-byte aligned, all-zero bytes at the start.
+ * mi_mono_stats_update: adds track positions [before, before + n) to the state.  fmt MI_PCM_PLANAR: src_dev is a contiguous planar
+ *   float32 (channels, n) block (src_ch is ignored); MI_PCM_I16 / _I24 / _F32: n interleaved frames of src_ch channels under
+ *   mi_pcm_planar's rules (alignment to the sample width, the channel map, no byte outside the block is read).  The caller
+ *   passes `before` as the sum of the earlier blocks' n; n = 0 does nothing.  Nothing outside the state is written.
+ * mi_mono_stats_finish: stats_dev[0], stats_dev[1] as mi_mono_stats writes them for the `length` positions added so far;
+ *   scratch_dev: mi_mono_stats_scratch_bytes() bytes.  The state is only read: a second call gives the same result, and more
+ *   blocks may follow. */
+int32_t mi_mono_stats_state_bytes(void);
+int mi_mono_stats_update(const void *src_dev, int32_t fmt, int32_t src_ch, int64_t n, int32_t channels, int64_t before, void *state_dev,
+                         void *stream);
+int mi_mono_stats_finish(const void *state_dev, int64_t length, void *scratch_dev, float *stats_dev, void *stream);
+
 /* mi_prevent_clip: `demucs.audio.prevent_clip(wav, mode)` (demucs/audio.py:218-234) on device stems: y = x / max(1.01 * max|x|, 1)
  *   ("rescale"; the peak is reduced on the device into peak_dev, 4 bytes), clamp(x, -0.99, 0.99) or tanh(x).
  * mi_two_stems: the `--two-stems` outputs of demucs/separate.py:189-218: minus = 0: y = 0 + (every stem but `selected`, in
