@@ -67,6 +67,35 @@ def ktab(Cin, K1, K2, dil1, dil2, pad1, pad2, chan_stride, D2, Kpad):
     return torch.from_numpy(t).cuda()
 
 
+def image_of(v):
+    """(B, C, ...) -> the operand image [C / 8][B * P][8] of gemm_conv.h: column n = b * P + p over the flattened trailing dims
+    (a row pitch is part of them), channel c in octet c / 8 at place c % 8."""
+    B, C = v.shape[:2]
+    return v.reshape(B, C // 8, 8, -1).permute(1, 0, 3, 2).reshape(C // 8, -1, 8).contiguous()
+
+
+def image_to(img, B, *dims):
+    """The inverse: the first B * P columns of an image [C / 8][>= B * P][8] -> (B, C, *dims), P the product of dims."""
+    P = int(np.prod(dims))
+    return img[:, :B * P].reshape(img.shape[0], B, P, 8).permute(1, 0, 3, 2).reshape(B, img.shape[0] * 8, *dims)
+
+
+def phase_image(v, axis_len, pq, freq, T, hdt):
+    """Host restatement of gemm_conv.h MI_FLAG_IMG4: v (B, C, Len[, T]) float -> int16 image [(C/8) * 4][B * pq][8]; slot
+    q = i // 4 + (i % 4 >= 2) of plane i % 4 (frequency rows: position q * T + t)."""
+    B, C = v.shape[:2]
+    img = torch.zeros(C // 8 * 4, B * pq, 8, dtype=hdt)
+    for i in range(axis_len):
+        rho, q = i % 4, i // 4 + (1 if i % 4 >= 2 else 0)
+        for b in range(B):
+            if freq:
+                blk = v[b, :, i, :].to(hdt).reshape(C // 8, 8, T).permute(0, 2, 1)                  # (oct, T, 8)
+                img[rho::4][:, b * pq + q * T:b * pq + (q + 1) * T, :] = blk
+            else:
+                img[rho::4][:, b * pq + q, :] = v[b, :, i].to(hdt).reshape(C // 8, 8)
+    return img.view(torch.int16)
+
+
 def conv_desc(**kw):
     """Fill a MiConvDesc from keyword arguments (tensors -> data_ptr) -> (descriptor, the tensors it points to)."""
     d = _lib.MiConvDesc()

@@ -131,7 +131,7 @@ def test_strip_transposes_are_bit_identical_to_the_tile_kernels(lib, L):
 
 # ------------------------------------------------------------------------------------------------
 from gpu_helpers import (EPI_BIAS_STATS, EPI_CONVTR, EPI_GLU, EPI_GN_GLU, EPI_LINEAR, EPI_STATS_ONLY, FLAG_EMB,  # noqa: E402
-                         FLAG_GELU, FLAG_RES, FLAG_SCALE, FLAG_TR_FREQ, SLOTS, conv_call, ktab, maxerr, pack_vec, pack_w)
+                         FLAG_GELU, FLAG_RES, FLAG_SCALE, FLAG_TR_FREQ, SLOTS, conv_call, ktab, maxerr, pack_vec, pack_w, phase_image)
 
 
 @pytest.fixture(params=[False, True, "bf16", "f16"], ids=["fp32mfma", "bf16x6", "bf16", "f16"])
@@ -524,22 +524,6 @@ def test_conv_transpose_on_operand_image(lib, freq, mode):
     assert e_tap < 2e-5 and e_ref < 2e-5 and maxerr(y_tap, y_ref) < 1e-5
 
 
-def _phase_image(v, axis_len, pq, freq, T, hdt):
-    """Host restatement of gemm_conv.h MI_FLAG_IMG4: v (B, C, Len[, T]) float -> int16 image [(C/8) * 4][B * pq][8]; slot
-    q = i // 4 + (i % 4 >= 2) of plane i % 4 (frequency rows: position q * T + t)."""
-    B, C = v.shape[:2]
-    img = torch.zeros(C // 8 * 4, B * pq, 8, dtype=hdt)
-    for i in range(axis_len):
-        rho, q = i % 4, i // 4 + (1 if i % 4 >= 2 else 0)
-        for b in range(B):
-            if freq:
-                blk = v[b, :, i, :].to(hdt).reshape(C // 8, 8, T).permute(0, 2, 1)                  # (oct, T, 8)
-                img[rho::4][:, b * pq + q * T:b * pq + (q + 1) * T, :] = blk
-            else:
-                img[rho::4][:, b * pq + q, :] = v[b, :, i].to(hdt).reshape(C // 8, 8)
-    return img.view(torch.int16)
-
-
 @pytest.mark.parametrize("freq", [True, False])
 @pytest.mark.parametrize("mode", ["bf16", "f16"])
 def test_encoder_conv_on_phase_split_image(lib, freq, mode):
@@ -579,7 +563,7 @@ def test_encoder_conv_on_phase_split_image(lib, freq, mode):
         want_y = F.glu(z, dim=1)
         yv = y.cpu() if freq else y.cpu()[..., :L]
         assert maxerr(yv.cuda(), want_y if freq else want_y[..., :L]) < 2e-5
-        want_img = _phase_image(yv, Len, pq, freq, T if freq else 0, hdt)
+        want_img = phase_image(yv, Len, pq, freq, T if freq else 0, hdt)
         assert torch.equal(img.cpu(), want_img), "phase-split image differs from the layout restatement"
         # (b) consumer: strided conv C -> Co on the image
         W, b = rnd(Co, C, 8, seed=34, scale=0.2), rnd(Co, seed=35)
