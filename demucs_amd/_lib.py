@@ -105,6 +105,13 @@ SIGNATURES = {
     "mi_mono_stats_state_bytes": (C.c_int32, []),
     "mi_mono_stats_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "mi_mono_stats_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_sdr_state_bytes": (C.c_int64, [C.c_int32]),
+    "mi_sdr_scratch_bytes": (C.c_int64, [C.c_int32]),
+    "mi_sdr_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                C.c_int64, C.c_void_p, C.c_void_p]),
+    "mi_sdr_finish": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_sdr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.c_void_p]),
     "mi_track_affine": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "mi_prevent_clip": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_two_stems": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -22,11 +22,11 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib
-from .audio import ConvertingStatsStream, MonoStatsStream, TrackStats, convert_audio
+from .audio import ConvertingStatsStream, MonoStatsStream, TrackScore, TrackStats, convert_audio
 from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
 from .stream import Delivery, ModelStream, StreamGroup
 
-__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "LoadModelError", "list_models"]
+__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "TrackScore", "LoadModelError", "list_models"]
 
 
 class LoadModelError(Exception):
@@ -247,6 +247,90 @@ class Separator:
             yield st.push(block)
         yield st.finish()
 
+    def _check_scoring(self, what: str) -> None:
+        """The refusals of the scoring entries (no device work, no RNG call): the score kernels have no CPU implementation."""
+        if not _is_engine(self._model) or torch.device(self._device).type != "cuda":
+            raise ValueError(f"{what} runs on the GPU engines (HTDemucs / HDemucs on a cuda device); score host stems with "
+                             "audio.new_sdr instead")
+        if not 1 <= len(self._model.sources) <= 8:
+            raise ValueError(f"{what}: 1 to 8 sources, the model has {len(self._model.sources)}")
+
+    def evaluate_blocks(self, source, references, sr: Optional[int] = None, channels: Optional[int] = None,
+                        pcm: Optional[str] = None, ref_pcm: Optional[str] = None) -> TrackScore:
+        """`separate_blocks` with the stems scored instead of returned: the `new_sdr` score (demucs/evaluate.py:30-43, what
+        `eval_track(..., compute_sdr=False)` computes) of a track that never exists whole on the host or the device, against
+        reference stems that arrive block by block.  `source` is `separate_blocks`' argument; `references()` returns an iterator
+        over blocks of the reference stems for the same track, at the model's sample rate and channel count: (sources, channels,
+        n) floating tensors in the model's source order, or with `ref_pcm=` lists of one interleaved PCM chunk per source
+        (`audio.SdrStream`).  Their block sizes need not match the mix's.  Every span pass 2 emits and every reference block goes
+        into an `audio.SdrStream`; references are read only as far as the stems have come, so the surplus the stream holds stays
+        below a block of either kind.  Returns the `audio.TrackScore`, with the bits of
+        `audio.new_sdr(refs[None], stems[None])[0]` for `stems` = `separate_tensor(wav, sr)`'s stacked in source order, and
+        `random` left as `separate_blocks` leaves it.
+
+        Host mix blocks are uploaded here (PCM bytes as they are, an incomplete frame carried to the next block), so the stream
+        emits device stems, the kernel reads them where they lie and no float stem visits the host.
+
+        Normalisation: the reference's `evaluate` normalises the mix by `ref.std()`, a `Separator` by `ref.std() + 1e-8`; this
+        method is the `Separator`'s chain (`separate_tensor`'s stems), so on a silent track the two differ."""
+        from .audio import PcmFeed, SdrStream
+        self._check_scoring("evaluate_blocks")
+        if ref_pcm is not None:
+            from .audio import check_pcm
+            check_pcm(ref_pcm)
+        self._check_stream_input(sr, channels, True, pcm)
+        self._convert_plan(sr, channels)
+        device = self._device_index()
+        src_channels = channels or self._audio_channels
+
+        def on_device():
+            feed = PcmFeed(pcm, src_channels) if pcm is not None else None
+            for block in source():
+                if feed is not None:
+                    blk = feed.accept(block)
+                    feed.commit(blk)
+                    with torch.cuda.device(device):
+                        yield blk.on_device(device, [])[:blk.nbytes]
+                elif isinstance(block, torch.Tensor):
+                    yield block.to(device)
+                else:
+                    yield block                            # refused by the stream, with its message
+
+        score = SdrStream(len(self._model.sources), self._audio_channels, device=device, pcm=ref_pcm,
+                          src_channels=None if ref_pcm is None else self._audio_channels)
+        refs = iter(references())
+        for out in self.separate_blocks(on_device, sr=sr, channels=channels, pcm=pcm):
+            score.push_estimates(_stacked(list(out.values())))
+            while score.references_pushed < score.estimates_pushed:
+                block = next(refs, None)
+                if block is None:
+                    break
+                score.push_references(block)
+        for block in refs:
+            score.push_references(block)
+        return score.finish()
+
+    def score_tensor(self, wav: torch.Tensor, references: torch.Tensor, sr: Optional[int] = None):
+        """The whole-track counterpart of `evaluate_blocks`: `separate_tensor(wav, sr)` followed by `audio.new_sdr` against
+        `references` (sources, channels, length) on the device.  A host `wav` is uploaded first, so the stems are scored where the
+        engine leaves them and cross to the host once, as `separate_tensor` returns them.  Returns `(TrackScore, stems)`."""
+        from .audio import sdr_sums
+        self._check_scoring("score_tensor")
+        if references.dim() != 3 or tuple(references.shape[:2]) != (len(self._model.sources), self._audio_channels):
+            raise ValueError(f"score_tensor: references must be ({len(self._model.sources)}, {self._audio_channels}, length), got "
+                             f"{tuple(references.shape)}")
+        device = self._device_index()
+        host_in = wav.device.type == "cpu"
+        with torch.cuda.device(device):
+            _, stems = self.separate_tensor(wav.to(device) if host_in else wav, sr)
+            est = _stacked(list(stems.values()))
+            if references.dim() != 3 or references.shape != est.shape:
+                raise ValueError(f"score_tensor: references {tuple(references.shape)} are not the stems' {tuple(est.shape)}")
+            score = TrackScore.from_sums(sdr_sums(references[None], est[None])[0], est.shape[-1])
+            if host_in:
+                stems = dict(zip(stems, _to_host(est[None], device)[0]))
+        return score, stems
+
     def _convert_plan(self, sr: Optional[int], channels: Optional[int]):
         """The refusals of a converting stream (before any device work or RNG call) and its `audio.ConvertPlan`; None when the
         input is already what the model takes."""
@@ -346,6 +430,18 @@ class Separator:
 def _named(sources, out) -> Dict[str, torch.Tensor]:
     """A stream's stems by source name; a delivering stream's result already is `{name: frames}`."""
     return out if isinstance(out, dict) else dict(zip(sources, out))
+
+
+def _stacked(stems) -> torch.Tensor:
+    """The per-source (channels, n) stems as one (sources, channels, n) tensor: the block they were cut from, without a copy, when
+    they still lie one behind the other in it (what a stream and `separate_tensor` return), else their stack."""
+    first = stems[0]
+    if first.numel() and first.is_contiguous() and all(
+            t.shape == first.shape and t.dtype == first.dtype and t.device == first.device and t.is_contiguous()
+            and t.untyped_storage().data_ptr() == first.untyped_storage().data_ptr()
+            and t.data_ptr() == first.data_ptr() + i * first.numel() * first.element_size() for i, t in enumerate(stems)):
+        return first.as_strided((len(stems), *first.shape), (first.numel(), *first.stride()))
+    return torch.stack(list(stems))
 
 
 class SeparatorStream:

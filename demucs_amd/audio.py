@@ -1000,3 +1000,296 @@ def wav_header(frames, samplerate: int, channels: int, fmt: str = "i16") -> byte
     return (b"RIFF" + struct.pack("<I", riff) + b"WAVEfmt " +
             struct.pack("<IHHIIHHH", 18, 3, channels, samplerate, samplerate * align, align, 32, 0) +
             b"fact" + struct.pack("<II", 4, count) + b"data" + struct.pack("<I", data))
+
+
+# ---- evaluation: the nSDR of stems against reference stems (demucs/evaluate.py:30-43; demucs_amd/csrc/score.hip) -----------------
+SDR_SLOTS = 131072                 # demucs_amd/csrc/sdr_sums.h: kSdrSlots, position p of a track belongs to slot p % SDR_SLOTS
+SDR_MAX_SOURCES = 8
+SDR_DELTA = 1e-7                   # evaluate.py:37
+
+
+def _check_n_sources(n_sources, what: str) -> int:
+    if isinstance(n_sources, bool) or int(n_sources) != n_sources or not 1 <= n_sources <= SDR_MAX_SOURCES:
+        raise ValueError(f"{what}: 1 to {SDR_MAX_SOURCES} sources, got {n_sources!r}")
+    return int(n_sources)
+
+
+def _sdr_scores(sums: torch.Tensor) -> torch.Tensor:
+    """evaluate.py:40-42 in float64 on the host: (..., 2) raw (num, den) -> 10 log10((num + 1e-7) / (den + 1e-7))."""
+    sums = sums.to(device="cpu", dtype=torch.float64)
+    return 10 * torch.log10((sums[..., 0] + SDR_DELTA) / (sums[..., 1] + SDR_DELTA))
+
+
+def sdr_sums(references: torch.Tensor, estimates: torch.Tensor) -> torch.Tensor:
+    """The raw float64 (B, S, 2) sums (num, den) of `new_sdr` as `mi_sdr` leaves them, on the engine device."""
+    if references.dim() != 4 or estimates.dim() != 4:
+        raise ValueError("new_sdr: (batch, sources, channels, length) tensors are expected")
+    if references.shape != estimates.shape:
+        raise ValueError(f"new_sdr: references {tuple(references.shape)} and estimates {tuple(estimates.shape)} differ in shape")
+    B, S, ch, L = references.shape
+    _check_n_sources(S, "new_sdr")
+    if ch < 1:
+        raise ValueError("new_sdr: at least one channel")
+    dev = _engine_device(references, estimates)
+    ref, est = _stage(references, dev, "new_sdr"), _stage(estimates, dev, "new_sdr")
+    sums = torch.zeros(B, S, 2, dtype=torch.float64, device=dev)
+    if B:
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            state = torch.empty(lib.mi_sdr_state_bytes(S), dtype=torch.uint8, device=dev)
+            scratch = torch.empty(lib.mi_sdr_scratch_bytes(S), dtype=torch.uint8, device=dev)
+            _lib.check(lib.mi_sdr(ref.data_ptr(), est.data_ptr(), B, S, ch, L, state.data_ptr(), scratch.data_ptr(), sums.data_ptr(),
+                                  C.c_void_p(_lib.current_stream_ptr())), "mi_sdr")
+    return sums
+
+
+def new_sdr(references: torch.Tensor, estimates: torch.Tensor) -> torch.Tensor:
+    """demucs/evaluate.py:30-43, the SDR of the MDX challenge definition: two (batch, sources, channels, length) floating
+    tensors -> float64 (batch, sources) scores `10 log10((sum ref^2 + 1e-7) / (sum (ref - est)^2 + 1e-7))`.  The two sums are
+    float64 reductions of the float32 samples on the engine device (`mi_sdr`, in the fixed order of demucs_amd/csrc/sdr_sums.h: the
+    same bits as an `SdrStream` fed the tracks in pieces); the logarithm is taken on the 2 x sources returned doubles on the host.
+    Host tensors are staged H2D as `prevent_clip` stages them, other floating dtypes are scored as float32; the result comes back on
+    the references' device.  NaN and Inf samples reach the score as in the reference; length 0 gives 0."""
+    return _sdr_scores(sdr_sums(references, estimates)).to(references.device)
+
+
+class TrackScore:
+    """The `new_sdr` score of one track: per source `nsdr` (dB), and the raw sums `num` = sum ref^2 and `den` = sum (ref - est)^2 it
+    comes from (before the 1e-7), as read-only float64 arrays, with the `length` scored in samples per channel.  Immutable; equal
+    when every bit is (every NaN counting as one value)."""
+    __slots__ = ("nsdr", "num", "den", "length")
+
+    def __init__(self, nsdr, num, den, length):
+        import numpy as np
+        arrays = []
+        for name, v in (("nsdr", nsdr), ("num", num), ("den", den)):
+            a = np.array(v, dtype=np.float64)
+            if a.ndim != 1 or not 1 <= a.size <= SDR_MAX_SOURCES:
+                raise ValueError(f"TrackScore: {name} must hold one value per source (1 to {SDR_MAX_SOURCES}), got shape {a.shape}")
+            a.setflags(write=False)
+            arrays.append(a)
+        if len({a.size for a in arrays}) != 1:
+            raise ValueError("TrackScore: nsdr, num and den must have one length")
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
+            raise ValueError(f"TrackScore: length must be a non-negative integer, got {length!r}")
+        for name, v in zip(self.__slots__, arrays + [int(length)]):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("TrackScore is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("TrackScore is immutable")
+
+    def _key(self):
+        return (*(tuple("nan" if math.isnan(v) else float(v).hex() for v in a) for a in (self.nsdr, self.num, self.den)), self.length)
+
+    def __eq__(self, other):
+        return isinstance(other, TrackScore) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return (f"TrackScore(nsdr={self.nsdr.tolist()!r}, num={self.num.tolist()!r}, den={self.den.tolist()!r}, "
+                f"length={self.length})")
+
+    @classmethod
+    def from_sums(cls, sums: torch.Tensor, length: int) -> "TrackScore":
+        """From the (sources, 2) raw sums of `mi_sdr` / `mi_sdr_finish`."""
+        sums = sums.to(device="cpu", dtype=torch.float64)
+        return cls(_sdr_scores(sums).numpy(), sums[:, 0].numpy(), sums[:, 1].numpy(), length)
+
+
+class SdrStream:
+    """`new_sdr` for a track whose references and estimates arrive block by block, each at its own pace: `push_references(block)`
+    and `push_estimates(block)` are independent, and the stream scores the positions both sides have reached
+    (`mi_sdr_update`, demucs_amd/csrc/score.hip).  `finish()` returns the `TrackScore`, whose bits depend on the two tracks alone:
+    not on the block sizes, nor on the interleaving of the two kinds of push, and they are those of `new_sdr` on the whole tracks.
+
+    A block is (n_sources, channels, n) floating, on the host (one H2D) or a device; a device block is read where it lies (a slice
+    of a longer tensor keeps its stride) and is held, not copied, until its last sample is scored, so the caller must not write
+    to it before then.  With `pcm=` and `src_channels=` a references block is instead a list of `n_sources` chunks of interleaved
+    wire PCM (`PCM_FORMATS`), one per source as MusDB keeps its stems in separate files, each as `ConvertStream` takes them: a
+    chunk may end inside a frame (one `PcmFeed` per source carries the rest), but the chunks of one push must complete the same
+    number of frames.  The kernel decodes them where they lie under `mi_pcm_planar`'s rules.
+
+    Device memory: the state (`mi_sdr_state_bytes`: 2 MiB per source) plus the surplus of whichever side is ahead -- references
+    normally lead the estimates by a stream's `latency` -- which is as large as the caller lets the two drift; `device_bytes()`
+    reports both.  A partly scored block stays allocated until it is used up.  `scores()` reads the state at any time."""
+
+    def __init__(self, n_sources: int, channels: int, device="cuda", pcm=None, src_channels=None):
+        self.n_sources = _check_n_sources(n_sources, "SdrStream")
+        self.channels = int(channels)
+        if self.channels < 1:
+            raise ValueError(f"channels must be >= 1, got {channels}")
+        self.feeds = None
+        if pcm is not None:
+            if src_channels is None:
+                raise ValueError("a PCM stream needs src_channels=: the frames do not say how many channels they hold")
+            self.feeds = [PcmFeed(pcm, src_channels) for _ in range(self.n_sources)]
+            check_stream_channels(self.feeds[0].src_channels, self.channels)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.EngineError("demucs_amd.audio.SdrStream only runs on a GPU device (MI355X)")
+        self.device = dev
+        self.references_pushed = self.estimates_pushed = self.scored = 0
+        self.finished = False
+        self._state = None
+        self._refs, self._ests = [], []           # blocks not yet used up: [rows or per-source chunks, row stride, n, frames used]
+
+    # ---- bookkeeping ------------------------------------------------------------------------------------------------------------
+    def _frame_bytes(self, pcm: bool) -> int:
+        if pcm:
+            return self.n_sources * self.feeds[0].frame_bytes
+        return self.n_sources * self.channels * 4
+
+    def device_bytes(self) -> int:
+        """The state plus the samples pushed and not yet scored."""
+        held = sum((n - used) * self._frame_bytes(isinstance(rows, list)) for rows, _, n, used in self._refs + self._ests)
+        return held + (0 if self._state is None else self._state.numel())
+
+    @property
+    def trailing_bytes(self) -> int:
+        """Bytes of an incomplete last frame of the PCM references, per source: carried to the next push, dropped by `finish()`."""
+        return 0 if self.feeds is None else self.feeds[0].trailing_bytes
+
+    def _on(self):
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        return torch.cuda.device(self.device)
+
+    def _rows(self, block, what: str):
+        S, ch = self.n_sources, self.channels
+        if not isinstance(block, torch.Tensor) or block.dim() != 3 or tuple(block.shape[:2]) != (S, ch):
+            shape = tuple(block.shape) if isinstance(block, torch.Tensor) else type(block).__name__
+            raise ValueError(f"{what}: expected a ({S}, {ch}, n) block, got {shape}")
+        if not block.dtype.is_floating_point:
+            raise TypeError(f"{what}: a floating-point tensor is expected, got {block.dtype}")
+        n = block.shape[2]
+        if n == 0:
+            return None
+        with self._on():
+            t = block.to(device=self.device, dtype=torch.float32)
+            stride = t.stride(1) if ch > 1 else t.stride(0) if S > 1 else n
+            if not ((n == 1 or t.stride(2) == 1) and stride >= n and (ch == 1 or S == 1 or t.stride(0) == ch * stride)):
+                t, stride = t.contiguous(), n
+        return [t, stride, n, 0]
+
+    def _drain(self) -> None:
+        """Scores what both sides hold: one `mi_sdr_update` per overlap of a references block with an estimates block."""
+        lib = _lib.load()
+        while self._refs and self._ests:
+            r, e = self._refs[0], self._ests[0]
+            n = min(r[2] - r[3], e[2] - e[3])
+            with self._on():
+                if self._state is None:
+                    self._state = torch.zeros(lib.mi_sdr_state_bytes(self.n_sources), dtype=torch.uint8, device=self.device)
+                if isinstance(r[0], list):
+                    feed = self.feeds[0]
+                    ptrs = (C.c_void_p * self.n_sources)(*[t.data_ptr() + r[3] * feed.frame_bytes for t in r[0]])
+                    code, src_ch = PCM_FORMATS[feed.fmt][0], feed.src_channels
+                else:
+                    ptrs = (C.c_void_p * 1)(r[0].data_ptr() + 4 * r[3])
+                    code, src_ch = PCM_PLANAR, self.channels
+                _lib.check(lib.mi_sdr_update(ptrs, code, src_ch, r[1], e[0].data_ptr() + 4 * e[3], e[1], self.n_sources, self.channels, n,
+                                             self.scored, self._state.data_ptr(), C.c_void_p(_lib.current_stream_ptr())),
+                           "mi_sdr_update")
+            self.scored += n
+            for queue in (self._refs, self._ests):
+                queue[0][3] += n
+                if queue[0][3] == queue[0][2]:
+                    queue.pop(0)
+
+    # ---- public -----------------------------------------------------------------------------------------------------------------
+    def push_references(self, block) -> None:
+        if self.finished:
+            raise RuntimeError("push after finish()")
+        if self.feeds is None:
+            seg = self._rows(block, "push_references")
+        else:
+            if not isinstance(block, (list, tuple)) or len(block) != self.n_sources:
+                got = len(block) if isinstance(block, (list, tuple)) else type(block).__name__
+                raise ValueError(f"push_references: expected a list of {self.n_sources} PCM chunks, one per source, got {got}")
+            blks = [feed.accept(chunk) for feed, chunk in zip(self.feeds, block)]
+            if len({b.n for b in blks}) != 1:
+                raise ValueError(f"push_references: the chunks of one push must complete the same number of frames, got "
+                                 f"{[b.n for b in blks]}")
+            for feed, b in zip(self.feeds, blks):
+                feed.commit(b)
+            seg = None
+            if blks[0].n:
+                keep = []
+                with self._on():
+                    seg = [[b.on_device(self.device, keep) for b in blks], 0, blks[0].n, 0]
+        if seg is not None:
+            self.references_pushed += seg[2]
+            self._refs.append(seg)
+            self._drain()
+
+    def push_estimates(self, block) -> None:
+        if self.finished:
+            raise RuntimeError("push after finish()")
+        seg = self._rows(block, "push_estimates")
+        if seg is not None:
+            self.estimates_pushed += seg[2]
+            self._ests.append(seg)
+            self._drain()
+
+    def scores(self) -> TrackScore:
+        """The `TrackScore` of the `scored` positions both sides have reached so far; the state is only read."""
+        lib = _lib.load()
+        with self._on():
+            sums = torch.zeros(self.n_sources, 2, dtype=torch.float64, device=self.device)
+            if self._state is not None:
+                scratch = torch.empty(lib.mi_sdr_scratch_bytes(self.n_sources), dtype=torch.uint8, device=self.device)
+                _lib.check(lib.mi_sdr_finish(self._state.data_ptr(), self.n_sources, scratch.data_ptr(), sums.data_ptr(),
+                                             C.c_void_p(_lib.current_stream_ptr())), "mi_sdr_finish")
+            return TrackScore.from_sums(sums, self.scored)
+
+    def finish(self) -> TrackScore:
+        if self.finished:
+            raise RuntimeError("finish() called twice")
+        if self.references_pushed != self.estimates_pushed:
+            raise ValueError(f"the references ended after {self.references_pushed} samples and the estimates after "
+                             f"{self.estimates_pushed}: a score needs both tracks whole")
+        if self.scored == 0:
+            raise ValueError("the stream ended before any sample was pushed")
+        self.finished = True
+        return self.scores()
+
+
+def summarise_scores(tracks, sources) -> dict:
+    """The aggregation of demucs/evaluate.py:157-173 for the `nsdr` metric, on the host.  `tracks` maps a track's name to its
+    scores: a `TrackScore` whose entries follow `sources`, or a `{source: score}` mapping whose scores are numbers or one-source
+    `TrackScore`s (an `SdrStream` per source).  Per source the per-track values -- `nanmedian` of a track's one value is that
+    value -- give `nsdr_<source>` (their mean) and `nsdr_med_<source>` (their median); `nsdr` and `nsdr_med` average those over
+    the sources.  A NaN score makes the figures it enters NaN, as numpy's mean and median do in the reference."""
+    import numpy as np
+    sources = list(sources)
+    if not tracks or not sources:
+        raise ValueError("summarise_scores: at least one track and one source")
+
+    def value(entry, source, idx):
+        if isinstance(entry, TrackScore):
+            if len(entry.nsdr) != len(sources):
+                raise ValueError(f"summarise_scores: a TrackScore of {len(entry.nsdr)} sources for {len(sources)} names")
+            return float(entry.nsdr[idx])
+        v = entry[source]
+        if isinstance(v, TrackScore):
+            if len(v.nsdr) != 1:
+                raise ValueError(f"summarise_scores: the score of {source!r} must be one source's, got {len(v.nsdr)}")
+            return float(v.nsdr[0])
+        return float(v)
+
+    result, avg, avg_of_medians = {}, 0.0, 0.0
+    for idx, source in enumerate(sources):
+        medians = np.array([value(tracks[name], source, idx) for name in tracks], dtype=np.float64)
+        mean, median = float(np.mean(medians)), float(np.median(medians))
+        result["nsdr_" + source] = mean
+        result["nsdr_med_" + source] = median
+        avg += mean / len(sources)
+        avg_of_medians += median / len(sources)
+    result["nsdr"] = avg
+    result["nsdr_med"] = avg_of_medians
+    return result

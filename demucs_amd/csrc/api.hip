@@ -492,6 +492,52 @@ int mi_mono_stats_finish(const void *state_dev, int64_t length, void *scratch_de
     return launch_mono_stats_finish((const double *)state_dev, length, (double *)scratch_dev, stats_dev, (hipStream_t)stream);
 }
 
+int64_t mi_sdr_state_bytes(int32_t n_sources) { return n_sources >= 1 && n_sources <= 8 ? sdr_state_bytes(n_sources) : 0; }
+int64_t mi_sdr_scratch_bytes(int32_t n_sources) { return n_sources >= 1 && n_sources <= 8 ? sdr_scratch_bytes(n_sources) : 0; }
+
+int mi_sdr_update(const void *const *refs, int32_t fmt, int32_t src_ch, int64_t ref_stride, const float *est_dev, int64_t est_stride,
+                  int32_t n_sources, int32_t channels, int64_t n, int64_t before, void *state_dev, void *stream) {
+    MI_REQUIRE(fmt == MI_PCM_PLANAR || fmt == MI_PCM_I16 || fmt == MI_PCM_I24 || fmt == MI_PCM_F32, "mi_sdr_update: unknown format %d", fmt);
+    MI_REQUIRE(n_sources >= 1 && n_sources <= 8, "mi_sdr_update: %d sources (1 to 8)", n_sources);
+    const bool planar = fmt == MI_PCM_PLANAR;
+    const int64_t rows = (int64_t)n_sources * channels, most = INT64_MAX / 4 / std::max<int64_t>(rows, 1);
+    MI_REQUIRE(channels >= 1 && channels <= 65535 && n >= 0 && before >= 0 && before <= INT64_MAX - n && est_stride >= n && est_stride <= most,
+               "mi_sdr_update: bad argument");
+    MI_REQUIRE(planar ? (ref_stride >= n && ref_stride <= most)
+                      : (src_ch >= 1 && (src_ch == 1 || src_ch >= channels) && n <= INT64_MAX / 4 / src_ch),
+               "mi_sdr_update: bad argument");
+    MI_REQUIRE(state_dev && (uintptr_t)state_dev % 8 == 0, "mi_sdr_update: the state is null or not aligned to its doubles");
+    if (n == 0) return MI_OK;
+    MI_REQUIRE(refs && est_dev && (uintptr_t)est_dev % 4 == 0, "mi_sdr_update: bad argument");
+    const int width = fmt == MI_PCM_I16 ? 2 : fmt == MI_PCM_I24 ? 3 : 4;
+    for (int s = 0; s < (planar ? 1 : n_sources); ++s) {
+        MI_REQUIRE(refs[s], "mi_sdr_update: null reference %d", s);
+        MI_REQUIRE(width == 3 || (uintptr_t)refs[s] % width == 0, "mi_sdr_update: reference %d is not aligned to its %d-byte samples", s,
+                   width);
+    }
+    return launch_sdr_update(refs, fmt, src_ch, ref_stride, est_dev, est_stride, n_sources, channels, n, before, (double *)state_dev,
+                             (hipStream_t)stream);
+}
+
+int mi_sdr_finish(const void *state_dev, int32_t n_sources, void *scratch_dev, double *sums_dev, void *stream) {
+    MI_REQUIRE(n_sources >= 1 && n_sources <= 8, "mi_sdr_finish: %d sources (1 to 8)", n_sources);
+    MI_REQUIRE(state_dev && (uintptr_t)state_dev % 8 == 0 && scratch_dev && (uintptr_t)scratch_dev % 8 == 0 && sums_dev &&
+                   (uintptr_t)sums_dev % 8 == 0, "mi_sdr_finish: bad argument");
+    return launch_sdr_finish((const double *)state_dev, n_sources, (double *)scratch_dev, sums_dev, (hipStream_t)stream);
+}
+
+int mi_sdr(const float *ref_dev, const float *est_dev, int32_t B, int32_t n_sources, int32_t channels, int64_t length, void *state_dev,
+           void *scratch_dev, double *sums_dev, void *stream) {
+    MI_REQUIRE(n_sources >= 1 && n_sources <= 8, "mi_sdr: %d sources (1 to 8)", n_sources);
+    MI_REQUIRE(B >= 1 && channels >= 1 && channels <= 65535 && length >= 0 && length <= INT64_MAX / 4 / ((int64_t)n_sources * channels) / B,
+               "mi_sdr: bad argument");
+    MI_REQUIRE(state_dev && (uintptr_t)state_dev % 8 == 0 && scratch_dev && (uintptr_t)scratch_dev % 8 == 0 && sums_dev &&
+                   (uintptr_t)sums_dev % 8 == 0, "mi_sdr: bad argument");
+    MI_REQUIRE(length == 0 || (ref_dev && est_dev && (uintptr_t)ref_dev % 4 == 0 && (uintptr_t)est_dev % 4 == 0), "mi_sdr: bad argument");
+    return launch_sdr(ref_dev, est_dev, B, n_sources, channels, length, (double *)state_dev, (double *)scratch_dev, sums_dev,
+                      (hipStream_t)stream);
+}
+
 int mi_track_affine(float *x_dev, int64_t numel, const float *stats_dev, int32_t inverse, void *stream) {
     MI_REQUIRE(x_dev && stats_dev && numel >= 1 && (inverse == 0 || inverse == 1), "mi_track_affine: bad argument");
     return launch_track_affine(x_dev, numel, stats_dev, inverse, (hipStream_t)stream);

@@ -260,6 +260,15 @@ int launch_mono_stats_update(const unsigned char *src, int fmt, int src_ch, int6
                              hipStream_t st);
 int launch_mono_stats_finish(const double *state, int64_t length, double *scratch, float *stats, hipStream_t st);
 
+// score.hip: the nSDR sums of stems against reference stems, whole or block by block (sdr_sums.h)
+int64_t sdr_state_bytes(int n_sources);
+int64_t sdr_scratch_bytes(int n_sources);
+int launch_sdr_update(const void *const *refs, int fmt, int src_ch, int64_t ref_stride, const float *est, int64_t est_stride, int n_sources,
+                      int channels, int64_t n, int64_t before, double *state, hipStream_t st);
+int launch_sdr_finish(const double *state, int n_sources, double *scratch, double *sums, hipStream_t st);
+int launch_sdr(const float *ref, const float *est, int B, int n_sources, int channels, int64_t length, double *state, double *scratch,
+               double *sums, hipStream_t st);
+
 const void *conv_zero_page();      // gemm_conv.hip: 256 bytes of device zeros
 // attention_heads.hip: half modes, per-head token-major 16-bit operands (MI_FLAG_HEADS), LDS-DMA ring
 int launch_attention_heads(const void *q, const void *k, const void *v, const void *zero_page, int B, int heads, int Tq, int Tk, int Tq_pitch,

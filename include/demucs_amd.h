@@ -447,6 +447,35 @@ int mi_mono_stats_update(const void *src_dev, int32_t fmt, int32_t src_ch, int64
                          void *stream);
 int mi_mono_stats_finish(const void *state_dev, int64_t length, void *scratch_dev, float *stats_dev, void *stream);
 
+/* ---- evaluation: the nSDR of separated stems against reference stems (demucs/evaluate.py:30-43, `new_sdr`) --------------------
+ * For source s over channels c and positions p, r = (double)ref[s, c, p], e = (double)est[s, c, p]:
+ *   num[s] = sum r * r,  den[s] = sum (r - e) * (r - e),  both in float64; the host takes 10 * log10((num + 1e-7) / (den + 1e-7)).
+ * Position p of a track belongs to slot p % 131072 (a constant of the build); a slot adds its positions in ascending order and
+ * the channels of a position in ascending order, and a fixed tree reduces the slots, so the sums have the same bits for the whole
+ * track in one call and for every partition of it into blocks (demucs_amd/csrc/sdr_sums.h).  NaN and Inf samples reach the sums.
+ * state_dev: mi_sdr_state_bytes(n_sources) = n_sources x 2 x 131072 x 8 bytes (2 MiB per source), 8-byte aligned, all-zero bytes at
+ *   the start of a track; scratch_dev: mi_sdr_scratch_bytes(n_sources) bytes, 8-byte aligned.  1 <= n_sources <= 8; the byte
+ *   counts are 0 outside that range.
+ * mi_sdr_update: adds track positions [before, before + n) to the state.  Estimates: planar float32 rows, (source s, channel c)
+ *   at est_dev + (s * channels + c) * est_stride, est_stride >= n -- the span a stream has just emitted, or a slice of a longer
+ *   (S, C, N) tensor, is read where it lies.  References: refs is a HOST array of device pointers.  fmt MI_PCM_PLANAR: refs[0] is
+ *   float32 rows in the same form with ref_stride >= n (src_ch is ignored); MI_PCM_I16 / _I24 / _F32: refs[s] is source s's
+ *   block of n interleaved frames of src_ch channels (ref_stride is ignored) under mi_pcm_planar's rules: alignment to the sample
+ *   width, a mono source feeds every channel and else src_ch >= channels, no byte outside a block is read.  The caller passes
+ *   `before` as the sum of the earlier blocks' n; n = 0 does nothing.  Nothing outside the state is written.
+ * mi_sdr_finish: sums_dev[n_sources][2] doubles, the raw (num, den) of the positions added so far.  The state is only read: a
+ *   second call gives the same bits, and more blocks may follow.
+ * mi_sdr: B independent tracks, ref_dev and est_dev contiguous (B, n_sources, channels, length) float32, sums_dev
+ *   [B][n_sources][2]: per track a memset of state_dev, one mi_sdr_update and mi_sdr_finish -- the same device code.  length = 0
+ *   gives zeros. */
+int64_t mi_sdr_state_bytes(int32_t n_sources);
+int64_t mi_sdr_scratch_bytes(int32_t n_sources);
+int mi_sdr_update(const void *const *refs, int32_t fmt, int32_t src_ch, int64_t ref_stride, const float *est_dev, int64_t est_stride,
+                  int32_t n_sources, int32_t channels, int64_t n, int64_t before, void *state_dev, void *stream);
+int mi_sdr_finish(const void *state_dev, int32_t n_sources, void *scratch_dev, double *sums_dev, void *stream);
+int mi_sdr(const float *ref_dev, const float *est_dev, int32_t B, int32_t n_sources, int32_t channels, int64_t length, void *state_dev,
+           void *scratch_dev, double *sums_dev, void *stream);
+
 /* mi_prevent_clip: `demucs.audio.prevent_clip(wav, mode)` (demucs/audio.py:218-234) on device stems: y = x / max(1.01 * max|x|, 1)
  *   ("rescale"; the peak is reduced on the device into peak_dev, 4 bytes), clamp(x, -0.99, 0.99) or tanh(x).
  * mi_two_stems: the `--two-stems` outputs of demucs/separate.py:189-218: minus = 0: y = 0 + (every stem but `selected`, in
