@@ -49,6 +49,7 @@ class MiConvDesc(C.Structure):
         ("wtap", C.c_void_p), ("ntaps", C.c_int32), ("tap_k2", C.c_int32), ("tap_pad1", C.c_int32), ("tap_pad2", C.c_int32),
         ("tap_dil1", C.c_int32), ("tap_dil2", C.c_int32), ("yh_pq", C.c_int64),
         ("dma_rows", C.c_int32), ("dma_rows_pad", C.c_int32),
+        ("dma_time", C.c_int32), ("dma_time_pad", C.c_int32),
     ]
 
 
@@ -172,6 +173,7 @@ SIGNATURES = {
     "mi_debug_set_post_launch_hook": (None, [C.c_void_p]),
     "mi_debug_last_conv_route": (C.c_int, []),
     "mi_debug_last_conv_tile": (C.c_int, []),
+    "mi_debug_conv_route_launches": (C.c_int64, [C.c_int32, C.c_int32]),
     "mi_debug_conv_route": (C.c_int, [C.POINTER(MiConvDesc), C.POINTER(C.c_int)]),
     "mi_debug_switches": (C.c_int, [C.c_char_p, C.c_int32]),
     "mi_last_error": (C.c_char_p, []),

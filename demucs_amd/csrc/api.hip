@@ -8,6 +8,7 @@ namespace mi {
 
 post_launch_hook_t g_post_launch_hook = nullptr;
 int g_last_conv_route = -1;
+long long g_conv_route_launches[16][8] = {};
 int g_last_conv_tile = -1;
 
 char *last_error_buf() {
@@ -140,6 +141,13 @@ const char *mi_last_error(void) { return last_error_buf(); }
 void mi_debug_set_post_launch_hook(void (*hook)(void *stream)) { g_post_launch_hook = hook; }
 int mi_debug_last_conv_route(void) { return g_last_conv_route; }
 int mi_debug_last_conv_tile(void) { return g_last_conv_tile; }
+int64_t mi_debug_conv_route_launches(int32_t route, int32_t epi) {
+    if (route < 0 || route >= 16 || epi >= 8) return -1;
+    int64_t n = 0;
+    for (int e = 0; e < 8; ++e)
+        if (epi < 0 || e == epi) n += mi::g_conv_route_launches[route][e];
+    return n;
+}
 int mi_debug_conv_route(const struct mi_conv_desc *desc, int *tile) {
     if (!desc) return -1;
     if (conv_check_tile_m(*desc) != MI_OK) return -1;

@@ -30,6 +30,7 @@ typedef void (*post_launch_hook_t)(void *stream);
 extern post_launch_hook_t g_post_launch_hook;
 extern int g_last_conv_route;          // mi_debug_last_conv_route (include/demucs_amd.h)
 extern int g_last_conv_tile;           // mi_debug_last_conv_tile
+extern long long g_conv_route_launches[16][8];   // mi_debug_conv_route_launches: launches per (mi_conv_route, mi_epilogue) of this process
 
 #define MI_CHECK_LAUNCH()                                                   \
     do {                                                                    \

@@ -59,6 +59,23 @@ static bool dmarow_eligible(const mi_conv_desc &d, int tile, bool plain, bool ha
            (d.epi == MI_EPI_CONVTR || tile != 64 || d.epi == MI_EPI_LINEAR);
 }
 
+// float32 1-D layer along the TIME axis with a split weight image (the caller vouches for the table and the layout: `dma_time`;
+// one row per channel, D1 = O1 = 1).  Its runs go global -> LDS by DMA in front of the split-bf16 main loop (gemm_x6.hip):
+//   * a transposed conv as a two-tap GEMM (conv_time_tr_x6_kernel): K ordered (ci, j) with tap j at column q - j, columns q = 0 .. D2
+//     on a pitch O2 % 4 == 0 with o2_valid = D2 + 1, so that a lane's 16-byte chunk never straddles two items;
+//   * a strided conv k = 8, s = 4, pad 2, + GELU (conv_time_enc_x6_kernel): K ordered (ci, t), column o reads samples 4 o - 2 + t.
+// MI_X6=0 / mi_set_split_bf16(0) leave the layer on the table-driven gather
+static bool dmatime_eligible(const mi_conv_desc &d, int tile, bool plain, bool has_image) {
+    const int ld = d.x_ld ? d.x_ld : d.D2, o2v = d.o2_valid ? d.o2_valid : d.O2;
+    const int lf = d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS | MI_FLAG_IMG | MI_FLAG_IMG4 | MI_FLAG_HEADS);
+    const bool tr = d.epi == MI_EPI_CONVTR && !(d.flags & (MI_FLAG_TR_FREQ | MI_FLAG_IMG)) && d.K % 2 == 0 && d.S2 == 1 && d.O2 % 4 == 0 &&
+                    d.o2_valid == d.D2 + 1 && d.o2_valid <= d.O2 && d.x_bstride == (int64_t)(d.K / 2) * ld;
+    const bool enc = d.epi == MI_EPI_LINEAR && lf == MI_FLAG_GELU && d.K % 8 == 0 && d.S2 == 4 && 4 * (int64_t)o2v <= (int64_t)d.D2 + 3 &&
+                     d.x_bstride == (int64_t)(d.K / 8) * ld;
+    return d.dma_time && !d.half && has_image && !plain && (tr || enc) && (tile == 96 || tile == 128) && d.Mpad % tile == 0 && d.D1 == 1 &&
+           d.O1 == 1 && d.S1 == 1 && ld >= d.D2 && ((uintptr_t)d.x & 3) == 0;
+}
+
 int conv_check_tile_m(const mi_conv_desc &d) {
     MI_REQUIRE(d.tile_m != 192 || (d.M > 0 && d.M % 192 == 0 && d.Mpad == d.M), "conv: tile_m 192 needs M %% 192 == 0 and no M padding (M %d, Mpad %d)", d.M, d.Mpad);
     return MI_OK;
@@ -164,6 +181,9 @@ ConvRoute conv_route(const mi_conv_desc &d) {
     if (!plain && !sw.x6_plain_only && dmatap_eligible(d, tile, image, true)) return {MI_ROUTE_TAP_X6, split_tile(d.ntaps), plain};
     // the frequency branch's encoder / transposed convs and the 1 x 1 + GLU rewrites: the DMA row loader in front of it
     if (!sw.x6_plain_only && dmarow_eligible(d, tile, plain, image, true)) return {MI_ROUTE_ROWS_X6, split_tile(kRowTaps), plain};
+    // the time branch's transposed and strided convs: runs along the time axis by DMA in front of it
+    if (!sw.x6_plain_only && dmatime_eligible(d, tile, plain, image))
+        return {MI_ROUTE_TIME_X6, split_tile(d.epi == MI_EPI_CONVTR ? kTimeTr : kTimeEnc), plain};
     // native DMA taps: an under-filled k x k GLU conv takes 96-row tiles
     const int ktile = small && !plain && d.epi == MI_EPI_GLU && d.Mpad % 96 == 0 ? 96 : tile;
     if (!plain && dmatap_eligible(d, ktile, image)) return {MI_ROUTE_DMATAP, ktile, plain};

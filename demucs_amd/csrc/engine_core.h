@@ -93,6 +93,7 @@ enum SplitScope {
     SPLIT_OPT_IN,      // no layer of this kind
     SPLIT_DEFAULT,     // the transformer linears and the decoders' 3 x 3 / k = 3 rewrite convs
     SPLIT_ROWS,        // the row-tap layers of the DMA row route: like SPLIT_DEFAULT, unless MI_NO_DMA_ROWS keeps them on the table routes
+    SPLIT_TIME,        // the time branch's inner strided and transposed convs (route 11): like SPLIT_DEFAULT
 };
 
 struct WeightTable {

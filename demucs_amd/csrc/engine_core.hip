@@ -106,11 +106,14 @@ int EngineCore::conv(const mi_conv_desc &d, hipStream_t st) {
     const int tile = d.tile_m && d.tile_m != 192 ? d.tile_m : conv_pick_tile(d.M), ti = tile == 32 ? 0 : tile == 64 ? 1 : tile == 96 ? 2 : 3;
     // bf16 / fp16 operand or split-bf16 main loops: classes of their own.  The split-bf16 tap convs (conv_tap_x6_kernel) and row-tap
     // convs (conv_rows_x6_kernel: the frequency branch's encoder / transposed convs, the encoders' 1 x 1 + GLU rewrites): rows of
-    // their own, named after the kernel -- the conv_gemm_x6 rows stay the linears' ones
-    const bool tap_x6 = route == MI_ROUTE_TAP_X6, rows_x6 = route == MI_ROUTE_ROWS_X6;
+    // their own, named after the kernel -- the conv_gemm_x6 rows stay the linears' ones.  The time branch's strided and transposed
+    // convs of route 11 (conv_time_enc_x6_kernel, conv_time_tr_x6_kernel) stay on the rows the layers had on the table route,
+    // conv_gemm<linear / convtr,tile>: the recorded launch census (tests/golden/launch_census.json) lists every row of a forward.
+    // Kernel profiles keep them apart by symbol, and mi_debug_conv_route_launches counts the launches of a route
+    const bool tap_x6 = route == MI_ROUTE_TAP_X6, rows_x6 = route == MI_ROUTE_ROWS_X6, time_x6 = route == MI_ROUTE_TIME_X6;
     const int cls = tap_x6    ? 105 + (d.ntaps == 9 ? 2 : 0) + (tile == 128 ? 1 : 0)
                     : rows_x6 ? 109 + (d.epi == MI_EPI_CONVTR ? 4 : d.epi == MI_EPI_GLU ? 2 : 0) + (tile == 128 ? 1 : 0)
-                              : (route >= MI_ROUTE_X6 ? 48 : 0) + d.epi * 8 + ti * 2 + (d.plain ? 1 : 0);
+                              : (route >= MI_ROUTE_X6 && !time_x6 ? 48 : 0) + d.epi * 8 + ti * 2 + (d.plain ? 1 : 0);
     const double N = (double)d.B * d.O1 * d.O2;
     // algorithmic work: 2*M*K flops per output column; bytes = input tensor + output tensor + weights, once each
     const double in_bytes = 4.0 * (double)d.B * (double)d.x_bstride;
@@ -142,14 +145,16 @@ int EngineCore::conv(const mi_conv_desc &d, hipStream_t st) {
 // + GLU), which the shifted-run DMA tap loader feeds (conv_tap_x6_kernel; the table-driven gather in front of the split loop had
 // measured slower than the native DMA tap loop), and the row-tap layers of the DMA row route (SPLIT_ROWS: enc[1..3].conv, k = 8,
 // s = 4, + GELU; dec[0..2].convtr; the 128-row 1 x 1 + GLU rewrites of enc / tenc[2..3]), which the DMA row loader feeds
-// (conv_rows_x6_kernel; not with MI_NO_DMA_ROWS=1, whose layers keep the native table routes); MI_X6=0 packs none (A/B runs), MI_X6=1 every layer whose tile has the split
+// (conv_rows_x6_kernel; not with MI_NO_DMA_ROWS=1, whose layers keep the native table routes), and the time branch's inner
+// strided and transposed convs (SPLIT_TIME: tenc[1..3].conv, tdec[0..2].convtr), which the time-axis DMA loaders feed
+// (conv_time_enc_x6_kernel, conv_time_tr_x6_kernel); MI_X6=0 packs none (A/B runs), MI_X6=1 every layer whose tile has the split
 // loop.  When several PROCESSES share one GPU, split-loop results were
 // intermittently corrupted (tests/test_gpu_distributed.py, tools/micro/det3.py; cause not found), so such a process
 // selects the native kernels at run time (mi_set_split_bf16(0): demucs_amd/distributed.py does it for ranks that share
 // a device); one process per GPU is the supported deployment.
 int EngineCore::pack_split(PackedConv *pc, SplitScope scope) {
     const Switches &sw = switches();
-    const bool in_default = scope == SPLIT_DEFAULT || (scope == SPLIT_ROWS && !sw.no_dma_rows);
+    const bool in_default = scope == SPLIT_DEFAULT || scope == SPLIT_TIME || (scope == SPLIT_ROWS && !sw.no_dma_rows);
     const bool want = sw.x6_scope == 2 || (sw.x6_scope == 1 && in_default && cfg.dtype == MI_DTYPE_F32);
     if (!want || !conv_x6_supported(pc->tile)) return MI_OK;
     // M % 192 == 0 (decoders 0 .. 2 and their time twins, the self-attention in_proj, the deeper frequency-branch layers): 96-row

@@ -130,6 +130,15 @@ typedef struct mi_conv_desc {
                                strided frequency-axis convs, frequency-axis transposed convs): admits the LDS-DMA main loop of
                                conv_gemm_dmarow_kernel (bit-identical results); 0 = table-driven gather                              */
     int32_t dma_rows_pad;
+    int32_t dma_time;       /* float32 layers: 1 = the caller vouches for a 1-D TIME-AXIS layer (D1 = O1 = 1, taps along the contiguous axis):
+                               a transposed conv whose table is its two taps, K ordered (ci, j), tap j at column q - j, with columns
+                               q = 0 .. D2 on a row pitch O2 % 4 == 0 and o2_valid = D2 + 1; or a strided conv k = 8, s = 4, pad 2
+                               + GELU, K ordered (ci, t), column o reading samples 4 o - 2 + t (S2 = 4).  With a split image it admits
+                               the LDS-DMA loaders of conv_time_tr_x6_kernel / conv_time_enc_x6_kernel (route 11; conv_route.hip
+                               dmatime_eligible), which read x itself -- up to 8 bytes BEFORE and 20 bytes AFTER the tensor at x, so
+                               the caller must own that much readable slack on both sides (gemm_loop.h TimeTrTaps, TimeEncTaps);
+                               0 = table-driven gather                                                                         */
+    int32_t dma_time_pad;
 } mi_conv_desc;
 
 #ifdef __cplusplus

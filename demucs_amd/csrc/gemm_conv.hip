@@ -248,6 +248,7 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
     const int image_tile = d.tile_m == 192 ? 96 : d.tile_m ? d.tile_m : conv_pick_tile(d.M);
     g_last_conv_route = r.route;
     g_last_conv_tile = r.tile;
+    if ((unsigned)r.route < 16u && (unsigned)d.epi < 8u) ++g_conv_route_launches[r.route][d.epi];
     switch (r.route) {
         case MI_ROUTE_TAP_HALF: return launch_conv_tap(d, r.tile, st);
         case MI_ROUTE_HALF:
@@ -255,6 +256,7 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
         case MI_ROUTE_HALF_IMG256: return launch_conv_half(d, r, st);
         case MI_ROUTE_TAP_X6: return launch_conv_tap_x6(d, r.tile, image_tile, st);
         case MI_ROUTE_ROWS_X6: return launch_conv_rows_x6(d, r.tile, image_tile, st);
+        case MI_ROUTE_TIME_X6: return launch_conv_time_x6(d, r.tile, image_tile, st);
         case MI_ROUTE_X6: return launch_conv_x6(d, r.tile, image_tile, r.plain, st);
         case MI_ROUTE_DMATAP:
             return d.epi == MI_EPI_GLU ? launch_dmatap<MI_EPI_GLU>(d, r.tile, st) : launch_dmatap<MI_EPI_BIAS_STATS>(d, r.tile, st);

@@ -1,6 +1,6 @@
 // The pieces the implicit-GEMM main loops share, each spelled once (gemm_conv.hip: fp32 MFMA; gemm_x6.hip: split-bf16 MFMA;
 // gemm_half.hip, gemm_tap.hip: 16-bit MFMA): workgroup prologue, accumulators, the K steps, the three-stage LDS-DMA ring, the plan
-// of a wave's A-image transfers, the three loaders of a raw float32 activation tile, and the host's launch geometry.
+// of a wave's A-image transfers, the loaders of a raw float32 activation tile, and the host's launch geometry.
 // Built both ways (-amdgpu-mfma-vgpr-form=1 for gemm_conv.hip, =0 for the others): nothing here depends on the form.
 #pragma once
 #include "gemm_tile.h"
@@ -334,9 +334,113 @@ struct RowTaps {
 };
 #undef MI_ROW_LOADS
 
-// NT: 0 plain, kRowTaps row taps, 9 or 3 shifted-run taps
+// Time-axis transposed conv (ConvTranspose1d k = 8, s = 4 as a two-tap GEMM; the caller vouches with `dma_time`): D1 = O1 = 1, the
+// columns are q = 0 .. D2 on a row pitch O2 % 4 == 0 (o2_valid = D2 + 1, so a lane's 4-column chunk never straddles two items), and
+// row k = 2 ci + j of the tile is the run of channel ci at the tile's columns shifted by -j: TapRows with two taps at offsets 0 and
+// -1.  The parity of a lane's rows 4 wave + 2 j + lh is lh, so a lane serves ONE tap: lh = 0 the run at q, lh = 1 the run at q - 1.
+// READ SLACK: the chunk at q = 0 of tap 1 starts 4 bytes BEFORE its channel, and the chunk that holds q = D2 ends up to 16 bytes
+// AFTER it (pitch == D2): that much must be readable around the tensor at d.x (gemm_conv.h beside `dma_time`).
+// fix() writes the conv's zeros over what the runs drag in (a zero weight would not do: NaN * 0 is NaN): sample -1 (tap 1 of q = 0:
+// the previous channel's last element or the slack) and samples >= D2 (tap 0 of q = D2, both taps of the padded columns: the pitch
+// padding, the next channel's first samples or the slack) -- only the lanes of the first chunk of an item and of the chunk
+// around its valid end take the branch.  The K padding and columns past N read the zero page.
+struct TimeTrTaps {
+    const float *xcol;                                       // this lane's 16 bytes of channel 0, shifted by its tap
+    int64_t chan;
+    int ci0, q0, tap, lofs;
+    bool valid, edge;
+    __device__ __forceinline__ TimeTrTaps(const mi_conv_desc &d, const Wg &w, int N, int64_t) {
+        const ColInfo lc = decompose(w.n0 + w.li * 4, N, w.P, d.O2, w.o2v);
+        valid = lc.valid; q0 = lc.o2; tap = w.lh;
+        chan = d.x_ld ? d.x_ld : d.D2;
+        ci0 = 2 * w.wave; lofs = w.lh * BN + w.li * 4;
+        xcol = d.x + (size_t)lc.b * d.x_bstride + lc.o2 - w.lh;
+        edge = valid && (q0 == 0 || q0 + 4 > d.D2);
+    }
+    __device__ __forceinline__ void prefetch(int) {}
+    __device__ __forceinline__ void issue(const mi_conv_desc &d, int kt, float *brows) const {
+        const float *const zero = d.sink + MI_SINK_FLOATS;   // both arms plain locals: a select, not a branch (TapRows::issue)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int ci = kt * (BK / 2) + ci0 + j;
+            const bool ok = valid && 2 * ci < d.K;
+            const float *g = xcol + (int64_t)ci * chan;
+            lds_dma16_tracked(ok ? g : zero, brows + 2 * j * BN);
+        }
+    }
+    __device__ __forceinline__ void fix(const mi_conv_desc &d, int, float *brows) const {
+        if (!edge) return;
+        float *sb = brows + lofs;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if ((unsigned)(q0 + e - tap) >= (unsigned)d.D2) sb[2 * j * BN + e] = 0.f;
+    }
+};
+
+// Time-axis strided conv (Conv1d k = 8, s = 4, pad 2; the caller vouches with `dma_time`): D1 = O1 = 1, K ordered (ci, t), column o
+// reads samples 4 o - 2 .. 4 o + 5 of channel ci -- eight CONSECUTIVE floats, so a K step of 16 (two channels) is, per column, two
+// runs of 32 bytes, each landed as two 16-byte chunks from a source that is 8 bytes off 16-byte alignment (the DMA takes 4-byte-aligned
+// sources).  Every column owns its eight floats: taps 4 .. 7 are landed again for the next column (from the caches), so nothing is
+// shared with a neighbour and the last column of a row, of an item or of the tile needs no special case.
+// The raw stage is not the [16][128] image of the other loaders but [channel 2][chunk 2][column 128][4 floats]: one transfer of a
+// wave lands one chunk of 64 consecutive columns (16 bytes per lane, LDS addresses consecutive), and the thread that owns (column,
+// k-half = channel) reads its taps as two conflict-free 16-byte reads (read()).  Wave w moves chunk w >> 1 of columns
+// [64 (w & 1), + 64) for both channels: two transfers per wave and tile, as every loader.
+// READ SLACK: column 0 starts at sample -2 and the last valid column ends at sample 4 o2_valid + 1 <= D2 + 4: up to 8 bytes BEFORE
+// the tensor at d.x and up to 20 bytes AFTER it (8 with a row pitch of 4 o2_valid floats) must be readable (gemm_conv.h beside
+// `dma_time`).
+// fix(): the lane that issued a chunk overwrites, after its own wait, the samples outside [0, D2) with the conv's zero padding
+// (samples -2, -1: the previous channel's end or the slack; samples >= D2: the pitch padding, the next channel's start or the
+// slack).  Channels past Cin (the K padding of an odd Cin), columns past o2_valid and past N read the zero page.
+struct TimeEncTaps {
+    const float *xcol;                                       // sample 4 o - 2 + 4 chunk of channel 0 at this lane's column
+    int64_t chan;
+    int s0, lofs, wbase;
+    bool valid, edge;
+    __device__ __forceinline__ TimeEncTaps(const mi_conv_desc &d, const Wg &w, int N, int64_t) {
+        const int half = w.wave & 1, chunk = w.wave >> 1, col = 64 * half + w.lane;
+        const ColInfo lc = decompose(w.n0 + col, N, w.P, d.O2, w.o2v);
+        valid = lc.valid;
+        s0 = 4 * lc.o2 - 2 + 4 * chunk;
+        chan = d.x_ld ? d.x_ld : d.D2;
+        xcol = d.x + (size_t)lc.b * d.x_bstride + s0;
+        wbase = (chunk * BN + 64 * half) * 4; lofs = wbase + 4 * w.lane;
+        edge = valid && (s0 < 0 || s0 + 3 >= d.D2);
+    }
+    __device__ __forceinline__ void prefetch(int) {}
+    // `stage`: the raw stage itself (not a wave's rows of it)
+    __device__ __forceinline__ void issue(const mi_conv_desc &d, int kt, float *stage) const {
+        const float *const zero = d.sink + MI_SINK_FLOATS;   // both arms plain locals: a select, not a branch (TapRows::issue)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int ci = 2 * kt + j;
+            const bool ok = valid && 8 * ci < d.K;
+            const float *g = xcol + (int64_t)ci * chan;
+            lds_dma16_tracked(ok ? g : zero, stage + j * (2 * BN * 4) + wbase);
+        }
+    }
+    __device__ __forceinline__ void fix(const mi_conv_desc &d, int, float *stage) const {
+        if (!edge) return;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if ((unsigned)(s0 + e) >= (unsigned)d.D2) stage[j * (2 * BN * 4) + lofs + e] = 0.f;
+    }
+    // the eight taps of column bn, channel bh of the K step
+    static __device__ __forceinline__ void read(const float *stage, int bn, int bh, float (&v)[8]) {
+        const float4 a = *reinterpret_cast<const float4 *>(stage + ((2 * bh) * BN + bn) * 4);
+        const float4 b = *reinterpret_cast<const float4 *>(stage + ((2 * bh + 1) * BN + bn) * 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    }
+};
+
+// NT: 0 plain, kRowTaps row taps, kTimeTr / kTimeEnc the time-axis transposed / strided conv, 9 or 3 shifted-run taps
 template <int NT, int DIL = 1>
-using BLoader = std::conditional_t<NT == 0, PlainRows, std::conditional_t<NT == kRowTaps, RowTaps, TapRows<(NT > 0 ? NT : 3), DIL>>>;
+using BLoader = std::conditional_t<NT == 0, PlainRows, std::conditional_t<NT == kRowTaps, RowTaps, std::conditional_t<NT == kTimeTr, TimeTrTaps,
+                                   std::conditional_t<NT == kTimeEnc, TimeEncTaps, TapRows<(NT > 0 ? NT : 3), DIL>>>>>;
 
 // ---- host: launch geometry -----------------------------------------------------------------------------------------------------
 // N output columns in NT tiles of `bn`, MT row tiles of `tile`; Mpad must be a multiple of `image_rows` (the tile, or the rows of the

@@ -19,7 +19,9 @@
 //                (v_cvt_pk_bf16_f32, round-to-nearest residuals) and writes three 16-byte words.  The values come from
 //                the raw fp32 tile that LDS-DMA lands two K steps ahead (plain layers: channel runs; the decoders' 3 x 3 /
 //                k = 3 convs, conv_tap_x6_kernel: tap-shifted runs; the frequency branch's strided and transposed convs,
-//                conv_rows_x6_kernel: row taps at the output's own columns), or else through the gather table of the fp32 kernel.
+//                conv_rows_x6_kernel: row taps at the output's own columns; the time branch's transposed convs,
+//                conv_time_tr_x6_kernel: two runs shifted along the time axis, and strided encoder convs,
+//                conv_time_enc_x6_kernel: the 8-sample run of each column), or else through the gather table of the fp32 kernel.
 // Epilogues are the shared ones of gemm_tile.h (the accumulator layout of all 32x32 MFMAs is the same).
 #include "gemm_loop.h"
 #include "split_bf16.h"
@@ -61,7 +63,9 @@ int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx,
 // the split image is pack_split's as for any layer.  kRowTaps (conv_rows_x6_kernel): the frequency branch's encoder convs k = 8,
 // s = 4 and transposed convs as two-tap GEMMs, rows q and q - 1, and the encoders' 1 x 1 + GLU rewrites, whose table is the
 // identity.  Their table entries of K step kt + 3 are loaded in the same asm statement as the end-of-step vmcnt(0) wait and
-// counted with lgkmcnt(0) there: their latency passes under the wait for the ring.
+// counted with lgkmcnt(0) there: their latency passes under the wait for the ring.  kTimeTr (conv_time_tr_x6_kernel): the time
+// branch's transposed convs as two-tap GEMMs along the contiguous axis, columns q and q - 1 (gemm_loop.h TimeTrTaps).  kTimeEnc
+// (conv_time_enc_x6_kernel): its strided encoder convs k = 8, s = 4, + GELU (gemm_loop.h TimeEncTaps: a stage layout of its own).
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG, int NT>
 __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N, const int MT, const int Gm) {
     constexpr int BM = WM * TM * 32;
@@ -70,7 +74,9 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
     static_assert(NT <= 0 || (!PLAIN && EPI == MI_EPI_GLU), "tap loader: GLU rewrite convs");
     static_assert(!ROWS || (!PLAIN && (EPI == MI_EPI_LINEAR || EPI == MI_EPI_CONVTR || EPI == MI_EPI_GLU)),
                   "row-tap loader: encoder / transposed convs, 1 x 1 + GLU rewrites");
-    static_assert(NT >= kRowTaps, "NT: taps, 0 or kRowTaps");
+    static_assert(NT != kTimeTr || (!PLAIN && EPI == MI_EPI_CONVTR), "time-axis two-tap loader: transposed convs");
+    static_assert(NT != kTimeEnc || (!PLAIN && EPI == MI_EPI_LINEAR && LFLAGS == MI_FLAG_GELU), "time-axis strided loader: encoder convs");
+    static_assert(NT >= kTimeEnc, "NT: taps, 0, kRowTaps, kTimeTr or kTimeEnc");
     static_assert(WN * TN * 32 == BN, "block N tile is 128");
     static_assert(WM * WN == 4, "4 waves");
     constexpr int A_BYTES = BM * 96, B_BYTES = BN * 96, STAGE = A_BYTES + B_BYTES;
@@ -119,12 +125,18 @@ __device__ __forceinline__ void conv_x6_body(const mi_conv_desc &d, const int N,
     float breg[8];
     // RAW: this wave's rows 4 wave .. 4 wave + 3 of the raw tile, by the loader NT selects; raw stage rs
     BLoader<NT> L(d, w, N, w.P);
-#define MI_BRAW_DMA(kt, rs) L.issue(d, (kt), braw + (rs) * (BK * BN) + (4 * w.wave) * BN)
+    // (the time-axis strided loader lays the stage out itself and takes the stage, not the wave's rows: gemm_loop.h TimeEncTaps)
+    constexpr bool OWN_STAGE = NT == kTimeEnc;
+#define MI_BRAW_DMA(kt, rs) L.issue(d, (kt), braw + (rs) * (BK * BN) + (OWN_STAGE ? 0 : 4 * w.wave) * BN)
 // taps: after this wave's wait for its transfers of tile kt, before the barrier (gemm_loop.h TapRows)
-#define MI_BRAW_FIX(kt, rs) L.fix(d, (kt), braw + (rs) * (BK * BN) + (4 * w.wave) * BN)
+#define MI_BRAW_FIX(kt, rs) L.fix(d, (kt), braw + (rs) * (BK * BN) + (OWN_STAGE ? 0 : 4 * w.wave) * BN)
 #define MI_BRAW_READ(rs)                                                                                            \
     do {                                                                                                            \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) breg[j] = braw[(rs) * (BK * BN) + (8 * bh + j) * BN + bn];     \
+        if constexpr (OWN_STAGE) {                                                                                  \
+            L.read(braw + (rs) * (BK * BN), bn, bh, breg);                                                          \
+        } else {                                                                                                    \
+            _Pragma("unroll") for (int j = 0; j < 8; ++j) breg[j] = braw[(rs) * (BK * BN) + (8 * bh + j) * BN + bn]; \
+        }                                                                                                           \
     } while (0)
 
 #define MI_B_LOAD(kt)                                                                                               \
@@ -264,6 +276,18 @@ __global__ __launch_bounds__(256, 2) void conv_rows_x6_kernel(const mi_conv_desc
     conv_x6_body<WM, WN, TM, TN, EPI, LFLAGS, false, HALF_IMG, kRowTaps>(d, N, MT, Gm);
 }
 
+// the float32 time-branch transposed convs (two shifted runs along the time axis): a symbol of their own, as the tap convs
+template <int WM, int WN, int TM, int TN, bool HALF_IMG>
+__global__ __launch_bounds__(256, 2) void conv_time_tr_x6_kernel(const mi_conv_desc d, const int N, const int MT, const int Gm) {
+    conv_x6_body<WM, WN, TM, TN, MI_EPI_CONVTR, 0, false, HALF_IMG, kTimeTr>(d, N, MT, Gm);
+}
+
+// ... and its strided encoder convs (k = 8, s = 4, + GELU: 8-sample runs per column)
+template <int WM, int WN, int TM, int TN, bool HALF_IMG>
+__global__ __launch_bounds__(256, 2) void conv_time_enc_x6_kernel(const mi_conv_desc d, const int N, const int MT, const int Gm) {
+    conv_x6_body<WM, WN, TM, TN, MI_EPI_LINEAR, MI_FLAG_GELU, false, HALF_IMG, kTimeEnc>(d, N, MT, Gm);
+}
+
 template <int WM, int WN, int TM, int TN, int EPI, int LFLAGS, bool PLAIN, bool HALF_IMG = false, int NTAPS = 0>
 static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     constexpr int BM = WM * TM * 32;
@@ -272,6 +296,8 @@ static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
     const int Gm = pick_m_groups(g.MT, (size_t)d.Kpad * d.Mpad * 6);
     if constexpr (NTAPS > 0) MI_LAUNCH_TILES((conv_tap_x6_kernel<WM, WN, TM, TN, HALF_IMG, NTAPS>), d, g, Gm, st);
     else if constexpr (NTAPS == kRowTaps) MI_LAUNCH_TILES((conv_rows_x6_kernel<WM, WN, TM, TN, EPI, LFLAGS, HALF_IMG>), d, g, Gm, st);
+    else if constexpr (NTAPS == kTimeTr) MI_LAUNCH_TILES((conv_time_tr_x6_kernel<WM, WN, TM, TN, HALF_IMG>), d, g, Gm, st);
+    else if constexpr (NTAPS == kTimeEnc) MI_LAUNCH_TILES((conv_time_enc_x6_kernel<WM, WN, TM, TN, HALF_IMG>), d, g, Gm, st);
     else MI_LAUNCH_TILES((conv_gemm_x6_kernel<WM, WN, TM, TN, EPI, LFLAGS, PLAIN, HALF_IMG>), d, g, Gm, st);
     return MI_OK;
 }
@@ -279,7 +305,8 @@ static int launch_cfg_x6(const mi_conv_desc &d, hipStream_t st) {
 // `tile` is the tile conv_route decided, `image_tile` the one the split image was packed for: they differ for the
 // under-filled 128-row layers, which run 64-row tiles that read the 128-row image (bit-identical to the 128-row tile, no second
 // image), and for the 192-row layers (image_tile 96), which run the 192-row tile on pairs of their 96-row images or, under-filled,
-// the 96-row tile.  NTAPS: the loader (0: plain / gather table, 9 or 3: shifted-run taps, kRowTaps: row taps)
+// the 96-row tile.  NTAPS: the loader (0: plain / gather table, 9 or 3: shifted-run taps, kRowTaps: row taps, kTimeTr / kTimeEnc:
+// time-axis transposed / strided conv)
 template <int EPI, int LFLAGS, bool PLAIN, int NTAPS>
 static int launch_tile_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st) {
     if (tile != image_tile) {
@@ -326,6 +353,22 @@ int launch_conv_rows_x6(const mi_conv_desc &d, int tile, int image_tile, hipStre
     MI_REQUIRE(d.epi == MI_EPI_LINEAR && (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) == MI_FLAG_GELU,
                "conv rows x6: LINEAR + GELU, CONVTR or GLU (epi %d, flags %d)", d.epi, d.flags);
     return launch_tile_x6<MI_EPI_LINEAR, MI_FLAG_GELU, false, kRowTaps>(d, tile, image_tile, st);
+}
+
+// d has been validated by launch_conv (gemm_conv.hip): a float32 1-D layer along the time axis (dma_time: D1 = O1 = 1), image tile 96
+// or 128 (conv_route.hip dmatime_eligible): a transposed conv as a two-tap GEMM (columns 0 .. D2 on a pitch O2 % 4 == 0, o2_valid =
+// D2 + 1; the epilogue reads its flag set at run time), or a strided conv k = 8, s = 4 + GELU
+int launch_conv_time_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st) {
+    MI_REQUIRE(d.wx && ((uintptr_t)d.wx & 15) == 0, "conv time x6: split weight image missing or misaligned");
+    MI_REQUIRE((image_tile == 96 || image_tile == 128) && d.D1 == 1 && d.O1 == 1, "conv time x6: a 1-D layer on a 96- or 128-row tile (tile %d)", image_tile);
+    if (d.epi == MI_EPI_CONVTR) {
+        MI_REQUIRE(d.O2 % 4 == 0 && d.o2_valid == d.D2 + 1 && d.o2_valid <= d.O2 && d.K % 2 == 0,
+                   "conv time x6: columns 0 .. D2 on a pitch that is a multiple of 4 (D2 %d, O2 %d, o2_valid %d)", d.D2, d.O2, d.o2_valid);
+        return launch_tile_x6<MI_EPI_CONVTR, 0, false, kTimeTr>(d, tile, image_tile, st);
+    }
+    MI_REQUIRE(d.epi == MI_EPI_LINEAR && (d.flags & (MI_FLAG_GELU | MI_FLAG_SCALE | MI_FLAG_RES | MI_FLAG_LN | MI_FLAG_STATS)) == MI_FLAG_GELU &&
+               d.S2 == 4 && d.K % 8 == 0, "conv time x6: CONVTR, or LINEAR + GELU with k = 8, s = 4 (epi %d, flags %d, S2 %d)", d.epi, d.flags, d.S2);
+    return launch_tile_x6<MI_EPI_LINEAR, MI_FLAG_GELU, false, kTimeEnc>(d, tile, image_tile, st);
 }
 
 // d has been validated by launch_conv (gemm_conv.hip); `plain` is conv_route's

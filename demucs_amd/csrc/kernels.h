@@ -124,7 +124,7 @@ int conv_validate(const mi_conv_desc &d);         // MI_OK, or MI_EINVAL with th
 extern int g_split_bf16;     // 0 (mi_set_split_bf16): native fp32 MFMA kernels even where a split weight image exists
 // Which kernel launch_conv runs for a descriptor, decided from the descriptor alone (no HIP call, no pointer followed):
 // route: mi_conv_route (include/demucs_amd.h); tile: the rows of the tile that kernel runs, after every substitution
-// (routes 4, 7, 8: 64 under a 128-row layer = the 64-row tile that reads the 128-row image; 192 or 96 under a tile_m = 192
+// (routes 4, 7, 8, 11: 64 under a 128-row layer = the 64-row tile that reads the 128-row image; 192 or 96 under a tile_m = 192
 // layer = the 192-row tile on pairs of its 96-row images, or the 96-row tile on them; routes 5, 9, 10: 256 = the half modes'
 // 256-row tiles); plain: the 1x1 / linear fast path; mgroups: MI_MGROUPS, the M-grouped tile order of routes 0 and 1
 struct ConvRoute { int route; int tile; bool plain; bool mgroups; };
@@ -172,16 +172,23 @@ constexpr bool conv_x6_supported(int tile) { return tile == 128 || tile == 96 ||
 // M % 192 == 0 -- the tap convs (GLU), the row-tap layers (LINEAR + GELU, CONVTR, 1 x 1 + GLU) and the self-attention in_proj
 // (plain LINEAR with MI_FLAG_LN).  Anything else with such an M runs the 96-row tile on the same image.  lflags: the GELU / SCALE /
 // RES / LN / STATS bits (0 for other epilogues); ntaps: the loader -- 9 or 3 shifted-run taps, kRowTaps row taps, 0 plain or
-// gather table.  conv_route asks with the descriptor's epilogue and flags, launch_tile_x6 with its template arguments
+// gather table, kTimeTr the time-axis transposed conv's two shifted runs (CONVTR), kTimeEnc the time-axis strided conv's 8-sample runs
+// (LINEAR + GELU).  conv_route asks with the descriptor's epilogue
+// and flags, launch_tile_x6 with its template arguments
 constexpr int kRowTaps = -1;
+constexpr int kTimeTr = -2;
+constexpr int kTimeEnc = -3;
 constexpr bool conv_x6_tile192(int epi, int lflags, bool plain, int ntaps) {
     if (ntaps > 0) return epi == MI_EPI_GLU;
+    if (ntaps == kTimeTr) return epi == MI_EPI_CONVTR;
+    if (ntaps == kTimeEnc) return epi == MI_EPI_LINEAR && lflags == MI_FLAG_GELU;
     if (ntaps == kRowTaps) return (epi == MI_EPI_LINEAR && lflags == MI_FLAG_GELU) || epi == MI_EPI_CONVTR || epi == MI_EPI_GLU;
     return plain && epi == MI_EPI_LINEAR && lflags == MI_FLAG_LN;
 }
 int launch_conv_x6(const mi_conv_desc &d, int tile, int image_tile, bool plain, hipStream_t st);
 int launch_conv_tap_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);      // stride-1 3 x 3 / k = 3 GLU convs (route 7)
 int launch_conv_rows_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);     // row-tap encoder / transposed convs (route 8)
+int launch_conv_time_x6(const mi_conv_desc &d, int tile, int image_tile, hipStream_t st);     // time-axis transposed / strided convs (route 11)
 int launch_pack_split(const float *wt, int Kpad, int Mpad, int tile_m, void *wx, hipStream_t st);
 
 // gemm_half.hip: bf16 / fp16 operand main loops (mi_config.dtype); `r` as decided by conv_route (routes 5, 9, 10)

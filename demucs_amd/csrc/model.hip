@@ -92,7 +92,8 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(wt.get(pt + ".rewrite.weight", (int64_t)2 * C * C, &rw));
         MI_TRY(wt.get(pt + ".rewrite.bias", 2 * C, &rb));
         EncW &te = tenc[i];
-        MI_TRY(pack_conv(w, b, C, Cint * 8, false, &te.conv));
+        // level 0 (K = 16) is bound by its output: native
+        MI_TRY(pack_conv(w, b, C, Cint * 8, false, &te.conv, 0, i > 0 ? SPLIT_TIME : SPLIT_OPT_IN));
         if (i) MI_TRY(pack_enc_tap(w, Cint, &te.conv));
         MI_TRY(make_ktab(Gather{Cint, 1, 8, 1, 1, 0, 2, (int64_t)Lp[i], Lp[i]}, te.conv.Kpad, &te.ktab_conv));
         MI_TRY(pack_conv(rw, rb, 2 * C, C, true, &te.rewrite, 0, i >= 2 ? SPLIT_ROWS : SPLIT_OPT_IN));
@@ -135,7 +136,8 @@ int Model::init(const mi_config &c, const mi_tensor_desc *weights, size_t n) {
         MI_TRY(pack_conv(rw, rb, 2 * C, C * 3, true, &td.rewrite, 3, SPLIT_DEFAULT));
         MI_TRY(make_ktab(Gather{C, 1, 3, 1, 1, 0, 1, (int64_t)L, L}, td.rewrite.Kpad, &td.ktab_rw));
         MI_TRY(load_dconv(wt, pt, C, (int64_t)L, L, false, &td.dconv));
-        MI_TRY(pack_convtr(w, b, C, Coutt, &td.convtr));
+        // the outermost one (K = 96, 32-row tile) is bound by its output: native
+        MI_TRY(pack_convtr(w, b, C, Coutt, &td.convtr, 4, j < 3 ? SPLIT_TIME : SPLIT_OPT_IN));
         MI_TRY(make_ktab(Gather{C, 1, 2, 1, -1, 0, 0, (int64_t)L, L}, td.convtr.Kpad, &td.ktab_tr));
     }
     // ---- bottleneck 1x1 and transformer ------------------------------------------------------------
@@ -277,7 +279,12 @@ int Model::fill_workspace(Workspace &w) {
     size_t big = 0;
     for (int i = 0; i < 4; ++i) {
         const size_t nf = (size_t)kCh[i] * kFr[i + 1] * T, nt = (size_t)kCh[i] * Lp[i + 1];
-        MI_TRY(A(&w.w_skip[i], nf)); MI_TRY(A(&w.w_skip_t[i], nt));
+        MI_TRY(A(&w.w_skip[i], nf));
+        // the time encoder's strided convs read their input by LDS-DMA from sample -2 to past the row's end (gemm_loop.h
+        // TimeEncTaps: up to 8 bytes before and 20 after the tensor): 128 bytes of slack on both sides
+        // (only the float32 route reads it; the half modes get the same layout, which keeps one allocation rule and 16-byte alignment)
+        MI_TRY(w.mem.alloc((void **)&w.w_skip_t[i], (nt * B + 64) * sizeof(float)));
+        w.w_skip_t[i] += 32;
         big = std::max(big, std::max(nf, nt));
     }
     if (cfg.dtype != MI_DTYPE_F32)
@@ -561,6 +568,8 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
             mi_conv_desc d = base_desc(tenc[i].conv, tenc[i].ktab_conv, xt, (int64_t)Cint * Lp[i], gin);
             d.O2 = Lp[i + 1]; d.o2_valid = Lt[i + 1]; d.S2 = 4; d.epi = MI_EPI_LINEAR; d.flags = MI_FLAG_GELU;
             d.y = w_ta; d.y_bstride = C * P; d.y_cstride = P;
+            // a split image: each column's 8-sample run by LDS-DMA (gemm_loop.h TimeEncTaps); w_skip_t carries the read slack
+            if (d.wx && !d.half) d.dma_time = 1;
             if (plan.enc_img[1][i]) {
                 const int Qp = round_up(ceil_div(Lt[i], 4) + 1, 4);
                 d.xh = w_eimg[1][i - 1]; d.xh_n = (int64_t)cfg.max_batch * Qp; d.wtap = tenc[i].conv.wtap; d.ntaps = 2; d.tap_k2 = 2;
@@ -667,6 +676,12 @@ int Model::run_core_impl(const float *mix, const float *mag, int B, hipStream_t 
             mi_conv_desc t = base_desc(tdec[j].convtr, tdec[j].ktab_tr, w_ta, (int64_t)C * L, g);
             t.O2 = Lv + 1; t.o2_valid = 0; t.epi = MI_EPI_CONVTR; t.out_len = Lout;     // q = 0 .. Lv, scattered to 4q + r - 2
             t.y_cstride = Lpo; t.y_bstride = (int64_t)Cout * Lpo;
+            if (t.wx && !t.half) {
+                // a split image: the two taps by LDS-DMA (gemm_loop.h TimeTrTaps).  The columns lie on a pitch that is a multiple of
+                // 4, so no 16-byte chunk straddles two items; the padded columns are computed and never stored.  w_ta carries the
+                // read slack (fill_workspace)
+                t.O2 = round_up(Lv + 1, 4); t.o2_valid = Lv + 1; t.dma_time = 1;
+            }
             if (last) t.y = w_ytime;
             else { t.flags |= MI_FLAG_GELU | MI_FLAG_RES; t.res = w_skip_t[2 - j]; t.y = dtin; }
             if (!last && tapimg) { t.flags |= MI_FLAG_IMG; t.yh = dtin; t.yh_n = (int64_t)B * t.y_cstride; }

@@ -627,7 +627,9 @@ int mi_item_denorm(const float *x_dev, int32_t rows, int64_t count, const float 
  *   136,153,287,294,313,326, demucs/demucs.py:138,140, demucs/htdemucs.py:589-599).
  *   See demucs_amd/csrc/gemm_conv.h (mi_conv_desc) for the field meanings.
  *   A float32 descriptor that states its kernel geometry (ntaps / tap_*) may run the shifted-run tap loader (routes 2 and 7), which
- *   reads up to 8 bytes before and 20 bytes after the tensor at `x`: the caller owns that slack (gemm_conv.h, beside `ntaps`). */
+ *   reads up to 8 bytes before and 20 bytes after the tensor at `x`: the caller owns that slack (gemm_conv.h, beside `ntaps`).
+ *   A float32 descriptor with a split image that sets `dma_time` (a 1-D time-axis strided or transposed conv) may run the time-axis
+ *   loaders (route 11), which read the same 8 bytes before and 20 bytes after the tensor at `x` (gemm_conv.h, beside `dma_time`). */
 struct mi_conv_desc;
 int mi_conv_forward(const struct mi_conv_desc *desc, void *stream);
 
@@ -825,8 +827,12 @@ enum mi_conv_route {
                               LINEAR + GELU or CONVTR on 96- / 128-row tiles, 1 x 1 + GLU on 128-row tiles -- with a split image) */
     MI_ROUTE_HALF_IMG = 9, /* half modes, operand-image input, 3-stage LDS-DMA ring (gemm_half.hip conv_gemm_half_img_kernel: plain
                               LINEAR with SCALE|RES or SCALE|RES|STATS); tile 256 where Mpad % 256 == 0, else 128 */
-    MI_ROUTE_HALF_IMG256 = 10 /* half modes, operand-image input, 512-thread 256 x 256 tile (gemm_half.hip conv_gemm_half_img256_kernel:
+    MI_ROUTE_HALF_IMG256 = 10, /* half modes, operand-image input, 512-thread 256 x 256 tile (gemm_half.hip conv_gemm_half_img256_kernel:
                               plain LINEAR with LN|HEADS or LN|GELU|IMG; with SCALE|RES under MI_IMG256=1 where Mpad % 256 == 0); tile 256 */
+    MI_ROUTE_TIME_X6 = 11  /* split-bf16 with LDS-DMA shifted-run taps along the time axis (gemm_x6.hip conv_time_tr_x6_kernel,
+                              conv_time_enc_x6_kernel: the time branch's transposed convs as two-tap GEMMs and its strided convs k = 8,
+                              s = 4 + GELU, `dma_time`, with a split image; 96- / 128-row tiles).  These loaders read up to 8 bytes
+                              before and 20 bytes after the tensor at x: the caller owns that slack (gemm_conv.h `dma_time`) */
 };
 
 /* Debug aid for the kernel tests: the route the LAST mi_conv_forward of this process took; -1 before any call.  Process-wide,
@@ -836,6 +842,11 @@ int mi_debug_last_conv_route(void);
 /* Debug aid, as mi_debug_last_conv_route: the rows of the tile the LAST mi_conv_forward of this process ran (what
  * mi_debug_conv_route answers in *tile); -1 before any call. */
 int mi_debug_last_conv_tile(void);
+
+/* Debug aid: how many layers this process has launched on `route` (enum mi_conv_route) with epilogue `epi` (enum mi_epilogue of
+ * gemm_conv.h; -1: any), through mi_conv_forward and through the engines' forwards alike; -1 for a route or epilogue out of
+ * range.  A test takes the difference around a forward.  Process-wide, not thread-safe. */
+int64_t mi_debug_conv_route_launches(int32_t route, int32_t epi);
 
 /* Debug aid: the route mi_conv_forward WOULD take for `desc` (under the environment switches and mi_set_split_bf16 as they
  * stand) and, in *tile (may be NULL), the rows of the tile that kernel runs, after every substitution: for the

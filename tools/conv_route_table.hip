@@ -2,7 +2,8 @@
 // prints for each descriptor below one line `name route tile plain`, or `name invalid: <message>` where conv_validate refuses
 // it.  No GPU, no HIP call, no pointer followed: small aligned numbers stand in for the descriptors' pointers.  The MI_*
 // environment decides as in the library; the argument `nosplit` is mi_set_split_bf16(0).  tests/test_conv_route_host.py
-// builds and runs it and holds the expectations.
+// builds and runs it and holds the expectations.  The argument `time` prints, INSTEAD of those rows, the time branch's transposed
+// and strided convs of route 11 (tests/test_conv_route_time_host.py).
 //   hipcc --offload-arch=gfx950 -std=c++17 tools/conv_route_table.hip demucs_amd/csrc/conv_route.hip demucs_amd/csrc/switches.hip -o conv_route_table
 #include "../demucs_amd/csrc/common.h"
 #include "../demucs_amd/csrc/kernels.h"
@@ -76,6 +77,49 @@ static mi_conv_desc half(int M, int flags, bool xh = true, int K = 64) {
     return d;
 }
 
+static void row(const char *name, const mi_conv_desc &d);
+// the time branch's transposed conv C -> M / 4 on Lv samples per item (row pitch Lp) as the engine describes it: columns 0 .. Lv on
+// a pitch that is a multiple of 4; `dma_time` 0: the same layer without the caller's promise
+static mi_conv_desc time_tr(bool image, int C, int M, int B, int Lv, int Lp, int dma_time = 1) {
+    mi_conv_desc d = base(M, 2 * C, conv_pick_tile(M), image);
+    if (image && M % 192 == 0) d.tile_m = 192;
+    d.B = B, d.D1 = d.O1 = 1, d.D2 = Lv, d.O2 = rup(Lv + 1, 4), d.o2_valid = Lv + 1, d.x_ld = Lp != Lv ? Lp : 0, d.x_bstride = (int64_t)C * Lp;
+    d.epi = MI_EPI_CONVTR, d.out_len = 4 * Lv, d.y_cstride = 4 * Lp, d.dma_time = dma_time;
+    return d;
+}
+// the time branch's strided conv Cin -> M, k = 8, s = 4, pad 2, + GELU on L samples per item (row pitch L rounded up to 4)
+static mi_conv_desc time_enc(bool image, int Cin, int M, int B, int L, int dma_time = 1) {
+    mi_conv_desc d = base(M, 8 * Cin, conv_pick_tile(M), image);
+    if (image && M % 192 == 0) d.tile_m = 192;
+    const int Lp = rup(L, 4), Lo = (L + 3) / 4;
+    d.B = B, d.D1 = d.O1 = 1, d.D2 = L, d.O2 = rup(Lo, 4), d.o2_valid = Lo, d.S2 = 4, d.x_ld = Lp != L ? Lp : 0, d.x_bstride = (int64_t)Cin * Lp;
+    d.epi = MI_EPI_LINEAR, d.flags = MI_FLAG_GELU, d.y_cstride = d.O2, d.dma_time = dma_time;
+    return d;
+}
+static void time_rows() {
+    char name[64];
+    // tenc[1 .. 3].conv of a 7.8 s segment, under-filled (B = 1) and filled; a 128-row layer (M = 128) for the small-batch tile
+    const int E[4][5] = {{48, 96, 85995, 1, 8}, {96, 192, 21499, 1, 5}, {192, 384, 5375, 1, 16}, {24, 128, 149, 3, 640}};
+    for (int image = 1; image >= 0; --image)
+        for (auto &l : E)
+            for (int f = 0; f < 2; ++f) {
+                snprintf(name, sizeof(name), "time_enc_M%d_%s%s", l[1], f ? "filled" : "under", image ? "+x6" : "");
+                row(name, time_enc(image, l[0], l[1], l[3 + f], l[2]));
+            }
+    row("time_enc_M384_nopromise+x6", time_enc(true, 192, 384, 16, 5375, 0));
+    // tdec[0 .. 2].convtr of a 7.8 s segment, under-filled (B = 1) and filled; a 128-row layer (M = 128) for the small-batch tile
+    const int L[4][6] = {{384, 768, 1344, 1344, 1, 8}, {192, 384, 5375, 5376, 1, 4}, {96, 192, 21499, 21500, 1, 2}, {36, 128, 5375, 5376, 1, 8}};
+    for (int image = 1; image >= 0; --image)
+        for (auto &l : L)
+            for (int f = 0; f < 2; ++f) {
+                snprintf(name, sizeof(name), "time_tr_M%d_%s%s", l[1], f ? "filled" : "under", image ? "+x6" : "");
+                row(name, time_tr(image, l[0], l[1], l[4 + f], l[2], l[3]));
+            }
+    row("time_tr_M768_nopromise+x6", time_tr(true, 384, 768, 8, 1344, 1344, 0));
+    { mi_conv_desc d = time_tr(true, 384, 768, 8, 1344, 1344); d.O2 = 1345, d.o2_valid = 0; row("time_tr_M768_pitch1345+x6", d); }
+    { mi_conv_desc d = time_tr(true, 384, 768, 8, 1344, 1344); d.flags = MI_FLAG_GELU | MI_FLAG_RES; d.res = kX; row("time_tr_M768_skip+x6", d); }
+}
+
 static void row(const char *name, const mi_conv_desc &d) {
     if (conv_validate(d) != MI_OK) { printf("%s invalid: %s\n", name, last_error_buf()); return; }
     const ConvRoute r = conv_route(d);
@@ -83,7 +127,12 @@ static void row(const char *name, const mi_conv_desc &d) {
 }
 
 int main(int argc, char **argv) {
-    if (argc > 1 && !strcmp(argv[1], "nosplit")) g_split_bf16 = 0;
+    bool time_only = false;
+    for (int i = 1; i < argc; ++i) {
+        if (!strcmp(argv[i], "nosplit")) g_split_bf16 = 0;
+        if (!strcmp(argv[i], "time")) time_only = true;
+    }
+    if (time_only) { time_rows(); return 0; }
     char name[64];
     for (int image = 1; image >= 0; --image) {       // rows A - I of tests/test_gpu_conv_route.py, with and without a split image
         const mi_conv_desc rows[9] = {linear(image, 3136), linear(image, 3200), glu3x3(image, 48, 2), glu3x3(image, 48, 2, false), glu3x3(image, 64, 1),
