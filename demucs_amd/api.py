@@ -22,11 +22,11 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib
-from .audio import ConvertingStatsStream, MonoStatsStream, TrackScore, TrackStats, convert_audio
+from .audio import ConvertingStatsStream, MonoStatsStream, TrackPeaks, TrackScore, TrackStats, convert_audio
 from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
 from .stream import Delivery, ModelStream, StreamGroup
 
-__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "TrackScore", "LoadModelError", "list_models"]
+__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "TrackPeaks", "TrackScore", "LoadModelError", "list_models"]
 
 
 class LoadModelError(Exception):
@@ -153,7 +153,11 @@ class Separator:
         With `deliver=Delivery(...)` (demucs_amd/stream.py) `push` / `finish` return what the reference would write to its files
         for those samples instead: `{name: (m, channels) frames}` in the order of its save loop, after `prevent_clip` and as
         int16 PCM or float32 with interleaved channels -- `audio.deliver`'s chain on the stems above, by one more launch per
-        push.  A stream refuses clip="rescale" and other_method="minus", which need the whole track.
+        push.  A stream refuses other_method="minus", which needs the whole track, and clip="rescale" without peaks: the divisor
+        is the whole output's peak.  `Delivery(clip="rescale", peaks="measure")` is a pass that finds those peaks: `push` returns
+        `{}`, nothing is copied to the host, and `finish()` returns an `audio.TrackPeaks`; a second stream over the same input, with
+        the same arguments, `random` in the same state and `Delivery(clip="rescale", peaks=<that TrackPeaks>)`, delivers the
+        frames of `audio.deliver(..., clip="rescale")` bit for bit (`separate_blocks` runs both).
 
         `Delivery(..., samplerate=R)` returns the frames at R Hz instead of the model's rate M, resampled on the device:
         `audio.deliver(..., samplerate=(M, R))` on the whole track, bit for bit.  A push returns the resampler frames whose last
@@ -233,7 +237,14 @@ class Separator:
         `pcm`, converted on the device when they are not the model's).  Pass 1 pushes them through `analyse_stream`, pass 2 through
         `separate_stream(stats=..., length=...)`; this generator yields what every `push` and then `finish` of pass 2 return.
         Concatenated, the stems equal `separate_tensor`'s bit for bit, with `random` left in the same state; with `deliver=` the
-        frames equal `audio.deliver`'s on those stems, under a delivering stream's refusals (raised before pass 1)."""
+        frames equal `audio.deliver`'s on those stems, under a delivering stream's refusals (raised before pass 1).
+
+        `deliver=Delivery(clip="rescale", peaks="measure")` reads the track a third time: between the two passes above a measuring
+        `separate_stream` runs the same forwards and keeps only `max |value|` per output on the device (`audio.TrackPeaks`); the
+        state of `random` is saved before it and restored after it, so pass 3 draws the same shift offsets, sees the same values
+        and divides by the whole track's peaks: the frames are `audio.deliver(..., clip="rescale")`'s bit for bit, and `random`
+        ends where `separate_tensor` leaves it.  Nothing but the 4 bytes per output leaves the device in the measuring pass."""
+        import random
         if deliver is not None:
             deliver.for_stream(self._model.sources, _is_engine(self._model) and torch.device(self._device).type == "cuda",
                                self._samplerate, self._audio_channels)
@@ -241,6 +252,14 @@ class Separator:
         for block in source():
             an.push(block)
         stats = an.finish()
+        if deliver is not None and deliver.measures:
+            state = random.getstate()
+            st = self.separate_stream(stats=stats, sr=sr, channels=channels, convert=True, pcm=pcm, deliver=deliver,
+                                      length=stats.input_length)
+            for block in source():
+                st.push(block)
+            deliver = deliver.with_peaks(st.finish())
+            random.setstate(state)
         st = self.separate_stream(stats=stats, sr=sr, channels=channels, convert=True, pcm=pcm, deliver=deliver,
                                   length=stats.input_length)
         for block in source():
@@ -428,8 +447,9 @@ class Separator:
 
 
 def _named(sources, out) -> Dict[str, torch.Tensor]:
-    """A stream's stems by source name; a delivering stream's result already is `{name: frames}`."""
-    return out if isinstance(out, dict) else dict(zip(sources, out))
+    """A stream's stems by source name; a delivering stream's result already is `{name: frames}`, a measuring stream's `{}` or
+    its `audio.TrackPeaks`."""
+    return out if isinstance(out, (dict, TrackPeaks)) else dict(zip(sources, out))
 
 
 def _stacked(stems) -> torch.Tensor:
@@ -530,6 +550,8 @@ class ConvertingSeparatorStream(SeparatorStream):
         y = self._cv.finish(on_device=True)
         parts = [self.stream.push(y)] if y.shape[1] else []
         parts.append(self.stream.finish())
+        if isinstance(parts[-1], TrackPeaks):               # a measuring stream: every push gave {}
+            return parts[-1]
         if isinstance(parts[0], dict):                      # delivered frames: (m, channels) per name
             return self._stems({k: torch.cat([p[k] for p in parts], 0) for k in parts[0]}, to)
         return self._stems(parts[0] if len(parts) == 1 else torch.cat(parts, -1), to)

@@ -807,6 +807,91 @@ def deliver_views(buf: torch.Tensor, outputs, offs, frames: int, channels: int, 
     return {name: buf[off:off + size].view(dtype).view(frames, channels) for (name, _, _), off in zip(outputs, offs)}
 
 
+class TrackPeaks:
+    """What a measuring pass over a stream found (`Delivery(clip="rescale", peaks="measure")`): per output of the reference's save
+    loop the peak that `prevent_clip(·, "rescale")` divides by, so that a second pass of the same stream can deliver with it.
+
+    `names` are the outputs in the reference's save order (`delivery_outputs` for `stem` / `other_method`), `bits` one uint32 per
+    output: the bit pattern of the float32 `max |value|` as `mi_deliver_peaks` writes it (a NaN sample gives a NaN pattern),
+    `samplerate` the rate of the delivered frames the peaks were measured at (None: the model's), `length` the model-rate samples
+    measured.  Constructible by hand: a caller who knows an upper bound of a live feed's peak passes its bits and gets the fixed,
+    reference-shaped gain `v / max(1.01 * peak, 1)`.  Immutable."""
+    __slots__ = ("names", "bits", "samplerate", "stem", "other_method", "length")
+
+    def __init__(self, names, bits, samplerate=None, stem=None, other_method: str = "add", length: int = 1):
+        import numpy as np
+        if isinstance(names, (str, bytes)) or not all(isinstance(n, str) for n in names):
+            raise ValueError(f"TrackPeaks: names must be a sequence of output names, got {names!r}")
+        names = tuple(names)
+        if other_method not in ("add", "minus", "none"):
+            raise ValueError(f"Invalid other_method {other_method}")
+        if stem is not None and not isinstance(stem, str):
+            raise ValueError(f"TrackPeaks: stem must be a source name or None, got {stem!r}")
+        if stem is None:
+            if not names or len(set(names)) != len(names):
+                raise ValueError(f"TrackPeaks: names must be the separated sources, each once, got {list(names)}")
+        else:
+            # the sources other than `stem` do not enter a two-stems output's name
+            want = tuple(name for name, _, _ in delivery_outputs([stem], stem, other_method))
+            if names != want:
+                raise ValueError(f"TrackPeaks: the outputs of stem={stem!r}, other_method={other_method!r} are {list(want)} in the "
+                                 f"reference's save order, got {list(names)}")
+        if isinstance(bits, (str, bytes)) or not hasattr(bits, "__len__"):
+            raise ValueError(f"TrackPeaks: bits must be a sequence of uint32 bit patterns, got {bits!r}")
+        if len(bits) != len(names):
+            raise ValueError(f"TrackPeaks: {len(names)} outputs need {len(names)} peaks, got {len(bits)}")
+        vals = []
+        for v in bits:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"TrackPeaks: a peak is the uint32 bit pattern of a float32 (see TrackPeaks.from_values), got {v!r}")
+            if int(v) & 0x80000000:
+                raise ValueError(f"TrackPeaks: a peak is max |value|, whose sign bit is clear, got {int(v):#010x}")
+            vals.append(int(v))
+        if samplerate is not None and (isinstance(samplerate, bool) or not isinstance(samplerate, (int, np.integer)) or samplerate <= 0):
+            raise ValueError(f"TrackPeaks: samplerate must be a positive integer or None, got {samplerate!r}")
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 1:
+            raise ValueError(f"TrackPeaks: length must be a positive integer, got {length!r}")
+        for name, v in zip(self.__slots__, (names, tuple(vals), None if samplerate is None else int(samplerate), stem, other_method,
+                                            int(length))):
+            object.__setattr__(self, name, v)
+
+    @classmethod
+    def from_values(cls, names, peaks, **kw) -> "TrackPeaks":
+        """From float peaks (each rounded to float32, its magnitude taken)."""
+        import numpy as np
+        return cls(names, [int(np.abs(np.float32(p)).view(np.uint32)) for p in peaks], **kw)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("TrackPeaks is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("TrackPeaks is immutable")
+
+    def peak(self, name: str):
+        """The float32 `max |value|` of output `name`."""
+        import numpy as np
+        return np.uint32(self.bits[self.names.index(name)]).view(np.float32)
+
+    def divisor(self, name: str):
+        """float32(peak * float32(1.01)): `clip_divisor` of post_ops.h; the frames are `v / divisor` when it exceeds 1 or is NaN."""
+        import numpy as np
+        with np.errstate(over="ignore", invalid="ignore"):
+            return np.float32(self.peak(name) * np.float32(1.01))
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, TrackPeaks) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return (f"TrackPeaks(names={list(self.names)}, bits={[hex(b) for b in self.bits]}, samplerate={self.samplerate}, "
+                f"stem={self.stem!r}, other_method={self.other_method!r}, length={self.length})")
+
+
 def _stems_block(tensors, dev: torch.device) -> torch.Tensor:
     """The stems as one contiguous float32 (S, channels, n) tensor on `dev`: read in place when they already are the rows of one
     (what `Separator.separate_tensor` returns for a device mix), else stacked once (host stems: stacked, then one H2D)."""

@@ -596,6 +596,38 @@ int mi_deliver_resample_pcm(const int64_t *table_dev, int32_t n_rows, int64_t ma
                                        hist_capacity, lds_floats, (unsigned char *)dst_dev, dst_capacity, (hipStream_t)stream);
 }
 
+int mi_deliver_peaks_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels, void *peaks_dev,
+                            int32_t n_peaks, void *stream) {
+    MI_REQUIRE(table_dev && peaks_dev && n_rows > 0 && n_rows <= 65535 && max_n >= 1 && max_n <= (int64_t)INT32_MAX * 1024 &&
+               n_sources > 0 && channels > 0 && n_peaks > 0, "mi_deliver_peaks_update: bad argument");
+    return launch_deliver_peaks_update(table_dev, n_rows, max_n, n_sources, channels, (unsigned *)peaks_dev, n_peaks, (hipStream_t)stream);
+}
+
+int mi_deliver_resample_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_groups, int32_t n_sources, int32_t channels,
+                              const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity, int32_t lds_floats,
+                              const int32_t *slots_dev, void *peaks_dev, int32_t n_peaks, void *stream) {
+    MI_REQUIRE(table_dev && slots_dev && peaks_dev && n_peaks > 0 && n_rows > 0 && n_rows <= 65535 && max_groups >= 1 &&
+               max_groups <= INT32_MAX && n_sources > 0 && channels > 0 && bank_capacity >= 0 && (bank_capacity == 0 || bank_dev) &&
+               hist_capacity >= 0 && (hist_capacity == 0 || hist_dev) && lds_floats >= 1 && lds_floats <= MI_RATE_LDS_FLOATS,
+               "mi_deliver_resample_peaks: bad argument");
+    return launch_deliver_resample_peaks(table_dev, n_rows, max_groups, n_sources, channels, bank_dev, bank_capacity, hist_dev,
+                                         hist_capacity, lds_floats, slots_dev, (unsigned *)peaks_dev, n_peaks, (hipStream_t)stream);
+}
+
+int mi_deliver_resample_pcm_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_groups, int32_t n_sources, int32_t channels,
+                                  const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity, int32_t lds_floats,
+                                  void *dst_dev, int64_t dst_capacity, const int32_t *slots_dev, const void *peaks_dev, int32_t n_peaks,
+                                  void *stream) {
+    MI_REQUIRE(table_dev && dst_dev && n_rows > 0 && n_rows <= 65535 && max_groups >= 1 && max_groups <= INT32_MAX && n_sources > 0 &&
+               channels > 0 && bank_capacity >= 0 && (bank_capacity == 0 || bank_dev) && hist_capacity >= 0 &&
+               (hist_capacity == 0 || hist_dev) && lds_floats >= 1 && lds_floats <= MI_RATE_LDS_FLOATS && dst_capacity >= 0 &&
+               slots_dev && n_peaks >= 0 && (n_peaks == 0 || peaks_dev), "mi_deliver_resample_pcm_peaks: bad argument");
+    MI_REQUIRE(((uintptr_t)dst_dev & 3) == 0, "mi_deliver_resample_pcm_peaks: dst_dev must be 4-byte aligned");
+    return launch_deliver_resample_pcm_peaks(table_dev, n_rows, max_groups, n_sources, channels, bank_dev, bank_capacity, hist_dev,
+                                             hist_capacity, lds_floats, (unsigned char *)dst_dev, dst_capacity, slots_dev,
+                                             (const unsigned *)peaks_dev, n_peaks, (hipStream_t)stream);
+}
+
 // Kernel-level entry points.  They allocate their scratch with hipMalloc and free it after a
 // stream synchronise: convenient for parity tests, not meant for the hot loop.
 int mi_stft_cac(const float *mix_dev, int32_t B, int32_t L, float *cac_dev, void *stream) {

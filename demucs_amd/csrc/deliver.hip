@@ -16,20 +16,23 @@ struct DeliverRow {
     bool ok, vec;
 };
 
-// One row of the table, with every rule under which it is skipped; both kernels read a row through this, so they agree on it
+// One row of the table, with every rule under which it is skipped; every kernel reads a row through this, so they agree on it.
+// DST = false is a row that writes no frames (mi_deliver_peaks_update): FMT and DST_OFF are not read, and dst_cap is not used
+template <bool DST = true>
 __device__ __forceinline__ DeliverRow deliver_row(const int64_t *__restrict__ t, int n_sources, int channels, int n_peaks, int64_t dst_cap) {
     DeliverRow r;
     r.src = reinterpret_cast<const float *>(static_cast<uintptr_t>(t[MI_DELIVER_SRC]));
     r.origin = reinterpret_cast<const float *>(static_cast<uintptr_t>(t[MI_DELIVER_ORIGIN]));
     r.n = t[MI_DELIVER_N];
-    r.dst_off = t[MI_DELIVER_DST_OFF];
-    const int64_t kind = t[MI_DELIVER_KIND], sel = t[MI_DELIVER_SEL], clip = t[MI_DELIVER_CLIP], fmt = t[MI_DELIVER_FMT];
+    r.dst_off = DST ? t[MI_DELIVER_DST_OFF] : 0;
+    const int64_t kind = t[MI_DELIVER_KIND], sel = t[MI_DELIVER_SEL], clip = t[MI_DELIVER_CLIP];
+    const int64_t fmt = DST ? t[MI_DELIVER_FMT] : MI_DELIVER_I16;
     const int64_t peak = t[MI_DELIVER_PEAK];
     r.ok = r.src && r.n > 0 && kind >= MI_DELIVER_STEM && kind <= MI_DELIVER_MINUS && sel >= 0 && sel < n_sources && clip >= 0 &&
            clip <= MI_CLIP_TANH && fmt >= MI_DELIVER_I16 && fmt <= MI_DELIVER_F32 && (clip != MI_CLIP_RESCALE || (peak >= 0 && peak < n_peaks)) &&
            (kind != MI_DELIVER_MINUS || r.origin) && r.dst_off >= 0 && (r.dst_off & 3) == 0;
     r.kind = (int)kind; r.sel = (int)sel; r.clip = (int)clip; r.fmt = (int)fmt; r.peak = (int)peak;
-    if (r.ok) {
+    if (DST && r.ok) {
         const int64_t frame = (int64_t)channels * (r.fmt == MI_DELIVER_F32 ? 4 : 2);        // bytes
         r.ok = r.n <= dst_cap / frame && r.dst_off <= dst_cap - r.n * frame;
     }
@@ -67,10 +70,12 @@ __device__ __forceinline__ void row_values(const DeliverRow &r, int n_sources, i
     }
 }
 
-// mi_deliver_peaks: grid (ceil(max_n / 1024), n_rows); a thread takes four consecutive frames of every channel of its row
+// mi_deliver_peaks (DST: the rows are those mi_deliver_pcm will write) and mi_deliver_peaks_update (no destination; the slots
+// carry the running maximum): grid (ceil(max_n / 1024), n_rows); a thread takes four consecutive frames of every channel of its row
+template <bool DST>
 __global__ __launch_bounds__(256) void deliver_peaks_kernel(const int64_t *__restrict__ table, int n_sources, int channels,
                                                             unsigned *__restrict__ peaks, int n_peaks, int64_t dst_cap) {
-    const DeliverRow r = deliver_row(table + (size_t)blockIdx.y * MI_DELIVER_COLS, n_sources, channels, n_peaks, dst_cap);
+    const DeliverRow r = deliver_row<DST>(table + (size_t)blockIdx.y * MI_DELIVER_COLS, n_sources, channels, n_peaks, dst_cap);
     if (!r.ok || r.clip != MI_CLIP_RESCALE) return;                // the same for the whole block
     const int64_t j0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     unsigned m = 0u;
@@ -134,8 +139,16 @@ __global__ __launch_bounds__(256) void deliver_pcm_kernel(const int64_t *__restr
 int launch_deliver_peaks(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks, int n_peaks,
                          int64_t dst_cap, hipStream_t st) {
     MI_HIP(hipMemsetAsync(peaks, 0, sizeof(unsigned) * (size_t)n_peaks, st));
-    hipLaunchKernelGGL(deliver_peaks_kernel, dim3(ceil_div(max_n, 1024), n_rows), dim3(256), 0, st, table, n_sources, channels, peaks,
-                       n_peaks, dst_cap);
+    hipLaunchKernelGGL(deliver_peaks_kernel<true>, dim3(ceil_div(max_n, 1024), n_rows), dim3(256), 0, st, table, n_sources, channels,
+                       peaks, n_peaks, dst_cap);
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}
+
+int launch_deliver_peaks_update(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks,
+                                int n_peaks, hipStream_t st) {
+    hipLaunchKernelGGL(deliver_peaks_kernel<false>, dim3(ceil_div(max_n, 1024), n_rows), dim3(256), 0, st, table, n_sources, channels,
+                       peaks, n_peaks, (int64_t)0);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }

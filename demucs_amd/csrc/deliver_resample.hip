@@ -16,6 +16,10 @@
 // loop has no branch.  A work item is (sub-run g of 8 frames, phase i): with the bank transposed ([klen][new]) a coefficient load
 // is coalesced over the phases and feeds the item's 8 accumulators of each channel, the value reads are LDS broadcasts, and an
 // int16 stereo frame is one 4-byte store, coalesced over the phases.  Memory bound on paper; the tap loop is LDS-issue bound.
+//
+// "rescale" (v / max(1.01 * peak, 1), the peak that of the whole resampled output) takes two passes over a stream: the same body
+// instantiated to MEASURE keeps the running max |frame| per output in a slot of peaks (mi_deliver_resample_peaks), and
+// instantiated to deliver with peaks divides by what an earlier pass measured (mi_deliver_resample_pcm_peaks).
 #include "common.h"
 #include "kernels.h"
 #include "post_ops.h"
@@ -49,24 +53,43 @@ __device__ __forceinline__ void rate_taps(const float *__restrict__ kb, int nsr,
     }
 }
 
+// The three entries are this one body.  RATE_PCM is mi_deliver_resample_pcm (no "rescale": slots / peaks are not read);
+// RATE_PCM_PEAKS is mi_deliver_resample_pcm_peaks, which also takes MI_CLIP_RESCALE rows and divides by the peak in the row's slot;
+// RATE_MEASURE is mi_deliver_resample_peaks: the same history and the same tap chains, but the frames go into the running maximum
+// of the row's slot instead of a destination (FMT and DST_OFF are not read, dst is not used)
+enum { RATE_PCM = 0, RATE_PCM_PEAKS = 1, RATE_MEASURE = 2 };
+
+template <int MODE>
 __global__ __launch_bounds__(256) void deliver_resample_pcm_kernel(const int64_t *__restrict__ table, int n_sources, int channels,
                                                                    const float *__restrict__ bank, int64_t bank_cap,
                                                                    float *__restrict__ hist, int64_t hist_cap, int lds_floats,
-                                                                   unsigned char *__restrict__ dst, int64_t dst_cap) {
+                                                                   unsigned char *__restrict__ dst, int64_t dst_cap,
+                                                                   const int32_t *__restrict__ slots, unsigned *__restrict__ peaks,
+                                                                   int n_peaks) {
     extern __shared__ float xs[];
     const int64_t *t = table + (size_t)blockIdx.y * MI_RATE_COLS;
     const int64_t n_in = t[MI_RATE_N_IN], P0 = t[MI_RATE_BEFORE];
-    const int64_t kind = t[MI_RATE_KIND], sel = t[MI_RATE_SEL], clip = t[MI_RATE_CLIP], fmt = t[MI_RATE_FMT];
+    const int64_t kind = t[MI_RATE_KIND], sel = t[MI_RATE_SEL], clip = t[MI_RATE_CLIP];
+    const int64_t fmt = MODE == RATE_MEASURE ? MI_DELIVER_I16 : t[MI_RATE_FMT];
     const int64_t old_sr = t[MI_RATE_OLD], new_sr = t[MI_RATE_NEW], width = t[MI_RATE_WIDTH], bank_off = t[MI_RATE_BANK_OFF];
     const int64_t out0 = t[MI_RATE_OUT0], n_out = t[MI_RATE_N_OUT], total = t[MI_RATE_TOTAL];
     const int64_t h_len = t[MI_RATE_HIST_LEN], h_rd = t[MI_RATE_HIST_RD], h_wr = t[MI_RATE_HIST_WR];
     const int64_t h0 = t[MI_RATE_HIST_START], h1 = t[MI_RATE_HIST_NEXT];
-    const int64_t dst_off = t[MI_RATE_DST_OFF];
+    const int64_t dst_off = MODE == RATE_MEASURE ? 0 : t[MI_RATE_DST_OFF];
     const float *src = reinterpret_cast<const float *>(static_cast<uintptr_t>(t[MI_RATE_SRC]));
     // every rule under which a row is skipped whole (nothing of it is read or written); the same for the whole workgroup
+    const bool clip_ok = MODE == RATE_MEASURE ? clip == MI_CLIP_RESCALE
+                                              : clip == 0 || clip == MI_CLIP_CLAMP || clip == MI_CLIP_TANH ||
+                                                    (MODE == RATE_PCM_PEAKS && clip == MI_CLIP_RESCALE);
     if (n_in < 0 || (n_in > 0 && !src) || P0 < 0 || kind < MI_DELIVER_STEM || kind > MI_DELIVER_ADD || sel < 0 || sel >= n_sources ||
-        (clip != 0 && clip != MI_CLIP_CLAMP && clip != MI_CLIP_TANH) || fmt < MI_DELIVER_I16 || fmt > MI_DELIVER_F32)
+        !clip_ok || fmt < MI_DELIVER_I16 || fmt > MI_DELIVER_F32)
         return;
+    // a row that measures or rescales names its slot of peaks; one outside [0, n_peaks) skips the row, history included
+    int slot = 0;
+    if (MODE != RATE_PCM && clip == MI_CLIP_RESCALE) {
+        slot = slots[blockIdx.y];
+        if (slot < 0 || slot >= n_peaks) return;
+    }
     if (old_sr < 1 || new_sr < 1 || new_sr > (1 << 24) || width < 1 || old_sr > lds_floats || width > lds_floats) return;
     const int G = rate_subruns(old_sr, width, channels, lds_floats);
     const int klen = (int)(2 * width + old_sr), nsr = (int)new_sr, osr = (int)old_sr;
@@ -81,7 +104,9 @@ __global__ __launch_bounds__(256) void deliver_resample_pcm_kernel(const int64_t
         return;
     }
     const int64_t frame = (int64_t)channels * (fmt == MI_DELIVER_F32 ? 4 : 2);      // bytes
-    if (n_out > 0 && (dst_off < 0 || (dst_off & 3) != 0 || n_out > dst_cap / frame || dst_off > dst_cap - n_out * frame)) return;
+    if (MODE != RATE_MEASURE && n_out > 0 &&
+        (dst_off < 0 || (dst_off & 3) != 0 || n_out > dst_cap / frame || dst_off > dst_cap - n_out * frame))
+        return;
 
     const int64_t stem_stride = (int64_t)channels * n_in;
     const float *hr = hist + h_rd;
@@ -127,6 +152,9 @@ __global__ __launch_bounds__(256) void deliver_resample_pcm_kernel(const int64_t
     const float *bk = bank + bank_off;
     unsigned char *out = dst + dst_off;                                      // frames [0, n_out) of the row: inside dst_cap, above
     const int mode = (int)clip;
+    // the divisor of a rescaling row, read once per workgroup; every other mode ignores it
+    const float d = (MODE == RATE_PCM_PEAKS && clip == MI_CLIP_RESCALE) ? clip_divisor(peaks[slot]) : 0.f;
+    unsigned m = 0u;                                                         // RATE_MEASURE: max |frame| over this item's frames
     for (int w = threadIdx.x; w < G * nsr; w += 256) {
         const int g = w / nsr, i = w - g * nsr;
         const int f0 = g * RATE_F;
@@ -141,7 +169,11 @@ __global__ __launch_bounds__(256) void deliver_resample_pcm_kernel(const int64_t
             for (int f = 0; f < RATE_F; ++f) {
                 const int64_t r = (fA + f0 + f) * new_sr + i;
                 if (f0 + f >= nf || r >= n_out) continue;
-                const float a = clip_sample(acc[0][f], mode, 0.f), b = clip_sample(acc[1][f], mode, 0.f);
+                if (MODE == RATE_MEASURE) {       // only frames of this call: a lane past n_out holds taps of no data
+                    m = max(m, max(abs_bits(acc[0][f]), abs_bits(acc[1][f])));
+                    continue;
+                }
+                const float a = clip_sample(acc[0][f], mode, d), b = clip_sample(acc[1][f], mode, d);
                 if (fmt == MI_DELIVER_I16) {
                     const unsigned lo = (unsigned short)pcm_i16(a), hi = (unsigned short)pcm_i16(b);
                     reinterpret_cast<unsigned *>(out)[r] = lo | (hi << 16);     // 4-byte aligned: dst is, and DST_OFF is a multiple of 4
@@ -159,22 +191,53 @@ __global__ __launch_bounds__(256) void deliver_resample_pcm_kernel(const int64_t
             for (int f = 0; f < RATE_F; ++f) {
                 const int64_t r = (fA + f0 + f) * new_sr + i;
                 if (f0 + f >= nf || r >= n_out) continue;
-                const float y = clip_sample(acc[0][f], mode, 0.f);
+                if (MODE == RATE_MEASURE) {
+                    m = max(m, abs_bits(acc[0][f]));
+                    continue;
+                }
+                const float y = clip_sample(acc[0][f], mode, d);
                 const int64_t at = r * channels + c;
                 if (fmt == MI_DELIVER_I16) reinterpret_cast<short *>(out)[at] = pcm_i16(y);
                 else reinterpret_cast<float *>(out)[at] = y;
             }
         }
     }
+    if (MODE == RATE_MEASURE) {          // every work item of the workgroup arrives here: the returns above are per workgroup
+        for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+        if ((threadIdx.x & 63) == 0 && m) atomicMax(peaks + slot, m);
+    }
+}
+
+template <int MODE>
+static int launch_rate(const int64_t *table, int n_rows, int64_t max_groups, int n_sources, int channels, const float *bank,
+                       int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, unsigned char *dst, int64_t dst_cap,
+                       const int32_t *slots, unsigned *peaks, int n_peaks, hipStream_t st) {
+    hipLaunchKernelGGL(deliver_resample_pcm_kernel<MODE>, dim3((unsigned)max_groups, n_rows), dim3(256),
+                       (size_t)lds_floats * sizeof(float), st, table, n_sources, channels, bank, bank_cap, hist, hist_cap, lds_floats, dst,
+                       dst_cap, slots, peaks, n_peaks);
+    MI_CHECK_LAUNCH();
+    return MI_OK;
 }
 
 int launch_deliver_resample_pcm(const int64_t *table, int n_rows, int64_t max_groups, int n_sources, int channels, const float *bank,
                                 int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, unsigned char *dst, int64_t dst_cap,
                                 hipStream_t st) {
-    hipLaunchKernelGGL(deliver_resample_pcm_kernel, dim3((unsigned)max_groups, n_rows), dim3(256), (size_t)lds_floats * sizeof(float),
-                       st, table, n_sources, channels, bank, bank_cap, hist, hist_cap, lds_floats, dst, dst_cap);
-    MI_CHECK_LAUNCH();
-    return MI_OK;
+    return launch_rate<RATE_PCM>(table, n_rows, max_groups, n_sources, channels, bank, bank_cap, hist, hist_cap, lds_floats, dst, dst_cap,
+                                 nullptr, nullptr, 0, st);
+}
+
+int launch_deliver_resample_pcm_peaks(const int64_t *table, int n_rows, int64_t max_groups, int n_sources, int channels,
+                                      const float *bank, int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, unsigned char *dst,
+                                      int64_t dst_cap, const int32_t *slots, const unsigned *peaks, int n_peaks, hipStream_t st) {
+    return launch_rate<RATE_PCM_PEAKS>(table, n_rows, max_groups, n_sources, channels, bank, bank_cap, hist, hist_cap, lds_floats, dst,
+                                       dst_cap, slots, const_cast<unsigned *>(peaks), n_peaks, st);       // only read in this mode
+}
+
+int launch_deliver_resample_peaks(const int64_t *table, int n_rows, int64_t max_groups, int n_sources, int channels, const float *bank,
+                                  int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, const int32_t *slots, unsigned *peaks,
+                                  int n_peaks, hipStream_t st) {
+    return launch_rate<RATE_MEASURE>(table, n_rows, max_groups, n_sources, channels, bank, bank_cap, hist, hist_cap, lds_floats, nullptr,
+                                     0, slots, peaks, n_peaks, st);
 }
 
 }  // namespace mi

@@ -311,4 +311,15 @@ int launch_deliver_resample_pcm(const int64_t *table, int n_rows, int64_t max_gr
                                 int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, unsigned char *dst, int64_t dst_cap,
                                 hipStream_t st);
 
+// "rescale" on a stream: the running per-output peaks of a measuring pass (deliver.hip at the model's rate, deliver_resample.hip
+// at another), and the resampling delivery that divides by peaks measured before
+int launch_deliver_peaks_update(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks,
+                                int n_peaks, hipStream_t st);
+int launch_deliver_resample_peaks(const int64_t *table, int n_rows, int64_t max_groups, int n_sources, int channels, const float *bank,
+                                  int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, const int32_t *slots, unsigned *peaks,
+                                  int n_peaks, hipStream_t st);
+int launch_deliver_resample_pcm_peaks(const int64_t *table, int n_rows, int64_t max_groups, int n_sources, int channels,
+                                      const float *bank, int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, unsigned char *dst,
+                                      int64_t dst_cap, const int32_t *slots, const unsigned *peaks, int n_peaks, hipStream_t st);
+
 }  // namespace mi

@@ -62,10 +62,18 @@ class Delivery:
     input.  A resampler frame is final once the stream has emitted its last tap, so after `emitted` model-rate samples
     `ConvertPlan(M, R).ready(emitted)` frames have been returned (`stream.delivered`), at most `stream.output_hold` fewer than
     floor(new * emitted / old); `finish()` returns the rest, floor(new * L / old) in all.  None, or the model's own rate, changes
-    nothing."""
+    nothing.
 
-    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16", samplerate=None):
-        from .audio import clip_code, deliver_layout
+    `clip="rescale"` (the reference's default, `v / max(1.01 * peak, 1)` with the whole output's peak) takes two passes over the
+    same stream.  `peaks="measure"` is the first: `push` returns `{}` (no frames are made and nothing is copied to the host), the
+    device keeps `max |value|` per output (4 bytes each), and `finish()` returns them as an `audio.TrackPeaks`.
+    `peaks=<TrackPeaks>` is the second: the frames are divided by those peaks.  The forwards are deterministic, so with the same
+    input, the same arguments and `random` in the same state both passes see the same values, the peaks are the whole track's and
+    the frames equal `audio.deliver(..., clip="rescale")` on it bit for bit (`Separator.separate_blocks` does all of this).  A
+    `TrackPeaks` made by hand (an upper bound of a live feed's peak) gives a fixed gain of the same shape in one pass."""
+
+    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16", samplerate=None, peaks=None):
+        from .audio import TrackPeaks, clip_code, deliver_layout
         if other_method not in ("add", "minus", "none"):
             raise ValueError(f"Invalid other_method {other_method}")
         self.stem, self.other_method, self.clip, self.fmt = stem, other_method, clip, fmt
@@ -74,10 +82,27 @@ class Delivery:
         self.samplerate = None if samplerate is None else int(samplerate)
         self.clip_code = clip_code(clip)
         deliver_layout([], 0, 1, fmt)                       # refuses an unknown format
+        if peaks is not None:
+            if not (isinstance(peaks, TrackPeaks) or (isinstance(peaks, str) and peaks == "measure")):
+                raise ValueError(f"peaks must be 'measure', an audio.TrackPeaks or None, got {peaks!r}")
+            if clip != "rescale":
+                raise ValueError(f"peaks={'measure' if isinstance(peaks, str) else 'TrackPeaks(...)'!r} belongs to clip='rescale': "
+                                 f"clip={clip!r} divides by no peak")
+        self.peaks = peaks
+
+    @property
+    def measures(self) -> bool:
+        """A measuring pass: no frames, `finish()` returns the `audio.TrackPeaks`."""
+        return isinstance(self.peaks, str)
+
+    def with_peaks(self, peaks) -> "Delivery":
+        """The same delivery with other `peaks` (what a measuring pass found, for the delivering pass)."""
+        return Delivery(self.stem, self.other_method, self.clip, self.fmt, self.samplerate, peaks)
 
     def __repr__(self):
+        tail = "" if self.peaks is None else f", peaks={self.peaks!r}"
         return (f"Delivery(stem={self.stem!r}, other_method={self.other_method!r}, clip={self.clip!r}, fmt={self.fmt!r}, "
-                f"samplerate={self.samplerate!r})")
+                f"samplerate={self.samplerate!r}{tail})")
 
     def outputs(self, sources) -> list:
         """[(name, KIND, SEL)] in the reference's save order (`audio.delivery_outputs`)."""
@@ -92,9 +117,10 @@ class Delivery:
 
     def for_stream(self, sources, engine: bool, model_rate=None, channels: int = 2) -> list:
         """The refusals of a delivering stream (no device work, no RNG call) and its outputs."""
-        if self.clip == "rescale":
+        if self.clip == "rescale" and self.peaks is None:
             raise ValueError("a stream cannot deliver with clip='rescale': the divisor is the whole track's peak per output; use "
-                             "'clamp', 'tanh' or None")
+                             "'clamp', 'tanh' or None, or measure the peaks in a pass of their own (peaks='measure', then "
+                             "peaks=<the TrackPeaks it returned>)")
         if self.stem is not None and self.other_method == "minus":
             raise ValueError("a stream cannot deliver other_method='minus': it keeps no copy of its input behind the emit point; "
                              "use 'add' or 'none'")
@@ -104,16 +130,55 @@ class Delivery:
                              "implementation of the delivery kernels in this package")
         if model_rate is not None:
             self.rate_plan(model_rate, channels)
+        if self.peaks is not None and not self.measures:
+            self._check_peaks(outs, model_rate)
         return outs
 
+    def _check_peaks(self, outs, model_rate) -> None:
+        """Refuses a `TrackPeaks` that was measured for other outputs or at another rate than this stream delivers."""
+        pk = self.peaks
+        names = [name for name, _, _ in outs]
+        if list(pk.names) != names:
+            raise ValueError(f"the peaks were measured for the outputs {list(pk.names)}, this stream delivers {names}")
+        if pk.stem != self.stem or (self.stem is not None and pk.other_method != self.other_method):
+            raise ValueError(f"the peaks were measured for stem={pk.stem!r}, other_method={pk.other_method!r}, this stream delivers "
+                             f"stem={self.stem!r}, other_method={self.other_method!r}")
 
-def _deliver_rows(outputs, dl: Delivery, src: int, n: int, offs) -> list:
-    """mi_deliver_pcm's rows (MI_DELIVER_*) for one stream's outputs on a push: `n` frames of the stems at device address `src`."""
+        def rate(r):
+            return None if r is None or (model_rate is not None and int(r) == int(model_rate)) else int(r)
+
+        if rate(pk.samplerate) != rate(self.samplerate):
+            own = "the model's rate"
+            raise ValueError(f"the peaks were measured at {pk.samplerate or own} (Hz), this stream delivers at "
+                             f"{self.samplerate or own}: a resampled output has another peak")
+
+
+def _deliver_rows(outputs, dl: Delivery, src: int, n: int, offs, slot0: int = 0) -> list:
+    """mi_deliver_pcm's rows (MI_DELIVER_*) for one stream's outputs on a push: `n` frames of the stems at device address `src`.
+    Output i of a rescaling stream names peak slot `slot0 + i`; a measuring stream's rows are mi_deliver_peaks_update's, which
+    reads no destination (`offs` None)."""
     from .audio import _FORMATS
     rows = []
-    for (_, kind, sel), off in zip(outputs, offs):
-        rows += [src, 0, n, kind, sel, dl.clip_code, 0, _FORMATS[dl.fmt][0], off]
+    for i, (_, kind, sel) in enumerate(outputs):
+        rows += [src, 0, n, kind, sel, dl.clip_code, slot0 + i if dl.peaks is not None else 0, _FORMATS[dl.fmt][0],
+                 0 if offs is None else offs[i]]
     return rows
+
+
+def _packed_slots(slots) -> list:
+    """int32 peak slots as int64 table entries (two a word, little-endian), so they ride in a call's one table upload."""
+    arr = np.zeros(2 * -(-len(slots) // 2), dtype=np.int32)
+    arr[:len(slots)] = slots
+    return arr.view(np.int64).tolist()
+
+
+def _track_peaks(st: "ModelStream", bits: torch.Tensor):
+    """The `audio.TrackPeaks` of a finished measuring stream from its slots' bits (int32 on the host)."""
+    from .audio import TrackPeaks
+    dl = st.deliver
+    return TrackPeaks([name for name, _, _ in st.outputs], [int(b) & 0xFFFFFFFF for b in bits.tolist()],
+                      samplerate=None if st.rate is None else dl.samplerate, stem=dl.stem, other_method=dl.other_method,
+                      length=st.emitted)
 
 
 class _Rate:
@@ -153,7 +218,8 @@ def apply_model_stream(model, shifts: int = 1, overlap: float = 0.25, transition
     returns the newly final stems (S, channels, m); `st.finish()` returns the rest.  `device` defaults to the first block's.
     With `deliver=Delivery(...)` both return `{name: (m, channels) frames}` instead (one more launch per push, `mi_deliver_pcm`
     on the emitted span; host blocks get the frames by one D2H of their bytes and no float stems leave the device).  With
-    `Delivery(samplerate=R)` the frames are at R Hz (`mi_deliver_resample_pcm` in that launch's place).
+    `Delivery(samplerate=R)` the frames are at R Hz (`mi_deliver_resample_pcm` in that launch's place).  With
+    `Delivery(clip="rescale", peaks="measure")` `push` returns `{}` and `finish()` the `audio.TrackPeaks` (see `Delivery`).
 
     With `pcm=` ("i16", "i24" or "f32"; `channels=` source channels, the model's by default, or 1 to feed every row) a block is
     wire PCM instead: little-endian frames with the channels interleaved, as a bytes-like object or a 1-D uint8 tensor that may
@@ -243,6 +309,8 @@ class ModelStream:
         self._out_device = None
         self.deliver, self.outputs, self.rate = deliver, None, None
         self.delivered = self.output_hold = 0
+        self.measure = deliver is not None and deliver.measures      # push returns {}, finish() the audio.TrackPeaks
+        self.peak_off = None               # first of the stream's peak slots in its executor's buffer (a rescaling delivery)
         if deliver is not None:
             engine = all(m.kind != "generic" for m in self.members) and (self.device is None or self.device.type == "cuda")
             self.outputs = deliver.for_stream(self.sources, engine, self.samplerate, self.audio_channels)
@@ -579,9 +647,11 @@ class _EngineExec:
         self.bases = [0] * len(st.passes)
         self.bufs = {}
         self.rate_hist = None              # a resampling delivery's carried values (`_Rate`)
+        self.peaks = self.slots = None     # a rescaling delivery's peak bits (measured here, or given) and its rows' slots
 
     def device_bytes(self) -> int:
         n = self.win.numel() + self.acc.numel() + sum(t.numel() for b in self.bufs.values() for t in set(b))
+        n += 0 if self.peaks is None else self.peaks.numel() + self.slots.numel()
         return 4 * (n + (0 if self.rate_hist is None else self.rate_hist.numel()))
 
     def _stream(self):
@@ -742,15 +812,22 @@ class _EngineExec:
                 from .audio import _BankArena, deliver_layout, rate_groups, rate_lds_floats
                 offs, total = deliver_layout(st.outputs, n_frames, channels, dl.fmt)
                 d_at = len(passes)
+                if dl.peaks is not None and self.peaks is None:
+                    # a measuring pass's running peaks, zero at the start of the track; a rescaling delivery's peaks as given
+                    n_pk = len(st.outputs)
+                    self.peaks = torch.zeros(n_pk, dtype=torch.int32, device=st.device) if st.measure else \
+                        _upload(list(dl.peaks.bits), torch.int32, st.device)
+                    self.slots, st.peak_off = torch.arange(n_pk, dtype=torch.int32, device=st.device), 0
                 if rt is None:
-                    passes = passes + _deliver_rows(st.outputs, dl, out.data_ptr(), t1 - t0, offs)
+                    passes = passes + _deliver_rows(st.outputs, dl, out.data_ptr(), t1 - t0, None if st.measure else offs)
                 else:
                     arena = _BankArena.get(st.device)
                     if self.rate_hist is None:
                         self.rate_hist, rt.off = torch.zeros(rt.size, device=st.device, dtype=torch.float32), 0
                     passes = passes + rt.rows(st.outputs, dl, out.data_ptr(), t1 - t0, t0, st.finished, arena.offset(rt.plan), offs)
                     total = max(total, 16)                     # a call that only carries values still names a destination
-                frames = (torch.empty(total, dtype=torch.uint8, device=st.device), offs)
+                if not st.measure:          # a measuring pass makes no frames
+                    frames = (torch.empty(total, dtype=torch.uint8, device=st.device), offs)
             t_passes = _upload(passes, torch.int64, st.device)
             keep.append(t_passes)
             if t1 > t0:
@@ -762,24 +839,40 @@ class _EngineExec:
                                                    int(st.bag_weights is not None),
                                                    self.stats.data_ptr() if self.stats is not None else None,
                                                    t1 - t0, out.data_ptr(), out.numel(), self._stream()), "mi_stream_emit")
-            if dl is not None and rt is None:
+            pk = (self.peaks.data_ptr(), self.peaks.numel()) if dl is not None and dl.peaks is not None else (None, 0)
+            rows_at = C.c_void_p(t_passes.data_ptr() + 8 * d_at) if dl is not None else None
+            if dl is not None and rt is None and st.measure:
                 keep.append(out)
-                _lib.check(self.lib.mi_deliver_pcm(C.c_void_p(t_passes.data_ptr() + 8 * d_at), len(st.outputs), t1 - t0, S, channels,
-                                                   None, 0, frames[0].data_ptr(), frames[0].numel(), self._stream()),
-                           "mi_deliver_pcm")
+                _lib.check(self.lib.mi_deliver_peaks_update(rows_at, len(st.outputs), t1 - t0, S, channels, *pk, self._stream()),
+                           "mi_deliver_peaks_update")
+            elif dl is not None and rt is None:
+                keep.append(out)
+                _lib.check(self.lib.mi_deliver_pcm(rows_at, len(st.outputs), t1 - t0, S, channels, *pk, frames[0].data_ptr(),
+                                                   frames[0].numel(), self._stream()), "mi_deliver_pcm")
             elif dl is not None:
                 keep.append(out)
                 bank, hist = arena.buf, self.rate_hist
-                _lib.check(self.lib.mi_deliver_resample_pcm(C.c_void_p(t_passes.data_ptr() + 8 * d_at), len(st.outputs),
-                                                            rate_groups(rt.plan, channels, n_frames), S, channels, bank.data_ptr(),
-                                                            bank.numel(), hist.data_ptr() if hist.numel() else None, hist.numel(),
-                                                            rate_lds_floats(rt.plan, channels), frames[0].data_ptr(),
-                                                            frames[0].numel(), self._stream()), "mi_deliver_resample_pcm")
+                rate_args = (rows_at, len(st.outputs), rate_groups(rt.plan, channels, n_frames), S, channels, bank.data_ptr(),
+                             bank.numel(), hist.data_ptr() if hist.numel() else None, hist.numel(), rate_lds_floats(rt.plan, channels))
+                if st.measure:
+                    _lib.check(self.lib.mi_deliver_resample_peaks(*rate_args, self.slots.data_ptr(), *pk, self._stream()),
+                               "mi_deliver_resample_peaks")
+                elif dl.peaks is not None:
+                    _lib.check(self.lib.mi_deliver_resample_pcm_peaks(*rate_args, frames[0].data_ptr(), frames[0].numel(),
+                                                                      self.slots.data_ptr(), *pk, self._stream()),
+                               "mi_deliver_resample_pcm_peaks")
+                else:
+                    _lib.check(self.lib.mi_deliver_resample_pcm(*rate_args, frames[0].data_ptr(), frames[0].numel(), self._stream()),
+                               "mi_deliver_resample_pcm")
                 st.delivered += n_frames
         st.emitted = t1
         return out if dl is None else (frames, n_frames)
 
     def _host(self, out):
+        if self.st.measure:                 # nothing was made and nothing leaves the device; finish() reads the peaks
+            if not self.st.finished:
+                return {}
+            return _track_peaks(self.st, self.peaks.cpu())      # ONE D2H, 4 bytes per output
         if self.st.deliver is not None:
             return self._frames(*out)
         dev = self.st._out_device
@@ -867,7 +960,11 @@ class StreamGroup:
     `mi_deliver_pcm` for all of them behind the emit; their host-bound frames leave in one D2H of the byte buffer, and their float
     stems never do.  Those whose `Delivery` names another sample rate share one `mi_deliver_resample_pcm` instead (so a call has at
     most one launch more, whatever the number of streams), their frames in the same byte buffer and their carried values in the
-    group's history buffer.  Streams opened with `convert=`
+    group's history buffer.  Streams that deliver with `clip="rescale"` keep their peaks (measured by the stream, or given to it) in
+    the group's peaks buffer: a rescaling row names its slot there, the resampled rows then share one
+    `mi_deliver_resample_pcm_peaks`, and measuring streams (`peaks="measure"`: no frames, `finish` returns their `TrackPeaks`) add
+    one `mi_deliver_peaks_update` for all of them at the model's rate and one `mi_deliver_resample_peaks` for all at other rates,
+    only on calls that have such rows.  Streams opened with `convert=`
     take blocks at another sample rate or channel count: one `mi_streams_convert_append` per call runs the streaming
     `convert_audio` (demucs_amd/audio.py, `ConvertPlan`) for all of them into their windows, and what the converter has made
     final is what the stream's scheduler sees as pushed.
@@ -1149,10 +1246,38 @@ class _GroupEngineExec:
         self.hist_used = 0
         self.hist_free = {}
         self.last_upload = (0, 0)          # bytes of the last call's table and of its whole pinned upload
+        # rescaling deliveries: every stream's peak slots (one uint32 bit pattern per output) in one buffer, managed as the
+        # history regions are: a measuring stream's are zeroed when it opens, a delivering stream's hold the peaks it was given
+        self.peaks = None
+        self.peaks_used = 0
+        self.peaks_free = {}
 
     def device_bytes(self) -> int:
         n = self.state.numel() + self.stats.numel() + sum(t.numel() for b in self.bufs.values() for t in set(b))
+        n += 0 if self.peaks is None else self.peaks.numel()
         return 4 * (n + (0 if self.hist is None else self.hist.numel()))
+
+    def _peak_region(self, st: ModelStream) -> None:
+        """Slots for the peaks of `st`'s outputs in the peaks buffer, filled at the stream's first call."""
+        n = len(st.outputs)
+        if st.peak_off is not None:
+            return
+        if self.peaks_free.get(n):
+            st.peak_off = self.peaks_free[n].pop()
+        else:
+            have = 0 if self.peaks is None else self.peaks.numel()
+            if self.peaks_used + n > have:
+                grown = torch.zeros(max(2 * have, self.peaks_used + n, 64), device=self.g.device, dtype=torch.int32)
+                if have:
+                    grown[:have] = self.peaks
+                self.peaks = grown
+            st.peak_off = self.peaks_used
+            self.peaks_used += n
+        region = self.peaks[st.peak_off:st.peak_off + n]
+        if st.measure:
+            region.zero_()
+        else:
+            region.copy_(torch.tensor(list(st.deliver.peaks.bits), dtype=torch.int32))
 
     def _hist_region(self, cv, size=None) -> None:
         """Room for `cv`'s carried samples (a `_Conv`'s input, a `_Rate`'s values) in the history buffer."""
@@ -1423,6 +1548,9 @@ class _GroupEngineExec:
                     if st.rate is not None and st.rate.off is not None:
                         self.hist_free.setdefault(st.rate.size, []).append(st.rate.off)
                         st.rate.off = None
+                    if st.peak_off is not None:
+                        self.peaks_free.setdefault(len(st.outputs), []).append(st.peak_off)
+                        st.peak_off = None
                     del self.slots[key]
                     self.dead = True
                 if not self.slots:
@@ -1566,27 +1694,48 @@ class _GroupEngineExec:
         out = torch.empty(off, device=g.device, dtype=torch.float32) if off else None
         d_rows, d_layout, d_off, d_host, d_longest = [], {}, 0, 0, 1
         r_rows, r_groups, r_lds, d_count = [], 1, 1, {}
+        # rescaling deliveries: the peak slot of every resampled row (-1: the row does not rescale), and the measuring streams'
+        # rows, which make no frames: mi_deliver_peaks_update's at the model's rate, mi_deliver_resample_peaks' at another
+        r_slots, r_rescales = [], False
+        m_rows, m_longest, mr_rows, mr_slots, mr_groups, mr_lds = [], 1, [], [], 1, 1
         for key, st, t0, _, to_host in sorted(spans, key=lambda s: not s[4]):
             f_off, n = layout[key]
-            rt = st.rate
-            if st.deliver is None or (n == 0 and rt is None):
+            rt, dl = st.rate, st.deliver
+            if dl is None:
                 continue
+            if dl.peaks is not None:
+                self._peak_region(st)
+            if n == 0 and rt is None:
+                continue
+            src = out.data_ptr() + 4 * f_off if n else 0
             if rt is not None:
                 # the frames whose last tap is emitted; a finishing stream has a tail even when it emits nothing
                 n_out = rt.plan.step(t0, n, st.finished)[1]
                 if n == 0 and n_out == 0:
                     continue
                 self._hist_region(rt, rt.size)
-                offs, d_off = deliver_layout(st.outputs, n_out, C_, st.deliver.fmt, d_off)
-                r_rows += rt.rows(st.outputs, st.deliver, out.data_ptr() + 4 * f_off if n else 0, n, t0, st.finished,
-                                  _BankArena.get(g.device).offset(rt.plan), offs)
+                bank_off = _BankArena.get(g.device).offset(rt.plan)
+                st.delivered += n_out
+                if st.measure:
+                    mr_rows += rt.rows(st.outputs, dl, src, n, t0, st.finished, bank_off, [0] * len(st.outputs))
+                    mr_slots += range(st.peak_off, st.peak_off + len(st.outputs))
+                    mr_groups = max(mr_groups, rate_groups(rt.plan, C_, n_out))
+                    mr_lds = max(mr_lds, rate_lds_floats(rt.plan, C_))
+                    continue
+                offs, d_off = deliver_layout(st.outputs, n_out, C_, dl.fmt, d_off)
+                r_rows += rt.rows(st.outputs, dl, src, n, t0, st.finished, bank_off, offs)
+                r_slots += range(st.peak_off, st.peak_off + len(st.outputs)) if dl.peaks is not None else [-1] * len(st.outputs)
+                r_rescales = r_rescales or dl.peaks is not None
                 r_groups = max(r_groups, rate_groups(rt.plan, C_, n_out))
                 r_lds = max(r_lds, rate_lds_floats(rt.plan, C_))
-                st.delivered += n_out
                 d_layout[key], d_count[key] = offs, n_out
+            elif st.measure:
+                m_rows += _deliver_rows(st.outputs, dl, src, n, None, st.peak_off)
+                m_longest = max(m_longest, n)
+                continue
             else:
-                offs, d_off = deliver_layout(st.outputs, n, C_, st.deliver.fmt, d_off)
-                d_rows += _deliver_rows(st.outputs, st.deliver, out.data_ptr() + 4 * f_off, n, offs)
+                offs, d_off = deliver_layout(st.outputs, n, C_, dl.fmt, d_off)
+                d_rows += _deliver_rows(st.outputs, dl, src, n, offs, st.peak_off or 0)
                 d_layout[key], d_count[key] = offs, n
                 d_longest = max(d_longest, n)
             if to_host:
@@ -1595,11 +1744,21 @@ class _GroupEngineExec:
         table += d_rows
         r_at = len(table)
         table += r_rows
+        rs_at = len(table)
+        table += _packed_slots(r_slots) if r_rescales else []
+        m_at = len(table)
+        table += m_rows
+        mr_at = len(table)
+        table += mr_rows
+        mrs_at = len(table)
+        table += _packed_slots(mr_slots)
         return dict(at=at, n_streams=len(streams) // STREAMS_EMIT_COLS, n_passes=len(passes) // 8, n_segs=len(segs) // 2,
                     total=off, host_n=host_n, longest=longest, layout=layout, order=[k for k, _, _ in work],
                     streams={k: st for k, st, _ in work}, out=out, d_at=d_at, d_rows=len(d_rows) // DELIVER_COLS, d_total=d_off,
                     d_host=d_host, d_longest=d_longest, d_layout=d_layout, d_count=d_count, r_at=r_at,
-                    r_rows=len(r_rows) // RATE_COLS, r_groups=r_groups, r_lds=r_lds)
+                    r_rows=len(r_rows) // RATE_COLS, r_groups=r_groups, r_lds=r_lds, r_rescales=r_rescales, rs_at=rs_at,
+                    m_at=m_at, m_rows=len(m_rows) // DELIVER_COLS, m_longest=m_longest, mr_at=mr_at,
+                    mr_rows=len(mr_rows) // RATE_COLS, mr_groups=mr_groups, mr_lds=mr_lds, mrs_at=mrs_at)
 
     def _emit(self, emit, base) -> dict:
         g = self.g
@@ -1621,16 +1780,30 @@ class _GroupEngineExec:
         if emit["d_rows"] or emit["r_rows"]:
             # at least 16 bytes: a call on which resampling streams only carry values still names a destination
             frames = torch.empty(max(emit["d_total"], 16), dtype=torch.uint8, device=dev)
+        pk = (None, 0) if self.peaks is None else (self.peaks.data_ptr(), self.peaks.numel())
         if emit["d_rows"]:
-            _lib.check(self.lib.mi_deliver_pcm(C.c_void_p(base + 8 * emit["d_at"]), emit["d_rows"], emit["d_longest"], S, C_, None, 0,
+            _lib.check(self.lib.mi_deliver_pcm(C.c_void_p(base + 8 * emit["d_at"]), emit["d_rows"], emit["d_longest"], S, C_, *pk,
                                                frames.data_ptr(), frames.numel(), self._stream()), "mi_deliver_pcm")
-        if emit["r_rows"]:
+        if emit["r_rows"] or emit["mr_rows"]:
             from .audio import _BankArena
             bank, hist = _BankArena.get(dev).buf, self.hist
-            _lib.check(self.lib.mi_deliver_resample_pcm(C.c_void_p(base + 8 * emit["r_at"]), emit["r_rows"], emit["r_groups"], S, C_,
-                                                        bank.data_ptr(), bank.numel(), hist.data_ptr(), hist.numel(), emit["r_lds"],
-                                                        frames.data_ptr(), frames.numel(), self._stream()),
-                       "mi_deliver_resample_pcm")
+        if emit["r_rows"]:
+            rate_args = (C.c_void_p(base + 8 * emit["r_at"]), emit["r_rows"], emit["r_groups"], S, C_, bank.data_ptr(), bank.numel(),
+                         hist.data_ptr(), hist.numel(), emit["r_lds"], frames.data_ptr(), frames.numel())
+            if emit["r_rescales"]:          # a row among them divides by its peak: the entry that reads the slots
+                _lib.check(self.lib.mi_deliver_resample_pcm_peaks(*rate_args, C.c_void_p(base + 8 * emit["rs_at"]), *pk,
+                                                                  self._stream()), "mi_deliver_resample_pcm_peaks")
+            else:
+                _lib.check(self.lib.mi_deliver_resample_pcm(*rate_args, self._stream()), "mi_deliver_resample_pcm")
+        # the measuring streams: one launch for those at the model's rate, one for those at another, and only when there are any
+        if emit["m_rows"]:
+            _lib.check(self.lib.mi_deliver_peaks_update(C.c_void_p(base + 8 * emit["m_at"]), emit["m_rows"], emit["m_longest"], S, C_,
+                                                        *pk, self._stream()), "mi_deliver_peaks_update")
+        if emit["mr_rows"]:
+            _lib.check(self.lib.mi_deliver_resample_peaks(C.c_void_p(base + 8 * emit["mr_at"]), emit["mr_rows"], emit["mr_groups"], S,
+                                                          C_, bank.data_ptr(), bank.numel(), hist.data_ptr(), hist.numel(),
+                                                          emit["mr_lds"], C.c_void_p(base + 8 * emit["mrs_at"]), *pk, self._stream()),
+                       "mi_deliver_resample_peaks")
         host = host_frames = None
         if emit["host_n"]:
             host = torch.empty(emit["host_n"], dtype=torch.float32, pin_memory=True)
@@ -1645,7 +1818,9 @@ class _GroupEngineExec:
             off, n = emit["layout"][key]
             st = emit["streams"][key]
             to = st._out_device
-            if st.deliver is not None:
+            if st.measure:                  # no frames; a finishing stream's peaks come back by ONE D2H of 4 bytes per output
+                res[key] = _track_peaks(st, self.peaks[st.peak_off:st.peak_off + len(st.outputs)].cpu()) if st.finished else {}
+            elif st.deliver is not None:
                 res[key] = self._frames(st, emit["d_count"].get(key, 0), emit["d_layout"].get(key), frames, host_frames,
                                         emit["d_host"])
             elif n == 0:

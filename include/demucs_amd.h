@@ -547,7 +547,8 @@ int mi_deliver_pcm(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int3
  *                         MI_DELIVER_SRC; may be 0 when n_in == 0);
  *     BEFORE              model-rate samples emitted before this call;
  *     KIND, SEL, CLIP, FMT  as MI_DELIVER_*: KIND is MI_DELIVER_STEM or MI_DELIVER_ADD, CLIP 0, MI_CLIP_CLAMP or MI_CLIP_TANH (the
- *                         whole-track modes "minus" and "rescale" do not exist on a stream);
+ *                         whole-track modes "minus" and "rescale" do not exist on a stream: this entry skips such a row.  A stream
+ *                         rescales in two passes by mi_deliver_resample_peaks and mi_deliver_resample_pcm_peaks, below);
  *     OLD, NEW, WIDTH, BANK_OFF   the rate entry as MI_CVT_*: the kernel bank TRANSPOSED, (klen, new) float32, at float offset bank_off
  *                         of bank_dev; width >= 1 (equal rates are mi_deliver_pcm's);
  *     OUT0, N_OUT         the first output frame (a multiple of new) and the number of frames to write;
@@ -590,6 +591,38 @@ int mi_deliver_pcm(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int3
 int mi_deliver_resample_pcm(const int64_t *table_dev, int32_t n_rows, int64_t max_groups, int32_t n_sources, int32_t channels,
                             const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity, int32_t lds_floats,
                             void *dst_dev, int64_t dst_capacity, void *stream);
+
+/* ---- "rescale" on a stream: peaks measured by one pass over the stream, frames delivered by a second ---------------------------
+ * `prevent_clip(wav, "rescale")` divides by max(1.01 * wav.abs().max(), 1) (demucs/audio.py:225-227), the whole output's peak.  A
+ * stream's forwards are deterministic, so a first pass that keeps only max |value| per output (4 bytes each, on the device) finds
+ * the peaks a second pass of the same stream divides by; the frames are mi_deliver_peaks + mi_deliver_pcm's on the whole track.
+ * peaks_dev: n_peaks uint32, the bit patterns of float32 max |value| as mi_deliver_peaks writes them (a NaN sample leaves a NaN
+ * pattern, which orders above +inf).  The caller zeroes a slot at the start of a track; nothing here does, and nothing
+ * synchronises with the host.
+ * mi_deliver_peaks_update: mi_deliver_peaks without the memset: max |value| of every row goes into peaks_dev[PEAK] by atomicMax,
+ *   so the slots carry the running maximum over the calls of a track.  Rows are MI_DELIVER_* rows with CLIP == MI_CLIP_RESCALE
+ *   (others are skipped); FMT and DST_OFF are not read, and no row is skipped for a destination.  The other skip rules are
+ *   mi_deliver_peaks': N <= 0, SRC 0, KIND / SEL out of range, PEAK outside [0, n_peaks), a MI_DELIVER_MINUS row without ORIGIN.
+ *   Delivering at the model's rate with peaks measured before needs no entry of its own: mi_deliver_pcm takes peaks_dev.
+ * mi_deliver_resample_peaks: mi_deliver_resample_pcm's arguments without dst, on the same MI_RATE_* rows with CLIP ==
+ *   MI_CLIP_RESCALE (others are skipped whole); FMT and DST_OFF are not read.  The history is carried exactly as
+ *   mi_deliver_resample_pcm carries it, every frame that entry would write on this call is computed by the same fmaf chain, and
+ *   max |frame| over frames [OUT0, OUT0 + N_OUT) and channels < channels goes into peaks_dev[slots_dev[r]] for row r: a
+ *   reduction over the wave, then one atomicMax per wave, none when the wave's maximum is 0.  slots_dev: n_rows int32, a DEVICE
+ *   array.  A row whose slot is outside [0, n_peaks) is skipped whole, its history included.
+ * mi_deliver_resample_pcm_peaks: mi_deliver_resample_pcm with slots_dev and peaks_dev (read only).  It also takes rows with CLIP
+ *   == MI_CLIP_RESCALE and writes v / max(1.01 * peak, 1) for them (mi_prevent_clip's operations, the divisor formed once per
+ *   workgroup from peaks_dev[slots_dev[r]]); such a row with a slot outside [0, n_peaks) is skipped whole.  slots_dev[r] is not
+ *   read for a row of another CLIP, whose bytes are mi_deliver_resample_pcm's.  peaks_dev may be null when n_peaks == 0. */
+int mi_deliver_peaks_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels, void *peaks_dev,
+                            int32_t n_peaks, void *stream);
+int mi_deliver_resample_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_groups, int32_t n_sources, int32_t channels,
+                              const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity, int32_t lds_floats,
+                              const int32_t *slots_dev, void *peaks_dev, int32_t n_peaks, void *stream);
+int mi_deliver_resample_pcm_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_groups, int32_t n_sources, int32_t channels,
+                                  const float *bank_dev, int64_t bank_capacity, float *hist_dev, int64_t hist_capacity, int32_t lds_floats,
+                                  void *dst_dev, int64_t dst_capacity, const int32_t *slots_dev, const void *peaks_dev, int32_t n_peaks,
+                                  void *stream);
 
 /* ---- kernel-level entry points (parity tests; same kernels the forward uses) --------------
  * mi_stft_cac: `_magnitude(_spec(mix))` (demucs/htdemucs.py:420-461, demucs/spec.py:11-27):
