@@ -122,6 +122,11 @@ SIGNATURES = {
     "mi_deliver_resample_pcm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "mi_deliver_peaks_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mi_deliver_mix_pcm": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
+    "mi_deliver_mix_peaks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
+                                       C.c_void_p]),
+    "mi_deliver_mix_peaks_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "mi_deliver_resample_peaks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mi_deliver_resample_pcm_peaks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
@@ -179,6 +184,7 @@ SIGNATURES = {
     "mi_debug_set_post_launch_hook": (None, [C.c_void_p]),
     "mi_debug_last_conv_route": (C.c_int, []),
     "mi_debug_last_conv_tile": (C.c_int, []),
+    "mi_debug_conv_staged": (C.c_int, []),
     "mi_debug_conv_route_launches": (C.c_int64, [C.c_int32, C.c_int32]),
     "mi_debug_conv_route": (C.c_int, [C.POINTER(MiConvDesc), C.POINTER(C.c_int)]),
     "mi_debug_switches": (C.c_int, [C.c_char_p, C.c_int32]),

@@ -153,8 +153,8 @@ class Separator:
         With `deliver=Delivery(...)` (demucs_amd/stream.py) `push` / `finish` return what the reference would write to its files
         for those samples instead: `{name: (m, channels) frames}` in the order of its save loop, after `prevent_clip` and as
         int16 PCM or float32 with interleaved channels -- `audio.deliver`'s chain on the stems above, by one more launch per
-        push.  A stream refuses other_method="minus", which needs the whole track, and clip="rescale" without peaks: the divisor
-        is the whole output's peak.  `Delivery(clip="rescale", peaks="measure")` is a pass that finds those peaks: `push` returns
+        push.  A stream refuses the spelling other_method="minus" (the residual is `Delivery(mix={"minus_STEM": {"mix": 1,
+        STEM: -1}})`, below) and clip="rescale" without peaks: the divisor is the whole output's peak.  `Delivery(clip="rescale", peaks="measure")` is a pass that finds those peaks: `push` returns
         `{}`, nothing is copied to the host, and `finish()` returns an `audio.TrackPeaks`; a second stream over the same input, with
         the same arguments, `random` in the same state and `Delivery(clip="rescale", peaks=<that TrackPeaks>)`, delivers the
         frames of `audio.deliver(..., clip="rescale")` bit for bit (`separate_blocks` runs both).
@@ -165,6 +165,11 @@ class Separator:
         the rest, floor(new * L / old) in all for L samples at M.  With `convert=True` and `samplerate=sr` a feed gets its stems back
         at its own rate; the length then is floor(new' * floor(new * N / old) / old') for N input samples (sr -> M reduces to
         old:new, M -> sr to old':new'), which can be a sample or two short of N: nothing is padded.
+
+        `Delivery(mix={output: {"mix" | source: gain}})` returns gain-weighted remixes of the stems and of the input mix instead
+        (vocals lowered rather than removed, `mix - vocals`): `audio.deliver_mix(origin, stems, mix, ...)` on the whole track bit
+        for bit, `origin` being the mix as `separate_tensor` hands back a device mix.  The stream reads the mix from its own input
+        window (`mi_deliver_mix_pcm` in the delivery launch's place), so nothing is kept for it.
 
         With `pcm=` ("i16", "i24" or "f32") a block is what a socket, a capture device or a WAV file read in pieces delivers:
         little-endian frames with the channels interleaved, as a bytes-like object or a 1-D uint8 tensor that may end anywhere

@@ -815,10 +815,12 @@ class TrackPeaks:
     output: the bit pattern of the float32 `max |value|` as `mi_deliver_peaks` writes it (a NaN sample gives a NaN pattern),
     `samplerate` the rate of the delivered frames the peaks were measured at (None: the model's), `length` the model-rate samples
     measured.  Constructible by hand: a caller who knows an upper bound of a live feed's peak passes its bits and gets the fixed,
-    reference-shaped gain `v / max(1.01 * peak, 1)`.  Immutable."""
-    __slots__ = ("names", "bits", "samplerate", "stem", "other_method", "length")
+    reference-shaped gain `v / max(1.01 * peak, 1)`.  Peaks of gain-weighted remixes (`Delivery(mix=...)`) carry the remixes'
+    identity in `mix`: `((output name, (g_mix, g_0 .. g_{S-1})), ...)`, the float32 gains per source as `mix_gains` resolves them
+    (None: the outputs are the reference's).  Immutable."""
+    __slots__ = ("names", "bits", "samplerate", "stem", "other_method", "length", "mix")
 
-    def __init__(self, names, bits, samplerate=None, stem=None, other_method: str = "add", length: int = 1):
+    def __init__(self, names, bits, samplerate=None, stem=None, other_method: str = "add", length: int = 1, mix=None):
         import numpy as np
         if isinstance(names, (str, bytes)) or not all(isinstance(n, str) for n in names):
             raise ValueError(f"TrackPeaks: names must be a sequence of output names, got {names!r}")
@@ -827,6 +829,18 @@ class TrackPeaks:
             raise ValueError(f"Invalid other_method {other_method}")
         if stem is not None and not isinstance(stem, str):
             raise ValueError(f"TrackPeaks: stem must be a source name or None, got {stem!r}")
+        if mix is not None:
+            if stem is not None:
+                raise ValueError(f"TrackPeaks: mix belongs to stem=None, got stem={stem!r}")
+            try:
+                mix = tuple((str(name), tuple(float(np.float32(g)) for g in gains)) for name, gains in mix)
+            except (TypeError, ValueError):
+                raise ValueError(f"TrackPeaks: mix must be ((output name, (g_mix, g_0, ...)), ...) as audio.mix_gains returns it, "
+                                 f"got {mix!r}") from None
+            if tuple(name for name, _ in mix) != names or len({len(g) for _, g in mix}) > 1 or \
+                    not all(len(g) >= 2 and all(np.isfinite(v) for v in g) for _, g in mix):
+                raise ValueError(f"TrackPeaks: mix must name the outputs {list(names)} in order, each with finite gains for the mix "
+                                 f"and every source, got {mix!r}")
         if stem is None:
             if not names or len(set(names)) != len(names):
                 raise ValueError(f"TrackPeaks: names must be the separated sources, each once, got {list(names)}")
@@ -852,7 +866,7 @@ class TrackPeaks:
         if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 1:
             raise ValueError(f"TrackPeaks: length must be a positive integer, got {length!r}")
         for name, v in zip(self.__slots__, (names, tuple(vals), None if samplerate is None else int(samplerate), stem, other_method,
-                                            int(length))):
+                                            int(length), mix)):
             object.__setattr__(self, name, v)
 
     @classmethod
@@ -889,7 +903,8 @@ class TrackPeaks:
 
     def __repr__(self):
         return (f"TrackPeaks(names={list(self.names)}, bits={[hex(b) for b in self.bits]}, samplerate={self.samplerate}, "
-                f"stem={self.stem!r}, other_method={self.other_method!r}, length={self.length})")
+                f"stem={self.stem!r}, other_method={self.other_method!r}, length={self.length}"
+                + ("" if self.mix is None else f", mix={self.mix!r}") + ")")
 
 
 def _stems_block(tensors, dev: torch.device) -> torch.Tensor:
@@ -1048,6 +1063,134 @@ def deliver(origin: torch.Tensor, stems: dict, stem=None, other_method: str = "a
         _lib.check(lib.mi_deliver_pcm(table.data_ptr(), len(outputs), n, len(names), channels,
                                       peaks.data_ptr() if peaks is not None else None, 0 if peaks is None else len(outputs),
                                       buf.data_ptr(), total, stream), "mi_deliver_pcm")
+        if home.type == "cpu":
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            host.copy_(buf, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            buf = host
+        elif home != dev:
+            buf = buf.to(home)
+    return deliver_views(buf, outputs, offs, n, channels, fmt)
+
+
+# ---- gain-weighted remixes of the stems and the mix (mi_deliver_mix_*, demucs_amd/csrc/deliver_mix.hip) --------------------------
+MIX_COLS = 15                      # include/demucs_amd.h: MI_MIX_*
+MIX_GAINS_AT, MIX_CLIP_AT, MIX_MAX_SOURCES = 6, 11, 8      # the nine gains take the five words before CLIP
+
+
+def mix_gains(mix, sources=None) -> list:
+    """`mix` -- `{output name: {"mix" | source name: gain}}` -- checked, its gains rounded to float32 once, outputs in dict order.
+    With `sources` it is resolved against them: `[(name, (g_mix, g_0 .. g_{S-1}))]`, a term that is not named having gain 0;
+    without, what can be checked before the sources are known is, and `[(name, {key: gain})]` comes back.  Raises ValueError for
+    an empty `mix`, an unknown source, a source literally named "mix", a non-finite gain, an output whose gains are all 0, or more
+    than 8 sources."""
+    import numpy as np
+    if not isinstance(mix, dict) or not mix:
+        raise ValueError(f"mix: a non-empty {{output name: {{'mix' | source name: gain}}}} is expected, got {mix!r}")
+    if sources is not None:
+        sources = list(sources)
+        if len(sources) > MIX_MAX_SOURCES:
+            raise ValueError(f"mix: at most {MIX_MAX_SOURCES} sources, got {len(sources)}")
+        if "mix" in sources:
+            raise ValueError("mix: a source is named 'mix', the name of the input mix in a remix; rename the source")
+    out = []
+    for name, gains in mix.items():
+        if not isinstance(name, str):
+            raise ValueError(f"mix: an output name is a string, got {name!r}")
+        if not isinstance(gains, dict):
+            raise ValueError(f"mix: output {name!r} needs {{'mix' | source name: gain}}, got {gains!r}")
+        vals = {}
+        for key, g in gains.items():
+            if sources is not None and key != "mix" and key not in sources:
+                raise ValueError(f"mix: output {name!r} names {key!r}, which is neither 'mix' nor one of the separated sources {sources}")
+            if isinstance(g, (bool, str, bytes)) or not isinstance(key, str):
+                raise ValueError(f"mix: output {name!r} needs {{'mix' | source name: gain}}, got {key!r}: {g!r}")
+            try:
+                with np.errstate(over="ignore"):
+                    v = np.float32(g)
+            except (TypeError, ValueError):
+                raise ValueError(f"mix: the gain of {key!r} in output {name!r} must be a number, got {g!r}") from None
+            if not np.isfinite(v):
+                raise ValueError(f"mix: the gain of {key!r} in output {name!r} must be finite in float32, got {g!r}")
+            vals[key] = float(v)
+        if not any(v != 0 for v in vals.values()):
+            raise ValueError(f"mix: every gain of output {name!r} is 0; it would be silence")
+        out.append((name, vals))
+    if sources is None:
+        return out
+    return [(name, tuple(vals.get(k, 0.0) for k in ["mix"] + sources)) for name, vals in out]
+
+
+def mix_outputs(gains) -> list:
+    """[(name, None, index)] of resolved remixes, the shape `deliver_layout` and `deliver_views` take."""
+    return [(name, None, i) for i, (name, _) in enumerate(gains)]
+
+
+def mix_identity(gains) -> tuple:
+    """Resolved remixes as `TrackPeaks.mix` keeps them."""
+    return tuple((name, tuple(g)) for name, g in gains)
+
+
+def mix_rows(gains, src: int, n: int, origin: int, pitch: int, affine, clip: int, slot0: int, fmt: str, offs) -> list:
+    """mi_deliver_mix_pcm's rows (MI_MIX_*) for resolved remixes of `n` frames of the stems at device address `src`.  `origin` is
+    the device address of the mix's frame 0 (channel rows `pitch` floats apart; 0: no remix reads it), `affine` (mean, s) when it is
+    stored normalised.  Remix i names peak slot `slot0 + i`; `offs` None: rows without a destination (mi_deliver_mix_peaks_update)."""
+    import numpy as np
+    aff = 0 if affine is None else int(np.array(affine, dtype=np.float32).view(np.int64)[0])
+    rows = []
+    for i, (_, g) in enumerate(gains):
+        packed = np.zeros(2 * (MIX_CLIP_AT - MIX_GAINS_AT), dtype=np.float32)
+        packed[:len(g)] = g
+        rows += [src, n, origin, pitch, aff, int(affine is not None), *packed.view(np.int64).tolist(), clip, slot0 + i,
+                 _FORMATS[fmt][0], 0 if offs is None else offs[i]]
+    return rows
+
+
+
+def deliver_mix(origin: torch.Tensor, stems: dict, mix: dict, clip="rescale", fmt: str = "i16") -> dict:
+    """Gain-weighted remixes of one separated track, what a user of the reference writes after `separate_tensor` as
+    `save_audio(sum(g * x for ...), path, clip=clip)`: `{name: (n, channels) frames}` in `mix`'s order, `mix` being `{output
+    name: {"mix" | source name: gain}}` ("mix" is `origin`).  Per sample `acc = 0`, then `acc = acc + g * x` for the mix first and
+    the sources in the stems' order, every product and sum rounded to float32 and a term with gain 0 left out (never read: a NaN
+    in a muted stem stays out); then `prevent_clip(·, clip)` with the peak per output, `i16_pcm` ("i16") or float32 ("f32"), the
+    channels interleaved.  `{"mix": 1, STEM: -1}` is the reference's "minus" output, gains of 1 on all sources but one its "add".
+    All remixes of the track take ONE `mi_deliver_mix_peaks` launch (only for "rescale") and ONE `mi_deliver_mix_pcm` launch;
+    host stems come back on the host by one D2H of the byte buffer."""
+    names = list(stems)
+    gains = mix_gains(mix, names)
+    outputs = mix_outputs(gains)
+    code = clip_code(clip)
+    if fmt not in _FORMATS:
+        raise ValueError(f"Invalid format {fmt!r}: 'i16' or 'f32'")
+    tensors = [stems[k] for k in names]
+    for t in tensors:
+        if not t.dtype.is_floating_point:
+            raise TypeError(f"deliver_mix: a floating-point tensor is expected, got {t.dtype}")
+        if t.dim() != 2 or t.shape != tensors[0].shape:
+            raise ValueError(f"deliver_mix: every stem is (channels, n), got {[tuple(x.shape) for x in tensors]}")
+    channels, n = tensors[0].shape
+    home = tensors[0].device
+    if n == 0 or channels == 0:
+        return {name: torch.empty(n, channels, dtype=_FORMATS[fmt][1], device=home) for name, _ in gains}
+    dev = _engine_device(*tensors)
+    with torch.cuda.device(dev):
+        block = _stems_block(tensors, dev)
+        org = _stage(origin, dev, "deliver_mix") if any(g[0] != 0 for _, g in gains) else None
+        if org is not None and org.shape != (channels, n):
+            raise ValueError(f"deliver_mix: the mix is {tuple(org.shape)}, the stems are {(channels, n)}")
+        offs, total = deliver_layout(outputs, n, channels, fmt)
+        rows = mix_rows(gains, block.data_ptr(), n, 0 if org is None else org.data_ptr(), n, None, code, 0, fmt, offs)
+        table = torch.tensor(rows, dtype=torch.int64).to(dev)
+        buf = torch.empty(total, dtype=torch.uint8, device=dev)
+        lib, stream = _lib.load(), C.c_void_p(_lib.current_stream_ptr())
+        peaks = None
+        if code == _CLIP_MODES["rescale"]:
+            peaks = torch.empty(len(outputs), dtype=torch.int32, device=dev)
+            _lib.check(lib.mi_deliver_mix_peaks(table.data_ptr(), len(outputs), n, len(names), channels, peaks.data_ptr(),
+                                                len(outputs), total, stream), "mi_deliver_mix_peaks")
+        _lib.check(lib.mi_deliver_mix_pcm(table.data_ptr(), len(outputs), n, len(names), channels,
+                                          peaks.data_ptr() if peaks is not None else None, 0 if peaks is None else len(outputs),
+                                          buf.data_ptr(), total, stream), "mi_deliver_mix_pcm")
         if home.type == "cpu":
             host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
             host.copy_(buf, non_blocking=True)

@@ -128,6 +128,37 @@ static Engine *engine_of(void *handle, EngineKind want, const char *entry) {
     }
     return static_cast<Engine *>(core);
 }
+// mi_conv_forward and the read slack of the shifted-run loaders (routes 2, 7 and 11: up to 8 bytes before and 20 bytes after the
+// tensor at x, gemm_loop.h TapRows / TimeTrTaps / TimeEncTaps).  The engines give their buffers that slack; a caller of the C entry
+// may hand in a tensor that begins or ends with its device allocation, and the transfer would then touch an address that is not
+// mapped.  True when the allocation that holds x reaches kConvSlack bytes past both ends of the tensor
+constexpr size_t kConvSlack = 128;
+int g_conv_staged = 0;                 // mi_debug_conv_staged
+static bool conv_reads_slack(int route) { return route == MI_ROUTE_DMATAP || route == MI_ROUTE_TAP_X6 || route == MI_ROUTE_TIME_X6; }
+static bool conv_owns_slack(const float *x, size_t bytes) {
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)x) != hipSuccess) {
+        (void)hipGetLastError();       // not an allocation the runtime knows: nothing to rely on
+        return false;
+    }
+    const uintptr_t lo = (uintptr_t)base, hi = lo + size, p = (uintptr_t)x;
+    return p >= lo + kConvSlack && p + bytes + kConvSlack <= hi;
+}
+// ... else the layer runs on a copy of x that has the slack: the same kernel on the same values.  The copy is scratch of the
+// call, freed after the stream has been waited for
+static int conv_forward_staged(const mi_conv_desc &din, size_t bytes, hipStream_t st) {
+    TestScratch ws;
+    unsigned char *buf = nullptr;
+    MI_TRY(ws.get(bytes + 2 * kConvSlack, &buf));
+    MI_HIP(hipMemsetAsync(buf, 0, bytes + 2 * kConvSlack, st));
+    MI_HIP(hipMemcpyAsync(buf + kConvSlack, din.x, bytes, hipMemcpyDeviceToDevice, st));
+    mi_conv_desc d = din;
+    d.x = reinterpret_cast<const float *>(buf + kConvSlack);
+    ++g_conv_staged;
+    return finish_entry(launch_conv(d, st), st, "mi_conv_forward");
+}
+
 static Model *as_model(void *handle, const char *entry) { return engine_of<Model>(handle, ENGINE_HTDEMUCS, entry); }
 static HModel *as_hmodel(void *handle, const char *entry) { return engine_of<HModel>(handle, ENGINE_HDEMUCS, entry); }
 
@@ -141,6 +172,7 @@ const char *mi_last_error(void) { return last_error_buf(); }
 void mi_debug_set_post_launch_hook(void (*hook)(void *stream)) { g_post_launch_hook = hook; }
 int mi_debug_last_conv_route(void) { return g_last_conv_route; }
 int mi_debug_last_conv_tile(void) { return g_last_conv_tile; }
+int mi_debug_conv_staged(void) { return g_conv_staged; }
 int64_t mi_debug_conv_route_launches(int32_t route, int32_t epi) {
     if (route < 0 || route >= 16 || epi >= 8) return -1;
     int64_t n = 0;
@@ -628,6 +660,33 @@ int mi_deliver_resample_pcm_peaks(const int64_t *table_dev, int32_t n_rows, int6
                                              (const unsigned *)peaks_dev, n_peaks, (hipStream_t)stream);
 }
 
+int mi_deliver_mix_pcm(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels,
+                       const void *peaks_dev, int32_t n_peaks, void *dst_dev, int64_t dst_capacity, void *stream) {
+    MI_REQUIRE(table_dev && dst_dev && n_rows > 0 && n_rows <= 65535 && max_n >= 1 && max_n <= (int64_t)INT32_MAX * 1024 &&
+               n_sources > 0 && n_sources <= MI_MIX_MAX_SOURCES && channels > 0 && n_peaks >= 0 && (n_peaks == 0 || peaks_dev) &&
+               dst_capacity >= 0, "mi_deliver_mix_pcm: bad argument");
+    MI_REQUIRE(((uintptr_t)dst_dev & 3) == 0, "mi_deliver_mix_pcm: dst_dev must be 4-byte aligned");
+    return launch_deliver_mix_pcm(table_dev, n_rows, max_n, n_sources, channels, (const unsigned *)peaks_dev, n_peaks,
+                                  (unsigned char *)dst_dev, dst_capacity, (hipStream_t)stream);
+}
+
+int mi_deliver_mix_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels, void *peaks_dev,
+                         int32_t n_peaks, int64_t dst_capacity, void *stream) {
+    MI_REQUIRE(table_dev && peaks_dev && n_rows > 0 && n_rows <= 65535 && max_n >= 1 && max_n <= (int64_t)INT32_MAX * 1024 &&
+               n_sources > 0 && n_sources <= MI_MIX_MAX_SOURCES && channels > 0 && n_peaks > 0 && dst_capacity >= 0,
+               "mi_deliver_mix_peaks: bad argument");
+    return launch_deliver_mix_peaks(table_dev, n_rows, max_n, n_sources, channels, (unsigned *)peaks_dev, n_peaks, dst_capacity,
+                                    (hipStream_t)stream);
+}
+
+int mi_deliver_mix_peaks_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels,
+                                void *peaks_dev, int32_t n_peaks, void *stream) {
+    MI_REQUIRE(table_dev && peaks_dev && n_rows > 0 && n_rows <= 65535 && max_n >= 1 && max_n <= (int64_t)INT32_MAX * 1024 &&
+               n_sources > 0 && n_sources <= MI_MIX_MAX_SOURCES && channels > 0 && n_peaks > 0, "mi_deliver_mix_peaks_update: bad argument");
+    return launch_deliver_mix_peaks_update(table_dev, n_rows, max_n, n_sources, channels, (unsigned *)peaks_dev, n_peaks,
+                                           (hipStream_t)stream);
+}
+
 // Kernel-level entry points.  They allocate their scratch with hipMalloc and free it after a
 // stream synchronise: convenient for parity tests, not meant for the hot loop.
 int mi_stft_cac(const float *mix_dev, int32_t B, int32_t L, float *cac_dev, void *stream) {
@@ -695,6 +754,11 @@ int mi_item_denorm(const float *x_dev, int32_t rows, int64_t count, const float 
 
 int mi_conv_forward(const struct mi_conv_desc *desc, void *stream) {
     MI_REQUIRE(desc, "mi_conv_forward: null descriptor");
+    // a loader that reads past the ends of x gets a copy with slack when the caller's allocation has none (conv_owns_slack)
+    if (desc->x && desc->B > 0 && desc->x_bstride > 0 && conv_check_tile_m(*desc) == MI_OK && conv_reads_slack(conv_route(*desc).route)) {
+        const size_t bytes = (size_t)desc->B * (size_t)desc->x_bstride * sizeof(float);
+        if (!conv_owns_slack(desc->x, bytes)) return conv_forward_staged(*desc, bytes, (hipStream_t)stream);
+    }
     return launch_conv(*desc, (hipStream_t)stream);
 }
 

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "post_ops.h"
+#include "deliver_io.h"
 
 namespace mi {
 
@@ -42,17 +43,6 @@ __device__ __forceinline__ DeliverRow deliver_row(const int64_t *__restrict__ t,
     return r;
 }
 
-// four consecutive samples from j0 of a row of n; positions past n read nothing and give 0
-__device__ __forceinline__ void load4(const float *__restrict__ p, int64_t j0, int64_t n, bool vec, float (&v)[4]) {
-    if (vec) {
-        const float4 q = *reinterpret_cast<const float4 *>(p + j0);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = j0 + e < n ? p[j0 + e] : 0.f;
-    }
-}
-
 // step 1, the value: frames j0 .. j0 + 3 of channel c of the row's output, before clipping
 __device__ __forceinline__ void row_values(const DeliverRow &r, int n_sources, int channels, int c, int64_t j0, float (&v)[4]) {
     const int64_t stem_stride = (int64_t)channels * r.n;
@@ -78,21 +68,10 @@ __global__ __launch_bounds__(256) void deliver_peaks_kernel(const int64_t *__res
     const DeliverRow r = deliver_row<DST>(table + (size_t)blockIdx.y * MI_DELIVER_COLS, n_sources, channels, n_peaks, dst_cap);
     if (!r.ok || r.clip != MI_CLIP_RESCALE) return;                // the same for the whole block
     const int64_t j0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    unsigned m = 0u;
-    if (j0 < r.n) {
-        for (int c = 0; c < channels; ++c) {
-            float v[4];
-            row_values(r, n_sources, channels, c, j0, v);          // positions past n give 0, which changes no maximum
-#pragma unroll
-            for (int e = 0; e < 4; ++e) m = max(m, abs_bits(v[e]));
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(peaks + r.peak, m);
+    deliver_peak4([&](int c, float (&v)[4]) { row_values(r, n_sources, channels, c, j0, v); }, channels, j0, r.n, peaks + r.peak);
 }
 
-// mi_deliver_pcm: the same grid and thread assignment.  Stores: one 16-byte store of four frames for int16 stereo when all four
-// exist and their address is 16-byte aligned; else one 4-byte store per int16 stereo frame; else element by element
+// mi_deliver_pcm: the same grid and thread assignment; the stores are deliver_store4's
 __global__ __launch_bounds__(256) void deliver_pcm_kernel(const int64_t *__restrict__ table, int n_sources, int channels,
                                                           const unsigned *__restrict__ peaks, int n_peaks, unsigned char *__restrict__ dst,
                                                           int64_t dst_cap) {
@@ -102,38 +81,8 @@ __global__ __launch_bounds__(256) void deliver_pcm_kernel(const int64_t *__restr
     if (j0 >= r.n) return;
     const float d = r.clip == MI_CLIP_RESCALE ? clip_divisor(peaks[r.peak]) : 0.f;
     unsigned char *out = dst + r.dst_off;                          // frames [0, n) of the row: inside dst_cap by deliver_row
-    if (channels == 2 && r.fmt == MI_DELIVER_I16) {
-        float a[4], b[4];
-        row_values(r, n_sources, channels, 0, j0, a);
-        row_values(r, n_sources, channels, 1, j0, b);
-        unsigned w[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const unsigned lo = (unsigned short)pcm_i16(clip_sample(a[e], r.clip, d)), hi = (unsigned short)pcm_i16(clip_sample(b[e], r.clip, d));
-            w[e] = lo | (hi << 16);
-        }
-        unsigned *frames = reinterpret_cast<unsigned *>(out) + j0;  // 4-byte aligned: dst is, and DST_OFF is a multiple of 4
-        if (j0 + 4 <= r.n && (reinterpret_cast<uintptr_t>(frames) & 15) == 0) {
-            *reinterpret_cast<uint4 *>(frames) = make_uint4(w[0], w[1], w[2], w[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (j0 + e < r.n) frames[e] = w[e];
-        }
-        return;
-    }
-    for (int c = 0; c < channels; ++c) {
-        float v[4];
-        row_values(r, n_sources, channels, c, j0, v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (j0 + e >= r.n) continue;
-            const float y = clip_sample(v[e], r.clip, d);
-            const int64_t at = (j0 + e) * channels + c;
-            if (r.fmt == MI_DELIVER_I16) reinterpret_cast<short *>(out)[at] = pcm_i16(y);
-            else reinterpret_cast<float *>(out)[at] = y;
-        }
-    }
+    deliver_store4([&](int c, float (&v)[4]) { row_values(r, n_sources, channels, c, j0, v); }, channels, j0, r.n, r.clip, d,
+                   r.fmt == MI_DELIVER_I16, out);
 }
 
 int launch_deliver_peaks(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks, int n_peaks,

@@ -306,6 +306,14 @@ int launch_deliver_peaks(const int64_t *table, int n_rows, int64_t max_n, int n_
 int launch_deliver_pcm(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, const unsigned *peaks, int n_peaks,
                        unsigned char *dst, int64_t dst_cap, hipStream_t st);
 
+// deliver_mix.hip: gain-weighted remixes of the stems and the mix, clipped, converted and interleaved, every remix of a call in one launch
+int launch_deliver_mix_pcm(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, const unsigned *peaks,
+                           int n_peaks, unsigned char *dst, int64_t dst_cap, hipStream_t st);
+int launch_deliver_mix_peaks(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks, int n_peaks,
+                             int64_t dst_cap, hipStream_t st);
+int launch_deliver_mix_peaks_update(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks,
+                                    int n_peaks, hipStream_t st);
+
 // deliver_resample.hip: a stream's outputs at another sample rate -- value, streaming resample_frac, clip, PCM -- in one launch
 int launch_deliver_resample_pcm(const int64_t *table, int n_rows, int64_t max_groups, int n_sources, int channels, const float *bank,
                                 int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, unsigned char *dst, int64_t dst_cap,

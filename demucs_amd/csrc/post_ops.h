@@ -1,6 +1,7 @@
-// Per-sample arithmetic of the stem post-processing, shared by post.hip (mi_prevent_clip, mi_two_stems: one output per call) and
-// deliver.hip (mi_deliver_peaks / mi_deliver_pcm: every output of a call in one launch), so both routes run the same float32
-// sequence.  Every step is a separately rounded operation (the library builds with -ffp-contract=off).
+// Per-sample arithmetic of the stem post-processing, shared by post.hip (mi_prevent_clip, mi_two_stems: one output per call),
+// deliver.hip (mi_deliver_peaks / mi_deliver_pcm: every output of a call in one launch) and deliver_mix.hip (the same for
+// gain-weighted remixes), so all routes run the same float32 sequence.  Every step is a separately rounded operation (the
+// library builds with -ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,34 @@ __device__ __forceinline__ void two_stems_add(int S, int sel, Stem stem, float (
 
 // "minus" (separate.py:197): origin - stem
 __device__ __forceinline__ float two_stems_minus(float origin, float stem) { return __fsub_rn(origin, stem); }
+
+// A gain-weighted remix of the mix and the stems, what a user of the reference writes as `sum(g * x for ...)` after
+// `separate_tensor`: acc = 0; if g_mix != 0: acc = acc + g_mix * o; for k ascending, if g_k != 0: acc = acc + g_k * s_k -- every
+// product and every sum a separately rounded float32 operation.  A term whose gain is 0 is NOT READ, so a NaN or Inf in a muted
+// stem never reaches the output.  gain(0) is the mix's, gain(1 + k) stem k's; origin(s) / stem(k, s) fill s[0 .. W-1]
+template <int W, class Gain, class Origin, class Stem>
+__device__ __forceinline__ void mix_values(int S, Gain gain, Origin origin, Stem stem, float (&a)[W]) {
+#pragma unroll
+    for (int e = 0; e < W; ++e) a[e] = 0.f;
+    const float g_mix = gain(0);
+    if (g_mix != 0.f) {
+        float s[W];
+        origin(s);
+#pragma unroll
+        for (int e = 0; e < W; ++e) a[e] = __fadd_rn(a[e], __fmul_rn(g_mix, s[e]));
+    }
+    for (int k = 0; k < S; ++k) {
+        const float g = gain(1 + k);
+        if (g == 0.f) continue;
+        float s[W];
+        stem(k, s);
+#pragma unroll
+        for (int e = 0; e < W; ++e) a[e] = __fadd_rn(a[e], __fmul_rn(g, s[e]));
+    }
+}
+
+// the Separator's inverse affine on a normalised sample (track_affine_kernel mode 1, api._restore_on_device): w * s, then + mean
+__device__ __forceinline__ float restore_sample(float w, float mean, float s) { return __fadd_rn(__fmul_rn(w, s), mean); }
 
 // the divisor of "rescale" from the peak's bit pattern: 1.01 * wav.abs().max() (demucs/audio.py:226)
 __device__ __forceinline__ float clip_divisor(unsigned peak_bits) { return __fmul_rn(__uint_as_float(peak_bits), 1.01f); }

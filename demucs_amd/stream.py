@@ -70,12 +70,29 @@ class Delivery:
     `peaks=<TrackPeaks>` is the second: the frames are divided by those peaks.  The forwards are deterministic, so with the same
     input, the same arguments and `random` in the same state both passes see the same values, the peaks are the whole track's and
     the frames equal `audio.deliver(..., clip="rescale")` on it bit for bit (`Separator.separate_blocks` does all of this).  A
-    `TrackPeaks` made by hand (an upper bound of a live feed's peak) gives a fixed gain of the same shape in one pass."""
+    `TrackPeaks` made by hand (an upper bound of a live feed's peak) gives a fixed gain of the same shape in one pass.
 
-    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16", samplerate=None, peaks=None):
-        from .audio import TrackPeaks, clip_code, deliver_layout
+    `mix={output name: {"mix" | source name: gain}}` delivers gain-weighted remixes instead of the reference's outputs: vocals
+    lowered by 12 dB rather than removed (`{"practice": {"mix": 1, "vocals": 10 ** -0.6 - 1}}`), drums raised, or `{"minus_vocals":
+    {"mix": 1, "vocals": -1}}`, the reference's "minus" residual.  The frames equal `audio.deliver_mix(origin, stems, mix, ...)` on
+    the whole track bit for bit, `origin` being the mix as `Separator.separate_tensor` hands back a device mix.  "mix" is the
+    stream's own input: its window still holds every position that is being emitted, so no copy is kept for it.  The gains are
+    fixed for the stream; `mix` goes with `stem=None`, the default `other_method` and the model's sample rate only."""
+
+    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16", samplerate=None, peaks=None, mix=None):
+        from .audio import TrackPeaks, clip_code, deliver_layout, mix_gains
         if other_method not in ("add", "minus", "none"):
             raise ValueError(f"Invalid other_method {other_method}")
+        if mix is not None:
+            if stem is not None or other_method != "add":
+                raise ValueError("mix= names every output by its gains: it goes with stem=None and the default other_method, got "
+                                 f"stem={stem!r}, other_method={other_method!r}")
+            if samplerate is not None:
+                raise ValueError(f"mix= delivers at the model's sample rate only, got samplerate={samplerate!r}: resample the "
+                                 "remixed frames, or deliver the stems at that rate and remix them")
+            mix_gains(mix)                                      # what can be refused before the sources are known
+            mix = {name: dict(gains) for name, gains in mix.items()}
+        self.mix = mix
         self.stem, self.other_method, self.clip, self.fmt = stem, other_method, clip, fmt
         if samplerate is not None and (int(samplerate) != samplerate or samplerate <= 0):
             raise ValueError(f"the delivered sample rate must be a positive integer, got {samplerate}")
@@ -97,16 +114,19 @@ class Delivery:
 
     def with_peaks(self, peaks) -> "Delivery":
         """The same delivery with other `peaks` (what a measuring pass found, for the delivering pass)."""
-        return Delivery(self.stem, self.other_method, self.clip, self.fmt, self.samplerate, peaks)
+        return Delivery(self.stem, self.other_method, self.clip, self.fmt, self.samplerate, peaks, self.mix)
 
     def __repr__(self):
         tail = "" if self.peaks is None else f", peaks={self.peaks!r}"
+        tail += "" if self.mix is None else f", mix={self.mix!r}"
         return (f"Delivery(stem={self.stem!r}, other_method={self.other_method!r}, clip={self.clip!r}, fmt={self.fmt!r}, "
                 f"samplerate={self.samplerate!r}{tail})")
 
     def outputs(self, sources) -> list:
         """[(name, KIND, SEL)] in the reference's save order (`audio.delivery_outputs`)."""
-        from .audio import delivery_outputs
+        from .audio import delivery_outputs, mix_gains, mix_outputs
+        if self.mix is not None:
+            return mix_outputs(mix_gains(self.mix, sources))
         return delivery_outputs(sources, self.stem, self.other_method)
 
     def rate_plan(self, model_rate: int, channels: int):
@@ -122,8 +142,8 @@ class Delivery:
                              "'clamp', 'tanh' or None, or measure the peaks in a pass of their own (peaks='measure', then "
                              "peaks=<the TrackPeaks it returned>)")
         if self.stem is not None and self.other_method == "minus":
-            raise ValueError("a stream cannot deliver other_method='minus': it keeps no copy of its input behind the emit point; "
-                             "use 'add' or 'none'")
+            raise ValueError("a stream does not deliver other_method='minus'; use 'add' or 'none', or name the residual by its "
+                             "gains: mix={'minus_STEM': {'mix': 1, STEM: -1}}")
         outs = self.outputs(sources)
         if not engine:
             raise ValueError("a delivering stream runs on the GPU engines (HTDemucs / HDemucs on a cuda device); there is no CPU "
@@ -131,13 +151,23 @@ class Delivery:
         if model_rate is not None:
             self.rate_plan(model_rate, channels)
         if self.peaks is not None and not self.measures:
-            self._check_peaks(outs, model_rate)
+            self._check_peaks(outs, model_rate, self.gains(sources))
         return outs
 
-    def _check_peaks(self, outs, model_rate) -> None:
+    def gains(self, sources):
+        """`mix` resolved against `sources` (`audio.mix_gains`: [(name, (g_mix, g_0 .. g_{S-1}))]), None without `mix`."""
+        from .audio import mix_gains
+        return None if self.mix is None else mix_gains(self.mix, sources)
+
+    def _check_peaks(self, outs, model_rate, gains=None) -> None:
         """Refuses a `TrackPeaks` that was measured for other outputs or at another rate than this stream delivers."""
+        from .audio import mix_identity
         pk = self.peaks
         names = [name for name, _, _ in outs]
+        own_mix = None if gains is None else mix_identity(gains)
+        if pk.mix != own_mix:
+            raise ValueError(f"the peaks were measured for mix={pk.mix!r}, this stream delivers mix={own_mix!r}: other gains have "
+                             "other peaks")
         if list(pk.names) != names:
             raise ValueError(f"the peaks were measured for the outputs {list(pk.names)}, this stream delivers {names}")
         if pk.stem != self.stem or (self.stem is not None and pk.other_method != self.other_method):
@@ -165,6 +195,19 @@ def _deliver_rows(outputs, dl: Delivery, src: int, n: int, offs, slot0: int = 0)
     return rows
 
 
+def _mix_rows(st: "ModelStream", src: int, n: int, t0: int, win: int, win0: int, pitch: int, offs, slot0: int = 0) -> list:
+    """mi_deliver_mix_pcm's rows (MI_MIX_*) for one stream's remixes on a push: `n` frames from track position `t0` of the stems at
+    device address `src`.  The mix is read from the stream's input window, (channels, pitch) floats at device address `win` whose
+    column 0 is track position `win0`: the window is trimmed to `_keep_from()` taken before the call dispatched, which no emit
+    point is behind, so it still holds [t0, t0 + n).  A stream with an affine keeps it normalised; the row carries (mean, s)."""
+    from .audio import mix_rows
+    origin = 0
+    if any(g[0] != 0 for _, g in st.gains):
+        assert win0 <= t0, f"the window starts at {win0}, past the emit point {t0}"
+        origin = win + 4 * (t0 - win0)
+    return mix_rows(st.gains, src, n, origin, pitch, st.affine, st.deliver.clip_code, slot0, st.deliver.fmt, offs)
+
+
 def _packed_slots(slots) -> list:
     """int32 peak slots as int64 table entries (two a word, little-endian), so they ride in a call's one table upload."""
     arr = np.zeros(2 * -(-len(slots) // 2), dtype=np.int32)
@@ -174,11 +217,11 @@ def _packed_slots(slots) -> list:
 
 def _track_peaks(st: "ModelStream", bits: torch.Tensor):
     """The `audio.TrackPeaks` of a finished measuring stream from its slots' bits (int32 on the host)."""
-    from .audio import TrackPeaks
+    from .audio import TrackPeaks, mix_identity
     dl = st.deliver
     return TrackPeaks([name for name, _, _ in st.outputs], [int(b) & 0xFFFFFFFF for b in bits.tolist()],
                       samplerate=None if st.rate is None else dl.samplerate, stem=dl.stem, other_method=dl.other_method,
-                      length=st.emitted)
+                      length=st.emitted, mix=None if st.gains is None else mix_identity(st.gains))
 
 
 class _Rate:
@@ -310,10 +353,12 @@ class ModelStream:
         self.deliver, self.outputs, self.rate = deliver, None, None
         self.delivered = self.output_hold = 0
         self.measure = deliver is not None and deliver.measures      # push returns {}, finish() the audio.TrackPeaks
+        self.gains = None                  # a remixing delivery's gains per output (`Delivery.gains`)
         self.peak_off = None               # first of the stream's peak slots in its executor's buffer (a rescaling delivery)
         if deliver is not None:
             engine = all(m.kind != "generic" for m in self.members) and (self.device is None or self.device.type == "cuda")
             self.outputs = deliver.for_stream(self.sources, engine, self.samplerate, self.audio_channels)
+            self.gains = deliver.gains(self.sources)
             plan = deliver.rate_plan(self.samplerate, self.audio_channels)
             if plan is not None:
                 self.rate = _Rate(plan, len(self.outputs), self.audio_channels)
@@ -818,7 +863,10 @@ class _EngineExec:
                     self.peaks = torch.zeros(n_pk, dtype=torch.int32, device=st.device) if st.measure else \
                         _upload(list(dl.peaks.bits), torch.int32, st.device)
                     self.slots, st.peak_off = torch.arange(n_pk, dtype=torch.int32, device=st.device), 0
-                if rt is None:
+                if st.gains is not None:
+                    passes = passes + _mix_rows(st, out.data_ptr(), t1 - t0, t0, self.win.data_ptr(), self.win0, self.win.shape[1],
+                                                None if st.measure else offs)
+                elif rt is None:
                     passes = passes + _deliver_rows(st.outputs, dl, out.data_ptr(), t1 - t0, None if st.measure else offs)
                 else:
                     arena = _BankArena.get(st.device)
@@ -841,14 +889,16 @@ class _EngineExec:
                                                    t1 - t0, out.data_ptr(), out.numel(), self._stream()), "mi_stream_emit")
             pk = (self.peaks.data_ptr(), self.peaks.numel()) if dl is not None and dl.peaks is not None else (None, 0)
             rows_at = C.c_void_p(t_passes.data_ptr() + 8 * d_at) if dl is not None else None
+            mixed = "_mix" if st.gains is not None else ""      # remixes: the entries that read MI_MIX_* rows
             if dl is not None and rt is None and st.measure:
                 keep.append(out)
-                _lib.check(self.lib.mi_deliver_peaks_update(rows_at, len(st.outputs), t1 - t0, S, channels, *pk, self._stream()),
-                           "mi_deliver_peaks_update")
+                name = f"mi_deliver{mixed}_peaks_update"
+                _lib.check(getattr(self.lib, name)(rows_at, len(st.outputs), t1 - t0, S, channels, *pk, self._stream()), name)
             elif dl is not None and rt is None:
                 keep.append(out)
-                _lib.check(self.lib.mi_deliver_pcm(rows_at, len(st.outputs), t1 - t0, S, channels, *pk, frames[0].data_ptr(),
-                                                   frames[0].numel(), self._stream()), "mi_deliver_pcm")
+                name = f"mi_deliver{mixed}_pcm"
+                _lib.check(getattr(self.lib, name)(rows_at, len(st.outputs), t1 - t0, S, channels, *pk, frames[0].data_ptr(),
+                                                   frames[0].numel(), self._stream()), name)
             elif dl is not None:
                 keep.append(out)
                 bank, hist = arena.buf, self.rate_hist
@@ -957,10 +1007,11 @@ class StreamGroup:
     together with its host blocks, one `mi_streams_append`, the pooled forwards (each a gather, the forward and an overlap-add
     driven by that table), one `mi_streams_emit` and one D2H of the host-bound stems, plus one `mi_streams_compact` when a
     stream outgrows its room in the state buffer (every stream's window and accumulators).  Streams opened with `deliver=` add one
-    `mi_deliver_pcm` for all of them behind the emit; their host-bound frames leave in one D2H of the byte buffer, and their float
-    stems never do.  Those whose `Delivery` names another sample rate share one `mi_deliver_resample_pcm` instead (so a call has at
-    most one launch more, whatever the number of streams), their frames in the same byte buffer and their carried values in the
-    group's history buffer.  Streams that deliver with `clip="rescale"` keep their peaks (measured by the stream, or given to it) in
+    `mi_deliver_pcm` for all of them behind the emit (and one `mi_deliver_mix_pcm` for all that deliver remixes, `Delivery(mix=)`,
+    which read the mix from their windows in the state buffer); their host-bound frames leave in one D2H of the byte buffer, and
+    their float stems never do.  Those whose `Delivery` names another sample rate share one `mi_deliver_resample_pcm` instead (so a
+    call has at most one launch more, whatever the number of streams), their frames in the same byte buffer and their carried
+    values in the group's history buffer.  Streams that deliver with `clip="rescale"` keep their peaks (measured by the stream, or given to it) in
     the group's peaks buffer: a rescaling row names its slot there, the resampled rows then share one
     `mi_deliver_resample_pcm_peaks`, and measuring streams (`peaks="measure"`: no frames, `finish` returns their `TrackPeaks`) add
     one `mi_deliver_peaks_update` for all of them at the model's rate and one `mi_deliver_resample_peaks` for all at other rates,
@@ -1498,7 +1549,7 @@ class _GroupEngineExec:
             append = self._append_rows(blocks, table, keep, staged)
             convert = self._convert_rows(jobs, table, keep, staged)
             plan = [(e, valid, fw, *self._forward_tables(e, valid, fw, table)) for e, valid, fw in self._plan(units)]
-            emit = self._emit_rows(work, table)
+            emit = self._emit_rows(work, table, self.state if compact is None else compact[0])
             base = self._upload(table, staged, keep)
             # 3. device work
             if compact is not None:
@@ -1652,11 +1703,13 @@ class _GroupEngineExec:
         keep += [host, dev_buf]
         return base
 
-    def _emit_rows(self, work, table):
+    def _emit_rows(self, work, table, state):
         """mi_streams_emit's tables for every stream of the call with new final samples; host-bound stems first.  Behind them the
-        rows of the delivering streams: mi_deliver_pcm's, then mi_deliver_resample_pcm's for those that deliver at another rate."""
+        rows of the delivering streams: mi_deliver_pcm's, then mi_deliver_resample_pcm's for those that deliver at another rate,
+        last mi_deliver_mix_pcm's for those that deliver remixes, which read the mix from their windows in `state` (the state
+        buffer as the emit will find it, after this call's compaction)."""
         g = self.g
-        from .audio import RATE_COLS, _BankArena, deliver_layout, rate_groups, rate_lds_floats
+        from .audio import MIX_COLS, RATE_COLS, _BankArena, deliver_layout, rate_groups, rate_lds_floats
         S, C_ = len(g.sources), g.audio_channels
         spans = []
         for key, st, _ in work:
@@ -1698,6 +1751,8 @@ class _GroupEngineExec:
         # rows, which make no frames: mi_deliver_peaks_update's at the model's rate, mi_deliver_resample_peaks' at another
         r_slots, r_rescales = [], False
         m_rows, m_longest, mr_rows, mr_slots, mr_groups, mr_lds = [], 1, [], [], 1, 1
+        # remixing deliveries: all of a call's in one launch more, the measuring ones among them in one of their own
+        x_rows, x_longest, xm_rows, xm_longest = [], 1, [], 1
         for key, st, t0, _, to_host in sorted(spans, key=lambda s: not s[4]):
             f_off, n = layout[key]
             rt, dl = st.rate, st.deliver
@@ -1729,10 +1784,21 @@ class _GroupEngineExec:
                 r_groups = max(r_groups, rate_groups(rt.plan, C_, n_out))
                 r_lds = max(r_lds, rate_lds_floats(rt.plan, C_))
                 d_layout[key], d_count[key] = offs, n_out
+            elif st.measure and st.gains is not None:
+                slot = self.slots[key]
+                xm_rows += _mix_rows(st, src, n, t0, state.data_ptr() + 4 * slot.w_base, slot.w0, slot.w_cap, None, st.peak_off)
+                xm_longest = max(xm_longest, n)
+                continue
             elif st.measure:
                 m_rows += _deliver_rows(st.outputs, dl, src, n, None, st.peak_off)
                 m_longest = max(m_longest, n)
                 continue
+            elif st.gains is not None:
+                slot = self.slots[key]
+                offs, d_off = deliver_layout(st.outputs, n, C_, dl.fmt, d_off)
+                x_rows += _mix_rows(st, src, n, t0, state.data_ptr() + 4 * slot.w_base, slot.w0, slot.w_cap, offs, st.peak_off or 0)
+                d_layout[key], d_count[key] = offs, n
+                x_longest = max(x_longest, n)
             else:
                 offs, d_off = deliver_layout(st.outputs, n, C_, dl.fmt, d_off)
                 d_rows += _deliver_rows(st.outputs, dl, src, n, offs, st.peak_off or 0)
@@ -1752,7 +1818,13 @@ class _GroupEngineExec:
         table += mr_rows
         mrs_at = len(table)
         table += _packed_slots(mr_slots)
+        x_at = len(table)
+        table += x_rows
+        xm_at = len(table)
+        table += xm_rows
         return dict(at=at, n_streams=len(streams) // STREAMS_EMIT_COLS, n_passes=len(passes) // 8, n_segs=len(segs) // 2,
+                    x_at=x_at, x_rows=len(x_rows) // MIX_COLS, x_longest=x_longest, xm_at=xm_at, xm_rows=len(xm_rows) // MIX_COLS,
+                    xm_longest=xm_longest,
                     total=off, host_n=host_n, longest=longest, layout=layout, order=[k for k, _, _ in work],
                     streams={k: st for k, st, _ in work}, out=out, d_at=d_at, d_rows=len(d_rows) // DELIVER_COLS, d_total=d_off,
                     d_host=d_host, d_longest=d_longest, d_layout=d_layout, d_count=d_count, r_at=r_at,
@@ -1777,7 +1849,7 @@ class _GroupEngineExec:
                                                 int(g.bag_weights is not None), self.stats.data_ptr(), self.n_stats, out.data_ptr(),
                                                 out.numel(), self._stream()), "mi_streams_emit")
         frames = None
-        if emit["d_rows"] or emit["r_rows"]:
+        if emit["d_rows"] or emit["r_rows"] or emit["x_rows"]:
             # at least 16 bytes: a call on which resampling streams only carry values still names a destination
             frames = torch.empty(max(emit["d_total"], 16), dtype=torch.uint8, device=dev)
         pk = (None, 0) if self.peaks is None else (self.peaks.data_ptr(), self.peaks.numel())
@@ -1804,6 +1876,13 @@ class _GroupEngineExec:
                                                           C_, bank.data_ptr(), bank.numel(), hist.data_ptr(), hist.numel(),
                                                           emit["mr_lds"], C.c_void_p(base + 8 * emit["mrs_at"]), *pk, self._stream()),
                        "mi_deliver_resample_peaks")
+        # the remixing streams: one launch for all that deliver, one for all that measure
+        if emit["x_rows"]:
+            _lib.check(self.lib.mi_deliver_mix_pcm(C.c_void_p(base + 8 * emit["x_at"]), emit["x_rows"], emit["x_longest"], S, C_, *pk,
+                                                   frames.data_ptr(), frames.numel(), self._stream()), "mi_deliver_mix_pcm")
+        if emit["xm_rows"]:
+            _lib.check(self.lib.mi_deliver_mix_peaks_update(C.c_void_p(base + 8 * emit["xm_at"]), emit["xm_rows"], emit["xm_longest"],
+                                                            S, C_, *pk, self._stream()), "mi_deliver_mix_peaks_update")
         host = host_frames = None
         if emit["host_n"]:
             host = torch.empty(emit["host_n"], dtype=torch.float32, pin_memory=True)

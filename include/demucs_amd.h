@@ -624,6 +624,51 @@ int mi_deliver_resample_pcm_peaks(const int64_t *table_dev, int32_t n_rows, int6
                                   void *dst_dev, int64_t dst_capacity, const int32_t *slots_dev, const void *peaks_dev, int32_t n_peaks,
                                   void *stream);
 
+/* ---- delivery of gain-weighted remixes of the stems and of the input mix, every remix of a call in ONE launch -------------------
+ * What a user of the reference writes after `separate_tensor` as `save_audio(sum(g * x for ...), path, clip=...)`: vocals lowered
+ * instead of removed, drums raised, `mix - vocals`.  For channel c and frame j of a row, with float32 gains g_mix, g_0 .. g_{S-1}:
+ *     acc = 0.0f;  if g_mix != 0: acc = acc + g_mix * o(c, j);  for k ascending, if g_k != 0: acc = acc + g_k * s_k(c, j)
+ * every product and sum a separately rounded float32 operation; a term whose gain is exactly 0 is NOT READ (a NaN or Inf in a
+ * muted stem does not reach the output).  CLIP, FMT and the interleaving follow as in mi_deliver_pcm.  Gains of 1 on every stem
+ * but SEL give MI_DELIVER_ADD's bits; {g_mix 1, g_SEL -1} gives MI_DELIVER_MINUS's int16 bytes, and its float32 values as numbers
+ * (only a -0.0 can come out as +0.0).  Row r of the table (MI_MIX_COLS int64, a DEVICE array) is ONE remix:
+ *     SRC, N         as MI_DELIVER_SRC / _N: the contiguous float32 (n_sources, channels, n) stems (trusted), n_sources <= 8;
+ *     ORIGIN         DEVICE address of frame 0 of the mix's channel 0, or 0 (read only when g_mix != 0; trusted);
+ *     ORIGIN_PITCH   floats between the mix's channel rows: channel c, frame j at ORIGIN + c * ORIGIN_PITCH + j.  A stream names
+ *                    its input window here, whose rows are longer than n;
+ *     ORIGIN_AFFINE  two float32 in one int64, mean in the low half and s in the high: when AFFINE_ON is not 0 the mix is stored
+ *     AFFINE_ON      normalised, and o = w * s, then + mean (two rounded operations, mi_track_affine's restore);
+ *     GAINS          nine float32 in five int64 (two a word, low half first): g_mix, g_0 .. g_7; those past n_sources are not read;
+ *     CLIP, PEAK, FMT, DST_OFF   as MI_DELIVER_*.
+ *   A row is skipped whole (nothing of it is read or written) under mi_deliver_pcm's rules -- its frames leave dst_capacity, DST_OFF
+ *   is negative or no multiple of 4, N <= 0, SRC is 0, CLIP / FMT out of range, a MI_CLIP_RESCALE row's PEAK outside [0, n_peaks) --
+ *   and when a gain among g_mix, g_0 .. g_{n_sources-1} is not finite, all of them are 0, g_mix != 0 without ORIGIN, or g_mix != 0
+ *   with ORIGIN_PITCH < N.  No kernel uses scratch memory and nothing synchronises with the host.
+ * mi_deliver_mix_pcm: writes every row's frames, four frames a thread on mi_deliver_pcm's grid, 16-byte loads where base, pitch
+ *   and N allow.  peaks_dev may be null when n_peaks == 0.
+ * mi_deliver_mix_peaks: zeroes peaks_dev and reduces max |value| of every MI_CLIP_RESCALE row into its slot, as mi_deliver_peaks.
+ * mi_deliver_mix_peaks_update: the same without the memset and without a destination (FMT, DST_OFF not read): the slots carry the
+ *   running maximum over the calls of a track, as mi_deliver_peaks_update's. */
+#define MI_MIX_SRC 0
+#define MI_MIX_N 1
+#define MI_MIX_ORIGIN 2
+#define MI_MIX_ORIGIN_PITCH 3
+#define MI_MIX_ORIGIN_AFFINE 4
+#define MI_MIX_AFFINE_ON 5
+#define MI_MIX_GAINS 6
+#define MI_MIX_CLIP 11
+#define MI_MIX_PEAK 12
+#define MI_MIX_FMT 13
+#define MI_MIX_DST_OFF 14
+#define MI_MIX_COLS 15
+#define MI_MIX_MAX_SOURCES 8
+int mi_deliver_mix_pcm(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels,
+                       const void *peaks_dev, int32_t n_peaks, void *dst_dev, int64_t dst_capacity, void *stream);
+int mi_deliver_mix_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels, void *peaks_dev,
+                         int32_t n_peaks, int64_t dst_capacity, void *stream);
+int mi_deliver_mix_peaks_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels,
+                                void *peaks_dev, int32_t n_peaks, void *stream);
+
 /* ---- kernel-level entry points (parity tests; same kernels the forward uses) --------------
  * mi_stft_cac: `_magnitude(_spec(mix))` (demucs/htdemucs.py:420-461, demucs/spec.py:11-27):
  *   mix_dev (B,2,L) -> cac_dev (B,4,2048,ceil(L/1024)), channel order [c0.re,c0.im,c1.re,c1.im]. */
@@ -662,7 +707,10 @@ int mi_item_denorm(const float *x_dev, int32_t rows, int64_t count, const float 
  *   A float32 descriptor that states its kernel geometry (ntaps / tap_*) may run the shifted-run tap loader (routes 2 and 7), which
  *   reads up to 8 bytes before and 20 bytes after the tensor at `x`: the caller owns that slack (gemm_conv.h, beside `ntaps`).
  *   A float32 descriptor with a split image that sets `dma_time` (a 1-D time-axis strided or transposed conv) may run the time-axis
- *   loaders (route 11), which read the same 8 bytes before and 20 bytes after the tensor at `x` (gemm_conv.h, beside `dma_time`). */
+ *   loaders (route 11), which read the same 8 bytes before and 20 bytes after the tensor at `x` (gemm_conv.h, beside `dma_time`).
+ *   Where the device allocation that holds `x` does not reach 128 bytes past both ends of the B * x_bstride floats at `x` (a tensor
+ *   that begins or ends with its allocation: the read could touch an unmapped address), this entry runs the same kernel on a copy
+ *   of `x` that has the slack, waits for the stream and frees the copy: same route, same bits (mi_debug_conv_staged counts these). */
 struct mi_conv_desc;
 int mi_conv_forward(const struct mi_conv_desc *desc, void *stream);
 
@@ -875,6 +923,10 @@ int mi_debug_last_conv_route(void);
 /* Debug aid, as mi_debug_last_conv_route: the rows of the tile the LAST mi_conv_forward of this process ran (what
  * mi_debug_conv_route answers in *tile); -1 before any call. */
 int mi_debug_last_conv_tile(void);
+
+/* Debug aid: how many calls of mi_conv_forward in this process ran on a copy of `x` with read slack, because the caller's
+ * allocation did not reach 128 bytes past both ends of the tensor (see mi_conv_forward).  Process-wide, not thread-safe. */
+int mi_debug_conv_staged(void);
 
 /* Debug aid: how many layers this process has launched on `route` (enum mi_conv_route) with epilogue `epi` (enum mi_epilogue of
  * gemm_conv.h; -1: any), through mi_conv_forward and through the engines' forwards alike; -1 for a route or epilogue out of

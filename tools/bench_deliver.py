@@ -20,6 +20,14 @@ same route at R Hz (`Delivery("vocals", samplerate=R)`: `mi_deliver_resample_pcm
 method; `rate_over_model` is the ratio of their median real-time factors.  No speed is claimed for it.
 
     python tools/bench_deliver.py --out-sr 48000 --out profiles/deliver_rate_bench.json
+
+With `--mix-kernel` the pair is two launches on the same device data, `--seconds` (180 for the run of record) of 4 stereo float32
+stems: `mi_deliver_pcm` with the four MI_DELIVER_ADD rows (every "no_STEM" output, clip "clamp", int16), and
+`mi_deliver_mix_pcm` with the four rows of add-equivalent gains (1 on every stem but one, no mix), which write the same bytes.
+Runs of `--reps` launches between two device events alternate (add, mix, add, mix, ...) `--pairs` times after a warm-up of each;
+reported per entry: microseconds per launch of every run, their median and spread, and the bytes moved per second at the median.
+
+    python tools/bench_deliver.py --mix-kernel --seconds 180 --out profiles/deliver_mix_kernel.json
 """
 from __future__ import annotations
 
@@ -91,7 +99,11 @@ def main():
     ap.add_argument("--modes", default="f32,bf16")
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-sr", type=int, default=None, help="compare delivery at the model's rate with delivery at this rate")
+    ap.add_argument("--mix-kernel", action="store_true", help="time mi_deliver_mix_pcm against mi_deliver_pcm's ADD rows")
+    ap.add_argument("--reps", type=int, default=20, help="launches per timed run of --mix-kernel")
     args = ap.parse_args()
+    if args.mix_kernel:
+        return mix_kernel_main(args)
     if args.out_sr is not None:
         return rate_main(args)
     length = int(args.seconds * SR)
@@ -152,6 +164,62 @@ def rate_main(args):
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         f.write(line + "\n")
+
+
+def mix_kernel_main(args):
+    import ctypes as C
+
+    from demucs_amd import _lib, audio
+    S, channels, n = 4, 2, int(args.seconds * SR)
+    dev = torch.device("cuda", 0)
+    stems = (torch.rand(S, channels, n, device=dev) * 2 - 1) * 0.4
+    outputs = [(f"no_{k}", audio.DELIVER_ADD, k) for k in range(S)]
+    offs, total = audio.deliver_layout(outputs, n, channels, "i16")
+    clamp = audio.clip_code("clamp")
+    add_rows = []
+    for (_, kind, sel), off in zip(outputs, offs):
+        add_rows += [stems.data_ptr(), 0, n, kind, sel, clamp, 0, 0, off]
+    gains = [(name, (0.0,) + tuple(0.0 if k == sel else 1.0 for k in range(S))) for name, _, sel in outputs]
+    mix_rows = audio.mix_rows(gains, stems.data_ptr(), n, 0, 0, None, clamp, 0, "i16", offs)
+    tables = {"add": torch.tensor(add_rows, dtype=torch.int64).to(dev), "mix": torch.tensor(mix_rows, dtype=torch.int64).to(dev)}
+    bufs = {k: torch.zeros(total, dtype=torch.uint8, device=dev) for k in tables}
+    lib = _lib.load()
+    entries = {"add": (lib.mi_deliver_pcm, "mi_deliver_pcm"), "mix": (lib.mi_deliver_mix_pcm, "mi_deliver_mix_pcm")}
+
+    def timed(which: str, reps: int) -> float:
+        entry, name = entries[which]
+        stream = C.c_void_p(_lib.current_stream_ptr())
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(reps):
+            _lib.check(entry(tables[which].data_ptr(), S, n, S, channels, None, 0, bufs[which].data_ptr(), total, stream), name)
+        t1.record()
+        t1.synchronize()
+        return 1e3 * t0.elapsed_time(t1) / reps                          # microseconds per launch
+
+    for which in entries:
+        timed(which, 3)
+    assert torch.equal(bufs["add"], bufs["mix"]), "the two entries must write the same bytes"
+    runs = {"add": [], "mix": []}
+    for _ in range(args.pairs):
+        for which in ("add", "mix"):
+            runs[which].append(timed(which, args.reps))
+    moved = (S - 1) * S * channels * n * 4 + S * channels * n * 2           # bytes read and written by a launch
+    result = {"what": f"{args.seconds:g} s of {S} stereo stems: mi_deliver_pcm's {S} ADD rows vs mi_deliver_mix_pcm with add-equivalent "
+                      "gains, clamp, int16; alternating runs",
+              "device": torch.cuda.get_device_name(0), "reps": args.reps, "pairs": args.pairs, "bytes_per_launch": moved}
+    for which, us in runs.items():
+        med = statistics.median(us)
+        result[which] = {"us_per_launch_runs": [round(x, 1) for x in us], "us_median": round(med, 1),
+                         "us_spread": round(max(us) - min(us), 1), "gb_per_s": round(moved / med / 1e3, 1)}
+    result["mix_over_add"] = round(result["mix"]["us_median"] / result["add"]["us_median"], 3)
+    result["within_add_spread"] = result["mix"]["us_median"] <= result["add"]["us_median"] + result["add"]["us_spread"]
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
