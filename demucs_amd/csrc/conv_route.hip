@@ -102,7 +102,7 @@ int conv_validate(const mi_conv_desc &d) {
     MI_REQUIRE(d.Kpad % BK == 0 && d.Kpad >= BK, "conv: Kpad %d must be a positive multiple of %d", d.Kpad, BK);
     MI_REQUIRE(d.Mpad % 4 == 0, "conv: Mpad %d must be a multiple of 4", d.Mpad);
     MI_REQUIRE(d.O2 >= 32 || d.row_mode == 0 || (d.epi != MI_EPI_BIAS_STATS && d.epi != MI_EPI_STATS_ONLY),
-               "conv: statistics epilogue needs O2 >= 32");
+               "conv: statistics epilogue with rows (b, o1) (row_mode 1) needs O2 >= 32");      // row_mode 0: any width (conv_stats_per_item)
     MI_REQUIRE(d.pro == 0, "conv: the fused GroupNorm+GELU prologue was replaced by launch_gn_gelu");
     MI_REQUIRE(!(d.flags & MI_FLAG_IMG4) || (d.epi == MI_EPI_GLU && d.half && d.yh && d.yh_pq > 0 && d.yh_n >= (int64_t)d.B * d.yh_pq && d.M % 32 == 0 &&
                                              ((uintptr_t)d.yh & 15) == 0),
@@ -141,6 +141,15 @@ int conv_validate(const mi_conv_desc &d) {
                    "conv: an operand-image input is not instantiated for LINEAR flags %d", d.flags);
     }
     return MI_OK;
+}
+
+// The statistics epilogues (gemm_tile.h conv_epilogue) reduce a wave's 32 consecutive columns into the row of its first column and
+// ONE other row.  Rows (b, o1) are 32 columns and more (checked above); a per-item row (row_mode 0) of P = O1 * O2 < 32 columns lets
+// three or more items share a wave -- time-branch DConv of the hdemucs engine on a batch of short chunks -- and the middle ones would
+// be credited to the last.  launch_conv then runs the layer once per item: one row per launch.  Two items never need it; P = 16, 24,
+// 28 never put three rows into an aligned 32-column window either, but the tensors are tiny and one rule is easier to hold
+bool conv_stats_per_item(const mi_conv_desc &d) {
+    return (d.epi == MI_EPI_BIAS_STATS || d.epi == MI_EPI_STATS_ONLY) && d.row_mode == 0 && d.B > 2 && (int64_t)d.O1 * d.O2 < 32;
 }
 
 // The decision, top to bottom; the first test that holds wins (kernels.h ConvRoute).  It never fails: what conv_validate refuses

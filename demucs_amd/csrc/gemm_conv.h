@@ -82,7 +82,8 @@ typedef struct mi_conv_desc {
     const float *emb;   /* GLU + MI_FLAG_EMB: [Cout][O1] */
     float *y;
     int64_t y_bstride, y_cstride;
-    double *stats;          /* [rows][32][2] fp64 partial sums (zeroed by the caller)   */
+    double *stats;          /* [rows][32][2] fp64 partial sums (zeroed by the caller); rows (b, o1) need O2 >= 32, a row per item b
+                               may have any width (below 32 columns the layer runs one item per launch) */
     const float *gn_stats;  /* float2 [rows] (mean, rstd) for MI_EPI_GN_GLU             */
     const float *gn_w, *gn_b; /* [Mpad] packed row order                                 */
     int32_t out_len;        /* CONVTR: valid output length along the scattered axis      */

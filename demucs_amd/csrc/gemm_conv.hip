@@ -237,12 +237,8 @@ const void *conv_zero_page() {
     return p ? p + MI_SINK_FLOATS : nullptr;
 }
 
-// fill the sink, validate and decide (conv_route.hip), launch
-int launch_conv(const mi_conv_desc &din, hipStream_t st) {
-    mi_conv_desc d = din;
-    if (!d.sink) d.sink = conv_sink();
-    MI_REQUIRE(d.sink && ((uintptr_t)d.sink & 15) == 0, "conv: the store sink could not be allocated or is not 16-byte aligned");
-    MI_TRY(conv_validate(d));
+// decide (conv_route.hip) and launch a validated descriptor whose sink is set
+static int launch_routed(const mi_conv_desc &d, hipStream_t st) {
     const ConvRoute r = conv_route(d);
     // the tile the layer's split image was packed for: a 192-row layer's is a run of 96-row images
     const int image_tile = d.tile_m == 192 ? 96 : d.tile_m ? d.tile_m : conv_pick_tile(d.M);
@@ -274,6 +270,26 @@ int launch_conv(const mi_conv_desc &din, hipStream_t st) {
         constexpr int E = decltype(epi)::value, F = decltype(lflags)::value;
         return r.plain ? launch_tile<E, F, true>(d, r, st) : launch_tile<E, F, false>(d, r, st);
     });
+}
+
+// fill the sink, validate, launch -- a statistics layer whose rows the epilogue cannot tell apart (conv_route.hip
+// conv_stats_per_item) item by item: tiny tensors, B launches, each with one statistics row
+int launch_conv(const mi_conv_desc &din, hipStream_t st) {
+    mi_conv_desc d = din;
+    if (!d.sink) d.sink = conv_sink();
+    MI_REQUIRE(d.sink && ((uintptr_t)d.sink & 15) == 0, "conv: the store sink could not be allocated or is not 16-byte aligned");
+    MI_TRY(conv_validate(d));
+    if (!conv_stats_per_item(d)) return launch_routed(d, st);
+    mi_conv_desc e = d;
+    e.B = 1;
+    for (int b = 0; b < d.B; ++b) {
+        e.x = d.x + (size_t)b * d.x_bstride;
+        e.y = d.y ? d.y + (size_t)b * d.y_bstride : nullptr;
+        e.res = d.res ? d.res + (size_t)b * d.y_bstride : nullptr;
+        e.stats = d.stats ? d.stats + (size_t)b * kStatSlots * 2 : nullptr;
+        MI_TRY(launch_routed(e, st));
+    }
+    return MI_OK;
 }
 
 }  // namespace mi

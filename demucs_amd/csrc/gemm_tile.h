@@ -302,7 +302,8 @@ __device__ __forceinline__ void conv_epilogue(const mi_conv_desc &d, f32x16 (&ac
             }
         }
         if (EPI == MI_EPI_BIAS_STATS || EPI == MI_EPI_STATS_ONLY || (EPI == MI_EPI_LINEAR && (LFLAGS & MI_FLAG_STATS))) {
-            // a wave's 32 columns span at most two statistics rows (O2 >= 32): reduce both groups
+            // a wave's 32 columns span at most two statistics rows: reduce both groups.  The host sees to it: rows (b, o1) and
+            // MI_FLAG_STATS need O2 >= 32 (conv_validate), a narrower per-item row runs one item per launch (conv_stats_per_item)
             double t1 = (double)s1, t2 = (double)s2;
             t1 += __shfl_xor(t1, 32); t2 += __shfl_xor(t2, 32);          // the two lane halves share a column
             const int rid = c.valid ? row : -1;

@@ -17,7 +17,8 @@
 namespace mi {
 
 constexpr int kMinLength = 1;          // the reference forwards chunks down to ONE sample (pad1d's zero-then-reflect rule); frequency-
-                                       // branch rows carry a pitch >= 32 frames (the row-statistics epilogues reduce 32 columns at a time)
+                                       // branch rows carry a pitch >= 32 frames (the row-statistics epilogues reduce 32 columns at a time);
+                                       // time-branch rows are the item's and may be narrower: launch_conv then runs items one by one
 constexpr size_t kMaxGeos = 24;        // cached input lengths per handle (least recently used one evicted)
 static const int hFr[5] = {2048, 512, 128, 32, 8};
 

@@ -121,6 +121,9 @@ constexpr int BN = 128;      // columns of a block tile
 int conv_pick_tile(int M);
 int conv_check_tile_m(const mi_conv_desc &d);     // MI_OK, or MI_EINVAL with the error set: tile_m = 192 on a layer that cannot take it
 int conv_validate(const mi_conv_desc &d);         // MI_OK, or MI_EINVAL with the error set: a descriptor no kernel takes (d.sink is not looked at)
+// true: launch_conv runs a statistics layer item by item (a per-item row of fewer than 32 columns, more than two items: the epilogue's
+// wave reduction tells at most two rows apart in a wave's 32 columns)
+bool conv_stats_per_item(const mi_conv_desc &d);
 extern int g_split_bf16;     // 0 (mi_set_split_bf16): native fp32 MFMA kernels even where a split weight image exists
 // Which kernel launch_conv runs for a descriptor, decided from the descriptor alone (no HIP call, no pointer followed):
 // route: mi_conv_route (include/demucs_amd.h); tile: the rows of the tile that kernel runs, after every substitution

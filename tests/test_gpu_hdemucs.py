@@ -303,3 +303,86 @@ def test_production_chunk_44s_against_float64_oracle():
     print(f"hdemucs 44 s item: engine vs float64 oracle max-abs {err:.3e}; float32 oracle vs float64 oracle {err32:.3e}; engine vs "
           f"float32 oracle {float((out - want32).abs().max()):.3e} (out rms {want.pow(2).mean().sqrt():.3f})")
     assert err <= TOL and err32 <= TOL
+
+
+# ------------------------------------------------------------------------------------------------
+# Batches of short chunks.  The time branch's DConv blocks (encoder levels 0 - 3) take their GroupNorm statistics per ITEM from the
+# k = 3 conv's epilogue, which reduces 32 consecutive columns at a time; level i's rows have a pitch of round_up(ceil(L / 4^(i+1)), 4)
+# floats, so below L = 3 072 (and for 4 097 .. 5 120) three or more items of a batch share such a run at some level.
+SHORT_LENGTHS = [40, 100, 777, 2561, 3000, 5000]
+
+
+def short_batch(length):
+    """four different items of `length` samples: kinds alternate, seeds differ"""
+    return torch.stack([torch.from_numpy(synth_mix(100 + 7 * b + length % 13, length, "tones" if b % 2 == 0 else "noise")) for b in range(4)])
+
+
+@pytest.fixture(scope="module")
+def short_f32():
+    """ONE float32 engine with max_batch = 4 for every length (a geometry change with B > 1 comes with it) and its batched
+    outputs, each computed once"""
+    m, outs = engine(2, max_batch=4), {}
+
+    def run(length):
+        if length not in outs:
+            outs[length] = m(short_batch(length).cuda()).cpu()
+        return outs[length]
+    run.model = m
+    yield run
+    m.release()
+
+
+@pytest.mark.parametrize("length", SHORT_LENGTHS)
+def test_batches_of_short_chunks_match_float64_oracle(short_f32, length):
+    """Every item of a batch of 4 short chunks against the float64 oracle at the suite's bar, and bit for bit equal to the
+    single-item forward of that item on the same handle."""
+    from demucs_amd.hdemucs_weights import hdemucs_layer_plan
+    from oracle import hdemucs_oracle as HO
+    cfg = HDemucsConfig()
+    sd = synthetic_hdemucs_state_dict(cfg, 2)
+    mix = short_batch(length)
+    out = short_f32(length)
+    assert out.shape == (4, 4, 2, length)
+    osd = {k: torch.from_numpy(v.copy()).double() for k, v in sd.items()}
+    with torch.no_grad():
+        want = HO.hdemucs_forward(osd, mix.double(), hdemucs_layer_plan(cfg), 4)
+    err = (out.double() - want).abs().amax(dim=(1, 2, 3))
+    print(f"hdemucs 4 x {length} samples: max-abs per item {[f'{e:.2e}' for e in err.tolist()]} (out rms {want.pow(2).mean().sqrt():.3f})")
+    singles = [short_f32.model(mix[b:b + 1].cuda()).cpu()[0] for b in range(4)]
+    assert float(err.max()) <= TOL
+    for b in range(4):
+        assert torch.equal(singles[b], out[b]), f"item {b} of the batch differs from its single-item forward by {float((singles[b] - out[b]).abs().max()):.3e}"
+
+
+@pytest.mark.parametrize("mode,floor_db", [("f16", 38.0), ("bf16", 20.0)])
+def test_batches_of_short_chunks_half_modes(short_f32, mode, floor_db):
+    """The same batches in the reduced-precision modes: batched == single-item bit for bit, finite, and at least the mode's SDR
+    floor of this file against the float32 mode's output."""
+    m = engine(2, max_batch=4, compute_dtype=mode)
+    for length in SHORT_LENGTHS:
+        mix = short_batch(length).cuda()
+        out = m(mix).cpu()
+        assert out.shape == (4, 4, 2, length) and bool(torch.isfinite(out).all())
+        want = short_f32(length).double()
+        noise = (out.double() - want).pow(2)
+        sdr = 10 * torch.log10(want.pow(2).sum() / noise.sum())
+        per_item = 10 * torch.log10(want.pow(2).sum((1, 2, 3)) / noise.sum((1, 2, 3)))
+        print(f"hdemucs {mode} 4 x {length} samples: SDR vs the float32 mode {float(sdr):.1f} dB (per item {[round(float(v), 1) for v in per_item]})")
+        for b in range(4):
+            single = m(mix[b:b + 1]).cpu()[0]
+            assert torch.equal(single, out[b]), f"{mode} {length}: item {b} of the batch differs from its single-item forward"
+        assert float(per_item.min()) >= floor_db, (mode, length, per_item.tolist())
+    m.release()
+
+
+def test_apply_model_on_four_short_tracks_equals_one_at_a_time(short_f32):
+    """`apply_model` on a (4, 2, 2561) mix on the engine with max_batch = 4: each track's result equals the one it gets alone,
+    bit for bit, however the tracks' chunks were grouped into forwards."""
+    m = short_f32.model
+    mix = short_batch(2561).cuda()
+    out = P.apply_model(m, mix, shifts=0)
+    assert out.shape == (4, 4, 2, 2561) and bool(torch.isfinite(out).all())
+    for b in range(4):
+        alone = P.apply_model(m, mix[b:b + 1], shifts=0)
+        assert torch.equal(alone[0], out[b]), f"track {b}: {float((alone[0] - out[b]).abs().max()):.3e}"
+    m.check()

@@ -602,11 +602,86 @@ def test_encoder_conv_on_phase_split_image(lib, freq, mode):
         _HALF_MODE[0] = None
 
 
-@pytest.mark.parametrize("freq", [True, False])
+def _dconv_layer_on_a_batch_of_short_rows(lib, x6):
+    """The same layer as the hdemucs engine chains it (csrc/engine_core.hip run_dconv) on a batch of short time-branch rows: B = 4
+    items of 18 valid samples on a pitch of 20 floats -- four statistics rows inside one tile's first 80 columns, up to three in a
+    wave's 32.  conv3 + per-item statistics (BIAS_STATS), their finalisation, GroupNorm + GELU in place with the Gram sums
+    (mi_dconv_gn_gelu_gram), the second GroupNorm's statistics from them (mi_gram_finalize), 1x1 + GroupNorm + GLU + LayerScale +
+    residual (GN_GLU).  Items differ in scale (2^b: exact in every operand type); padding columns hold NaN throughout."""
+    C, h, dil, B, L, pitch, slots = 48, 6, 2, 4, 18, 20, 8
+    hp, C2, P = 16, 2 * C, pitch
+    x4 = rnd(B, C, L, seed=25) * (2.0 ** torch.arange(B, dtype=torch.float64))[:, None, None]
+    W0, b0 = rnd(h, C, 3, seed=26, scale=0.2), rnd(h, seed=27)
+    g1w, g1b = 1 + 0.2 * rnd(h, seed=28), 0.1 * rnd(h, seed=29)
+    W3, b3 = rnd(C2, h, 1, seed=30, scale=0.5), rnd(C2, seed=31)
+    g2w, g2b = 1 + 0.2 * rnd(C2, seed=32), 0.1 * rnd(C2, seed=33)
+    ls = 1 + 0.3 * rnd(C, seed=34)
+    ref_h = F.conv1d(x4, W0, b0, dilation=dil, padding=dil)
+    y = F.gelu(F.group_norm(ref_h, 1, g1w, g1b, eps=1e-5))
+    y = F.group_norm(F.conv1d(y, W3, b3), 1, g2w, g2b, eps=1e-5)
+    want = x4 + ls[:, None] * F.glu(y, dim=1)
+
+    xp = torch.full((B, C, pitch), float("nan"))
+    xp[..., :L] = x4.float()
+    xd = xp.cuda()
+    pitched = dict(o2_valid=L, x_ld=pitch)
+    # conv3 + bias, per-item statistics
+    wt0, bias0, M0, Mpad0, K0, Kpad0, tile0 = pack_w(W0.reshape(h, -1), b0)
+    kt0 = ktab(C, 1, 3, 1, dil, 0, dil, P, pitch, Kpad0)
+    hid = torch.full((B, hp, pitch), float("nan"), device="cuda")
+    stats = torch.zeros(B, SLOTS, 2, dtype=torch.float64, device="cuda")
+    conv_call(x6=x6, wt=wt0, M=M0, Mpad=Mpad0, K=K0, Kpad=Kpad0, ktab=kt0, x=xd, x_bstride=C * P, B=B, D1=1, D2=L, O1=1, O2=pitch, S1=1,
+              S2=1, row_mode=0, epi=EPI_BIAS_STATS, bias=bias0, y=hid, y_bstride=hp * P, y_cstride=P, stats=stats, tile_m=tile0, **pitched)
+    assert bool(torch.isfinite(hid[:, :h, :L]).all()) and bool(torch.isnan(hid[..., L:]).all())
+    s = stats.sum(1).cpu()
+    mean = s[:, 0] / (h * L)
+    var = s[:, 1] / (h * L) - mean ** 2
+    unit = 2.0 ** torch.arange(B, dtype=torch.float64)
+    e_mean = ((mean - ref_h.mean(dim=(1, 2))).abs() / unit).max().item()
+    e_var = ((var - ref_h.var(dim=(1, 2), unbiased=False)).abs() / unit ** 2).max().item()
+    print(f"short rows: per-item mean err / 2^b {e_mean:.2e}, variance err / 4^b {e_var:.2e}")
+    assert e_mean < 1e-6 and e_var < 1e-5          # the bars of the long case in units of the item: its values are 2^b times item 0's
+    st1 = torch.stack([mean, 1.0 / torch.sqrt(var + 1e-5)], 1).float().cuda().contiguous()
+    # GroupNorm + GELU in place with the Gram sums; the second GroupNorm's statistics from them (weights as load_dconv builds them)
+    HP = lib.mi_gram_order(h)
+    Wd = W3.reshape(C2, h)
+    A = Wd.t() @ Wd
+    gw = torch.zeros(HP, HP, dtype=torch.float64)
+    gw[:h, :h] = A                                  # h <= 32: one 32-channel block, every pair once
+    gw[:h, h] = 2.0 * (Wd.t() @ b3)
+    gc = torch.zeros(HP, dtype=torch.float64)
+    gc[:h] = Wd.sum(0)
+    gwd, gcd, g1wd, g1bd = gw.cuda(), gc.cuda(), g1w.float().cuda(), g1b.float().cuda()
+    gram = torch.zeros(B * slots * HP * HP, dtype=torch.float64, device="cuda")
+    st2 = torch.empty(B, 2, device="cuda")
+    _lib.check(lib.mi_dconv_gn_gelu_gram(hid.data_ptr(), B, h, hp, 1, L, pitch, 0, st1.data_ptr(), g1wd.data_ptr(), g1bd.data_ptr(),
+                                         gram.data_ptr(), slots, stream()), "mi_dconv_gn_gelu_gram")
+    _lib.check(lib.mi_gram_finalize(gram.data_ptr(), B, h, slots, gwd.data_ptr(), gcd.data_ptr(), float(b3.sum()), float((b3 ** 2).sum()),
+                                    float(L), float(L * C2), 1e-5, st2.data_ptr(), stream()), "mi_gram_finalize")
+    torch.cuda.synchronize()
+    # 1x1 on the zero-padded hidden channels, GroupNorm + GLU + LayerScale + residual
+    W3p = torch.zeros(C2, hp, dtype=torch.float64)
+    W3p[:, :h] = Wd
+    wt3, bias3, M3, Mpad3, K3, Kpad3, tile3 = pack_w(W3p, b3, glu=True)
+    kt3 = ktab(hp, 1, 1, 1, 1, 0, 0, P, L, Kpad3)
+    out = torch.full((B, C, pitch), float("nan"), device="cuda")
+    conv_call(x6=x6, wt=wt3, M=M3, Mpad=Mpad3, K=K3, Kpad=Kpad3, ktab=kt3, x=hid, x_bstride=hp * P, B=B, D1=1, D2=L, O1=1, O2=pitch, S1=1,
+              S2=1, row_mode=0, bias=bias3, tile_m=tile3, plain=1, epi=EPI_GN_GLU, gn_stats=st2, gn_w=pack_vec(g2w, Mpad3, glu=True),
+              gn_b=pack_vec(g2b, Mpad3, glu=True), scale=ls.float().cuda(), res=xd, y=out, y_bstride=C * P, y_cstride=P, **pitched)
+    got = out[..., :L].cpu()
+    err = maxerr(got, want)
+    print(f"short rows: layer output, max err {err:.2e}")
+    assert bool(torch.isfinite(got).all()) and err < chained_tol(3e-5)       # the long cases' bar: the normalised branch is O(1) for every item
+
+
+@pytest.mark.parametrize("freq", [True, False, "short"])
 def test_dconv_layer_three_passes(lib, freq, x6):
     """One DConv residual layer (demucs.py:138-143,151-154): dilated conv3 + per-row statistics,
     in-place GroupNorm(1)+GELU pass, 1x1 with statistics-only pass, then GroupNorm + GLU + LayerScale +
-    residual epilogue.  Frequency branch rows are (b, fr); time branch rows are b."""
+    residual epilogue.  Frequency branch rows are (b, fr); time branch rows are b.  "short": a batch of short time-branch rows,
+    chained as the engine chains it (the helper above)."""
+    if freq == "short":
+        return _dconv_layer_on_a_batch_of_short_rows(lib, x6)
     C, h, dil = 48, 6, 2
     if freq:
         B, Fr, T = 2, 5, 336

@@ -3,7 +3,8 @@
 // it.  No GPU, no HIP call, no pointer followed: small aligned numbers stand in for the descriptors' pointers.  The MI_*
 // environment decides as in the library; the argument `nosplit` is mi_set_split_bf16(0).  tests/test_conv_route_host.py
 // builds and runs it and holds the expectations.  The argument `time` prints, INSTEAD of those rows, the time branch's transposed
-// and strided convs of route 11 (tests/test_conv_route_time_host.py).
+// and strided convs of route 11 (tests/test_conv_route_time_host.py); the argument `stats`, instead of them, the statistics epilogues
+// on narrow rows (tests/test_gpu_conv_stats_rows.py).
 //   hipcc --offload-arch=gfx950 -std=c++17 tools/conv_route_table.hip demucs_amd/csrc/conv_route.hip demucs_amd/csrc/switches.hip -o conv_route_table
 #include "../demucs_amd/csrc/common.h"
 #include "../demucs_amd/csrc/kernels.h"
@@ -120,6 +121,25 @@ static void time_rows() {
     { mi_conv_desc d = time_tr(true, 384, 768, 8, 1344, 1344); d.flags = MI_FLAG_GELU | MI_FLAG_RES; d.res = kX; row("time_tr_M768_skip+x6", d); }
 }
 
+// the statistics epilogues on narrow rows: a DConv block's k = 3 conv 48 -> 12 (BIAS_STATS) and the statistics-only form, B items of
+// O1 x O2 columns; after the three numbers a fourth, 1 where launch_conv runs the layer item by item (conv_stats_per_item)
+static void stats_rows() {
+    char name[64];
+    for (int epi : {MI_EPI_BIAS_STATS, MI_EPI_STATS_ONLY})
+        for (int row_mode = 0; row_mode < 2; ++row_mode)
+            for (int B = 1; B <= 13; ++B)
+                for (int O1 : {1, 3})
+                    for (int O2 = 1; O2 <= 40; ++O2) {
+                        mi_conv_desc c = base(12, 144, 32, false);
+                        c.B = B, c.D1 = c.O1 = O1, c.D2 = c.O2 = O2, c.x_bstride = 48 * O1 * O2, c.epi = epi, c.row_mode = row_mode, c.y_cstride = O1 * O2;
+                        c.stats = (double *)kPtr;
+                        snprintf(name, sizeof(name), "stats_e%d_r%d_B%d_%dx%d", epi, row_mode, B, O1, O2);
+                        if (conv_validate(c) != MI_OK) { printf("%s invalid: %s\n", name, last_error_buf()); continue; }
+                        const ConvRoute r = conv_route(c);
+                        printf("%s %d %d %d %d\n", name, r.route, r.tile, (int)r.plain, (int)conv_stats_per_item(c));
+                    }
+}
+
 static void row(const char *name, const mi_conv_desc &d) {
     if (conv_validate(d) != MI_OK) { printf("%s invalid: %s\n", name, last_error_buf()); return; }
     const ConvRoute r = conv_route(d);
@@ -127,12 +147,14 @@ static void row(const char *name, const mi_conv_desc &d) {
 }
 
 int main(int argc, char **argv) {
-    bool time_only = false;
+    bool time_only = false, stats_only = false;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "nosplit")) g_split_bf16 = 0;
         if (!strcmp(argv[i], "time")) time_only = true;
+        if (!strcmp(argv[i], "stats")) stats_only = true;
     }
     if (time_only) { time_rows(); return 0; }
+    if (stats_only) { stats_rows(); return 0; }
     char name[64];
     for (int image = 1; image >= 0; --image) {       // rows A - I of tests/test_gpu_conv_route.py, with and without a split image
         const mi_conv_desc rows[9] = {linear(image, 3136), linear(image, 3200), glu3x3(image, 48, 2), glu3x3(image, 48, 2, false), glu3x3(image, 64, 1),
