@@ -169,7 +169,9 @@ class Separator:
         `Delivery(mix={output: {"mix" | source: gain}})` returns gain-weighted remixes of the stems and of the input mix instead
         (vocals lowered rather than removed, `mix - vocals`): `audio.deliver_mix(origin, stems, mix, ...)` on the whole track bit
         for bit, `origin` being the mix as `separate_tensor` hands back a device mix.  The stream reads the mix from its own input
-        window (`mi_deliver_mix_pcm` in the delivery launch's place), so nothing is kept for it.
+        window (`mi_deliver_mix_pcm` in the delivery launch's place), so nothing is kept for it.  `Delivery(mix=, changes=)` and
+        the stream's `change_mix(mix, at=None, ramp=0)` move those gains along the track by steps and linear ramps
+        (`audio.deliver_mix(..., changes=)` bit for bit; `mi_deliver_mix_auto_pcm` from the first change on).
 
         With `pcm=` ("i16", "i24" or "f32") a block is what a socket, a capture device or a WAV file read in pieces delivers:
         little-endian frames with the channels interleaved, as a bytes-like object or a 1-D uint8 tensor that may end anywhere
@@ -481,6 +483,11 @@ class SeparatorStream:
     def finish(self) -> Dict[str, torch.Tensor]:
         return _named(self.sources, self.stream.finish())
 
+    def change_mix(self, mix, at=None, ramp=0) -> None:
+        """Moves the gains of a `Delivery(mix=)` stream's outputs named in `mix` to the given ones from delivered frame `at` (None:
+        as soon as nothing delivered is contradicted) over `ramp` frames; see `ModelStream.change_mix`."""
+        self.stream.change_mix(mix, at=at, ramp=ramp)
+
     @property
     def emitted(self) -> int:
         return self.stream.emitted
@@ -617,6 +624,10 @@ class SeparatorStreamGroup:
 
     def emitted(self, key) -> int:
         return self.group.emitted(key)
+
+    def change_mix(self, key, mix, at=None, ramp=0) -> None:
+        """`SeparatorStream.change_mix` for stream `key`."""
+        self.group.change_mix(key, mix, at=at, ramp=ramp)
 
     def delivered(self, key) -> int:
         return self.group.delivered(key)

@@ -1146,8 +1146,102 @@ def mix_rows(gains, src: int, n: int, origin: int, pitch: int, affine, clip: int
     return rows
 
 
+# ---- remixes whose gains change along the track (mi_deliver_mix_auto_*, demucs_amd/csrc/deliver_mix_auto.hip) ---------------------
+AUTO_COLS, AUTO_CHG_COLS = 18, 7   # include/demucs_amd.h: MI_AUTO_* (MI_MIX_*'s columns, then T0, CHG_OFF, CHG_N), MI_AUTO_CHG_*
+AUTO_GAIN_MAX = 2.0 ** 64          # of a change's gains: the difference of two cannot overflow float32
 
-def deliver_mix(origin: torch.Tensor, stems: dict, mix: dict, clip="rescale", fmt: str = "i16") -> dict:
+
+def mix_changes(changes, gains, sources=None) -> dict:
+    """`changes` -- `{output name: [(at, ramp, {"mix" | source name: gain}), ...]}` -- checked and ordered by `at` against `gains`
+    (what `mix_gains` returned, in either form: its output names are what a change may name).  From track position `at` (model-rate
+    frames) the output's gains move to the named ones over `ramp` frames (`0`: a step; a term that is not named has gain 0, and all
+    of them may be 0: a fade to silence); frame `at` still has the old gains, frame `at + ramp` is the first with the new ones.
+    With `sources` the gains are resolved as `mix_gains` resolves them: `{name: [(at, ramp, (g_mix, g_0 .. g_{S-1}))]}`; without,
+    `{name: [(at, ramp, {key: gain})]}`.  Outputs without a change are left out, so None and `{}` give `{}`.  Raises ValueError for
+    an unknown output or term, a gain that is not finite or above 2**64 in magnitude, a negative or fractional `at` or `ramp`, and
+    changes of one output that overlap (`at[i] < at[i-1] + ramp[i-1]`)."""
+    import numpy as np
+    if changes is None:
+        return {}
+    if not isinstance(changes, dict):
+        raise ValueError(f"changes: {{output name: [(at, ramp, {{'mix' | source name: gain}}), ...]}} is expected, got {changes!r}")
+    names = [name for name, _ in gains]
+    if sources is not None:
+        sources = list(sources)
+    out = {}
+    for name, items in changes.items():
+        if name not in names:
+            raise ValueError(f"changes: {name!r} is none of the outputs {names}")
+        if not isinstance(items, (list, tuple)):
+            raise ValueError(f"changes: output {name!r} needs a list of (at, ramp, gains), got {items!r}")
+        rows = []
+        for item in items:
+            if not isinstance(item, (list, tuple)) or len(item) != 3 or not isinstance(item[2], dict):
+                raise ValueError(f"changes: output {name!r} needs (at, ramp, {{'mix' | source name: gain}}), got {item!r}")
+            at, ramp, g = item
+            for what, v in (("at", at), ("ramp", ramp)):
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v or int(v) != v or v < 0 \
+                        or v >= 2 ** 61:
+                    raise ValueError(f"changes: `{what}` of output {name!r} is a frame count >= 0, got {v!r}")
+            vals = {}
+            for key, x in g.items():
+                if not isinstance(key, str) or (sources is not None and key != "mix" and key not in sources):
+                    raise ValueError(f"changes: output {name!r} names {key!r}, which is neither 'mix' nor one of the separated "
+                                     f"sources {sources}")
+                if isinstance(x, (bool, str, bytes)):
+                    raise ValueError(f"changes: the gain of {key!r} in output {name!r} must be a number, got {x!r}")
+                try:
+                    with np.errstate(over="ignore"):
+                        v = np.float32(x)
+                except (TypeError, ValueError):
+                    raise ValueError(f"changes: the gain of {key!r} in output {name!r} must be a number, got {x!r}") from None
+                if not np.isfinite(v) or abs(float(v)) > AUTO_GAIN_MAX:
+                    raise ValueError(f"changes: the gain of {key!r} in output {name!r} must be finite and at most 2**64 in magnitude, "
+                                     f"got {x!r}")
+                vals[key] = float(v)
+            rows.append((int(at), int(ramp), vals if sources is None else tuple(vals.get(k, 0.0) for k in ["mix"] + sources)))
+        rows.sort(key=lambda r: r[0])                       # stable: changes at one position keep the order they were given in
+        for prev, cur in zip(rows, rows[1:]):
+            if cur[0] < prev[0] + prev[1]:
+                raise ValueError(f"changes: output {name!r} has a change at {cur[0]} before the ramp from {prev[0]} ends at "
+                                 f"{prev[0] + prev[1]}; changes of one output do not overlap")
+        if rows:
+            out[name] = rows
+    return out
+
+
+def auto_span(base, schedule, t0: int, n: int):
+    """What a call that delivers track positions [t0, t0 + n) needs of one output's ordered `schedule` [(at, ramp, gains)] whose
+    gains before it are `base`: `(gains in force before the listed changes, the listed changes, how many are behind)`.  A change is
+    behind once its ramp has ended at or before t0 (frame at + ramp has the new gains exactly), and those form a prefix; listed are
+    the ones after them that begin before t0 + n."""
+    done = 0
+    while done < len(schedule) and schedule[done][0] + schedule[done][1] <= t0:
+        base = schedule[done][2]
+        done += 1
+    end = done
+    while end < len(schedule) and schedule[end][0] < t0 + n:
+        end += 1
+    return tuple(base), list(schedule[done:end]), done
+
+
+def auto_table(rows, t0s, changes) -> list:
+    """mi_deliver_mix_auto_pcm's table (MI_AUTO_*) from `mix_rows`' words `rows` (their gains being each remix's base gains), the
+    track position `t0s[i]` of remix i's frame 0 and its changes `changes[i]` [(at, ramp, resolved gains)]: the rows first, the
+    changes of all of them behind, each row naming where its own begin."""
+    import numpy as np
+    n = len(rows) // MIX_COLS
+    head, tail = [], []
+    for i in range(n):
+        head += rows[i * MIX_COLS:(i + 1) * MIX_COLS] + [t0s[i], n * AUTO_COLS + len(tail), len(changes[i])]
+        for at, ramp, g in changes[i]:
+            packed = np.zeros(2 * (MIX_CLIP_AT - MIX_GAINS_AT), dtype=np.float32)
+            packed[:len(g)] = g
+            tail += [at, ramp, *packed.view(np.int64).tolist()]
+    return head + tail
+
+
+def deliver_mix(origin: torch.Tensor, stems: dict, mix: dict, clip="rescale", fmt: str = "i16", changes=None) -> dict:
     """Gain-weighted remixes of one separated track, what a user of the reference writes after `separate_tensor` as
     `save_audio(sum(g * x for ...), path, clip=clip)`: `{name: (n, channels) frames}` in `mix`'s order, `mix` being `{output
     name: {"mix" | source name: gain}}` ("mix" is `origin`).  Per sample `acc = 0`, then `acc = acc + g * x` for the mix first and
@@ -1155,9 +1249,16 @@ def deliver_mix(origin: torch.Tensor, stems: dict, mix: dict, clip="rescale", fm
     in a muted stem stays out); then `prevent_clip(·, clip)` with the peak per output, `i16_pcm` ("i16") or float32 ("f32"), the
     channels interleaved.  `{"mix": 1, STEM: -1}` is the reference's "minus" output, gains of 1 on all sources but one its "add".
     All remixes of the track take ONE `mi_deliver_mix_peaks` launch (only for "rescale") and ONE `mi_deliver_mix_pcm` launch;
-    host stems come back on the host by one D2H of the byte buffer."""
+    host stems come back on the host by one D2H of the byte buffer.
+
+    `changes` (`mix_changes`: `{output: [(at, ramp, {term: gain}), ...]}`) moves an output's gains along the track: they are
+    `mix`'s until a change, and from frame `at` move to the change's over `ramp` frames, `g = P + (G - P) * (float32(k) /
+    float32(ramp))` at frame `at + k`, each operation rounded to float32; a term is left out at exactly the samples where its gain
+    is 0.  The launches are then `mi_deliver_mix_auto_peaks` / `mi_deliver_mix_auto_pcm`, still one each; None or `{}` is the call
+    without it."""
     names = list(stems)
     gains = mix_gains(mix, names)
+    schedule = mix_changes(changes, gains, names)
     outputs = mix_outputs(gains)
     code = clip_code(clip)
     if fmt not in _FORMATS:
@@ -1175,22 +1276,29 @@ def deliver_mix(origin: torch.Tensor, stems: dict, mix: dict, clip="rescale", fm
     dev = _engine_device(*tensors)
     with torch.cuda.device(dev):
         block = _stems_block(tensors, dev)
-        org = _stage(origin, dev, "deliver_mix") if any(g[0] != 0 for _, g in gains) else None
+        mixed = any(g[0] != 0 for _, g in gains) or any(g[0] != 0 for rows in schedule.values() for _, _, g in rows)
+        org = _stage(origin, dev, "deliver_mix") if mixed else None
         if org is not None and org.shape != (channels, n):
             raise ValueError(f"deliver_mix: the mix is {tuple(org.shape)}, the stems are {(channels, n)}")
         offs, total = deliver_layout(outputs, n, channels, fmt)
         rows = mix_rows(gains, block.data_ptr(), n, 0 if org is None else org.data_ptr(), n, None, code, 0, fmt, offs)
+        auto, head = "", ()
+        if schedule:                        # MI_AUTO_* rows with their changes behind them; the entries take the table's length
+            rows = auto_table(rows, [0] * len(gains), [schedule.get(name, []) for name, _ in gains])
+            auto, head = "_auto", (len(rows),)
         table = torch.tensor(rows, dtype=torch.int64).to(dev)
         buf = torch.empty(total, dtype=torch.uint8, device=dev)
         lib, stream = _lib.load(), C.c_void_p(_lib.current_stream_ptr())
         peaks = None
         if code == _CLIP_MODES["rescale"]:
             peaks = torch.empty(len(outputs), dtype=torch.int32, device=dev)
-            _lib.check(lib.mi_deliver_mix_peaks(table.data_ptr(), len(outputs), n, len(names), channels, peaks.data_ptr(),
-                                                len(outputs), total, stream), "mi_deliver_mix_peaks")
-        _lib.check(lib.mi_deliver_mix_pcm(table.data_ptr(), len(outputs), n, len(names), channels,
-                                          peaks.data_ptr() if peaks is not None else None, 0 if peaks is None else len(outputs),
-                                          buf.data_ptr(), total, stream), "mi_deliver_mix_pcm")
+            name = f"mi_deliver_mix{auto}_peaks"
+            _lib.check(getattr(lib, name)(table.data_ptr(), *head, len(outputs), n, len(names), channels, peaks.data_ptr(),
+                                          len(outputs), total, stream), name)
+        name = f"mi_deliver_mix{auto}_pcm"
+        _lib.check(getattr(lib, name)(table.data_ptr(), *head, len(outputs), n, len(names), channels,
+                                      peaks.data_ptr() if peaks is not None else None, 0 if peaks is None else len(outputs),
+                                      buf.data_ptr(), total, stream), name)
         if home.type == "cpu":
             host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
             host.copy_(buf, non_blocking=True)

@@ -687,6 +687,27 @@ int mi_deliver_mix_peaks_update(const int64_t *table_dev, int32_t n_rows, int64_
                                            (hipStream_t)stream);
 }
 
+int mi_deliver_mix_auto_pcm(const int64_t *table_dev, int64_t table_len, int32_t n_rows, int64_t max_n, int32_t n_sources,
+                            int32_t channels, const void *peaks_dev, int32_t n_peaks, void *dst_dev, int64_t dst_capacity, void *stream) {
+    MI_REQUIRE(table_dev && dst_dev && n_rows > 0 && n_rows <= 65535 && table_len <= INT32_MAX &&
+               table_len >= (int64_t)n_rows * MI_AUTO_COLS && max_n >= 1 && max_n <= (int64_t)INT32_MAX * 1024 && n_sources > 0 &&
+               n_sources <= MI_MIX_MAX_SOURCES && channels > 0 && n_peaks >= 0 && (n_peaks == 0 || peaks_dev) && dst_capacity >= 0,
+               "mi_deliver_mix_auto_pcm: bad argument");
+    MI_REQUIRE(((uintptr_t)dst_dev & 3) == 0, "mi_deliver_mix_auto_pcm: dst_dev must be 4-byte aligned");
+    return launch_deliver_mix_auto_pcm(table_dev, table_len, n_rows, max_n, n_sources, channels, (const unsigned *)peaks_dev, n_peaks,
+                                       (unsigned char *)dst_dev, dst_capacity, (hipStream_t)stream);
+}
+
+int mi_deliver_mix_auto_peaks(const int64_t *table_dev, int64_t table_len, int32_t n_rows, int64_t max_n, int32_t n_sources,
+                              int32_t channels, void *peaks_dev, int32_t n_peaks, int64_t dst_capacity, void *stream) {
+    MI_REQUIRE(table_dev && peaks_dev && n_rows > 0 && n_rows <= 65535 && table_len <= INT32_MAX &&
+               table_len >= (int64_t)n_rows * MI_AUTO_COLS && max_n >= 1 && max_n <= (int64_t)INT32_MAX * 1024 && n_sources > 0 &&
+               n_sources <= MI_MIX_MAX_SOURCES && channels > 0 && n_peaks > 0 && dst_capacity >= 0,
+               "mi_deliver_mix_auto_peaks: bad argument");
+    return launch_deliver_mix_auto_peaks(table_dev, table_len, n_rows, max_n, n_sources, channels, (unsigned *)peaks_dev, n_peaks,
+                                         dst_capacity, (hipStream_t)stream);
+}
+
 // Kernel-level entry points.  They allocate their scratch with hipMalloc and free it after a
 // stream synchronise: convenient for parity tests, not meant for the hot loop.
 int mi_stft_cac(const float *mix_dev, int32_t B, int32_t L, float *cac_dev, void *stream) {

@@ -317,6 +317,12 @@ int launch_deliver_mix_peaks(const int64_t *table, int n_rows, int64_t max_n, in
 int launch_deliver_mix_peaks_update(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, unsigned *peaks,
                                     int n_peaks, hipStream_t st);
 
+// deliver_mix_auto.hip: the same for remixes whose gains change along the track (steps and linear ramps at track positions)
+int launch_deliver_mix_auto_pcm(const int64_t *table, int64_t table_len, int n_rows, int64_t max_n, int n_sources, int channels,
+                                const unsigned *peaks, int n_peaks, unsigned char *dst, int64_t dst_cap, hipStream_t st);
+int launch_deliver_mix_auto_peaks(const int64_t *table, int64_t table_len, int n_rows, int64_t max_n, int n_sources, int channels,
+                                  unsigned *peaks, int n_peaks, int64_t dst_cap, hipStream_t st);
+
 // deliver_resample.hip: a stream's outputs at another sample rate -- value, streaming resample_frac, clip, PCM -- in one launch
 int launch_deliver_resample_pcm(const int64_t *table, int n_rows, int64_t max_groups, int n_sources, int channels, const float *bank,
                                 int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, unsigned char *dst, int64_t dst_cap,

@@ -1,6 +1,7 @@
 // Per-sample arithmetic of the stem post-processing, shared by post.hip (mi_prevent_clip, mi_two_stems: one output per call),
-// deliver.hip (mi_deliver_peaks / mi_deliver_pcm: every output of a call in one launch) and deliver_mix.hip (the same for
-// gain-weighted remixes), so all routes run the same float32 sequence.  Every step is a separately rounded operation (the
+// deliver.hip (mi_deliver_peaks / mi_deliver_pcm: every output of a call in one launch), deliver_mix.hip (the same for
+// gain-weighted remixes) and deliver_mix_auto.hip (remixes whose gains change along the track), so all routes run the same float32
+// sequence.  Every step is a separately rounded operation (the
 // library builds with -ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,6 +48,30 @@ __device__ __forceinline__ void mix_values(int S, Gain gain, Origin origin, Stem
         stem(k, s);
 #pragma unroll
         for (int e = 0; e < W; ++e) a[e] = __fadd_rn(a[e], __fmul_rn(g, s[e]));
+    }
+}
+
+// mix_values with a gain per ELEMENT (deliver_mix_auto.hip: gains that change along the track).  gain(i, g) fills the W gains of
+// term i (0: the mix, 1 + k: stem k).  Element e of a term is added only where g[e] != 0, so a NaN in a stem stays out of exactly
+// the samples at which the stem is muted; a term whose W gains are all 0 is not loaded at all.  With W equal gains per term this is
+// mix_values' sequence, operation for operation
+template <int W, class Gain, class Origin, class Stem>
+__device__ __forceinline__ void mix_values_each(int S, Gain gain, Origin origin, Stem stem, float (&a)[W]) {
+#pragma unroll
+    for (int e = 0; e < W; ++e) a[e] = 0.f;
+    for (int i = 0; i <= S; ++i) {
+        float g[W];
+        gain(i, g);
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < W; ++e) any = any || g[e] != 0.f;
+        if (!any) continue;
+        float s[W];
+        if (i == 0) origin(s);
+        else stem(i - 1, s);
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+            if (g[e] != 0.f) a[e] = __fadd_rn(a[e], __fmul_rn(g[e], s[e]));
     }
 }
 

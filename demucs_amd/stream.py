@@ -76,11 +76,18 @@ class Delivery:
     lowered by 12 dB rather than removed (`{"practice": {"mix": 1, "vocals": 10 ** -0.6 - 1}}`), drums raised, or `{"minus_vocals":
     {"mix": 1, "vocals": -1}}`, the reference's "minus" residual.  The frames equal `audio.deliver_mix(origin, stems, mix, ...)` on
     the whole track bit for bit, `origin` being the mix as `Separator.separate_tensor` hands back a device mix.  "mix" is the
-    stream's own input: its window still holds every position that is being emitted, so no copy is kept for it.  The gains are
-    fixed for the stream; `mix` goes with `stem=None`, the default `other_method` and the model's sample rate only."""
+    stream's own input: its window still holds every position that is being emitted, so no copy is kept for it.  `mix` goes with
+    `stem=None`, the default `other_method` and the model's sample rate only.
 
-    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16", samplerate=None, peaks=None, mix=None):
-        from .audio import TrackPeaks, clip_code, deliver_layout, mix_gains
+    The gains are `mix`'s until a change takes effect.  `changes={output name: [(at, ramp, {"mix" | source name: gain}), ...]}` is
+    a schedule known when the stream opens (`audio.mix_changes`): from delivered frame `at` the output's gains move to the named
+    ones over `ramp` frames, linearly and in float32 (`ramp=0`: a step; all gains 0: a fade to silence).  `change_mix` on the open
+    stream appends further changes.  Either way the frames equal `audio.deliver_mix(..., changes=)` on the whole track bit for bit.
+    A stream with changes does not deliver with `clip="rescale"`: a `TrackPeaks` carries no schedule."""
+
+    def __init__(self, stem=None, other_method: str = "add", clip="clamp", fmt: str = "i16", samplerate=None, peaks=None, mix=None,
+                 changes=None):
+        from .audio import TrackPeaks, clip_code, deliver_layout, mix_changes, mix_gains
         if other_method not in ("add", "minus", "none"):
             raise ValueError(f"Invalid other_method {other_method}")
         if mix is not None:
@@ -90,9 +97,12 @@ class Delivery:
             if samplerate is not None:
                 raise ValueError(f"mix= delivers at the model's sample rate only, got samplerate={samplerate!r}: resample the "
                                  "remixed frames, or deliver the stems at that rate and remix them")
-            mix_gains(mix)                                      # what can be refused before the sources are known
+            named = mix_gains(mix)                              # what can be refused before the sources are known
             mix = {name: dict(gains) for name, gains in mix.items()}
-        self.mix = mix
+            changes = mix_changes(changes, named) or None       # ordered; the terms are checked once the sources are known
+        elif changes:
+            raise ValueError(f"changes= moves the gains of mix= outputs: it goes with mix=, got changes={changes!r} without it")
+        self.mix, self.changes = mix, changes or None
         self.stem, self.other_method, self.clip, self.fmt = stem, other_method, clip, fmt
         if samplerate is not None and (int(samplerate) != samplerate or samplerate <= 0):
             raise ValueError(f"the delivered sample rate must be a positive integer, got {samplerate}")
@@ -114,11 +124,12 @@ class Delivery:
 
     def with_peaks(self, peaks) -> "Delivery":
         """The same delivery with other `peaks` (what a measuring pass found, for the delivering pass)."""
-        return Delivery(self.stem, self.other_method, self.clip, self.fmt, self.samplerate, peaks, self.mix)
+        return Delivery(self.stem, self.other_method, self.clip, self.fmt, self.samplerate, peaks, self.mix, self.changes)
 
     def __repr__(self):
         tail = "" if self.peaks is None else f", peaks={self.peaks!r}"
         tail += "" if self.mix is None else f", mix={self.mix!r}"
+        tail += "" if self.changes is None else f", changes={self.changes!r}"
         return (f"Delivery(stem={self.stem!r}, other_method={self.other_method!r}, clip={self.clip!r}, fmt={self.fmt!r}, "
                 f"samplerate={self.samplerate!r}{tail})")
 
@@ -137,6 +148,10 @@ class Delivery:
 
     def for_stream(self, sources, engine: bool, model_rate=None, channels: int = 2) -> list:
         """The refusals of a delivering stream (no device work, no RNG call) and its outputs."""
+        if self.clip == "rescale" and self.changes is not None:
+            raise ValueError("a stream with gain changes (changes=) does not deliver with clip='rescale': the peaks of a track "
+                             "belong to one schedule of gains and audio.TrackPeaks carries none; use 'clamp', 'tanh' or None, or "
+                             "audio.deliver_mix(..., clip='rescale', changes=) on the whole track")
         if self.clip == "rescale" and self.peaks is None:
             raise ValueError("a stream cannot deliver with clip='rescale': the divisor is the whole track's peak per output; use "
                              "'clamp', 'tanh' or None, or measure the peaks in a pass of their own (peaks='measure', then "
@@ -145,6 +160,7 @@ class Delivery:
             raise ValueError("a stream does not deliver other_method='minus'; use 'add' or 'none', or name the residual by its "
                              "gains: mix={'minus_STEM': {'mix': 1, STEM: -1}}")
         outs = self.outputs(sources)
+        self.schedule(sources)              # refuses a change that names an unknown term
         if not engine:
             raise ValueError("a delivering stream runs on the GPU engines (HTDemucs / HDemucs on a cuda device); there is no CPU "
                              "implementation of the delivery kernels in this package")
@@ -158,6 +174,11 @@ class Delivery:
         """`mix` resolved against `sources` (`audio.mix_gains`: [(name, (g_mix, g_0 .. g_{S-1}))]), None without `mix`."""
         from .audio import mix_gains
         return None if self.mix is None else mix_gains(self.mix, sources)
+
+    def schedule(self, sources) -> dict:
+        """`changes` resolved against `sources` (`audio.mix_changes`: {output: [(at, ramp, (g_mix, g_0 .. g_{S-1}))]}), {} without."""
+        from .audio import mix_changes
+        return {} if self.changes is None else mix_changes(self.changes, self.gains(sources), sources)
 
     def _check_peaks(self, outs, model_rate, gains=None) -> None:
         """Refuses a `TrackPeaks` that was measured for other outputs or at another rate than this stream delivers."""
@@ -206,6 +227,26 @@ def _mix_rows(st: "ModelStream", src: int, n: int, t0: int, win: int, win0: int,
         assert win0 <= t0, f"the window starts at {win0}, past the emit point {t0}"
         origin = win + 4 * (t0 - win0)
     return mix_rows(st.gains, src, n, origin, pitch, st.affine, st.deliver.clip_code, slot0, st.deliver.fmt, offs)
+
+
+def _auto_rows(st: "ModelStream", src: int, n: int, t0: int, win: int, win0: int, pitch: int, offs, slot0: int = 0):
+    """`_mix_rows`' sibling for a stream whose gains change (`st.schedule`): `(rows, changes)` for `audio.auto_table`, one entry per
+    remix.  The rows are `_mix_rows`' with the gains in force before the changes that reach into [t0, t0 + n), `changes` those
+    changes (`audio.auto_span`): a call passes no change that lies wholly behind or ahead of it.  Changes that are behind leave the
+    schedule for good and their gains become the output's base.  The mix is named when any of the call's gains reads it."""
+    from .audio import auto_span, mix_rows
+    base, changes = [], []
+    for i, (name, _) in enumerate(st.gains):
+        gains, listed, done = auto_span(st.auto_base[i], st.schedule[i], t0, n)
+        st.auto_base[i] = gains
+        del st.schedule[i][:done]
+        base.append((name, gains))
+        changes.append(listed)
+    origin = 0
+    if any(g[0] != 0 for _, g in base) or any(g[0] != 0 for listed in changes for _, _, g in listed):
+        assert win0 <= t0, f"the window starts at {win0}, past the emit point {t0}"
+        origin = win + 4 * (t0 - win0)
+    return mix_rows(base, src, n, origin, pitch, st.affine, st.deliver.clip_code, slot0, st.deliver.fmt, offs), changes
 
 
 def _packed_slots(slots) -> list:
@@ -355,10 +396,17 @@ class ModelStream:
         self.measure = deliver is not None and deliver.measures      # push returns {}, finish() the audio.TrackPeaks
         self.gains = None                  # a remixing delivery's gains per output (`Delivery.gains`)
         self.peak_off = None               # first of the stream's peak slots in its executor's buffer (a rescaling delivery)
+        # gain changes (`Delivery(changes=)`, `change_mix`): per output the changes not yet behind the emit point, the gains in
+        # force before them and the end of the last ramp; None until the first change, and the stream's launches are the fixed
+        # gains' until then
+        self.schedule = self.auto_base = self.auto_end = None
         if deliver is not None:
             engine = all(m.kind != "generic" for m in self.members) and (self.device is None or self.device.type == "cuda")
             self.outputs = deliver.for_stream(self.sources, engine, self.samplerate, self.audio_channels)
             self.gains = deliver.gains(self.sources)
+            for name, rows in deliver.schedule(self.sources).items():
+                for row in rows:
+                    self._add_change([n for n, _ in self.gains].index(name), row)
             plan = deliver.rate_plan(self.samplerate, self.audio_channels)
             if plan is not None:
                 self.rate = _Rate(plan, len(self.outputs), self.audio_channels)
@@ -404,6 +452,46 @@ class ModelStream:
                     plen = self.length - origin
                     for _ in range(m.draws * len(range(0, plen, m.stride))):
                         random.randrange(1)
+
+    # ---- gain changes ---------------------------------------------------------------------------------------------------
+    def _add_change(self, i: int, change) -> None:
+        if self.schedule is None:
+            self.schedule = [[] for _ in self.gains]
+            self.auto_base = [tuple(g) for _, g in self.gains]
+            self.auto_end = [0] * len(self.gains)
+        self.schedule[i].append(change)
+        self.auto_end[i] = change[0] + change[1]
+
+    def change_mix(self, mix, at=None, ramp=0) -> None:
+        """Moves the gains of the outputs named in `mix` (`{output name: {"mix" | source name: gain}}`, a term that is not named
+        going to 0) to the given ones: from delivered frame `at` (model-rate frames, as `emitted` counts them) over `ramp` frames,
+        as a change of `Delivery(changes=)` does.  `at=None` is the earliest position that contradicts nothing: the later of
+        `emitted` and the end of the output's last ramp.  What has been delivered stays as it is, so an `at` before `emitted`, or
+        before the end of the output's last ramp, is refused, and so is a stream without `Delivery(mix=)`.  Nothing runs on the
+        device here; from its first change on the stream's frames come from `mi_deliver_mix_auto_pcm`."""
+        from .audio import mix_changes
+        if self.gains is None:
+            raise ValueError("change_mix: the stream delivers no remix; open it with Delivery(mix=...)")
+        if self.finished:
+            raise ValueError("change_mix: the stream is finished")
+        if self.deliver.clip == "rescale":
+            raise ValueError("change_mix: a stream that delivers with clip='rescale' divides by peaks measured for fixed gains; "
+                             "audio.TrackPeaks carries no schedule")
+        if not isinstance(mix, dict) or not mix:
+            raise ValueError(f"change_mix: a non-empty {{output name: {{'mix' | source name: gain}}}} is expected, got {mix!r}")
+        names = [name for name, _ in self.gains]
+        planned = []
+        for name, gains in mix.items():
+            end = self.auto_end[names.index(name)] if self.schedule is not None and name in names else 0
+            a = max(self.emitted, end) if at is None else at
+            change = mix_changes({name: [(a, ramp, gains)]}, self.gains, self.sources)[name][0]
+            if a < self.emitted:
+                raise ValueError(f"change_mix: at={a} lies before the {self.emitted} frames that were delivered already")
+            if a < end:
+                raise ValueError(f"change_mix: at={a} lies before {end}, where the last ramp of output {name!r} ends")
+            planned.append((names.index(name), change))
+        for i, change in planned:           # all of them, or none
+            self._add_change(i, change)
 
     # ---- scheduling (device independent) ------------------------------------------------------------------------------
     def _ready(self, final: bool):
@@ -863,7 +951,14 @@ class _EngineExec:
                     self.peaks = torch.zeros(n_pk, dtype=torch.int32, device=st.device) if st.measure else \
                         _upload(list(dl.peaks.bits), torch.int32, st.device)
                     self.slots, st.peak_off = torch.arange(n_pk, dtype=torch.int32, device=st.device), 0
-                if st.gains is not None:
+                auto_len = None                 # a stream whose gains change: MI_AUTO_* rows, their changes behind them
+                if st.schedule is not None:
+                    from .audio import auto_table
+                    rows, changes = _auto_rows(st, out.data_ptr(), t1 - t0, t0, self.win.data_ptr(), self.win0, self.win.shape[1],
+                                               offs)
+                    rows = auto_table(rows, [t0] * len(changes), changes)
+                    passes, auto_len = passes + rows, len(rows)
+                elif st.gains is not None:
                     passes = passes + _mix_rows(st, out.data_ptr(), t1 - t0, t0, self.win.data_ptr(), self.win0, self.win.shape[1],
                                                 None if st.measure else offs)
                 elif rt is None:
@@ -894,6 +989,11 @@ class _EngineExec:
                 keep.append(out)
                 name = f"mi_deliver{mixed}_peaks_update"
                 _lib.check(getattr(self.lib, name)(rows_at, len(st.outputs), t1 - t0, S, channels, *pk, self._stream()), name)
+            elif dl is not None and rt is None and auto_len is not None:
+                keep.append(out)
+                _lib.check(self.lib.mi_deliver_mix_auto_pcm(rows_at, auto_len, len(st.outputs), t1 - t0, S, channels, *pk,
+                                                            frames[0].data_ptr(), frames[0].numel(), self._stream()),
+                           "mi_deliver_mix_auto_pcm")
             elif dl is not None and rt is None:
                 keep.append(out)
                 name = f"mi_deliver{mixed}_pcm"
@@ -1008,7 +1108,8 @@ class StreamGroup:
     driven by that table), one `mi_streams_emit` and one D2H of the host-bound stems, plus one `mi_streams_compact` when a
     stream outgrows its room in the state buffer (every stream's window and accumulators).  Streams opened with `deliver=` add one
     `mi_deliver_pcm` for all of them behind the emit (and one `mi_deliver_mix_pcm` for all that deliver remixes, `Delivery(mix=)`,
-    which read the mix from their windows in the state buffer); their host-bound frames leave in one D2H of the byte buffer, and
+    which read the mix from their windows in the state buffer, and one `mi_deliver_mix_auto_pcm` for all of those whose gains
+    change, `Delivery(changes=)` / `change_mix`); their host-bound frames leave in one D2H of the byte buffer, and
     their float stems never do.  Those whose `Delivery` names another sample rate share one `mi_deliver_resample_pcm` instead (so a
     call has at most one launch more, whatever the number of streams), their frames in the same byte buffer and their carried
     values in the group's history buffer.  Streams that deliver with `clip="rescale"` keep their peaks (measured by the stream, or given to it) in
@@ -1107,6 +1208,10 @@ class StreamGroup:
 
     def pushed(self, key) -> int:
         return self._stream(key).pushed
+
+    def change_mix(self, key, mix, at=None, ramp=0) -> None:
+        """`ModelStream.change_mix` for stream `key`: its gains move to `mix`'s from delivered frame `at` over `ramp` frames."""
+        self._stream(key).change_mix(mix, at=at, ramp=ramp)
 
     def trailing_bytes(self, key) -> int:
         """Bytes of an incomplete last frame of a PCM stream, carried to its next push."""
@@ -1707,9 +1812,10 @@ class _GroupEngineExec:
         """mi_streams_emit's tables for every stream of the call with new final samples; host-bound stems first.  Behind them the
         rows of the delivering streams: mi_deliver_pcm's, then mi_deliver_resample_pcm's for those that deliver at another rate,
         last mi_deliver_mix_pcm's for those that deliver remixes, which read the mix from their windows in `state` (the state
-        buffer as the emit will find it, after this call's compaction)."""
+        buffer as the emit will find it, after this call's compaction), and mi_deliver_mix_auto_pcm's table (`audio.auto_table`)
+        for the remixing streams whose gains change."""
         g = self.g
-        from .audio import MIX_COLS, RATE_COLS, _BankArena, deliver_layout, rate_groups, rate_lds_floats
+        from .audio import MIX_COLS, RATE_COLS, _BankArena, auto_table, deliver_layout, rate_groups, rate_lds_floats
         S, C_ = len(g.sources), g.audio_channels
         spans = []
         for key, st, _ in work:
@@ -1753,6 +1859,8 @@ class _GroupEngineExec:
         m_rows, m_longest, mr_rows, mr_slots, mr_groups, mr_lds = [], 1, [], [], 1, 1
         # remixing deliveries: all of a call's in one launch more, the measuring ones among them in one of their own
         x_rows, x_longest, xm_rows, xm_longest = [], 1, [], 1
+        # those among them whose gains change: one launch for all of them too, their changes behind their rows
+        a_rows, a_t0s, a_changes, a_longest = [], [], [], 1
         for key, st, t0, _, to_host in sorted(spans, key=lambda s: not s[4]):
             f_off, n = layout[key]
             rt, dl = st.rate, st.deliver
@@ -1793,6 +1901,16 @@ class _GroupEngineExec:
                 m_rows += _deliver_rows(st.outputs, dl, src, n, None, st.peak_off)
                 m_longest = max(m_longest, n)
                 continue
+            elif st.schedule is not None:
+                slot = self.slots[key]
+                offs, d_off = deliver_layout(st.outputs, n, C_, dl.fmt, d_off)
+                rows, changes = _auto_rows(st, src, n, t0, state.data_ptr() + 4 * slot.w_base, slot.w0, slot.w_cap, offs,
+                                           st.peak_off or 0)
+                a_rows += rows
+                a_t0s += [t0] * len(changes)
+                a_changes += changes
+                d_layout[key], d_count[key] = offs, n
+                a_longest = max(a_longest, n)
             elif st.gains is not None:
                 slot = self.slots[key]
                 offs, d_off = deliver_layout(st.outputs, n, C_, dl.fmt, d_off)
@@ -1822,9 +1940,12 @@ class _GroupEngineExec:
         table += x_rows
         xm_at = len(table)
         table += xm_rows
+        a_at = len(table)
+        a_table = auto_table(a_rows, a_t0s, a_changes)
+        table += a_table
         return dict(at=at, n_streams=len(streams) // STREAMS_EMIT_COLS, n_passes=len(passes) // 8, n_segs=len(segs) // 2,
                     x_at=x_at, x_rows=len(x_rows) // MIX_COLS, x_longest=x_longest, xm_at=xm_at, xm_rows=len(xm_rows) // MIX_COLS,
-                    xm_longest=xm_longest,
+                    xm_longest=xm_longest, a_at=a_at, a_rows=len(a_t0s), a_len=len(a_table), a_longest=a_longest,
                     total=off, host_n=host_n, longest=longest, layout=layout, order=[k for k, _, _ in work],
                     streams={k: st for k, st, _ in work}, out=out, d_at=d_at, d_rows=len(d_rows) // DELIVER_COLS, d_total=d_off,
                     d_host=d_host, d_longest=d_longest, d_layout=d_layout, d_count=d_count, r_at=r_at,
@@ -1849,7 +1970,7 @@ class _GroupEngineExec:
                                                 int(g.bag_weights is not None), self.stats.data_ptr(), self.n_stats, out.data_ptr(),
                                                 out.numel(), self._stream()), "mi_streams_emit")
         frames = None
-        if emit["d_rows"] or emit["r_rows"] or emit["x_rows"]:
+        if emit["d_rows"] or emit["r_rows"] or emit["x_rows"] or emit["a_rows"]:
             # at least 16 bytes: a call on which resampling streams only carry values still names a destination
             frames = torch.empty(max(emit["d_total"], 16), dtype=torch.uint8, device=dev)
         pk = (None, 0) if self.peaks is None else (self.peaks.data_ptr(), self.peaks.numel())
@@ -1880,6 +2001,10 @@ class _GroupEngineExec:
         if emit["x_rows"]:
             _lib.check(self.lib.mi_deliver_mix_pcm(C.c_void_p(base + 8 * emit["x_at"]), emit["x_rows"], emit["x_longest"], S, C_, *pk,
                                                    frames.data_ptr(), frames.numel(), self._stream()), "mi_deliver_mix_pcm")
+        if emit["a_rows"]:                  # and one for all whose gains change
+            _lib.check(self.lib.mi_deliver_mix_auto_pcm(C.c_void_p(base + 8 * emit["a_at"]), emit["a_len"], emit["a_rows"],
+                                                        emit["a_longest"], S, C_, *pk, frames.data_ptr(), frames.numel(),
+                                                        self._stream()), "mi_deliver_mix_auto_pcm")
         if emit["xm_rows"]:
             _lib.check(self.lib.mi_deliver_mix_peaks_update(C.c_void_p(base + 8 * emit["xm_at"]), emit["xm_rows"], emit["xm_longest"],
                                                             S, C_, *pk, self._stream()), "mi_deliver_mix_peaks_update")

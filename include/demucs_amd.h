@@ -669,6 +669,60 @@ int mi_deliver_mix_peaks(const int64_t *table_dev, int32_t n_rows, int64_t max_n
 int mi_deliver_mix_peaks_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels,
                                 void *peaks_dev, int32_t n_peaks, void *stream);
 
+/* ---- remixes whose gains change along the track (gain automation), every such remix of a call in ONE launch ---------------------
+ * What a user of the reference writes after `separate_tensor` as `save_audio(sum(g(p) * x for ...), path, clip=...)` with gain
+ * curves g(p) made of steps and linear ramps: vocals brought down for a chorus and back up, a fade written over track time.  A row
+ * has base gains and an ordered list of CHANGES (AT, RAMP, target gains G).  At track position p = T0 + j the change in force is
+ * the last one with AT <= p (none: the base gains); with P the gains before it (the change before it fully reached, or the base
+ * gains) and k = p - AT, term i has the gain
+ *     k >= RAMP:  G_i exactly;        else  t = float(k) / float(RAMP),  g_i = P_i + (G_i - P_i) * t
+ * every conversion, quotient, difference, product and sum a separately rounded float32 operation (no fused multiply-add).  Frame
+ * AT therefore still has the old gains and frame AT + RAMP is the first with the new ones; RAMP = 0 is a step.  The value is
+ * mi_deliver_mix_pcm's chain with these per-sample gains: acc = 0, then acc = acc + g_i * x_i for the mix first and the stems in
+ * order, a term being added only at the samples where its gain is not 0 (a NaN in a stem stays out of exactly the samples at which
+ * the stem is muted; a term none of whose gains is non-zero over a thread's four frames is not loaded).  CLIP, FMT and the
+ * interleaving follow as in mi_deliver_pcm.  A row without changes, or whose changes all equal its base gains, gives
+ * mi_deliver_mix_pcm's bytes.
+ * The table (table_len int64, a DEVICE array, table_len <= INT32_MAX) begins with n_rows rows of MI_AUTO_COLS words; the changes
+ * lie anywhere in the same table.  Row r:
+ *     SRC .. DST_OFF   MI_MIX_*'s columns at the same indices; GAINS are the BASE gains, in force before the row's first change;
+ *     T0               track position of the row's frame 0;
+ *     CHG_OFF, CHG_N   the row's changes: CHG_N records of MI_AUTO_CHG_COLS words from word CHG_OFF of the table, each
+ *                      AT, RAMP (int64) and nine float32 target gains in five words, packed as MI_MIX_GAINS.
+ *   There is no cap on CHG_N; the change in force is found by bisection over AT.  A row is skipped whole (nothing of it is written)
+ *   under mi_deliver_mix_pcm's rules, except that all gains may be 0 (a fade to silence), the mix being needed (ORIGIN, ORIGIN_PITCH)
+ *   when g_mix is not 0 in the base gains or in any change, and when: the change list reaches outside [0, table_len); changes are
+ *   out of order or overlap (AT[i] < AT[i-1] + RAMP[i-1]); RAMP < 0; |AT|, RAMP or |T0| exceed 2^61; a gain of a change is not
+ *   finite or exceeds 2^64 in magnitude (so that G - P cannot overflow).  No kernel uses scratch memory, nothing synchronises with
+ *   the host.
+ * mi_deliver_mix_auto_pcm: writes every row's frames on mi_deliver_mix_pcm's grid (four frames a thread, 16-byte loads and stores
+ *   where base, pitch and N allow).  peaks_dev may be null when n_peaks == 0.
+ * mi_deliver_mix_auto_peaks: zeroes peaks_dev and reduces max |value| of every MI_CLIP_RESCALE row into its slot, as
+ *   mi_deliver_mix_peaks. */
+#define MI_AUTO_SRC 0
+#define MI_AUTO_N 1
+#define MI_AUTO_ORIGIN 2
+#define MI_AUTO_ORIGIN_PITCH 3
+#define MI_AUTO_ORIGIN_AFFINE 4
+#define MI_AUTO_AFFINE_ON 5
+#define MI_AUTO_GAINS 6
+#define MI_AUTO_CLIP 11
+#define MI_AUTO_PEAK 12
+#define MI_AUTO_FMT 13
+#define MI_AUTO_DST_OFF 14
+#define MI_AUTO_T0 15
+#define MI_AUTO_CHG_OFF 16
+#define MI_AUTO_CHG_N 17
+#define MI_AUTO_COLS 18
+#define MI_AUTO_CHG_AT 0
+#define MI_AUTO_CHG_RAMP 1
+#define MI_AUTO_CHG_GAINS 2
+#define MI_AUTO_CHG_COLS 7
+int mi_deliver_mix_auto_pcm(const int64_t *table_dev, int64_t table_len, int32_t n_rows, int64_t max_n, int32_t n_sources,
+                            int32_t channels, const void *peaks_dev, int32_t n_peaks, void *dst_dev, int64_t dst_capacity, void *stream);
+int mi_deliver_mix_auto_peaks(const int64_t *table_dev, int64_t table_len, int32_t n_rows, int64_t max_n, int32_t n_sources,
+                              int32_t channels, void *peaks_dev, int32_t n_peaks, int64_t dst_capacity, void *stream);
+
 /* ---- kernel-level entry points (parity tests; same kernels the forward uses) --------------
  * mi_stft_cac: `_magnitude(_spec(mix))` (demucs/htdemucs.py:420-461, demucs/spec.py:11-27):
  *   mix_dev (B,2,L) -> cac_dev (B,4,2048,ceil(L/1024)), channel order [c0.re,c0.im,c1.re,c1.im]. */

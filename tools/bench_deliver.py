@@ -28,6 +28,14 @@ Runs of `--reps` launches between two device events alternate (add, mix, add, mi
 reported per entry: microseconds per launch of every run, their median and spread, and the bytes moved per second at the median.
 
     python tools/bench_deliver.py --mix-kernel --seconds 180 --out profiles/deliver_mix_kernel.json
+
+With `--auto-kernel` the launches are `mi_deliver_mix_pcm` and `mi_deliver_mix_auto_pcm` on the same four remix rows (the mix and
+two stems each, clip "clamp", int16) of the same device data, by the same method.  The automated rows carry ONE ramp each, to the
+row's own gains, so both entries read the same terms and must write the same bytes, while every frame inside the ramp takes the
+per-frame path: leg `auto` with a ramp of `--ramp-seconds` in the middle of the track (the blocks outside it run on uniform gains),
+leg `auto_ramping` with a ramp over the whole track (every block on the per-frame path: the worst case).
+
+    python tools/bench_deliver.py --auto-kernel --seconds 180 --out profiles/deliver_mix_auto_kernel.json
 """
 from __future__ import annotations
 
@@ -100,10 +108,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-sr", type=int, default=None, help="compare delivery at the model's rate with delivery at this rate")
     ap.add_argument("--mix-kernel", action="store_true", help="time mi_deliver_mix_pcm against mi_deliver_pcm's ADD rows")
-    ap.add_argument("--reps", type=int, default=20, help="launches per timed run of --mix-kernel")
+    ap.add_argument("--auto-kernel", action="store_true", help="time mi_deliver_mix_auto_pcm against mi_deliver_mix_pcm on the same rows")
+    ap.add_argument("--ramp-seconds", type=float, default=10.0, help="length of each row's ramp in the `auto` leg of --auto-kernel")
+    ap.add_argument("--reps", type=int, default=20, help="launches per timed run of --mix-kernel / --auto-kernel")
     args = ap.parse_args()
     if args.mix_kernel:
         return mix_kernel_main(args)
+    if args.auto_kernel:
+        return auto_kernel_main(args)
     if args.out_sr is not None:
         return rate_main(args)
     length = int(args.seconds * SR)
@@ -214,6 +226,70 @@ def mix_kernel_main(args):
                          "us_spread": round(max(us) - min(us), 1), "gb_per_s": round(moved / med / 1e3, 1)}
     result["mix_over_add"] = round(result["mix"]["us_median"] / result["add"]["us_median"], 3)
     result["within_add_spread"] = result["mix"]["us_median"] <= result["add"]["us_median"] + result["add"]["us_spread"]
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def auto_kernel_main(args):
+    import ctypes as C
+
+    from demucs_amd import _lib, audio
+    S, channels, n = 4, 2, int(args.seconds * SR)
+    dev = torch.device("cuda", 0)
+    stems = (torch.rand(S, channels, n, device=dev) * 2 - 1) * 0.4
+    origin = (torch.rand(channels, n, device=dev) * 2 - 1) * 0.4
+    # the mix and two stems per remix: "STEM lowered", as a practice feed asks for
+    gains = [(f"practice_{k}", (1.0,) + tuple(-0.75 if j == k else 0.5 if j == (k + 1) % S else 0.0 for j in range(S))) for k in range(S)]
+    offs, total = audio.deliver_layout(audio.mix_outputs(gains), n, channels, "i16")
+    clamp = audio.clip_code("clamp")
+    rows = audio.mix_rows(gains, stems.data_ptr(), n, origin.data_ptr(), n, None, clamp, 0, "i16", offs)
+    ramp = min(n, int(args.ramp_seconds * SR))
+    words = {"mix": rows,
+             "auto": audio.auto_table(rows, [0] * S, [[((n - ramp) // 2 + 1000 * k, ramp - 1000 * S, g)] for k, (_, g) in enumerate(gains)]),
+             "auto_ramping": audio.auto_table(rows, [0] * S, [[(-1 - k, n + 2 + k, g)] for k, (_, g) in enumerate(gains)])}
+    tables = {k: torch.tensor(v, dtype=torch.int64).to(dev) for k, v in words.items()}
+    bufs = {k: torch.zeros(total, dtype=torch.uint8, device=dev) for k in tables}
+    lib = _lib.load()
+
+    def timed(which: str, reps: int) -> float:
+        stream = C.c_void_p(_lib.current_stream_ptr())
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(reps):
+            if which == "mix":
+                _lib.check(lib.mi_deliver_mix_pcm(tables[which].data_ptr(), S, n, S, channels, None, 0, bufs[which].data_ptr(), total,
+                                                  stream), "mi_deliver_mix_pcm")
+            else:
+                _lib.check(lib.mi_deliver_mix_auto_pcm(tables[which].data_ptr(), len(words[which]), S, n, S, channels, None, 0,
+                                                       bufs[which].data_ptr(), total, stream), "mi_deliver_mix_auto_pcm")
+        t1.record()
+        t1.synchronize()
+        return 1e3 * t0.elapsed_time(t1) / reps                          # microseconds per launch
+
+    for which in tables:
+        timed(which, 3)
+    for which in ("auto", "auto_ramping"):
+        assert torch.equal(bufs["mix"], bufs[which]), f"{which}: a ramp to the row's own gains must write the fixed gains' bytes"
+    assert int(bufs["mix"].count_nonzero()) > total // 2
+    runs = {k: [] for k in tables}
+    for _ in range(args.pairs):
+        for which in tables:
+            runs[which].append(timed(which, args.reps))
+    moved = S * 3 * channels * n * 4 + S * channels * n * 2                 # bytes read (three terms a row) and written by a launch
+    result = {"what": f"{args.seconds:g} s of {S} stereo stems and the mix: mi_deliver_mix_pcm vs mi_deliver_mix_auto_pcm on the same "
+                      f"{S} rows of three terms, clamp, int16; one ramp per automated row ({ramp / SR:g} s, or the whole track); "
+                      "alternating runs",
+              "device": torch.cuda.get_device_name(0), "reps": args.reps, "pairs": args.pairs, "bytes_per_launch": moved}
+    for which, us in runs.items():
+        med = statistics.median(us)
+        result[which] = {"us_per_launch_runs": [round(x, 1) for x in us], "us_median": round(med, 1),
+                         "us_spread": round(max(us) - min(us), 1), "gb_per_s": round(moved / med / 1e3, 1)}
+    for which in ("auto", "auto_ramping"):
+        result[f"{which}_over_mix"] = round(result[which]["us_median"] / result["mix"]["us_median"], 3)
     line = json.dumps(result)
     print(line)
     if args.out:
