@@ -22,11 +22,12 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib
-from .audio import ConvertingStatsStream, MonoStatsStream, TrackPeaks, TrackScore, TrackStats, convert_audio
+from .audio import ConvertingStatsStream, MonoStatsStream, TrackLoudness, TrackPeaks, TrackScore, TrackStats, convert_audio
 from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
 from .stream import Delivery, ModelStream, StreamGroup
 
-__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "TrackPeaks", "TrackScore", "LoadModelError", "list_models"]
+__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "TrackPeaks", "TrackScore", "TrackLoudness", "LoadModelError",
+           "list_models"]
 
 
 class LoadModelError(Exception):
@@ -356,6 +357,122 @@ class Separator:
             if host_in:
                 stems = dict(zip(stems, _to_host(est[None], device)[0]))
         return score, stems
+
+    def _check_loudness(self, what: str, mix):
+        """The refusals of the loudness entries (no device work, no RNG call) and the remixes they measure: `mix` as
+        `audio.deliver_mix` takes it; None is every source by itself and the mix as output "mix"."""
+        from .audio import _check_loudness_format, mix_gains
+        if not _is_engine(self._model) or torch.device(self._device).type != "cuda":
+            raise ValueError(f"{what} runs on the GPU engines (HTDemucs / HDemucs on a cuda device); there is no CPU meter in this "
+                             "package")
+        sources = list(self._model.sources)
+        if not 1 <= len(sources) <= 8:
+            raise ValueError(f"{what}: 1 to 8 sources, the model has {len(sources)}")
+        _check_loudness_format(self._samplerate, self._audio_channels)
+        if mix is None:
+            mix = {**{name: {name: 1.0} for name in sources}, "mix": {"mix": 1.0}}
+        return mix, any(g[0] != 0 for _, g in mix_gains(mix, sources))
+
+    def loudness_tensor(self, wav: torch.Tensor, mix=None, sr: Optional[int] = None
+                        ) -> Tuple[TrackLoudness, torch.Tensor, Dict[str, torch.Tensor]]:
+        """`separate_tensor(wav, sr)` followed by `audio.loudness` where the stems lie: ITU-R BS.1770-4 loudness of the
+        gain-weighted remixes `mix` (`audio.deliver_mix`'s `{output: {"mix" | source: gain}}`; None: every source by itself and
+        the mix) without a float stem crossing to the host for it.  Returns `(TrackLoudness, origin, stems)`, `origin` and `stems`
+        as `separate_tensor` returns them -- a host `wav` is uploaded first and the stems cross to the host once -- and the
+        `TrackLoudness` that of `audio.loudness(origin, stems, mix)` on exactly those: for a host `wav` the mix as given (or as
+        converted from `sr`), for a device `wav` the mix as `separate_tensor` leaves it after normalising and restoring it in
+        place."""
+        from .audio import loudness
+        mix, _ = self._check_loudness("loudness_tensor", mix)
+        device = self._device_index()
+        host_in = wav.device.type == "cpu"
+        with torch.cuda.device(device):
+            dev = wav.to(device) if host_in else wav
+            converted = sr is not None and sr != self._samplerate
+            if converted:
+                dev = convert_audio(dev, sr, self._samplerate, self._audio_channels, device=device)
+            raw = dev.clone() if host_in else None               # the forward normalises its input in place
+            origin, stems = self.separate_tensor(dev, None)
+            measured = loudness(raw if host_in else origin, stems, mix, self._samplerate)
+            if host_in:
+                stems = dict(zip(stems, _to_host(_stacked(list(stems.values()))[None], device)[0]))
+                origin = _to_host(raw, device) if converted else wav
+        return measured, origin, stems
+
+    def loudness_blocks(self, source, mix=None, sr: Optional[int] = None, channels: Optional[int] = None,
+                        pcm: Optional[str] = None) -> TrackLoudness:
+        """`separate_blocks` with the loudness of remixes measured instead of stems returned: the `audio.TrackLoudness` of a track
+        that never exists whole on the host or the device, with the bits of `loudness_tensor(wav, mix, sr)` for a host `wav`.
+        `source` is `separate_blocks`' argument, read twice (the analysis pass, the separating pass); host blocks are uploaded
+        here, so the stream emits device stems and every emitted span goes into an `audio.LoudnessStream` where it lies.  When an
+        output has a gain on "mix" the blocks of the second pass also go through `audio.convert_audio_stream` (straight through
+        when they already are what the model takes), which has `convert_audio`'s bits; the model-rate mix waits in a queue until
+        the stems of its positions arrive, at most one segment plus one block of it.
+
+        The state of `random` is saved on entry and restored on exit, as the measuring pass of `separate_blocks` does: a following
+        `separate_blocks(source, deliver=Delivery(mix=result.normalised(-14), clip="clamp"))` draws the same shift offsets and
+        delivers the remixes that were measured, each at -14 LUFS."""
+        import random
+        from .audio import ConvertStream, LoudnessStream, PcmFeed
+        mix, mixed = self._check_loudness("loudness_blocks", mix)
+        self._check_stream_input(sr, channels, True, pcm)
+        plan = self._convert_plan(sr, channels)
+        device = self._device_index()
+        src_channels = channels or self._audio_channels
+
+        def on_device():
+            feed = PcmFeed(pcm, src_channels) if pcm is not None else None
+            for block in source():
+                if feed is not None:
+                    blk = feed.accept(block)
+                    feed.commit(blk)
+                    with torch.cuda.device(device):
+                        yield blk.on_device(device, [])[:blk.nbytes]
+                elif isinstance(block, torch.Tensor):
+                    yield block.to(device)
+                else:
+                    yield block                            # refused by the stream, with its message
+
+        state = random.getstate()
+        try:
+            an = self.analyse_stream(sr=sr, channels=channels, convert=True, pcm=pcm)
+            for block in on_device():
+                an.push(block)
+            stats = an.finish()
+            st = self.separate_stream(stats=stats, sr=sr, channels=channels, convert=True, pcm=pcm, length=stats.input_length)
+            meter = LoudnessStream(self._model.sources, self._audio_channels, self._samplerate, mix, device=device)
+            convert = None
+            if mixed and (plan is not None or pcm is not None):
+                convert = ConvertStream(sr or self._samplerate, self._samplerate, self._audio_channels, device=device, plan=plan,
+                                        pcm=pcm, src_channels=src_channels if pcm is not None else None)
+            queue = []
+
+            def measure(out):
+                stems = _stacked(list(out.values()))
+                need, parts = stems.shape[-1], []
+                while mixed and need:
+                    head = queue[0]
+                    k = min(need, head.shape[1])
+                    parts.append(head[:, :k])
+                    if k == head.shape[1]:
+                        queue.pop(0)
+                    else:
+                        queue[0] = head[:, k:]
+                    need -= k
+                origin = None if not mixed else parts[0] if len(parts) == 1 else torch.cat(parts, 1) if parts else \
+                    stems.new_empty(self._audio_channels, 0)
+                meter.push(stems, origin)
+
+            for block in on_device():
+                if mixed:
+                    queue.append(block if convert is None else convert.push(block, on_device=True))
+                measure(st.push(block))
+            if convert is not None:
+                queue.append(convert.finish(on_device=True))
+            measure(st.finish())
+            return meter.finish()
+        finally:
+            random.setstate(state)
 
     def _convert_plan(self, sr: Optional[int], channels: Optional[int]):
         """The refusals of a converting stream (before any device work or RNG call) and its `audio.ConvertPlan`; None when the

@@ -1629,3 +1629,335 @@ def summarise_scores(tracks, sources) -> dict:
     result["nsdr"] = avg
     result["nsdr_med"] = avg_of_medians
     return result
+
+
+# ---- loudness of remixes: ITU-R BS.1770-4 / EBU R 128 (mi_loudness_update, demucs_amd/csrc/loudness.hip) -------------------------
+LOUD_COLS = 22                     # include/demucs_amd.h: MI_LOUD_* (MI_MIX_*'s columns up to the gains, then its own)
+LOUD_CHUNK = 1 << 20               # samples per push of the whole-track call: bounds its work area
+LOUD_ABSOLUTE_GATE = -70.0         # LUFS
+LOUD_RELATIVE_GATE = -10.0         # LU below the loudness of the blocks over the absolute gate
+
+
+def _check_loudness_format(samplerate, channels) -> None:
+    if isinstance(samplerate, bool) or int(samplerate) != samplerate or samplerate <= 0:
+        raise ValueError(f"loudness: the sample rate must be a positive integer, got {samplerate!r}")
+    if int(samplerate) % 10:
+        raise ValueError(f"loudness: the sample rate {samplerate} is no multiple of 10: a 100 ms sub-block is no whole number of samples")
+    if isinstance(channels, bool) or int(channels) != channels or not 1 <= channels <= 2:
+        raise ValueError(f"loudness: 1 or 2 channels (both weighted 1), got {channels!r}; the surround weights are not implemented")
+
+
+def k_weighting(samplerate):
+    """The K-weighting of BS.1770-4 at `samplerate` as a float64 array `[stage][b | a][3]`: the shelf, then the high-pass, each
+    `y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2]` with `a0 = 1`.  At 48 000 Hz these are the recommendation's
+    tabulated coefficients (to 9e-16); at other rates the same analogue prototypes through the bilinear transform."""
+    import numpy as np
+    fs = float(samplerate)
+    if not fs > 0:
+        raise ValueError(f"loudness: the sample rate must be positive, got {samplerate!r}")
+    f0, gain, q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    k = math.tan(math.pi * f0 / fs)
+    vh = 10.0 ** (gain / 20.0)
+    vb = vh ** 0.4996667741545416
+    a0 = 1.0 + k / q + k * k
+    shelf = [[(vh + vb * k / q + k * k) / a0, 2.0 * (k * k - vh) / a0, (vh - vb * k / q + k * k) / a0],
+             [1.0, 2.0 * (k * k - 1.0) / a0, (1.0 - k / q + k * k) / a0]]
+    f0, q = 38.13547087602444, 0.5003270373238773
+    k = math.tan(math.pi * f0 / fs)
+    d = 1.0 + k / q + k * k
+    high = [[1.0, -2.0, 1.0], [1.0, 2.0 * (k * k - 1.0) / d, (1.0 - k / q + k * k) / d]]
+    return np.array([shelf, high], dtype=np.float64)
+
+
+def loudness_warmup(samplerate) -> int:
+    """Samples a sub-block's recursion runs from zero state before its first counted sample (loudness.hip): by then the
+    high-pass's response to everything earlier is below float64 rounding."""
+    return 16384 * -(-int(samplerate) // 48000)
+
+
+def _block_powers(energies, hop: int):
+    """P[j] of the 400 ms gating blocks (75 % overlap) from (channels, Hn) sub-block energies; empty below 4 sub-blocks."""
+    import numpy as np
+    e = np.asarray(energies, dtype=np.float64)
+    if e.shape[-1] < 4:
+        return np.zeros(0, dtype=np.float64)
+    return (e[:, :-3] + e[:, 1:-2] + e[:, 2:-1] + e[:, 3:]).sum(0) / (4.0 * hop)
+
+
+def _lufs(power):
+    import numpy as np
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return -0.691 + 10.0 * np.log10(power)
+
+
+def gated_loudness(energies, hop: int) -> float:
+    """Integrated loudness (LUFS) from (channels, Hn) sub-block energies of `hop` samples: BS.1770-4's absolute gate at -70 LUFS
+    and relative gate 10 LU below the loudness of what passed it.  -inf when no block passes or there are fewer than 4
+    sub-blocks; NaN when an energy is NaN."""
+    import numpy as np
+    e = np.asarray(energies, dtype=np.float64)
+    if np.isnan(e).any():
+        return float("nan")
+    power = _block_powers(e, hop)
+    l = _lufs(power)
+    keep = l > LOUD_ABSOLUTE_GATE
+    if not keep.any():
+        return float("-inf")
+    keep &= l > _lufs(power[keep].mean()) + LOUD_RELATIVE_GATE
+    if not keep.any():
+        return float("-inf")
+    return float(_lufs(power[keep].mean()))
+
+
+class TrackLoudness:
+    """What a loudness pass over a track found (`audio.loudness`, `LoudnessStream`, `Separator.loudness_blocks`): per output the
+    K-weighted energies of its 100 ms sub-blocks, from which every BS.1770-4 figure of the track follows on the host.
+
+    `names` are the outputs, `sources` the separated sources their gains refer to, `mix` the outputs' identity `((output name,
+    (g_mix, g_0 .. g_{S-1})), ...)` as `mix_gains` resolves it (`TrackPeaks.mix`'s form), `samplerate`, `channels` and `length`
+    those of the measured frames, `energies` a read-only float64 array (outputs, channels, length // (samplerate // 10)).
+    Immutable."""
+    __slots__ = ("names", "sources", "samplerate", "channels", "length", "energies", "mix")
+
+    def __init__(self, names, sources, samplerate, channels, length, energies, mix):
+        import numpy as np
+        for what, v in (("names", names), ("sources", sources)):
+            if isinstance(v, (str, bytes)) or not all(isinstance(n, str) for n in v) or len(set(v)) != len(tuple(v)) or not len(v):
+                raise ValueError(f"TrackLoudness: {what} must be a sequence of names, each once, got {v!r}")
+        names, sources = tuple(names), tuple(sources)
+        _check_loudness_format(samplerate, channels)
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
+            raise ValueError(f"TrackLoudness: length must be a non-negative integer, got {length!r}")
+        try:
+            mix = tuple((str(name), tuple(float(np.float32(g)) for g in gains)) for name, gains in mix)
+        except (TypeError, ValueError):
+            raise ValueError(f"TrackLoudness: mix must be ((output name, (g_mix, g_0, ...)), ...) as audio.mix_gains returns it, got "
+                             f"{mix!r}") from None
+        if tuple(name for name, _ in mix) != names or \
+                not all(len(g) == 1 + len(sources) and all(np.isfinite(v) for v in g) for _, g in mix):
+            raise ValueError(f"TrackLoudness: mix must name the outputs {list(names)} in order, each with finite gains for the mix and "
+                             f"the {len(sources)} sources, got {mix!r}")
+        e = np.array(energies, dtype=np.float64)
+        want = (len(names), int(channels), int(length) // (int(samplerate) // 10))
+        if e.shape != want:
+            raise ValueError(f"TrackLoudness: the energies of {length} samples are {want} (outputs, channels, sub-blocks), got {e.shape}")
+        e.setflags(write=False)
+        for name, v in zip(self.__slots__, (names, sources, int(samplerate), int(channels), int(length), e, mix)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("TrackLoudness is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("TrackLoudness is immutable")
+
+    @property
+    def hop(self) -> int:
+        """Samples of a sub-block: 100 ms."""
+        return self.samplerate // 10
+
+    def _row(self, name: str):
+        if name not in self.names:
+            raise KeyError(f"output {name!r} is not among the measured outputs {list(self.names)}")
+        return self.energies[self.names.index(name)]
+
+    def integrated(self, name: str) -> float:
+        """Integrated (gated) loudness of output `name` in LUFS; -inf for silence or less than 400 ms, NaN for a NaN sample."""
+        return gated_loudness(self._row(name), self.hop)
+
+    def momentary(self, name: str):
+        """The loudness of every 400 ms gating block of output `name` (a block every 100 ms), in LUFS, ungated."""
+        return _lufs(_block_powers(self._row(name), self.hop))
+
+    def gain(self, name: str, target: float) -> float:
+        """The linear gain that brings output `name` to `target` LUFS."""
+        have = self.integrated(name)
+        if not math.isfinite(have) or not math.isfinite(float(target)):
+            raise ValueError(f"TrackLoudness: output {name!r} measures {have} LUFS; no gain brings that to {target} LUFS")
+        return 10.0 ** ((float(target) - have) / 20.0)
+
+    def normalised(self, target: float = -14.0) -> dict:
+        """The measured remixes with every gain scaled so that each output reads `target` LUFS: `{output: {"mix" | source:
+        gain}}`, what `deliver_mix` and `Delivery(mix=)` take."""
+        terms = ("mix",) + self.sources
+        out = {}
+        for name, gains in self.mix:
+            k = self.gain(name, target)
+            out[name] = {t: g * k for t, g in zip(terms, gains) if g != 0}
+        return out
+
+    def _key(self):
+        return (self.names, self.sources, self.samplerate, self.channels, self.length, self.energies.tobytes(), self.mix)
+
+    def __eq__(self, other):
+        return isinstance(other, TrackLoudness) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return (f"TrackLoudness(names={list(self.names)}, sources={list(self.sources)}, samplerate={self.samplerate}, "
+                f"channels={self.channels}, length={self.length}, integrated={[self.integrated(n) for n in self.names]})")
+
+
+def loud_rows(gains, src: int, src_pitch: int, n: int, origin: int, pitch: int, affine, before: int, hist_len: int, side: int,
+              hist_start: int, hist_next: int, channels: int, e_pitch: int, work_pitch: int) -> list:
+    """mi_loudness_update's rows (MI_LOUD_*) for resolved remixes of `n` frames from track position `before`.  Output i keeps its
+    history at `(side, i)` of a (2, outputs, channels, hist_len) buffer, its energies at row i of (outputs, channels, e_pitch) and
+    works in row i of (outputs, channels, work_pitch)."""
+    import numpy as np
+    aff = 0 if affine is None else int(np.array(affine, dtype=np.float32).view(np.int64)[0])
+    per = channels * hist_len
+    rows = []
+    for i, (_, g) in enumerate(gains):
+        packed = np.zeros(2 * (MIX_CLIP_AT - MIX_GAINS_AT), dtype=np.float32)
+        packed[:len(g)] = g
+        rows += [src, n, origin, pitch, aff, int(affine is not None), *packed.view(np.int64).tolist(), src_pitch, before, hist_len,
+                 (side * len(gains) + i) * per, ((1 - side) * len(gains) + i) * per, hist_start, hist_next,
+                 i * channels * e_pitch, e_pitch, i * channels * work_pitch, work_pitch]
+    return rows
+
+
+class LoudnessStream:
+    """BS.1770-4 loudness of gain-weighted remixes of a track that arrives block by block, measured where the stems lie.
+    `push(stems_block, origin=None)` takes the next `n >= 0` samples as a device float32 (sources, channels, n) and the mix of the
+    same positions as (channels, n) (required when an output has a gain on "mix"; `affine=(mean, s)` when it is stored normalised,
+    as a stream's window is); `finish()` returns the `TrackLoudness`.  `mix` is `deliver_mix`'s; None measures every source by
+    itself.  The measured values are `deliver_mix(..., clip=None, fmt="f32")`'s, and the energies have the same bits for every
+    partition of the track into pushes.
+
+    Every push is ONE `mi_loudness_update` call for all outputs; nothing visits the host before `finish()`, which copies the
+    energies once.  Device state: two sides of (outputs, channels, warm-up + hop) carried values, and the energies, 8 bytes per
+    output, channel and 100 ms; a push also uses a work area of (outputs, channels, carried + n) floats for its duration."""
+
+    def __init__(self, sources, channels: int, samplerate: int, mix=None, device="cuda"):
+        self.sources = list(sources)
+        _check_loudness_format(samplerate, channels)
+        if not self.sources:
+            raise ValueError("loudness: at least one source")
+        if mix is None:
+            mix = {name: {name: 1.0} for name in self.sources}
+        self.gains = mix_gains(mix, self.sources)
+        self.channels, self.samplerate = int(channels), int(samplerate)
+        self.hop, self.warm = self.samplerate // 10, loudness_warmup(samplerate)
+        self.mixed = any(g[0] != 0 for _, g in self.gains)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.EngineError("demucs_amd.audio.LoudnessStream only runs on a GPU device (MI355X)")
+        self.device = dev
+        self.pushed = 0
+        self.finished = False
+        self._coef = k_weighting(self.samplerate)
+        self._hist = self._energies = None
+        self._side = self._h0 = 0
+
+    @property
+    def device_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self._hist, self._energies) if t is not None)
+
+    def _rows_of(self, t: torch.Tensor):
+        """`t` as float32 on the stream's device with unit stride along time and evenly pitched rows, read in place when it
+        already is (a span of a whole track's stems): (tensor, pitch)."""
+        t = t.to(device=self.device, dtype=torch.float32)
+        n = t.shape[-1]
+        pitch = t.stride(-2)
+        if t.stride(-1) != 1 or pitch < n or (t.dim() == 3 and t.stride(0) != self.channels * pitch):
+            t, pitch = t.contiguous(), n
+        return t, pitch
+
+    def push(self, stems_block: torch.Tensor, origin=None, affine=None) -> None:
+        if self.finished:
+            raise RuntimeError("push after finish()")
+        S, ch, R = len(self.sources), self.channels, len(self.gains)
+        if not isinstance(stems_block, torch.Tensor) or stems_block.dim() != 3 or tuple(stems_block.shape[:2]) != (S, ch) or \
+                not stems_block.dtype.is_floating_point:
+            raise ValueError(f"loudness: expected a floating ({S}, {ch}, n) block of stems, got "
+                             f"{tuple(getattr(stems_block, 'shape', ()))}")
+        n = stems_block.shape[2]
+        if self.mixed:
+            if origin is None:
+                raise ValueError("loudness: an output has a gain on 'mix'; push the mix of the same positions as origin=")
+            if not isinstance(origin, torch.Tensor) or tuple(origin.shape) != (ch, n) or not origin.dtype.is_floating_point:
+                raise ValueError(f"loudness: the mix is {tuple(getattr(origin, 'shape', ()))}, the stems are {(ch, n)}")
+        if n == 0:
+            return
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        dev, hop, warm = self.device, self.hop, self.warm
+        with torch.cuda.device(dev):
+            block, src_pitch = self._rows_of(stems_block)
+            org, pitch = self._rows_of(origin) if self.mixed else (None, 0)
+            hist_len = warm + hop
+            if self._hist is None:
+                self._hist = torch.zeros(2, R, ch, hist_len, device=dev)
+            end = self.pushed + n
+            done = end // hop
+            if self._energies is None or self._energies.shape[2] < done:
+                grown = torch.zeros(R, ch, max(done, 600, 0 if self._energies is None else 2 * self._energies.shape[2]),
+                                    dtype=torch.float64, device=dev)
+                if self._energies is not None:
+                    grown[:, :, :self._energies.shape[2]] = self._energies
+                self._energies = grown
+            kept = self.pushed - self._h0
+            nxt = max(0, done * hop - warm)
+            work = torch.empty(R * ch * (kept + n), dtype=torch.float32, device=dev)
+            rows = loud_rows(self.gains, block.data_ptr(), src_pitch, n, 0 if org is None else org.data_ptr(), pitch, affine,
+                             self.pushed, hist_len, self._side, self._h0, nxt, ch, self._energies.shape[2], kept + n)
+            table = torch.tensor(rows, dtype=torch.int64).to(dev)
+            coef = (C.c_double * 10)(*[*self._coef[0, 0], *self._coef[0, 1, 1:], *self._coef[1, 0], *self._coef[1, 1, 1:]])
+            _lib.check(_lib.load().mi_loudness_update(
+                table.data_ptr(), R, kept + n, done - self.pushed // hop, S, ch, coef, hop, warm, self._hist.data_ptr(),
+                self._hist.numel(), self._energies.data_ptr(), self._energies.numel(), work.data_ptr(), work.numel(),
+                C.c_void_p(_lib.current_stream_ptr())), "mi_loudness_update")
+        self._side, self._h0, self.pushed = 1 - self._side, nxt, end
+
+    def finish(self) -> TrackLoudness:
+        if self.finished:
+            raise RuntimeError("finish() called twice")
+        self.finished = True
+        import numpy as np
+        done = self.pushed // self.hop
+        if done:
+            energies = self._energies[:, :, :done].cpu().numpy()
+        else:
+            energies = np.zeros((len(self.gains), self.channels, 0), dtype=np.float64)
+        return TrackLoudness([name for name, _ in self.gains], self.sources, self.samplerate, self.channels, self.pushed, energies,
+                             mix_identity(self.gains))
+
+
+def loudness(origin, stems: dict, mix=None, samplerate: int = 44100) -> TrackLoudness:
+    """ITU-R BS.1770-4 / EBU R 128 loudness of gain-weighted remixes of one separated track, measured on the stems' device: the
+    `TrackLoudness` of the frames `deliver_mix(origin, stems, mix, clip=None, fmt="f32")` returns, none of which is produced.
+    `stems` is `{name: (channels, n)}` as `deliver_mix` takes it, `mix` its `{output: {"mix" | source: gain}}`; None measures
+    every source by itself, and the mix as output "mix" when `origin` is given.  The track goes through a `LoudnessStream` in
+    pushes of `LOUD_CHUNK` samples read in place, so the memory used beside the stems stays bounded."""
+    names = list(stems)
+    if mix is None:
+        mix = {name: {name: 1.0} for name in names}
+        if origin is not None:
+            mix["mix"] = {"mix": 1.0}
+    tensors = [stems[k] for k in names]
+    for t in tensors:
+        if not t.dtype.is_floating_point:
+            raise TypeError(f"loudness: a floating-point tensor is expected, got {t.dtype}")
+        if t.dim() != 2 or t.shape != tensors[0].shape:
+            raise ValueError(f"loudness: every stem is (channels, n), got {[tuple(x.shape) for x in tensors]}")
+    if not tensors:
+        raise ValueError("loudness: at least one source")
+    channels, n = tensors[0].shape
+    _check_loudness_format(samplerate, channels)
+    gains = mix_gains(mix, names)
+    mixed = any(g[0] != 0 for _, g in gains)
+    if mixed and origin is None:
+        raise ValueError("loudness: an output has a gain on 'mix'; pass the mix as origin")
+    if mixed and tuple(origin.shape) != (channels, n):
+        raise ValueError(f"loudness: the mix is {tuple(origin.shape)}, the stems are {(channels, n)}")
+    dev = _engine_device(*tensors)
+    stream = LoudnessStream(names, channels, samplerate, mix, device=dev)
+    with torch.cuda.device(dev):
+        block = _stems_block(tensors, dev)
+        org = _stage(origin, dev, "loudness") if mixed else None
+        for a in range(0, n, LOUD_CHUNK):
+            b = min(n, a + LOUD_CHUNK)
+            stream.push(block[:, :, a:b], None if org is None else org[:, a:b])
+    return stream.finish()

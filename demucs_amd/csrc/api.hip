@@ -708,6 +708,19 @@ int mi_deliver_mix_auto_peaks(const int64_t *table_dev, int64_t table_len, int32
                                          dst_capacity, (hipStream_t)stream);
 }
 
+int mi_loudness_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int64_t max_blocks, int32_t n_sources, int32_t channels,
+                       const double *coef, int64_t hop, int64_t warm, float *hist_dev, int64_t hist_capacity, double *energies_dev,
+                       int64_t energies_capacity, float *work_dev, int64_t work_capacity, void *stream) {
+    MI_REQUIRE(table_dev && coef && energies_dev && work_dev && n_rows > 0 && n_rows <= 65535 && max_n >= 1 &&
+               max_n <= (int64_t)INT32_MAX * 256 && max_blocks >= 0 && max_blocks <= (int64_t)INT32_MAX * 64 && n_sources > 0 &&
+               n_sources <= MI_MIX_MAX_SOURCES && channels > 0 && channels <= 65535 && hist_capacity >= 0 &&
+               (hist_dev || hist_capacity == 0) && energies_capacity >= 0 && work_capacity >= 0,
+               "mi_loudness_update: bad argument");
+    if (hop < 1 || warm < 0) return MI_OK;                         // every row is skipped whole
+    return launch_loudness_update(table_dev, n_rows, max_n, max_blocks, n_sources, channels, coef, hop, warm, hist_dev, hist_capacity,
+                                  energies_dev, energies_capacity, work_dev, work_capacity, (hipStream_t)stream);
+}
+
 // Kernel-level entry points.  They allocate their scratch with hipMalloc and free it after a
 // stream synchronise: convenient for parity tests, not meant for the hot loop.
 int mi_stft_cac(const float *mix_dev, int32_t B, int32_t L, float *cac_dev, void *stream) {

@@ -339,4 +339,9 @@ int launch_deliver_resample_pcm_peaks(const int64_t *table, int n_rows, int64_t 
                                       const float *bank, int64_t bank_cap, float *hist, int64_t hist_cap, int lds_floats, unsigned char *dst,
                                       int64_t dst_cap, const int32_t *slots, const unsigned *peaks, int n_peaks, hipStream_t st);
 
+// loudness.hip: K-weighted sub-block energies of gain-weighted remixes (ITU-R BS.1770-4), whole or streamed; coef is a HOST array
+int launch_loudness_update(const int64_t *table, int n_rows, int64_t max_n, int64_t max_blocks, int n_sources, int channels,
+                           const double *coef, int64_t hop, int64_t warm, float *hist, int64_t hist_cap, double *energies, int64_t e_cap,
+                           float *work, int64_t work_cap, hipStream_t st);
+
 }  // namespace mi

@@ -723,6 +723,68 @@ int mi_deliver_mix_auto_pcm(const int64_t *table_dev, int64_t table_len, int32_t
 int mi_deliver_mix_auto_peaks(const int64_t *table_dev, int64_t table_len, int32_t n_rows, int64_t max_n, int32_t n_sources,
                               int32_t channels, void *peaks_dev, int32_t n_peaks, int64_t dst_capacity, void *stream);
 
+/* ---- loudness of remixes (ITU-R BS.1770-4 / EBU R 128): K-weighted sub-block energies, whole or streamed ------------------------
+ * No counterpart in the reference: what a user of it does with a CPU meter on the float stems after `separate_tensor`.  The
+ * measured signal of a row is mi_deliver_mix_pcm's value before clipping -- acc = 0, + g_mix * o, + g_k * s_k in index order,
+ * float32, a term with gain 0 not read, the mix through ORIGIN / ORIGIN_PITCH / ORIGIN_AFFINE.  It passes two cascaded biquads
+ * in float64, each y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2]; coef (a HOST array of 10 doubles, copied
+ * into the launch) holds b0, b1, b2, a1, a2 of the first and then of the second.  Sub-block h of a channel is the track positions
+ * [h * hop, (h + 1) * hop), and its energy e[c][h] the sum of y * y over them in ascending order, where y comes from running both
+ * biquads from zero state over [h * hop - warm, (h + 1) * hop), positions below 0 reading 0.  e[c][h] is a pure function of the
+ * values in that window, so the energies of a track have the same bits for every partition of it into calls; against the
+ * recursion over the whole track they differ by the filters' response after `warm` samples (below float64 rounding for the
+ * BS.1770 filters at warm = 16384 * ceil(fs / 48000)).  Gating and the logarithm are the host's (a few numbers per second).
+ * mi_loudness_update: ONE call takes the next N samples of every output of a track (or of a push) in two launches, one that
+ *   lays the carried and the new values side by side in work_dev and rewrites the history, one that runs the recursions of the
+ *   sub-blocks that became complete, one work item each; nothing synchronises with the host and no atomics are used.
+ *   Row r of the table (MI_LOUD_COLS int64, a DEVICE array) is ONE output:
+ *     SRC, N, ORIGIN, ORIGIN_PITCH, ORIGIN_AFFINE, AFFINE_ON, GAINS   as MI_MIX_*, at the same indices;
+ *     SRC_PITCH           floats between the (source, channel) rows of the stems: source k, channel c, frame j at
+ *                         SRC + (k * channels + c) * SRC_PITCH + j (N for a contiguous block; longer for a view of a whole track);
+ *     BEFORE              track position of the row's frame 0: the samples of this output taken by earlier calls;
+ *     HIST_LEN, HIST_RD, HIST_WR, HIST_START, HIST_NEXT
+ *                         the carried VALUES of this output, as MI_RATE_HIST_*: (channels, hist_len) floats at float offset
+ *                         hist_rd of hist_dev hold positions [hist_start, before); the call writes positions [hist_next,
+ *                         before + n) (at most hist_len) at float offset hist_wr, a side apart from the read one; hist_next < 0:
+ *                         nothing is written.  A stream carries from max(0, (before + n) / hop * hop - warm) on: at most
+ *                         warm + hop - 1 values;
+ *     E_OFF, E_PITCH      the row's energies: (channels, e_pitch) doubles at double offset e_off of energies_dev; the call writes
+ *                         e[c][h] for before / hop <= h < (before + n) / hop, every channel;
+ *     WORK_OFF, WORK_PITCH  the row's work area: (channels, work_pitch) floats at float offset work_off of work_dev,
+ *                         work_pitch >= before - hist_start + n.  Its contents mean nothing after the call.
+ *   max_n >= every row's before - hist_start + n, max_blocks >= every row's number of sub-blocks that become complete (grid
+ *   sizes; max_blocks == 0: the second launch is left out).  Rows must not share history sides, energies or work areas.
+ *   A row is skipped whole (nothing of it is read or written, its history included) under mi_deliver_mix_pcm's rules for SRC, N,
+ *   the gains and ORIGIN -- SRC is 0, N <= 0, a gain among g_mix, g_0 .. g_{n_sources-1} is not finite, all of them are 0,
+ *   g_mix != 0 without ORIGIN or with ORIGIN_PITCH < N -- and when SRC_PITCH < N; BEFORE or HIST_START is negative, HIST_START >
+ *   BEFORE, or before - hist_start > hist_len; a history side leaves hist_capacity (floats) or the sides overlap; HIST_NEXT >= 0
+ *   lies outside [hist_start, before + n] or before + n - hist_next > hist_len; a sub-block becomes complete whose window begins
+ *   before HIST_START (max(0, before / hop * hop - warm) < hist_start); the energies or the work area leave their capacity
+ *   (doubles, floats), E_PITCH < (before + n) / hop or WORK_PITCH is too small; N or BEFORE exceed 2^61.  With hop < 1 or
+ *   warm < 0 every row is skipped.  hop and warm are arguments, not constants of the build. */
+#define MI_LOUD_SRC 0
+#define MI_LOUD_N 1
+#define MI_LOUD_ORIGIN 2
+#define MI_LOUD_ORIGIN_PITCH 3
+#define MI_LOUD_ORIGIN_AFFINE 4
+#define MI_LOUD_AFFINE_ON 5
+#define MI_LOUD_GAINS 6
+#define MI_LOUD_SRC_PITCH 11
+#define MI_LOUD_BEFORE 12
+#define MI_LOUD_HIST_LEN 13
+#define MI_LOUD_HIST_RD 14
+#define MI_LOUD_HIST_WR 15
+#define MI_LOUD_HIST_START 16
+#define MI_LOUD_HIST_NEXT 17
+#define MI_LOUD_E_OFF 18
+#define MI_LOUD_E_PITCH 19
+#define MI_LOUD_WORK_OFF 20
+#define MI_LOUD_WORK_PITCH 21
+#define MI_LOUD_COLS 22
+int mi_loudness_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int64_t max_blocks, int32_t n_sources, int32_t channels,
+                       const double *coef, int64_t hop, int64_t warm, float *hist_dev, int64_t hist_capacity, double *energies_dev,
+                       int64_t energies_capacity, float *work_dev, int64_t work_capacity, void *stream);
+
 /* ---- kernel-level entry points (parity tests; same kernels the forward uses) --------------
  * mi_stft_cac: `_magnitude(_spec(mix))` (demucs/htdemucs.py:420-461, demucs/spec.py:11-27):
  *   mix_dev (B,2,L) -> cac_dev (B,4,2048,ceil(L/1024)), channel order [c0.re,c0.im,c1.re,c1.im]. */
