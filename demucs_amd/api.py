@@ -22,12 +22,12 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib
-from .audio import ConvertingStatsStream, MonoStatsStream, TrackLoudness, TrackPeaks, TrackScore, TrackStats, convert_audio
+from .audio import ConvertingStatsStream, MonoStatsStream, TrackLoudness, TrackPeaks, TrackScore, TrackStats, TrackTruePeaks, convert_audio
 from .apply import BagOfModels, _is_engine, _to_host, apply_model, apply_model_many
 from .stream import Delivery, ModelStream, StreamGroup
 
-__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "TrackPeaks", "TrackScore", "TrackLoudness", "LoadModelError",
-           "list_models"]
+__all__ = ["Separator", "SeparatorStream", "Delivery", "TrackStats", "TrackPeaks", "TrackScore", "TrackLoudness", "TrackTruePeaks",
+           "LoadModelError", "list_models"]
 
 
 class LoadModelError(Exception):
@@ -384,20 +384,7 @@ class Separator:
         place."""
         from .audio import loudness
         mix, _ = self._check_loudness("loudness_tensor", mix)
-        device = self._device_index()
-        host_in = wav.device.type == "cpu"
-        with torch.cuda.device(device):
-            dev = wav.to(device) if host_in else wav
-            converted = sr is not None and sr != self._samplerate
-            if converted:
-                dev = convert_audio(dev, sr, self._samplerate, self._audio_channels, device=device)
-            raw = dev.clone() if host_in else None               # the forward normalises its input in place
-            origin, stems = self.separate_tensor(dev, None)
-            measured = loudness(raw if host_in else origin, stems, mix, self._samplerate)
-            if host_in:
-                stems = dict(zip(stems, _to_host(_stacked(list(stems.values()))[None], device)[0]))
-                origin = _to_host(raw, device) if converted else wav
-        return measured, origin, stems
+        return self._meter_tensor(wav, mix, sr, [loudness])
 
     def loudness_blocks(self, source, mix=None, sr: Optional[int] = None, channels: Optional[int] = None,
                         pcm: Optional[str] = None) -> TrackLoudness:
@@ -412,9 +399,60 @@ class Separator:
         The state of `random` is saved on entry and restored on exit, as the measuring pass of `separate_blocks` does: a following
         `separate_blocks(source, deliver=Delivery(mix=result.normalised(-14), clip="clamp"))` draws the same shift offsets and
         delivers the remixes that were measured, each at -14 LUFS."""
-        import random
-        from .audio import ConvertStream, LoudnessStream, PcmFeed
+        from .audio import LoudnessStream
         mix, mixed = self._check_loudness("loudness_blocks", mix)
+        return self._meter_blocks(source, mix, mixed, sr, channels, pcm, [LoudnessStream])[0]
+
+    def _check_levels(self, what: str, mix):
+        """`_check_loudness` and the true-peak meter's own refusal."""
+        from .audio import _check_true_peak_format
+        checked = self._check_loudness(what, mix)
+        _check_true_peak_format(self._samplerate, self._audio_channels)
+        return checked
+
+    def levels_tensor(self, wav: torch.Tensor, mix=None, sr: Optional[int] = None
+                      ) -> Tuple[TrackLoudness, TrackTruePeaks, torch.Tensor, Dict[str, torch.Tensor]]:
+        """`loudness_tensor` with the second meter of EBU R 128 beside the first: one separation, then `audio.loudness` and
+        `audio.true_peak` (BS.1770-4 Annex 2) where the stems lie.  Returns `(TrackLoudness, TrackTruePeaks, origin, stems)`;
+        `loudness.normalised(-14, true_peaks=peaks)` is the `mix` that delivers every remix at -14 LUFS or, where its peaks do
+        not allow that, at -1 dBTP."""
+        from .audio import loudness, true_peak
+        mix, _ = self._check_levels("levels_tensor", mix)
+        return self._meter_tensor(wav, mix, sr, [loudness, true_peak])
+
+    def levels_blocks(self, source, mix=None, sr: Optional[int] = None, channels: Optional[int] = None,
+                      pcm: Optional[str] = None) -> Tuple[TrackLoudness, TrackTruePeaks]:
+        """`loudness_blocks` with both meters fed by one separating pass: `(TrackLoudness, TrackTruePeaks)` with the bits of
+        `levels_tensor(wav, mix, sr)` for a host `wav`.  Every emitted span goes into an `audio.LoudnessStream` and an
+        `audio.TruePeakStream` where it lies; the state of `random` is restored on exit as `loudness_blocks` restores it."""
+        from .audio import LoudnessStream, TruePeakStream
+        mix, mixed = self._check_levels("levels_blocks", mix)
+        loud, peaks = self._meter_blocks(source, mix, mixed, sr, channels, pcm, [LoudnessStream, TruePeakStream])
+        return loud, peaks
+
+    def _meter_tensor(self, wav: torch.Tensor, mix, sr: Optional[int], meters):
+        """`separate_tensor(wav, sr)` followed by every whole-track meter of `meters` (`audio.loudness`'s arguments) on the same
+        mix and stems: `(*results, origin, stems)`, `origin` and `stems` as `loudness_tensor` documents them."""
+        device = self._device_index()
+        host_in = wav.device.type == "cpu"
+        with torch.cuda.device(device):
+            dev = wav.to(device) if host_in else wav
+            converted = sr is not None and sr != self._samplerate
+            if converted:
+                dev = convert_audio(dev, sr, self._samplerate, self._audio_channels, device=device)
+            raw = dev.clone() if host_in else None               # the forward normalises its input in place
+            origin, stems = self.separate_tensor(dev, None)
+            measured = [meter(raw if host_in else origin, stems, mix, self._samplerate) for meter in meters]
+            if host_in:
+                stems = dict(zip(stems, _to_host(_stacked(list(stems.values()))[None], device)[0]))
+                origin = _to_host(raw, device) if converted else wav
+        return (*measured, origin, stems)
+
+    def _meter_blocks(self, source, mix, mixed: bool, sr: Optional[int], channels: Optional[int], pcm: Optional[str], meters) -> list:
+        """The two passes of `loudness_blocks` with every emitted span pushed into each of the stream meters that `meters`
+        constructs (`audio.LoudnessStream`'s arguments and interface); returns what their `finish()` return, in order."""
+        import random
+        from .audio import ConvertStream, PcmFeed
         self._check_stream_input(sr, channels, True, pcm)
         plan = self._convert_plan(sr, channels)
         device = self._device_index()
@@ -440,7 +478,7 @@ class Separator:
                 an.push(block)
             stats = an.finish()
             st = self.separate_stream(stats=stats, sr=sr, channels=channels, convert=True, pcm=pcm, length=stats.input_length)
-            meter = LoudnessStream(self._model.sources, self._audio_channels, self._samplerate, mix, device=device)
+            streams = [meter(self._model.sources, self._audio_channels, self._samplerate, mix, device=device) for meter in meters]
             convert = None
             if mixed and (plan is not None or pcm is not None):
                 convert = ConvertStream(sr or self._samplerate, self._samplerate, self._audio_channels, device=device, plan=plan,
@@ -461,7 +499,8 @@ class Separator:
                     need -= k
                 origin = None if not mixed else parts[0] if len(parts) == 1 else torch.cat(parts, 1) if parts else \
                     stems.new_empty(self._audio_channels, 0)
-                meter.push(stems, origin)
+                for meter in streams:
+                    meter.push(stems, origin)
 
             for block in on_device():
                 if mixed:
@@ -470,7 +509,7 @@ class Separator:
             if convert is not None:
                 queue.append(convert.finish(on_device=True))
             measure(st.finish())
-            return meter.finish()
+            return [meter.finish() for meter in streams]
         finally:
             random.setstate(state)
 

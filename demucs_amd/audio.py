@@ -1776,13 +1776,24 @@ class TrackLoudness:
             raise ValueError(f"TrackLoudness: output {name!r} measures {have} LUFS; no gain brings that to {target} LUFS")
         return 10.0 ** ((float(target) - have) / 20.0)
 
-    def normalised(self, target: float = -14.0) -> dict:
+    def normalised(self, target: float = -14.0, true_peaks=None, ceiling: float = -1.0) -> dict:
         """The measured remixes with every gain scaled so that each output reads `target` LUFS: `{output: {"mix" | source:
-        gain}}`, what `deliver_mix` and `Delivery(mix=)` take."""
+        gain}}`, what `deliver_mix` and `Delivery(mix=)` take.  With `true_peaks`, the `TrackTruePeaks` of the same remixes of
+        the same track, an output whose peak that scale would lift over `ceiling` dBTP gets `true_peaks.gain_limit(name,
+        ceiling)` instead and stays below the target loudness: R 128's other half."""
+        if true_peaks is not None:
+            if not isinstance(true_peaks, TrackTruePeaks):
+                raise ValueError(f"TrackLoudness: true_peaks must be a TrackTruePeaks, got {type(true_peaks).__name__}")
+            for what in ("names", "sources", "mix", "samplerate", "channels", "length"):
+                if getattr(true_peaks, what) != getattr(self, what):
+                    raise ValueError(f"TrackLoudness: the true peaks were measured with {what}={getattr(true_peaks, what)!r}, the "
+                                     f"loudness with {getattr(self, what)!r}")
         terms = ("mix",) + self.sources
         out = {}
         for name, gains in self.mix:
             k = self.gain(name, target)
+            if true_peaks is not None:
+                k = min(k, true_peaks.gain_limit(name, ceiling))
             out[name] = {t: g * k for t, g in zip(terms, gains) if g != 0}
         return out
 
@@ -1961,3 +1972,289 @@ def loudness(origin, stems: dict, mix=None, samplerate: int = 44100) -> TrackLou
             b = min(n, a + LOUD_CHUNK)
             stream.push(block[:, :, a:b], None if org is None else org[:, a:b])
     return stream.finish()
+
+
+# ---- true peak of remixes: ITU-R BS.1770-4 Annex 2 (mi_true_peak_update, demucs_amd/csrc/true_peak.hip) ---------------------------
+TP_COLS = 20                       # include/demucs_amd.h: MI_TP_* (MI_MIX_*'s columns up to the gains, then its own)
+TP_MAX_PHASES = 8                  # MI_TP_MAX_PHASES
+TP_MAX_TAPS = 32                   # MI_TP_MAX_TAPS
+# Annex 2's order-48, 4-phase FIR interpolator: phases 0 and 1; phase 2 is phase 1 reversed and phase 3 phase 0 reversed.  Every
+# coefficient is a multiple of 2^-13, hence exact in float32
+_TP_PHASE0 = (0.0017089843750, 0.0109863281250, -0.0196533203125, 0.0332031250000, -0.0594482421875, 0.1373291015625,
+              0.9721679687500, -0.1022949218750, 0.0476074218750, -0.0266113281250, 0.0148925781250, -0.0083007812500)
+_TP_PHASE1 = (-0.0291748046875, 0.0292968750000, -0.0517578125000, 0.0891113281250, -0.1665039062500, 0.4650878906250,
+              0.7797851562500, -0.2003173828125, 0.1015625000000, -0.0582275390625, 0.0330810546875, -0.0189208984375)
+
+
+def _check_true_peak_format(samplerate, channels) -> None:
+    if isinstance(samplerate, bool) or int(samplerate) != samplerate or samplerate <= 0:
+        raise ValueError(f"true peak: the sample rate must be a positive integer, got {samplerate!r}")
+    if samplerate >= 96000:
+        raise ValueError(f"true peak: Annex 2's 4-times oversampling is for sample rates below 96 kHz, got {samplerate}; the 2-times "
+                         "bank of higher rates is not implemented")
+    if isinstance(channels, bool) or int(channels) != channels or channels < 1:
+        raise ValueError(f"true peak: at least one channel, got {channels!r}")
+
+
+def true_peak_bank(samplerate):
+    """The polyphase bank of BS.1770-4 Annex 2's 4-times oversampling filter as a float32 array (4 phases, 12 taps), for sample
+    rates below 96 kHz; other rates are refused.  Output `4 n + p` of the oversampled signal is `sum_k bank[p][k] * x[n - k]`."""
+    import numpy as np
+    _check_true_peak_format(samplerate, 1)
+    return np.array([_TP_PHASE0, _TP_PHASE1, _TP_PHASE1[::-1], _TP_PHASE0[::-1]], dtype=np.float32)
+
+
+def _peak_value(bits: int):
+    import numpy as np
+    return float(np.uint32(bits).view(np.float32))
+
+
+class TrackTruePeaks:
+    """What a true-peak pass over a track found (`audio.true_peak`, `TruePeakStream`, `Separator.levels_blocks`): per output the
+    bit patterns of two float32 maxima, `bits` of the 4-times oversampled signal of BS.1770-4 Annex 2 and `sample_bits` of the
+    samples themselves (a NaN sample gives a NaN pattern).  The oversampled estimate can lie below the sample peak, so a limit
+    uses the larger of the two.
+
+    `names`, `sources`, `samplerate`, `channels`, `length` and `mix` are `TrackLoudness`'s.  Immutable."""
+    __slots__ = ("names", "sources", "samplerate", "channels", "length", "bits", "sample_bits", "mix")
+
+    def __init__(self, names, sources, samplerate, channels, length, bits, sample_bits, mix):
+        import numpy as np
+        for what, v in (("names", names), ("sources", sources)):
+            if isinstance(v, (str, bytes)) or not all(isinstance(n, str) for n in v) or len(set(v)) != len(tuple(v)) or not len(v):
+                raise ValueError(f"TrackTruePeaks: {what} must be a sequence of names, each once, got {v!r}")
+        names, sources = tuple(names), tuple(sources)
+        _check_true_peak_format(samplerate, channels)
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 0:
+            raise ValueError(f"TrackTruePeaks: length must be a non-negative integer, got {length!r}")
+        try:
+            mix = tuple((str(name), tuple(float(np.float32(g)) for g in gains)) for name, gains in mix)
+        except (TypeError, ValueError):
+            raise ValueError(f"TrackTruePeaks: mix must be ((output name, (g_mix, g_0, ...)), ...) as audio.mix_gains returns it, got "
+                             f"{mix!r}") from None
+        if tuple(name for name, _ in mix) != names or \
+                not all(len(g) == 1 + len(sources) and all(np.isfinite(v) for v in g) for _, g in mix):
+            raise ValueError(f"TrackTruePeaks: mix must name the outputs {list(names)} in order, each with finite gains for the mix "
+                             f"and the {len(sources)} sources, got {mix!r}")
+        both = []
+        for what, seq in (("bits", bits), ("sample_bits", sample_bits)):
+            if isinstance(seq, (str, bytes)) or not hasattr(seq, "__len__") or len(seq) != len(names):
+                raise ValueError(f"TrackTruePeaks: {what} must hold one uint32 bit pattern for each of the {len(names)} outputs, got "
+                                 f"{seq!r}")
+            vals = []
+            for v in seq:
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0x7FFFFFFF:
+                    raise ValueError(f"TrackTruePeaks: a peak is the uint32 bit pattern of a float32 max |value|, whose sign bit is "
+                                     f"clear, got {v!r}")
+                vals.append(int(v))
+            both.append(tuple(vals))
+        for name, v in zip(self.__slots__, (names, sources, int(samplerate), int(channels), int(length), both[0], both[1], mix)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("TrackTruePeaks is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("TrackTruePeaks is immutable")
+
+    def _at(self, name: str) -> int:
+        if name not in self.names:
+            raise KeyError(f"output {name!r} is not among the measured outputs {list(self.names)}")
+        return self.names.index(name)
+
+    def true_peak(self, name: str) -> float:
+        """The largest magnitude of output `name`'s 4-times oversampled signal (linear; Annex 2's estimate of the true peak)."""
+        return _peak_value(self.bits[self._at(name)])
+
+    def sample_peak(self, name: str) -> float:
+        """The largest magnitude among output `name`'s samples (linear)."""
+        return _peak_value(self.sample_bits[self._at(name)])
+
+    def dbtp(self, name: str) -> float:
+        """`true_peak(name)` in dBTP: -inf for silence, NaN for a NaN sample."""
+        v = self.true_peak(name)
+        if v != v:
+            return float("nan")
+        return 20.0 * math.log10(v) if v > 0 else float("-inf")
+
+    def gain_limit(self, name: str, ceiling: float = -1.0) -> float:
+        """The largest linear scale that keeps `max(true_peak, sample_peak)` of output `name` at or below `ceiling` dBTP; inf for
+        silence.  A NaN peak has no such scale and raises."""
+        over, sample = self.true_peak(name), self.sample_peak(name)
+        if over != over or sample != sample or not math.isfinite(float(ceiling)):
+            raise ValueError(f"TrackTruePeaks: output {name!r} has the peaks {over} / {sample}; no gain keeps that below "
+                             f"{ceiling} dBTP")
+        peak = max(over, sample)
+        return 10.0 ** (float(ceiling) / 20.0) / peak if peak > 0 else float("inf")
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, TrackTruePeaks) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return (f"TrackTruePeaks(names={list(self.names)}, sources={list(self.sources)}, samplerate={self.samplerate}, "
+                f"channels={self.channels}, length={self.length}, dbtp={[self.dbtp(n) for n in self.names]})")
+
+
+def true_peak_rows(gains, src: int, src_pitch: int, n: int, origin: int, pitch: int, affine, before: int, tail: int, hist_len: int,
+                   side: int, hist_start: int, hist_next: int, channels: int) -> list:
+    """mi_true_peak_update's rows (MI_TP_*) for resolved remixes of `n` frames from track position `before`.  Output i keeps its
+    history at `(side, i)` of a (2, outputs, channels, hist_len) buffer and its two maxima in slot i."""
+    import numpy as np
+    aff = 0 if affine is None else int(np.array(affine, dtype=np.float32).view(np.int64)[0])
+    per = channels * hist_len
+    rows = []
+    for i, (_, g) in enumerate(gains):
+        packed = np.zeros(2 * (MIX_CLIP_AT - MIX_GAINS_AT), dtype=np.float32)
+        packed[:len(g)] = g
+        rows += [src, n, origin, pitch, aff, int(affine is not None), *packed.view(np.int64).tolist(), src_pitch, before, tail,
+                 hist_len, (side * len(gains) + i) * per, ((1 - side) * len(gains) + i) * per, hist_start, hist_next, i]
+    return rows
+
+
+def _true_peak_call(table, rows: int, max_n: int, n_sources: int, channels: int, bank, hist, peaks) -> None:
+    _lib.check(_lib.load().mi_true_peak_update(
+        table.data_ptr(), rows, max_n, n_sources, channels, bank.data_ptr(), bank.shape[0], bank.shape[1],
+        0 if hist is None else hist.data_ptr(), 0 if hist is None else hist.numel(), peaks.data_ptr(), peaks.numel() // 2,
+        C.c_void_p(_lib.current_stream_ptr())), "mi_true_peak_update")
+
+
+class TruePeakStream:
+    """BS.1770-4 Annex 2 true peak (and sample peak) of gain-weighted remixes of a track that arrives block by block, measured
+    where the stems lie.  The interface is `LoudnessStream`'s: `push(stems_block, origin=None, affine=None)` takes the next
+    `n >= 0` samples as a device float32 (sources, channels, n) and the mix of the same positions, `finish()` returns the
+    `TrackTruePeaks`.  The measured values are `deliver_mix(..., clip=None, fmt="f32")`'s, and the peaks have the same bits for
+    every partition of the track into pushes.
+
+    Every push is ONE `mi_true_peak_update` call for all outputs, reading a span of a larger tensor in place; `finish()` issues
+    the one call for the positions past the end and copies 8 bytes per output.  Device state: two sides of (outputs, channels,
+    taps - 1) carried values, and the slots."""
+
+    def __init__(self, sources, channels: int, samplerate: int, mix=None, device="cuda"):
+        self.sources = list(sources)
+        _check_true_peak_format(samplerate, channels)
+        if not self.sources:
+            raise ValueError("true peak: at least one source")
+        if mix is None:
+            mix = {name: {name: 1.0} for name in self.sources}
+        self.gains = mix_gains(mix, self.sources)
+        self.channels, self.samplerate = int(channels), int(samplerate)
+        self.bank = true_peak_bank(self.samplerate)
+        self.mixed = any(g[0] != 0 for _, g in self.gains)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.EngineError("demucs_amd.audio.TruePeakStream only runs on a GPU device (MI355X)")
+        self.device = dev
+        self.pushed = 0
+        self.finished = False
+        self._hist = self._peaks = self._bank = None
+        self._side = self._h0 = 0
+
+    @property
+    def device_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self._hist, self._peaks, self._bank) if t is not None)
+
+    _rows_of = LoudnessStream._rows_of
+
+    def _state(self):
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self._peaks is None:
+            with torch.cuda.device(self.device):
+                self._hist = torch.zeros(2, len(self.gains), self.channels, self.bank.shape[1] - 1, device=self.device)
+                self._peaks = torch.zeros(2 * len(self.gains), dtype=torch.int32, device=self.device)
+                self._bank = torch.from_numpy(self.bank).to(self.device)
+
+    def push(self, stems_block: torch.Tensor, origin=None, affine=None) -> None:
+        if self.finished:
+            raise RuntimeError("push after finish()")
+        S, ch, R = len(self.sources), self.channels, len(self.gains)
+        if not isinstance(stems_block, torch.Tensor) or stems_block.dim() != 3 or tuple(stems_block.shape[:2]) != (S, ch) or \
+                not stems_block.dtype.is_floating_point:
+            raise ValueError(f"true peak: expected a floating ({S}, {ch}, n) block of stems, got "
+                             f"{tuple(getattr(stems_block, 'shape', ()))}")
+        n = stems_block.shape[2]
+        if self.mixed:
+            if origin is None:
+                raise ValueError("true peak: an output has a gain on 'mix'; push the mix of the same positions as origin=")
+            if not isinstance(origin, torch.Tensor) or tuple(origin.shape) != (ch, n) or not origin.dtype.is_floating_point:
+                raise ValueError(f"true peak: the mix is {tuple(getattr(origin, 'shape', ()))}, the stems are {(ch, n)}")
+        if n == 0:
+            return
+        self._state()
+        keep = self.bank.shape[1] - 1
+        with torch.cuda.device(self.device):
+            block, src_pitch = self._rows_of(stems_block)
+            org, pitch = self._rows_of(origin) if self.mixed else (None, 0)
+            end = self.pushed + n
+            nxt = max(0, end - keep)
+            rows = true_peak_rows(self.gains, block.data_ptr(), src_pitch, n, 0 if org is None else org.data_ptr(), pitch, affine,
+                                  self.pushed, 0, keep, self._side, self._h0, nxt, ch)
+            table = torch.tensor(rows, dtype=torch.int64).to(self.device)
+            _true_peak_call(table, R, n, S, ch, self._bank, self._hist, self._peaks)
+        self._side, self._h0, self.pushed = 1 - self._side, nxt, end
+
+    def finish(self) -> TrackTruePeaks:
+        if self.finished:
+            raise RuntimeError("finish() called twice")
+        self.finished = True
+        R = len(self.gains)
+        bits = [0] * (2 * R)
+        if self.pushed:
+            keep = self.bank.shape[1] - 1
+            with torch.cuda.device(self.device):
+                # the positions past the end: no new sample, the history alone
+                rows = true_peak_rows(self.gains, 0, 0, 0, 0, 0, None, self.pushed, keep, keep, self._side, self._h0, -1, self.channels)
+                table = torch.tensor(rows, dtype=torch.int64).to(self.device)
+                _true_peak_call(table, R, keep, len(self.sources), self.channels, self._bank, self._hist, self._peaks)
+                bits = [v & 0xFFFFFFFF for v in self._peaks.cpu().tolist()]
+        return TrackTruePeaks([name for name, _ in self.gains], self.sources, self.samplerate, self.channels, self.pushed, bits[0::2],
+                              bits[1::2], mix_identity(self.gains))
+
+
+def true_peak(origin, stems: dict, mix=None, samplerate: int = 44100) -> TrackTruePeaks:
+    """BS.1770-4 Annex 2 true peaks of gain-weighted remixes of one separated track, measured on the stems' device in ONE
+    `mi_true_peak_update` call: the `TrackTruePeaks` of the frames `deliver_mix(origin, stems, mix, clip=None, fmt="f32")`
+    returns, none of which is produced.  The arguments and their defaults are `audio.loudness`'s."""
+    names = list(stems)
+    if mix is None:
+        mix = {name: {name: 1.0} for name in names}
+        if origin is not None:
+            mix["mix"] = {"mix": 1.0}
+    tensors = [stems[k] for k in names]
+    for t in tensors:
+        if not t.dtype.is_floating_point:
+            raise TypeError(f"true peak: a floating-point tensor is expected, got {t.dtype}")
+        if t.dim() != 2 or t.shape != tensors[0].shape:
+            raise ValueError(f"true peak: every stem is (channels, n), got {[tuple(x.shape) for x in tensors]}")
+    if not tensors:
+        raise ValueError("true peak: at least one source")
+    channels, n = tensors[0].shape
+    _check_true_peak_format(samplerate, channels)
+    gains = mix_gains(mix, names)
+    mixed = any(g[0] != 0 for _, g in gains)
+    if mixed and origin is None:
+        raise ValueError("true peak: an output has a gain on 'mix'; pass the mix as origin")
+    if mixed and tuple(origin.shape) != (channels, n):
+        raise ValueError(f"true peak: the mix is {tuple(origin.shape)}, the stems are {(channels, n)}")
+    dev = _engine_device(*tensors)
+    R = len(gains)
+    bits = [0] * (2 * R)
+    if n:
+        bank = true_peak_bank(samplerate)
+        with torch.cuda.device(dev):
+            block = _stems_block(tensors, dev)
+            org = _stage(origin, dev, "true peak").contiguous() if mixed else None
+            tail = bank.shape[1] - 1
+            rows = true_peak_rows(gains, block.data_ptr(), n, n, 0 if org is None else org.data_ptr(), n if mixed else 0, None, 0, tail,
+                                  0, 0, 0, -1, channels)
+            table = torch.tensor(rows, dtype=torch.int64).to(dev)
+            peaks = torch.zeros(2 * R, dtype=torch.int32, device=dev)
+            _true_peak_call(table, R, n + tail, len(names), channels, torch.from_numpy(bank).to(dev), None, peaks)
+            bits = [v & 0xFFFFFFFF for v in peaks.cpu().tolist()]
+    return TrackTruePeaks([name for name, _ in gains], names, samplerate, channels, n, bits[0::2], bits[1::2], mix_identity(gains))

@@ -721,6 +721,18 @@ int mi_loudness_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, 
                                   energies_dev, energies_capacity, work_dev, work_capacity, (hipStream_t)stream);
 }
 
+int mi_true_peak_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels,
+                        const float *bank_dev, int32_t phases, int32_t taps, float *hist_dev, int64_t hist_capacity, void *peaks_dev,
+                        int32_t n_peaks, void *stream) {
+    MI_REQUIRE(table_dev && bank_dev && peaks_dev && n_rows > 0 && n_rows <= 65535 && max_n >= 1 &&
+               max_n <= (int64_t)INT32_MAX * 1024 && n_sources > 0 && n_sources <= MI_MIX_MAX_SOURCES && channels > 0 &&
+               channels <= 65535 && phases >= 1 && phases <= MI_TP_MAX_PHASES && taps >= 1 && taps <= MI_TP_MAX_TAPS &&
+               hist_capacity >= 0 && (hist_dev || hist_capacity == 0) && n_peaks > 0 && n_peaks <= INT32_MAX / 2,
+               "mi_true_peak_update: bad argument");
+    return launch_true_peak_update(table_dev, n_rows, max_n, n_sources, channels, bank_dev, phases, taps, hist_dev, hist_capacity,
+                                   (unsigned *)peaks_dev, n_peaks, (hipStream_t)stream);
+}
+
 // Kernel-level entry points.  They allocate their scratch with hipMalloc and free it after a
 // stream synchronise: convenient for parity tests, not meant for the hot loop.
 int mi_stft_cac(const float *mix_dev, int32_t B, int32_t L, float *cac_dev, void *stream) {

@@ -344,4 +344,8 @@ int launch_loudness_update(const int64_t *table, int n_rows, int64_t max_n, int6
                            const double *coef, int64_t hop, int64_t warm, float *hist, int64_t hist_cap, double *energies, int64_t e_cap,
                            float *work, int64_t work_cap, hipStream_t st);
 
+// true_peak.hip: oversampled (BS.1770-4 Annex 2) and sample peaks of gain-weighted remixes, whole or streamed; bank is (phases, taps)
+int launch_true_peak_update(const int64_t *table, int n_rows, int64_t max_n, int n_sources, int channels, const float *bank, int phases,
+                            int taps, float *hist, int64_t hist_cap, unsigned *peaks, int n_peaks, hipStream_t st);
+
 }  // namespace mi

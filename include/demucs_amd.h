@@ -785,6 +785,68 @@ int mi_loudness_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, 
                        const double *coef, int64_t hop, int64_t warm, float *hist_dev, int64_t hist_capacity, double *energies_dev,
                        int64_t energies_capacity, float *work_dev, int64_t work_capacity, void *stream);
 
+/* ---- true peak of remixes (ITU-R BS.1770-4 Annex 2 / EBU R 128): oversampled and sample peaks, whole or streamed -----------------
+ * No counterpart in the reference: the other half of a delivery specification (-14 LUFS at no more than -1 dBTP).  The measured
+ * signal v[c][j], 0 <= j < L, of a row is mi_deliver_mix_pcm's value before clipping, exactly as mi_loudness_update reads it;
+ * v = 0 outside [0, L).  bank_dev is a DEVICE array of (phases, taps) float32, h[p][k] (for Annex 2 the 4 x 12 polyphase table of
+ * its 4-times oversampling filter).  For every phase p, channel c and position n in [0, L + taps - 1):
+ *     acc = 0.0f;  for k = 0 .. taps-1 ascending:  acc = acc + h[p][k] * v[c][n - k]
+ * every product and every sum a separately rounded float32 operation (no fused multiply-add).  Per output two uint32 bit patterns
+ * of float32 are kept in peaks_dev (2 * n_peaks uint32): `over` = max |acc| over p, c, n at peaks_dev[2 * PEAK], and `sample` =
+ * max |v| over c, j at peaks_dev[2 * PEAK + 1], each reduced over a workgroup and then by at most one atomicMax per workgroup, none
+ * when the maximum is 0 or the slot already holds at least as much; a NaN leaves a NaN pattern, which orders above +inf.  The
+ * caller zeroes a row's slots at the start of a track.
+ * Both are pure functions of the values and max is order-free: the slots have the same bits for every partition of a track into
+ * calls.  The oversampled estimate can lie below the sample peak (a tone at fs/4 sampled at its crests), so both are kept.
+ * mi_true_peak_update: ONE launch takes the next N samples of every output of a track (or of a push), grid (ceil(max_n / 1024),
+ *   n_rows); nothing synchronises with the host.  Row r of the table (MI_TP_COLS int64, a DEVICE array) is ONE output:
+ *     SRC, N, ORIGIN, ORIGIN_PITCH, ORIGIN_AFFINE, AFFINE_ON, GAINS   as MI_MIX_*, at the same indices;
+ *     SRC_PITCH, BEFORE   as MI_LOUD_*: floats between the (source, channel) rows of the stems, and the track position of frame 0;
+ *     TAIL                positions past BEFORE + N that the call also evaluates, reading 0 there: 0 on a push, taps - 1 on the final
+ *                         call of a track, after which every position of [0, L + taps - 1) has been evaluated once.  The call
+ *                         evaluates the positions [BEFORE, BEFORE + N + TAIL);
+ *     HIST_LEN, HIST_RD, HIST_WR, HIST_START, HIST_NEXT
+ *                         the carried VALUES of this output, as MI_RATE_HIST_*: (channels, hist_len) floats at float offset
+ *                         hist_rd of hist_dev hold positions [hist_start, before); the call (workgroup 0 of the row) writes positions
+ *                         [hist_next, before + n) (at most hist_len), taken from the read side below BEFORE, at float offset
+ *                         hist_wr, a side apart from the read one; hist_next < 0: nothing is written.  A stream carries from
+ *                         max(0, before + n - (taps - 1)) on: taps - 1 values a channel.  hist_len == 0: no history, for a track
+ *                         measured in one call (before == 0, hist_next < 0);
+ *     PEAK                the row's slot in peaks_dev.
+ *   max_n >= every row's N + TAIL (grid size).  Rows must not share history sides; rows that share a slot share its maximum.
+ *   A row is skipped whole (nothing of it is read or written, its history and its slots included) under mi_loudness_update's rules
+ *   -- SRC is 0 (with N > 0), a gain among g_mix, g_0 .. g_{n_sources-1} is not finite, all of them are 0, g_mix != 0 (with N > 0)
+ *   without ORIGIN or with ORIGIN_PITCH < N, SRC_PITCH < N; BEFORE or HIST_START is negative, HIST_START > BEFORE, or before -
+ *   hist_start > hist_len; a history side leaves hist_capacity (floats) or the sides overlap; HIST_NEXT >= 0 lies outside
+ *   [hist_start, before + n] or before + n - hist_next > hist_len; N or BEFORE exceed 2^61 -- and when N < 0, or N == 0 with
+ *   TAIL == 0 (N may be 0 when TAIL > 0: the final call of a stream, which reads only its history; SRC and ORIGIN are then not
+ *   read); TAIL is outside [0, taps); PEAK is outside [0, n_peaks); HIST_START > 0 with fewer than taps - 1 values carried
+ *   (before - hist_start < taps - 1: the chains of the first positions would miss values).
+ *   1 <= phases <= MI_TP_MAX_PHASES and 1 <= taps <= MI_TP_MAX_TAPS are arguments, not constants of the build; the 4 x 12 bank
+ *   runs an instance of the kernel with its window in registers, every other bank a generic loop with the same arithmetic. */
+#define MI_TP_SRC 0
+#define MI_TP_N 1
+#define MI_TP_ORIGIN 2
+#define MI_TP_ORIGIN_PITCH 3
+#define MI_TP_ORIGIN_AFFINE 4
+#define MI_TP_AFFINE_ON 5
+#define MI_TP_GAINS 6
+#define MI_TP_SRC_PITCH 11
+#define MI_TP_BEFORE 12
+#define MI_TP_TAIL 13
+#define MI_TP_HIST_LEN 14
+#define MI_TP_HIST_RD 15
+#define MI_TP_HIST_WR 16
+#define MI_TP_HIST_START 17
+#define MI_TP_HIST_NEXT 18
+#define MI_TP_PEAK 19
+#define MI_TP_COLS 20
+#define MI_TP_MAX_PHASES 8
+#define MI_TP_MAX_TAPS 32
+int mi_true_peak_update(const int64_t *table_dev, int32_t n_rows, int64_t max_n, int32_t n_sources, int32_t channels,
+                        const float *bank_dev, int32_t phases, int32_t taps, float *hist_dev, int64_t hist_capacity, void *peaks_dev,
+                        int32_t n_peaks, void *stream);
+
 /* ---- kernel-level entry points (parity tests; same kernels the forward uses) --------------
  * mi_stft_cac: `_magnitude(_spec(mix))` (demucs/htdemucs.py:420-461, demucs/spec.py:11-27):
  *   mix_dev (B,2,L) -> cac_dev (B,4,2048,ceil(L/1024)), channel order [c0.re,c0.im,c1.re,c1.im]. */
